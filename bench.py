@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the fused safe-MPC solve on the BASELINE.json workloads: CEM particle-step evaluations/s.
 
-    python bench.py [--config {1,2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--backend {nccl,gloo}]
+    python bench.py [--config {1,2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--backend {nccl,gloo}] [--dump-outputs DIR]
 
 `--config` picks a BASELINE.json workload by number (default 2, the one the metric is quoted on; the constants live in
 safe_exploration_amd/problems.py:baseline_workload).  `--gpus N` alone is enough: the parent process starts N fresh
@@ -16,6 +16,10 @@ every GPU holds the workload's per-GPU particle count; configs 2-4 shard ONE pro
 with ONE all-gather per iteration, config 5 stripes independent episodes (no collective).  Inputs are synthetic (seeded)
 and resident in HBM before the timed region.  Rank 0 prints ONE JSON line; a non-zero device status (the reference would
 have raised ValueError on this workload) is an error, not a throughput.
+
+The solver's noise stream starts over from a fixed seed right before the timed steps, so the same arguments give the timed
+steps the same inputs in every run.  `--dump-outputs DIR` writes what the last timed step returned (rank 0's) as
+DIR/<name>.npy in float64, which lets two builds be compared output for output.
 """
 import argparse
 import ctypes
@@ -143,6 +147,38 @@ def total_mfmas(form, n_s):
 # profiles/r03_timer_sweep.txt: the same 20 timed solves read 2.5-4 % slower behind 5 warm-up solves than behind 50).  Before
 # the W warm-up steps bench.py therefore runs untimed solves for this long; the JSON line says how many (`prewarm_solves`).
 PREWARM_S = 0.10
+# The prewarm's solve count follows the clock, so the solver's generator is re-seeded with this before the timed steps
+NOISE_SEED = 1
+DUMP_MAX_BYTES = 64 << 20
+
+
+def restart_noise(mpc):
+    """The solver's noise stream from NOISE_SEED again, as its constructor seeds it; the pool of pre-drawn normals goes too,
+    so the first timed solve draws from the start of the stream."""
+    from safe_exploration_amd import distributed
+    mpc._gen.manual_seed(distributed.rank_seed(NOISE_SEED, mpc._rank))
+    mpc._noise_pool = None
+
+
+def episode_outputs(episodes, envs):
+    """Config 5: the arrays do_rollout_batch hands its caller (every episode runs all steps, so they stack over episodes),
+    plus the states the last step left the environments in.  Longer runs than DUMP_MAX_BYTES holds keep their last steps."""
+    import numpy as np
+    out = {'xx': np.stack([r.xx for r in episodes]), 'yy': np.stack([r.yy for r in episodes]),
+           'exit_codes': np.stack([r.exit_codes[:, 0] for r in episodes]), 'final_states': np.stack([e.state for e in envs])}
+    per_step = sum(a[:, :1].nbytes for k, a in out.items() if k != 'final_states')
+    keep = (DUMP_MAX_BYTES - out['final_states'].nbytes) // per_step
+    return {k: a if k == 'final_states' else a[:, max(0, a.shape[1] - keep):] for k, a in out.items()}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    print(f'bench.py: wrote {", ".join(sorted(arrays))} to {out_dir}', file=sys.stderr)
 
 
 def cpu_baseline(w, budget_s=12.0):
@@ -297,7 +333,13 @@ def main():
     ap.add_argument('--no-kernel-timer', action='store_true', help='leave the per-launch HIP events off (no roofline object)')
     ap.add_argument('--profile-stride', type=int, default=0,
                     help='bracket every n-th launch of a kernel with HIP events (0 = PROFILE_STRIDE: 16, less in short runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (rank 0) as DIR/<name>.npy, float64, at most 64 MB')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup is not None and args.warmup < 0:
+        ap.error('--warmup must not be negative')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -429,7 +471,7 @@ def main():
         class Conf:
             mpc_time_horizon, cem_num_rollouts, cem_num_elites, cem_num_iterations, cem_init_std = H, P, elites, iters, init_std
             device, use_state_constraint, use_prior_model = str(dev), True, True
-            exact_gp_training_iterations, exact_gp_kernel, cem_seed = 0, 'rbf', 1
+            exact_gp_training_iterations, exact_gp_kernel, cem_seed = 0, 'rbf', NOISE_SEED
             plot_cem_optimisation = plot_cem_terminal_states = False
 
         envs = [problems.StubEnv(spec, x, never_done=True) for x in x0.cpu().numpy()]
@@ -437,6 +479,7 @@ def main():
         mpc = solver._solver()
         prewarm_solves = prewarm(lambda: do_rollout_batch(envs, 1, solver))
         do_rollout_batch(envs, warmup, solver)
+        restart_noise(mpc)
         start_timer()
         barrier()
         t0 = time.perf_counter()
@@ -447,13 +490,15 @@ def main():
         from safe_exploration_amd.safempc_cem import MpcResult
         ok = torch.tensor([int(any(MpcResult.FOUND_SOLUTION in r.mpc_results for r in episodes))])
         assert all(r.episode_length == steps for r in episodes)
+        outputs = episode_outputs(episodes, envs) if args.dump_outputs else None
     else:
-        mpc = FusedCemMpc(ssm, env, H, total_particles, elites, iters, device=dev, seed=1, init_std=init_std,
+        mpc = FusedCemMpc(ssm, env, H, total_particles, elites, iters, device=dev, seed=NOISE_SEED, init_std=init_std,
                           warm_start='safe_policy' if w.warm_start != 'zero' else 'zero', process_group=solver_group,
                           force_exchange=force_exchange)
         prewarm_solves = prewarm(lambda: mpc.solve(x0))
         for _ in range(warmup):
             mpc.solve(x0)
+        restart_noise(mpc)
         start_timer()
         if ((world > 1 and w.sharded) or force_exchange) and not args.no_exchange_timer:
             mpc.exchange_events = []
@@ -466,6 +511,9 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         status = torch.cat([t.reshape(-1) for t in statuses])   # EVERY timed solve's status word is checked below
+        outputs = None
+        if args.dump_outputs:   # what solve() returned for the last timed step (the history is empty: nothing recorded)
+            outputs = {'best_actions': best.cpu().numpy(), 'best_ok': ok.cpu().numpy(), 'status': statuses[-1].cpu().numpy()}
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
@@ -512,6 +560,8 @@ def main():
 
     rc = 0
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         if status_word != 0:
             print(f'bench.py: device status {status_word} (SX_STATUS_* bits) on {w.name}: the reference would have raised '
                   f'on this workload; no throughput reported', file=sys.stderr)
