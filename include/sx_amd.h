@@ -178,7 +178,9 @@ int sx_profile_disable(void);
 #define SX_WAVES 8               /* waves per workgroup in the GP kernels (the stage table is laid out for it) */
 #endif
 
-/* Sizes of sx_gp_model.a_pack (doubles) and sx_gp_model.stage_tab (int32). */
+/* Sizes of sx_gp_model.a_pack (doubles) and sx_gp_model.stage_tab (int32).
+ * sx_gp_pack_sizes, sx_gp_fit and sx_gp_pack take any n_u with n_s + n_u <= SX_MAX_D: beyond SX_MAX_NU that is the
+ * widened GP of sx_cem_rollout_junk (n_u = real actions + query shift), which only that entry point consumes. */
 int sx_gp_pack_sizes(int n_s, int n_u, int n_train, int64_t* a_doubles, int64_t* tab_ints);
 
 #define SX_STATUS_NOT_PD 8       /* sx_gp_fit: K + noise I is not positive definite (gpytorch would raise too) */
@@ -282,6 +284,32 @@ int sx_cem_rollout(const sx_gp_model* model, const sx_env* env, int E, int P, in
 int sx_cem_rollout_elites(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                           const double* elite_rows, int k, const double* noise, double* actions, double* traj, double* sigma,
                           double* obj_cost, double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream);
+
+/* sx_cem_rollout for a JunkDimensionsSSM over an exact RBF GP (n_s real states and n_u real actions padded with J_s junk
+ * states and J_a junk actions, all zero).  Input columns that are zero in every training row and every query add nothing
+ * to any kernel value, so the padded GP's real outputs are those of a GP over the D = n_s + n_u + s columns that are ever
+ * non-zero, s = query_shift = min(J_s, n_u): training rows [x, u, 0_s], queries [x, 0_s, u].  `model` is that GP
+ * (model->n_s == env->n_s, model->n_u == env->n_u + query_shift); `env` and every buffer are shaped by (n_s, n_u) exactly as
+ * in sx_cem_rollout.  The reachability step receives the Jacobian's leading n_s + n_u columns -- for the "action" block
+ * the derivative by the training rows' action columns, as the reference's padding has it.
+ *   query_shift 0 .. env->n_u; 0 is sx_cem_rollout itself (every form, the workspace path included).
+ * SX_ERR_ARG (checked before any device access) for null pointers, non-positive sizes or inconsistent shapes;
+ * SX_ERR_UNSUPPORTED for query_shift > 0 where the training set needs the workspace path (sx_cem_rollout_workspace_bytes()
+ * of the model > 0 -- roll out step by step there) or the shape is not instantiated (n_s + n_u + query_shift <= 6, n_u <= 2).
+ * Replaces: the H dynamics callbacks through JunkDimensionsSSM (ssm_cem/ssm_cem.py:134-210) that the optimiser makes per
+ * iteration for the reference's junk-dimension experiment (utils_config.py:45-47, safempc_cem.py:288-312). */
+int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H, const double* x0,
+                        const double* q0, const double* mean, const double* std, const double* noise, double* actions,
+                        double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
+/* sx_cem_rollout_elites for the same models as sx_cem_rollout_junk (the refit from the previous iteration's elite rows, whose
+ * action part is H * env->n_u wide).  query_shift 0 is sx_cem_rollout_elites itself.
+ * Replaces: as sx_cem_rollout_junk, for every CEM iteration after the first (ConstrainedCemMpc.get_actions' refit step). */
+int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                               const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                               double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                               int32_t* status, double* mean_out, double* std_out, void* stream);
 
 /* Bytes of workspace sx_cem_rollout needs for this model and problem size: 0 = the fused single-launch path applies;
  * < 0 = bad arguments. */

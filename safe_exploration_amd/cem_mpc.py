@@ -75,6 +75,9 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
                                           _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj),
                                           _lib.ptr(con), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_cem_rollout_mlp')
         return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+    if getattr(ssm, 'kernel_family', 'rbf') == 'rbf_junk':
+        return _cem_rollout_junk(ssm, env, x0, horizon, E, P, actions, traj, sigma, obj, con, status, q0=q0, mean=mean,
+                                 std=std, noise=noise, elite_rows=elite_rows, want_dist=want_dist)
     model = ssm.device_model
     if elite_rows is not None:
         k = elite_rows.size(1)
@@ -98,16 +101,61 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
 
 
+class FusedJunkUnsupported(_lib.SxError):
+    """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
+
+
+def _cem_rollout_junk(ssm, env, x0, horizon, E, P, actions, traj, sigma, obj, con, status, *, q0, mean, std, noise,
+                      elite_rows, want_dist):
+    """cem_rollout for JunkDimensionsSSM over an exact RBF GP: the real-output GP over the kept columns
+    (`real_output_view`) with the query shift, through sx_cem_rollout_junk / sx_cem_rollout_elites_junk.  Raises
+    FusedJunkUnsupported where the library has no single-launch form for it."""
+    lib = _lib.lib()
+    view = ssm.real_output_view()
+    model, shift, n_u = view.device_model, ssm.query_shift, ssm.num_actions
+
+    def check(code, what):
+        if code == _lib.SX_ERR_UNSUPPORTED:
+            raise FusedJunkUnsupported(f'{what}: no single-launch form for this model')
+        _lib.check(code, what)
+
+    if elite_rows is not None:
+        k = elite_rows.size(1)
+        if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
+            raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
+        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=x0.device) if want_dist else None
+        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=x0.device) if want_dist else None
+        check(lib.sx_cem_rollout_elites_junk(ctypes.byref(model), ctypes.byref(env), shift, E, P, horizon,
+                                             _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(elite_rows), k, _lib.ptr(noise),
+                                             _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con),
+                                             _lib.ptr(status), _lib.ptr(m_out), _lib.ptr(s_out), _lib.stream_ptr(x0.device)),
+              'sx_cem_rollout_elites_junk')
+        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
+    # (query shift 0 is sx_cem_rollout itself, the workspace path included; a shift > 0 never takes a workspace)
+    ws_bytes = int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(model), E, P, horizon)) if shift == 0 else 0
+    if ws_bytes < 0:
+        raise _lib.SxError('sx_cem_rollout_workspace_bytes: bad arguments')
+    workspace = view.workspace(ws_bytes)
+    check(lib.sx_cem_rollout_junk(ctypes.byref(model), ctypes.byref(env), shift, E, P, horizon, _lib.ptr(x0.contiguous()),
+                                  _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
+                                  _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                  _lib.ptr(workspace), ws_bytes, _lib.stream_ptr(x0.device)), 'sx_cem_rollout_junk')
+    return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+
+
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
     """May the elite refit move from the ranking kernel's tail into the next rollout's prologue (sx_cem_rollout_elites)?
     Exact-GP models on the single-launch path whose H n_u means and standard deviations fit the prologue's scratch, where
-    the ranking that produces the rows (over `candidates` rows per problem; default: the particles) is the counting one."""
-    if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
+    the ranking that produces the rows (over `candidates` rows per problem; default: the particles) is the counting one.
+    (JunkDimensionsSSM over an exact GP, 'rbf_junk': the same for its real-output GP, sx_cem_rollout_elites_junk.)"""
+    family = getattr(ssm, 'kernel_family', 'rbf')
+    if family not in ('rbf', 'rbf_junk'):
         return False
     if 2 * horizon * ssm.num_actions > 256 * (1 + ssm.num_states):
         return False
     lib = _lib.lib()
-    if int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(ssm.device_model), episodes, particles, horizon)) != 0:
+    model = ssm.real_output_view().device_model if family == 'rbf_junk' else ssm.device_model
+    if int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(model), episodes, particles, horizon)) != 0:
         return False
     # worth it where the ranking spreads over the chip and its refit would be a serial tail; many problems at once
     # (config 5: 8 episodes per GPU) rank and refit side by side, one workgroup each
@@ -468,19 +516,31 @@ class FusedCemMpc:
             if self.rollout_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(torch.cuda.current_stream(dev))
-            if stepwise:
+
+            def rollout_stepwise():
                 acts = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x H x n_u]
                 per_e = [cem_rollout_stepwise(self._ssm, self._env, x0[e], acts[e], status=status,
                                               group=self._group if self._world > 1 else None,
                                               objective_hook=self._objective_hook) for e in range(E)]
-                r = dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
-                         con_cost=torch.stack([q['con_cost'] for q in per_e]))
+                return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
+                            con_cost=torch.stack([q['con_cost'] for q in per_e]))
+
+            if stepwise:
+                r = rollout_stepwise()
             elif rows is not None:
                 r = cem_rollout(self._ssm, self._env, x0, H, elite_rows=rows, noise=eps.contiguous(),
                                 want_traj=self._record or self._objective_hook is not None, status=status)
             else:
-                r = cem_rollout(self._ssm, self._env, x0, H, mean=mean, std=std, noise=eps.contiguous(),
-                                want_traj=self._record or self._objective_hook is not None, status=status)
+                try:
+                    r = cem_rollout(self._ssm, self._env, x0, H, mean=mean, std=std, noise=eps.contiguous(),
+                                    want_traj=self._record or self._objective_hook is not None, status=status)
+                except FusedJunkUnsupported:
+                    # (answered before any launch) the junk-dimension model has no single-launch form for this training
+                    # set: the whole solve goes step by step through the wrapper
+                    if it != 0:
+                        raise
+                    stepwise, in_prologue = True, False
+                    r = rollout_stepwise()
             if self._objective_hook is not None and not stepwise:
                 n_s = self._ssm.num_states
                 centres = r['traj'][..., :n_s]                                   # [E x P x H x n_s]

@@ -20,6 +20,7 @@
 #include "sx_rollout.hpp"
 #include "sx_launch.hpp"
 #include "sx_rw_launch.hpp"
+#include "sx_junk_launch.hpp"
 #include "sx_rank.hpp"
 #include "sx_rank_count.hpp"
 #include "sx_feat.hpp"
@@ -567,11 +568,11 @@ static int launch_predict_big(const sx_gp_model* m, const double* z, int P, doub
 }
 
 // does the single-launch kernel's LDS budget hold Kstar for this model -- of all outputs at once (ns_lds = ns), or of one
-// output at a time (ns_lds = 1)?
-static bool fused_fits(int ns, int nu, int n_train, int n_pad, int H, int ns_lds = -1) {
+// output at a time (ns_lds = 1)?  (sh: the query shift of sx_cem_rollout_junk -- the GP is ns + nu + sh wide, the actions nu)
+static bool fused_fits(int ns, int nu, int n_train, int n_pad, int H, int ns_lds = -1, int sh = 0) {
     const int nw = kRolloutThreads / 64;
     const size_t lds =
-        (gp_tile_lds_doubles(ns, ns + nu, n_train, n_pad, nw, ns_lds) + (size_t)SX_TILE * H * nu) * sizeof(double);
+        (gp_tile_lds_doubles(ns, ns + nu + sh, n_train, n_pad, nw, ns_lds) + (size_t)SX_TILE * H * nu) * sizeof(double);
     return lds <= kMaxLdsBytes && n_pad <= 1024;
 }
 
@@ -660,6 +661,25 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
                gc, gc.stage_tab, rc, cc, rp);
     }
     return check_launch();
+}
+
+// sx_cem_rollout_junk with a query shift SH > 0: the GP model is (NS, NU + SH), the environment (NS, NU).  The streaming
+// kernel only (all outputs' Kstar in LDS, or one output at a time); a training set that needs the workspace path is
+// SX_ERR_UNSUPPORTED (the caller rolls out step by step).
+template <int NS, int NU, int SH>
+static int launch_rollout_junk(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, hipStream_t stream) {
+    const bool all_at_once = fused_fits(NS, NU, m->n_train, m->n_pad, rp.H, -1, SH);
+    if (!all_at_once && !(NS > 1 && fused_fits(NS, NU, m->n_train, m->n_pad, rp.H, 1, SH))) return SX_ERR_UNSUPPORTED;
+    if (rp.elite_rows && 2 * rp.H * NU > 256 + 256 * NS) return SX_ERR_UNSUPPORTED;
+    const int nw = kRolloutThreads / 64;
+    auto gc = make_gp_const<NS, NU + SH>(m, nw);
+    ReachConst<NS, NU> rc;
+    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    make_cost_const<NS, NU>(env, cc);
+    const size_t lds = (gp_tile_lds_doubles(NS, NS + NU + SH, m->n_train, m->n_pad, nw, all_at_once ? NS : 1) +
+                        (size_t)SX_TILE * rp.H * NU) * sizeof(double);
+    return launch_rollout_shifted<NS, NU, SH>(gc, rc, cc, rp, all_at_once, lds, stream);
 }
 
 }  // namespace sx
@@ -849,7 +869,7 @@ int sx_profile_disable(void) {
 }
 
 int sx_gp_pack_sizes(int n_s, int n_u, int n_train, int64_t* a_doubles, int64_t* tab_ints) {
-    if (n_s <= 0 || n_s > SX_MAX_NS || n_u <= 0 || n_u > SX_MAX_NU || n_train <= 0) return SX_ERR_ARG;
+    if (n_s <= 0 || n_s > SX_MAX_NS || n_u <= 0 || n_s + n_u > SX_MAX_D || n_train <= 0) return SX_ERR_ARG;
     const int n_pad = sx::gp_n_pad(n_train, n_s + n_u);
     if (a_doubles) *a_doubles = sx::a_pack_doubles(n_s, n_pad);
     if (tab_ints) *tab_ints = sx::gp_stage_tab_ints(n_s, n_pad, SX_WAVES);
@@ -859,7 +879,7 @@ int sx_gp_pack_sizes(int n_s, int n_u, int n_train, int64_t* a_doubles, int64_t*
 int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, double* linv, double* alpha,
               double* logdet, int32_t* status, void* stream) {
     if (!model || !model->x_train || !y_train || !work || !linv || !alpha || !logdet || !status) return SX_ERR_ARG;
-    if (model->n_s <= 0 || model->n_s > SX_MAX_NS || model->n_u <= 0 || model->n_u > SX_MAX_NU || model->n_train <= 0)
+    if (model->n_s <= 0 || model->n_s > SX_MAX_NS || model->n_u <= 0 || model->n_s + model->n_u > SX_MAX_D || model->n_train <= 0)
         return SX_ERR_ARG;
     if (model->n_train > sx::kFitMaxN) return SX_ERR_UNSUPPORTED;
     sx::FitArgs fa;
@@ -1031,7 +1051,7 @@ int sx_gp_predict_mean_hessian(const sx_gp_model* model, const double* alpha, co
 
 int sx_gp_pack(sx_gp_model* model, const double* linv, const double* alpha, void* stream) {
     if (!model || !linv || !alpha || !model->x_train || !model->a_pack || !model->stage_tab) return SX_ERR_ARG;
-    if (model->n_s <= 0 || model->n_s > SX_MAX_NS || model->n_u <= 0 || model->n_u > SX_MAX_NU || model->n_train <= 0)
+    if (model->n_s <= 0 || model->n_s > SX_MAX_NS || model->n_u <= 0 || model->n_s + model->n_u > SX_MAX_D || model->n_train <= 0)
         return SX_ERR_ARG;
     const int D = model->n_s + model->n_u;
     model->n_pad = sx::gp_n_pad(model->n_train, D);
@@ -1150,6 +1170,63 @@ int sx_cem_rollout_elites(const sx_gp_model* model, const sx_env* env, int E, in
     rp.std_out = std_out;
 #define CALL(NS, NU) sx::launch_rollout<NS, NU>(model, env, rp, nullptr, 0, (hipStream_t)stream)
     SX_DISPATCH(model->n_s, model->n_u, CALL);
+#undef CALL
+}
+
+// (model, env, query_shift) of the junk entries: checked before anything touches the device
+static bool junk_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
+    return model->n_s == env->n_s && query_shift >= 0 && query_shift <= env->n_u && model->n_u == env->n_u + query_shift;
+}
+
+// the instantiated (n_s, n_u, shift > 0) of cem_rollout_kernel (sx_junk_ns*.hip); CALL(NS, NU, SH)
+#define SX_JUNK_DISPATCH(ns, nu, sh, CALL)                                    \
+    do {                                                                      \
+        if ((ns) == 2 && (nu) == 1 && (sh) == 1) return CALL(2, 1, 1);        \
+        if ((ns) == 4 && (nu) == 1 && (sh) == 1) return CALL(4, 1, 1);        \
+        if ((ns) == 3 && (nu) == 1 && (sh) == 1) return CALL(3, 1, 1);        \
+        if ((ns) == 2 && (nu) == 2 && (sh) == 1) return CALL(2, 2, 1);        \
+        if ((ns) == 2 && (nu) == 2 && (sh) == 2) return CALL(2, 2, 2);        \
+        if ((ns) == 3 && (nu) == 2 && (sh) == 1) return CALL(3, 2, 1);        \
+        if ((ns) == 1 && (nu) == 1 && (sh) == 1) return CALL(1, 1, 1);        \
+        return SX_ERR_UNSUPPORTED;                                            \
+    } while (0)
+
+int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H, const double* x0,
+                        const double* q0, const double* mean, const double* std, const double* noise, double* actions,
+                        double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
+    if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
+    if (noise && (!mean || !std)) return SX_ERR_ARG;
+    if (!junk_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
+    if (query_shift == 0)
+        return sx_cem_rollout(model, env, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status,
+                              workspace, workspace_bytes, stream);
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+#define CALL(NS, NU, SH) sx::launch_rollout_junk<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
+    SX_JUNK_DISPATCH(model->n_s, env->n_u, query_shift, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                               const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                               double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                               int32_t* status, double* mean_out, double* std_out, void* stream) {
+    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
+    if (E <= 0 || P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
+    if (!junk_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
+    if (query_shift == 0)
+        return sx_cem_rollout_elites(model, env, E, P, H, x0, q0, elite_rows, k, noise, actions, traj, sigma, obj_cost,
+                                     con_cost, status, mean_out, std_out, stream);
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    rp.elite_rows = elite_rows;
+    rp.elite_k = k;
+    rp.mean_out = mean_out;
+    rp.std_out = std_out;
+#define CALL(NS, NU, SH) sx::launch_rollout_junk<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
+    SX_JUNK_DISPATCH(model->n_s, env->n_u, query_shift, CALL);
 #undef CALL
 }
 

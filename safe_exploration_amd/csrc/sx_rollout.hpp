@@ -57,12 +57,16 @@ struct RolloutPtrs {
 // BYOUT = true: for training sets whose n_s Kstar buffers do not fit in LDS together, one output at a time
 // (Kstar_d | MFMA_d for d = 0 .. n_s - 1: 2 n_s barriers per step, per-output stage streams), still ONE launch for the
 // whole rollout and no Kstar in HBM.
-template <int NS, int NU, bool BYOUT = false>
-__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS, NS + NU> gc,
+// SH > 0 (sx_cem_rollout_junk): the GP's inputs are D = NS + NU + SH columns -- training rows [x, u, 0_SH], queries
+// [p, 0_SH, u] -- while the reachability and the costs see (NS, NU) and the Jacobian's leading NS + NU columns (the
+// exact-GP form of JunkDimensionsSSM).  SH = 0 is the plain rollout.
+template <int NS, int NU, bool BYOUT = false, int SH = 0>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS, NS + NU + SH> gc,
                                                                       const int4* __restrict__ stage_tab,
                                                                       ReachConst<NS, NU> rc,
                                                                       CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp) {
-    constexpr int D = NS + NU;
+    constexpr int D = NS + NU + SH;
+    constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     GpTileLds<NS, D> lds;
@@ -161,7 +165,9 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
 #pragma unroll
         for (int i = 0; i < NS; ++i) lds.zs[tid * D + i] = p[i];
 #pragma unroll
-        for (int cidx = 0; cidx < NU; ++cidx) lds.zs[tid * D + NS + cidx] = acts[(tid * H + 0) * NU + cidx];
+        for (int j = NS; j < UC; ++j) lds.zs[tid * D + j] = 0.0;
+#pragma unroll
+        for (int cidx = 0; cidx < NU; ++cidx) lds.zs[tid * D + UC + cidx] = acts[(tid * H + 0) * NU + cidx];
     }
     __syncthreads();
 
@@ -182,7 +188,7 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
 #pragma unroll
             for (int j = 0; j < NS; ++j) s = fma(rc.a[i * NS + j], z_prev[j], s);
 #pragma unroll
-            for (int cidx = 0; cidx < NU; ++cidx) s = fma(rc.b[i * NU + cidx], z_prev[NS + cidx], s);
+            for (int cidx = 0; cidx < NU; ++cidx) s = fma(rc.b[i * NU + cidx], z_prev[UC + cidx], s);
             out[i] = s;
         }
     };
@@ -191,14 +197,26 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
 #pragma unroll
         for (int j = 0; j < NS; ++j) z[j] = p[j];
 #pragma unroll
+        for (int j = NS; j < UC; ++j) z[j] = 0.0;
+#pragma unroll
         for (int cidx = 0; cidx < NU; ++cidx) {
             u[cidx] = acts[(tid * H + t) * NU + cidx];
-            z[NS + cidx] = u[cidx];
+            z[UC + cidx] = u[cidx];
         }
         int st_step = 0;
         if (have_q) {
             gp_collect<NS, D, true>(gc, lds, nw, tid, z, mean, var, jac);
-            reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st_step);
+            if constexpr (SH == 0) {
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st_step);
+            } else {
+                // [A | B]: the derivatives by the TRAINING rows' state and action columns (the reference's padding)
+                double jab[NS][NS + NU];
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+#pragma unroll
+                    for (int j = 0; j < NS + NU; ++j) jab[i][j] = jac[i][j];
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jab, p1, Q1, st_step);
+            }
         } else {
             gp_collect<NS, D, false>(gc, lds, nw, tid, z, mean, var, jac);
             reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st_step);
@@ -210,14 +228,16 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
 #pragma unroll
             for (int j = 0; j < NS; ++j) zt[j] = p[j];
 #pragma unroll
-            for (int cidx = 0; cidx < NU; ++cidx) zt[NS + cidx] = u[cidx];
+            for (int cidx = 0; cidx < NU; ++cidx) zt[UC + cidx] = u[cidx];
             next_centre(tid, zt, p1);
             if (t + 1 < H) {
                 double* zn = zs_base + ((t + 1) & 1) * 16 * D + tid * D;
 #pragma unroll
                 for (int i = 0; i < NS; ++i) zn[i] = p1[i];
 #pragma unroll
-                for (int cidx = 0; cidx < NU; ++cidx) zn[NS + cidx] = acts[(tid * H + t + 1) * NU + cidx];
+                for (int j = NS; j < UC; ++j) zn[j] = 0.0;
+#pragma unroll
+                for (int cidx = 0; cidx < NU; ++cidx) zn[UC + cidx] = acts[(tid * H + t + 1) * NU + cidx];
             }
         }
         if (valid) st |= st_step;
@@ -288,7 +308,9 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
 #pragma unroll
                 for (int i = 0; i < NS; ++i) zq[i] = pc[i];
 #pragma unroll
-                for (int cidx = 0; cidx < NU; ++cidx) zq[NS + cidx] = acts[(c * H + t) * NU + cidx];
+                for (int j = NS; j < UC; ++j) zq[j] = 0.0;
+#pragma unroll
+                for (int cidx = 0; cidx < NU; ++cidx) zq[UC + cidx] = acts[(c * H + t) * NU + cidx];
             }
         }
         if constexpr (BYOUT) {

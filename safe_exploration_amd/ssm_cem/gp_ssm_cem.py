@@ -41,14 +41,18 @@ class GpCemSSM(CemSSM):
             return super().__new__(FeatureGpCemSSM)
         return super().__new__(cls)
 
-    def __init__(self, conf, state_dimen: int, action_dimen: int, model=None):
+    def __init__(self, conf, state_dimen: int, action_dimen: int, model=None, *, wide_inputs: bool = False):
+        """wide_inputs: the GP of JunkDimensionsSSM's fused rollout (sx_cem_rollout_junk), whose "action" inputs are the
+        real actions plus the junk columns that queries fill: up to SX_MAX_D inputs in all, any split.  Such a model is fit
+        and packed for the rollout kernel only; sx_gp_predict is not instantiated beyond SX_MAX_NU actions."""
         super().__init__(state_dimen, action_dimen)
         if model is not None:
             raise NotImplementedError('injecting a gpytorch model is not supported: the GP is evaluated by libsxamd')
         kernel = getattr(conf, 'exact_gp_kernel', 'rbf')
         if kernel != 'rbf':
             raise ValueError(f'Unknown kernel {kernel}')
-        if state_dimen > _lib.SX_MAX_NS or action_dimen > _lib.SX_MAX_NU:
+        too_wide = (state_dimen + action_dimen > _lib.SX_MAX_D) if wide_inputs else (action_dimen > _lib.SX_MAX_NU)
+        if state_dimen > _lib.SX_MAX_NS or too_wide:
             raise ValueError(f'state/action dimension ({state_dimen}, {action_dimen}) beyond the compiled limits')
         self._device = torch.device(get_device(conf))
         self._training_iterations = int(getattr(conf, 'exact_gp_training_iterations', 0))

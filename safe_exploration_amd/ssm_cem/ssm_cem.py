@@ -11,6 +11,11 @@ from torch import Tensor
 
 from ..utils import assert_shape
 
+# (n_s, n_u, query shift) that sx_cem_rollout_junk rolls out in one launch per iteration: shift 0 is sx_cem_rollout's
+# shapes, shift > 0 the instantiations of csrc/sx_junk_ns*.hip (n_s + n_u + shift <= SX_MAX_D)
+JUNK_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1, 0), (1, 1, 0),
+                               (2, 1, 1), (4, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1), (1, 1, 1)})
+
 
 class CemSSM(ABC):
     def __init__(self, state_dimen: int, action_dimen: int):
@@ -92,14 +97,17 @@ class JunkDimensionsSSM(CemSSM):
     directly while the padded sizes stay within its limits (n_s <= 4, n_u <= 2), and beyond them in a FOLDED form that gives
     the padded model's numbers (`_construct_folded`).
 
-    The CEM solver (CemSafeMPC / FusedCemMpc) takes the wrapper too, through its STEP-BY-STEP rollout (`kernel_family =
-    'stepwise'`: H x (predict through this wrapper + sx_onestep_reach) per CEM iteration, the way the reference's optimiser
-    drives its dynamics callback), not through the fused kernel: the wrapper's placement of the junk is not a GP over the
-    real dimensions -- training rows are [z, junk] but queries [states, junk, actions, junk], so with junk states the
+    The CEM solver (CemSafeMPC / FusedCemMpc) takes the wrapper too.  The wrapper's placement of the junk is not a GP over
+    the real dimensions -- training rows are [z, junk] but queries [states, junk, actions, junk], so with junk states the
     action meets training columns that only ever held zeros, and the "action" columns of the returned Jacobian are
-    derivatives with respect to junk STATE inputs -- and the step-by-step path reproduces exactly that, whatever it means.
+    derivatives with respect to junk STATE inputs -- but over an exact RBF GP it is an exact GP over the columns that are
+    ever non-zero, [0, n_s + n_u) and [n_s + J_s, n_s + J_s + n_u): training rows [x, u, 0_s], queries [x, 0_s, u],
+    s = `query_shift` = min(J_s, n_u), real outputs only.  That model (`real_output_view`) is what the fused rollout
+    sx_cem_rollout_junk takes (`kernel_family = 'rbf_junk'`, one launch per CEM iteration).  Every other inner model, and
+    shapes the kernel is not instantiated for (n_s + n_u + s > 6), are rolled out STEP BY STEP (`kernel_family =
+    'stepwise'`: H x (predict through this wrapper + sx_onestep_reach) per CEM iteration, the way the reference's optimiser
+    drives its dynamics callback).  Both reproduce the reference's numbers, the Jacobian's "action" block included.
     """
-    kernel_family = 'stepwise'
 
     def __init__(self, constructor: Callable[..., CemSSM], state_dimen: int, action_dimen: int, junk_states: int,
                  junk_actions: int):
@@ -107,6 +115,9 @@ class JunkDimensionsSSM(CemSSM):
         self._junk_states = junk_states
         self._junk_actions = junk_actions
         self._cols: Optional[Tensor] = None      # folded form: the padded input columns the inner model keeps
+        self._constructor = constructor
+        self._view: Optional[CemSSM] = None      # real-output model of the fused rollout (built on first use)
+        self._view_of = None                     # ... and the inner device model it was built from
         try:
             self._ssm = constructor(state_dimen=state_dimen + junk_states, action_dimen=action_dimen + junk_actions)
         except ValueError as too_large:
@@ -131,6 +142,48 @@ class JunkDimensionsSSM(CemSSM):
             raise too_large     # (only the RBF exact GP is known to fold exactly)
         self._cols = torch.tensor(keep, dtype=torch.long)
         return inner
+
+    @property
+    def query_shift(self) -> int:
+        """s = min(J_s, n_u): the junk columns between the states and the actions of a query in the real-output model."""
+        return min(self._junk_states, self.num_actions)
+
+    def _kept_columns(self) -> Tuple[int, ...]:
+        n_s, n_u, js = self.num_states, self.num_actions, self._junk_states
+        return tuple(sorted(set(range(n_s + n_u)) | set(range(n_s + js, n_s + js + n_u))))
+
+    @property
+    def kernel_family(self) -> str:
+        """'rbf_junk' (fused rollout, sx_cem_rollout_junk) over an RBF exact GP where the kernel is instantiated for
+        (n_s, n_u, query_shift); 'stepwise' otherwise."""
+        if getattr(self._ssm, 'kernel_family', None) != 'rbf':
+            return 'stepwise'
+        if (self.num_states, self.num_actions, self.query_shift) not in JUNK_FUSED_SHAPES:
+            return 'stepwise'
+        return 'rbf_junk'
+
+    def real_output_view(self) -> CemSSM:
+        """The exact GP over the kept columns with the n_s real outputs (n_s states, n_u + query_shift "actions"): the
+        model sx_cem_rollout_junk takes.  Folded wrappers: the inner model itself.  Otherwise a GpCemSSM built through the
+        wrapper's constructor on first use, with the inner model's hyper-parameters of the first n_s outputs at the kept
+        columns (K over the kept columns is K over the padded ones entry for entry), rebuilt whenever the inner model's
+        device model changes (new training data or hyper-parameters)."""
+        if self._cols is not None:
+            return self._ssm
+        inner_model = self._ssm.device_model
+        if self._view is None or self._view_of is not inner_model:
+            n_s, cols = self.num_states, list(self._kept_columns())
+            view = self._constructor(state_dimen=n_s, action_dimen=len(cols) - n_s, wide_inputs=True)
+            state = self._ssm.state_dict()
+            view.load_state_dict({'gp_model': {'raw_lengthscale': state['gp_model']['raw_lengthscale'][:n_s][:, cols],
+                                               'raw_outputscale': state['gp_model']['raw_outputscale'][:n_s]},
+                                  'gp_likelihood': {'raw_noise': state['gp_likelihood']['raw_noise'][:n_s],
+                                                    'noise_floor': state['gp_likelihood']['noise_floor']}})
+            x = self._x_train
+            view.update_model(torch.cat((x, x.new_zeros((x.size(0), self.query_shift))), dim=1), self._y_train,
+                              opt_hyp=False, replace_old=True)
+            self._view, self._view_of = view, inner_model
+        return self._view
 
     @property
     def folded_columns(self) -> Optional[Tuple[int, ...]]:
