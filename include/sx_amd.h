@@ -321,7 +321,9 @@ int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, i
  *   SX_FORM_STREAM  cem_rollout_kernel: the factors streamed from L2, Kstar of all outputs in LDS
  *   SX_FORM_BYOUT   cem_rollout_kernel, one output's Kstar in LDS at a time
  *   SX_FORM_BIG     the three-launch-per-step path (Kstar in HBM)
- * or < 0 for bad arguments.  Reporting only (bench.py names the kernel it timed); the choice itself is the library's.
+ * or < 0 for bad arguments and wherever sx_cem_rollout would answer SX_ERR_UNSUPPORTED ((n_s, n_u) without a rollout
+ * kernel; SX_ROLLOUT_STRICT with a forced form that does not apply).  Reporting only (bench.py names the kernel it timed);
+ * the choice itself is the library's, and the same one sx_cem_rollout makes.
  * No counterpart in the reference. */
 #define SX_FORM_STREAM 0
 #define SX_FORM_RW 1

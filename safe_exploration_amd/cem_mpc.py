@@ -35,7 +35,7 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
                 mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
                 q0: Optional[Tensor] = None, want_traj: bool = False, want_sigma: bool = False,
                 status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False):
-    """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites.
+    """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites (and their _junk, _feat and _mlp counterparts).
 
     x0 [E x n_s]; either `actions` [E x P x H x n_u] (given), or (`mean`, `std` [E x H x n_u], `noise` [E x P x H x n_u]),
     or (`elite_rows` [E x k x (2 + H n_u)], `noise`): the distribution is then refit from the previous iteration's elite
@@ -60,62 +60,26 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
     lib = _lib.lib()
-    if getattr(ssm, 'kernel_family', 'rbf') == 'feature':
-        # degenerate kernels ('linear', 'nn'): the weight-space rollout, one particle per lane (csrc/sx_feat.hpp)
-        _lib.check(lib.sx_cem_rollout_feat(ctypes.byref(ssm.feat_model), ctypes.byref(env), E, P, horizon,
-                                           _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std),
-                                           _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj),
-                                           _lib.ptr(con), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_cem_rollout_feat')
-        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
-    if getattr(ssm, 'kernel_family', 'rbf') == 'mlp':
-        # MC-dropout ensembles over the frozen members: matrix cores for 1-2 hidden layers of <= 64 units
+    family = getattr(ssm, 'kernel_family', 'rbf')
+    if family in ('feature', 'mlp'):
+        # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
+        # 'mlp': MC-dropout ensembles over the frozen members, matrix cores for 1-2 hidden layers of <= 64 units
         # (csrc/sx_mlp_mfma.hpp), one particle per lane otherwise (csrc/sx_mlp.hpp)
-        _lib.check(lib.sx_cem_rollout_mlp(ctypes.byref(ssm.mlp_model), ctypes.byref(env), E, P, horizon,
-                                          _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std),
-                                          _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj),
-                                          _lib.ptr(con), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_cem_rollout_mlp')
+        entry, model = ('sx_cem_rollout_feat', ssm.feat_model) if family == 'feature' else ('sx_cem_rollout_mlp', ssm.mlp_model)
+        _lib.check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
+                                       _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
+                                       _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                       _lib.stream_ptr(dev)), entry)
         return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
-    if getattr(ssm, 'kernel_family', 'rbf') == 'rbf_junk':
-        return _cem_rollout_junk(ssm, env, x0, horizon, E, P, actions, traj, sigma, obj, con, status, q0=q0, mean=mean,
-                                 std=std, noise=noise, elite_rows=elite_rows, want_dist=want_dist)
-    model = ssm.device_model
-    if elite_rows is not None:
-        k = elite_rows.size(1)
-        if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
-            raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
-        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
-        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
-        _lib.check(lib.sx_cem_rollout_elites(ctypes.byref(model), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
-                                             _lib.ptr(q0), _lib.ptr(elite_rows), k, _lib.ptr(noise), _lib.ptr(actions),
-                                             _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                             _lib.ptr(m_out), _lib.ptr(s_out), _lib.stream_ptr(dev)), 'sx_cem_rollout_elites')
-        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
-    ws_bytes = int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(model), E, P, horizon))
-    if ws_bytes < 0:
-        raise _lib.SxError('sx_cem_rollout_workspace_bytes: bad arguments')
-    workspace = ssm.workspace(ws_bytes)   # None on the fused path; cached on the model otherwise
-    _lib.check(lib.sx_cem_rollout(ctypes.byref(model), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
-                                  _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
-                                  _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                  _lib.ptr(workspace), ws_bytes, _lib.stream_ptr(dev)), 'sx_cem_rollout')
-    return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
-
-
-class FusedJunkUnsupported(_lib.SxError):
-    """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
-
-
-def _cem_rollout_junk(ssm, env, x0, horizon, E, P, actions, traj, sigma, obj, con, status, *, q0, mean, std, noise,
-                      elite_rows, want_dist):
-    """cem_rollout for JunkDimensionsSSM over an exact RBF GP: the real-output GP over the kept columns
-    (`real_output_view`) with the query shift, through sx_cem_rollout_junk / sx_cem_rollout_elites_junk.  Raises
-    FusedJunkUnsupported where the library has no single-launch form for it."""
-    lib = _lib.lib()
-    view = ssm.real_output_view()
-    model, shift, n_u = view.device_model, ssm.query_shift, ssm.num_actions
+    # exact RBF GP ('rbf') through sx_cem_rollout[_elites]; JunkDimensionsSSM over one ('rbf_junk') through the _junk entries:
+    # the real-output GP over the kept columns (`real_output_view`) with the query shift.  That GP also owns the workspace.
+    junk = family == 'rbf_junk'
+    owner = ssm.real_output_view() if junk else ssm
+    model, shift = owner.device_model, ssm.query_shift if junk else 0
+    suffix, shift_arg = ('_junk', (shift,)) if junk else ('', ())
 
     def check(code, what):
-        if code == _lib.SX_ERR_UNSUPPORTED:
+        if junk and code == _lib.SX_ERR_UNSUPPORTED:
             raise FusedJunkUnsupported(f'{what}: no single-launch form for this model')
         _lib.check(code, what)
 
@@ -123,24 +87,29 @@ def _cem_rollout_junk(ssm, env, x0, horizon, E, P, actions, traj, sigma, obj, co
         k = elite_rows.size(1)
         if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
             raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
-        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=x0.device) if want_dist else None
-        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=x0.device) if want_dist else None
-        check(lib.sx_cem_rollout_elites_junk(ctypes.byref(model), ctypes.byref(env), shift, E, P, horizon,
-                                             _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(elite_rows), k, _lib.ptr(noise),
-                                             _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con),
-                                             _lib.ptr(status), _lib.ptr(m_out), _lib.ptr(s_out), _lib.stream_ptr(x0.device)),
-              'sx_cem_rollout_elites_junk')
+        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
+        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
+        entry = 'sx_cem_rollout_elites' + suffix
+        check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), *shift_arg, E, P, horizon, _lib.ptr(x0.contiguous()),
+                                  _lib.ptr(q0), _lib.ptr(elite_rows), k, _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj),
+                                  _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(m_out),
+                                  _lib.ptr(s_out), _lib.stream_ptr(dev)), entry)
         return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
-    # (query shift 0 is sx_cem_rollout itself, the workspace path included; a shift > 0 never takes a workspace)
+    # (a query shift > 0 never takes a workspace)
     ws_bytes = int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(model), E, P, horizon)) if shift == 0 else 0
     if ws_bytes < 0:
         raise _lib.SxError('sx_cem_rollout_workspace_bytes: bad arguments')
-    workspace = view.workspace(ws_bytes)
-    check(lib.sx_cem_rollout_junk(ctypes.byref(model), ctypes.byref(env), shift, E, P, horizon, _lib.ptr(x0.contiguous()),
-                                  _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
-                                  _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                  _lib.ptr(workspace), ws_bytes, _lib.stream_ptr(x0.device)), 'sx_cem_rollout_junk')
+    workspace = owner.workspace(ws_bytes)   # None on the fused path; cached on the model otherwise
+    entry = 'sx_cem_rollout' + suffix
+    check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), *shift_arg, E, P, horizon, _lib.ptr(x0.contiguous()),
+                              _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj),
+                              _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(workspace), ws_bytes,
+                              _lib.stream_ptr(dev)), entry)
     return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+
+
+class FusedJunkUnsupported(_lib.SxError):
+    """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:

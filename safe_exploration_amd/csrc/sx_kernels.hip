@@ -20,7 +20,7 @@
 #include "sx_rollout.hpp"
 #include "sx_launch.hpp"
 #include "sx_rw_launch.hpp"
-#include "sx_junk_launch.hpp"
+#include "sx_stream_launch.hpp"
 #include "sx_rank.hpp"
 #include "sx_rank_count.hpp"
 #include "sx_feat.hpp"
@@ -567,16 +567,6 @@ static int launch_predict_big(const sx_gp_model* m, const double* z, int P, doub
     return check_launch();
 }
 
-// does the single-launch kernel's LDS budget hold Kstar for this model -- of all outputs at once (ns_lds = ns), or of one
-// output at a time (ns_lds = 1)?  (sh: the query shift of sx_cem_rollout_junk -- the GP is ns + nu + sh wide, the actions nu)
-static bool fused_fits(int ns, int nu, int n_train, int n_pad, int H, int ns_lds = -1, int sh = 0) {
-    const int nw = kRolloutThreads / 64;
-    const size_t lds =
-        (gp_tile_lds_doubles(ns, ns + nu + sh, n_train, n_pad, nw, ns_lds) + (size_t)SX_TILE * H * nu) * sizeof(double);
-    return lds <= kMaxLdsBytes && n_pad <= 1024;
-}
-
-
 template <int NS, int NU>
 static int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, double* workspace,
                               int64_t workspace_bytes, hipStream_t stream) {
@@ -606,80 +596,119 @@ static int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const Rol
     return check_launch();
 }
 
-template <int NS, int NU>
-static int launch_rollout(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, double* workspace,
-                          int64_t workspace_bytes, hipStream_t stream) {
-    const bool all_at_once = fused_fits(NS, NU, m->n_train, m->n_pad, rp.H);
-    if (!all_at_once && !(NS > 1 && fused_fits(NS, NU, m->n_train, m->n_pad, rp.H, 1))) {
-        if (rp.elite_rows) return SX_ERR_UNSUPPORTED;   // the refit prologue belongs to the single-launch kernel
-        return launch_rollout_big<NS, NU>(m, env, rp, workspace, workspace_bytes, stream);
-    }
-    // (the refit prologue keeps 2 H n_u doubles in the Kstar / mean-row buffers: at least 256 + 256 NS of them)
-    if (rp.elite_rows && 2 * rp.H * NU > 256 + 256 * NS) return SX_ERR_UNSUPPORTED;
-    const int nw = kRolloutThreads / 64;
-    auto gc = make_gp_const<NS, NU>(m, nw);
-    ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
-    CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
-    const size_t lds = (gp_tile_lds_doubles(NS, NS + NU, m->n_train, m->n_pad, nw, all_at_once ? NS : 1) +
-                        (size_t)SX_TILE * rp.H * NU) * sizeof(double);
-    const int tiles = (rp.P + SX_TILE - 1) / SX_TILE;
-    if (all_at_once) {
-        // Three forms of the kernel: W partly resident on 8 waves (sx_rollout_rh.hpp: n_s <= 2), all of
-        // W in the registers of 4 waves (sx_rollout_rw.hpp: every n_s, smaller N), W streamed from L2 (cem_rollout_kernel: any
-        // size that fits the LDS).  By default the first of the three that is instantiated for the shape: the 4-wave form
-        // loses to the streaming kernel only where the 8-wave form exists (n_s = 2, n_u = 1: 126.6 against 125.7 us at config
-        // 2), and beats it by 7 - 16 % on the shapes the 8-wave form does not cover (n_s = 3, 4; n_s = n_u = 2 beyond N = 128).
-        // SX_ROLLOUT=rh|rw|stream picks ONE form for A/B runs (falling back to the streaming kernel where it is not
-        // instantiated, unless SX_ROLLOUT_STRICT is set, so that a run knows what it timed).
-        static const int form = [] {
-            const char* e = std::getenv("SX_ROLLOUT");
-            if (e && std::strcmp(e, "stream") == 0) return 0;
-            if (e && std::strcmp(e, "rw") == 0) return 1;
-            if (e && std::strcmp(e, "rh") == 0) return 2;
-            return 3;
-        }();
-        if (form != 0) {
-            static const bool strict = std::getenv("SX_ROLLOUT_STRICT") != nullptr;
-            RolloutPtrs rps = rp;
-#ifdef SX_STAMPS
-            rps.stamps = g_stamp_host;
-#endif
-            int r = SX_ERR_UNSUPPORTED;
-            if (form >= 2) r = launch_rollout_rh<NS, NU>(make_gp_const<NS, NU>(m, 8), rc, cc, rps, stream);
-            if (r == SX_ERR_UNSUPPORTED && form != 2)
-                r = launch_rollout_rw<NS, NU>(make_gp_const<NS, NU>(m, kRwWaves), rc, cc, rps, stream);
-            if (r != SX_ERR_UNSUPPORTED || (strict && form != 3)) return r;
-        }
-        if (int r = allow_lds(cem_rollout_kernel<NS, NU, false>, lds)) return r;
-        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_kernel<NS, NU, false>, dim3(rp.E * tiles), dim3(kRolloutThreads), lds, stream,
-               gc, gc.stage_tab, rc, cc, rp);
-    } else {
-        if (int r = allow_lds(cem_rollout_kernel<NS, NU, true>, lds)) return r;
-        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_kernel<NS, NU, true>, dim3(rp.E * tiles), dim3(kRolloutThreads), lds, stream,
-               gc, gc.stage_tab, rc, cc, rp);
-    }
-    return check_launch();
+// The rollout form of a model, decided here only: sx_cem_rollout[_elites][_junk] launch it,
+// sx_cem_rollout_form reports it, sx_cem_rollout_workspace_bytes sizes the workspace path by it.  No HIP call.
+struct RolloutPlan {
+    int form;     // SX_FORM_*
+    bool ok;      // false: sx_cem_rollout answers SX_ERR_UNSUPPORTED
+    size_t lds;   // dynamic LDS bytes of the form's kernel (not SX_FORM_BIG)
+    int nrb;      // SX_FORM_RH / SX_FORM_RW: n_pad / 16, the kernel's instantiation
+};
+
+// SX_ROLLOUT=rh|rw|stream forces one form of the single-launch kernel (A/B runs); where it does not apply the rollout
+// takes the streaming kernel, or answers SX_ERR_UNSUPPORTED with SX_ROLLOUT_STRICT set (so that a run knows what it timed).
+struct FormOverride {
+    int form;   // SX_FORM_RH / SX_FORM_RW / SX_FORM_STREAM, or -1: none
+    bool strict;
+    bool refuses() const { return strict && form >= 0; }
+};
+static const FormOverride& form_override() {
+    static const FormOverride o = [] {
+        const char* e = std::getenv("SX_ROLLOUT");
+        const int form = !e                            ? -1
+                         : std::strcmp(e, "stream") == 0 ? SX_FORM_STREAM
+                         : std::strcmp(e, "rw") == 0     ? SX_FORM_RW
+                         : std::strcmp(e, "rh") == 0     ? SX_FORM_RH
+                                                         : -1;
+        return FormOverride{form, std::getenv("SX_ROLLOUT_STRICT") != nullptr};
+    }();
+    return o;
 }
 
-// sx_cem_rollout_junk with a query shift SH > 0: the GP model is (NS, NU + SH), the environment (NS, NU).  The streaming
-// kernel only (all outputs' Kstar in LDS, or one output at a time); a training set that needs the workspace path is
-// SX_ERR_UNSUPPORTED (the caller rolls out step by step).
+static bool rollout_compiled(int ns, int nu, int sh) {
+#define SX_COMPILED(NS, NU, SH, unused) if (ns == NS && nu == NU && sh == SH) return true;
+    SX_ROLLOUT_SHAPES(SX_COMPILED, 0)
+#undef SX_COMPILED
+    return false;
+}
+
+template <int NS, int NU>
+static int resident_lds_bytes(int n_train, int n_pad, int H, size_t* rh, size_t* rw) {
+    *rh = rollout_rh_lds_bytes<NS, NU>(n_train, n_pad, H);
+    *rw = rollout_rw_lds_bytes<NS, NU>(n_train, n_pad, H);
+    return SX_OK;
+}
+// LDS bytes of the 8-wave and the 4-wave form for a plain rollout of a compiled shape (~0: that form has no instantiation)
+static int resident_lds_bytes(int ns, int nu, int n_train, int n_pad, int H, size_t* rh, size_t* rw) {
+#define CALL(NS, NU) resident_lds_bytes<NS, NU>(n_train, n_pad, H, rh, rw)
+    SX_DISPATCH(ns, nu, CALL);
+#undef CALL
+}
+
+// `m` is the GP over ns + nu + sh columns (m->n_u = nu + sh), sh the query shift of sx_cem_rollout_junk.
+static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites) {
+    const int ns = m->n_s, nu = m->n_u - sh, n_train = m->n_train, n_pad = m->n_pad;
+    auto stream_lds = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, sh, n_train, n_pad, H, byout); };
+    const bool all_at_once = n_pad <= 1024 && stream_lds(false) <= kMaxLdsBytes;
+    const bool by_output = !all_at_once && ns > 1 && n_pad <= 1024 && stream_lds(true) <= kMaxLdsBytes;
+    bool ok = rollout_compiled(ns, nu, sh);
+    // Kstar in HBM: plain rollouts only, without elite rows (the refit prologue belongs to the single-launch kernel)
+    if (!all_at_once && !by_output) return {SX_FORM_BIG, ok && sh == 0 && !elites, 0, 0};
+    // (the refit prologue keeps 2 H n_u doubles in the Kstar / mean-row buffers: at least 256 + 256 n_s of them)
+    if (elites && 2 * H * nu > 256 + 256 * ns) ok = false;
+    if (by_output) return {SX_FORM_BYOUT, ok, stream_lds(true), 0};
+    const RolloutPlan stream{SX_FORM_STREAM, ok, stream_lds(false), 0};
+    const FormOverride& o = form_override();
+    if (!ok || sh > 0 || o.form == SX_FORM_STREAM) return stream;
+    // W partly resident on 8 waves (n_s <= 2), then all of W in the registers of 4 waves (smaller N), then W streamed from
+    // L2: the 4-wave form loses to the streaming kernel only where the 8-wave form exists (n_s = 2, n_u = 1: 126.6
+    // against 125.7 us at config 2), and beats it by 7 - 16 % on the shapes the 8-wave form does not cover (n_s = 3, 4;
+    // n_s = n_u = 2 beyond N = 128).
+    size_t rh, rw;
+    resident_lds_bytes(ns, nu, n_train, n_pad, H, &rh, &rw);
+    if (o.form != SX_FORM_RW && rh <= kMaxLdsBytes) return {SX_FORM_RH, true, rh, n_pad >> 4};
+    if (o.form != SX_FORM_RH && rw <= kMaxLdsBytes) return {SX_FORM_RW, true, rw, n_pad >> 4};
+    return {SX_FORM_STREAM, !o.refuses(), stream.lds, 0};
+}
+
+// The rollout of a GP over NS + NU + SH columns (SH: the query shift of sx_cem_rollout_junk) in the form plan_rollout picks.
 template <int NS, int NU, int SH>
-static int launch_rollout_junk(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, hipStream_t stream) {
-    const bool all_at_once = fused_fits(NS, NU, m->n_train, m->n_pad, rp.H, -1, SH);
-    if (!all_at_once && !(NS > 1 && fused_fits(NS, NU, m->n_train, m->n_pad, rp.H, 1, SH))) return SX_ERR_UNSUPPORTED;
-    if (rp.elite_rows && 2 * rp.H * NU > 256 + 256 * NS) return SX_ERR_UNSUPPORTED;
-    const int nw = kRolloutThreads / 64;
-    auto gc = make_gp_const<NS, NU + SH>(m, nw);
+static int launch_rollout(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, double* workspace,
+                          int64_t workspace_bytes, hipStream_t stream) {
+    RolloutPlan plan = plan_rollout(m, SH, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    if constexpr (SH == 0) {
+        if (plan.form == SX_FORM_BIG) return launch_rollout_big<NS, NU>(m, env, rp, workspace, workspace_bytes, stream);
+    }
     ReachConst<NS, NU> rc;
     if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
     make_cost_const<NS, NU>(env, cc);
-    const size_t lds = (gp_tile_lds_doubles(NS, NS + NU + SH, m->n_train, m->n_pad, nw, all_at_once ? NS : 1) +
-                        (size_t)SX_TILE * rp.H * NU) * sizeof(double);
-    return launch_rollout_shifted<NS, NU, SH>(gc, rc, cc, rp, all_at_once, lds, stream);
+    RolloutPtrs rps = rp;
+#ifdef SX_STAMPS
+    rps.stamps = g_stamp_host;
+#endif
+    if constexpr (SH == 0) {
+        if (plan.form == SX_FORM_RH || plan.form == SX_FORM_RW) {
+            const int r = plan.form == SX_FORM_RH
+                              ? launch_rollout_rh<NS, NU>(make_gp_const<NS, NU>(m, 8), rc, cc, rps, plan.nrb, plan.lds, stream)
+                              : launch_rollout_rw<NS, NU>(make_gp_const<NS, NU>(m, kRwWaves), rc, cc, rps, plan.nrb, plan.lds,
+                                                          stream);
+            if (r != SX_ERR_UNSUPPORTED || form_override().refuses()) return r;
+            plan = {SX_FORM_STREAM, true, rollout_stream_lds_bytes(NS, NU, SH, m->n_train, m->n_pad, rp.H, false), 0};
+        }
+    }
+    return launch_rollout_stream<NS, NU, SH>(make_gp_const<NS, NU + SH>(m, kRolloutThreads / 64), rc, cc, rps,
+                                             plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
+// sx_cem_rollout[_elites][_junk] after their argument checks
+static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+#define CALL(NS, NU, SH) launch_rollout<NS, NU, SH>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
+    SX_ROLLOUT_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
+#undef CALL
 }
 
 }  // namespace sx
@@ -787,17 +816,6 @@ static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const Fe
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
-#define SX_DISPATCH(ns, nu, CALL)                              \
-    do {                                                       \
-        if ((ns) == 2 && (nu) == 1) return CALL(2, 1);         \
-        if ((ns) == 4 && (nu) == 1) return CALL(4, 1);         \
-        if ((ns) == 2 && (nu) == 2) return CALL(2, 2);         \
-        if ((ns) == 4 && (nu) == 2) return CALL(4, 2);         \
-        if ((ns) == 3 && (nu) == 1) return CALL(3, 1);         \
-        if ((ns) == 1 && (nu) == 1) return CALL(1, 1);         \
-        return SX_ERR_UNSUPPORTED;                             \
-    } while (0)
-
 extern "C" {
 
 #ifdef SX_STAMPS
@@ -1119,77 +1137,36 @@ int sx_polytope_distance(const sx_env* env, int P, const double* p, const double
 
 int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, int H) {
     if (!model || E <= 0 || P <= 0 || H <= 0) return -1;
-    if (sx::fused_fits(model->n_s, model->n_u, model->n_train, model->n_pad, H)) return 0;
-    if (model->n_s > 1 && sx::fused_fits(model->n_s, model->n_u, model->n_train, model->n_pad, H, 1)) return 0;
+    if (sx::plan_rollout(model, 0, H, false).form != SX_FORM_BIG) return 0;
     return sx::big_ws_layout(nullptr, model->n_s, model->n_s + model->n_u, model->n_pad, (int64_t)E * P).total *
            (int64_t)sizeof(double);
 }
 
 int sx_cem_rollout_form(const sx_gp_model* model, int H) {
     if (!model || H <= 0) return -1;
-    const int ns = model->n_s, nu = model->n_u;
-    if (!sx::fused_fits(ns, nu, model->n_train, model->n_pad, H))
-        return (ns > 1 && sx::fused_fits(ns, nu, model->n_train, model->n_pad, H, 1)) ? SX_FORM_BYOUT : SX_FORM_BIG;
-    const char* e = std::getenv("SX_ROLLOUT");
-    if (e && std::strcmp(e, "stream") == 0) return SX_FORM_STREAM;
-    const bool only_rw = e && std::strcmp(e, "rw") == 0, only_rh = e && std::strcmp(e, "rh") == 0;
-#define CALL(NS, NU) \
-    ((!only_rw && sx::rollout_rh_applies<NS, NU>(model->n_train, model->n_pad, H)) ? SX_FORM_RH \
-     : ((!only_rh && sx::rollout_rw_applies<NS, NU>(model->n_train, model->n_pad, H)) ? SX_FORM_RW : SX_FORM_STREAM))
-    SX_DISPATCH(ns, nu, CALL);
-#undef CALL
+    const sx::RolloutPlan plan = sx::plan_rollout(model, 0, H, false);
+    return plan.ok ? plan.form : -1;
 }
 
 int sx_cem_rollout(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                    const double* mean, const double* std, const double* noise, double* actions, double* traj,
                    double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
                    int64_t workspace_bytes, void* stream) {
-    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
-    if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-#define CALL(NS, NU) \
-    sx::launch_rollout<NS, NU>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
-    SX_DISPATCH(model->n_s, model->n_u, CALL);
-#undef CALL
+    return sx_cem_rollout_junk(model, env, 0, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost,
+                               status, workspace, workspace_bytes, stream);
 }
 
 int sx_cem_rollout_elites(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                           const double* elite_rows, int k, const double* noise, double* actions, double* traj, double* sigma,
                           double* obj_cost, double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream) {
-    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
-    if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-    rp.elite_rows = elite_rows;
-    rp.elite_k = k;
-    rp.mean_out = mean_out;
-    rp.std_out = std_out;
-#define CALL(NS, NU) sx::launch_rollout<NS, NU>(model, env, rp, nullptr, 0, (hipStream_t)stream)
-    SX_DISPATCH(model->n_s, model->n_u, CALL);
-#undef CALL
+    return sx_cem_rollout_elites_junk(model, env, 0, E, P, H, x0, q0, elite_rows, k, noise, actions, traj, sigma, obj_cost,
+                                      con_cost, status, mean_out, std_out, stream);
 }
 
-// (model, env, query_shift) of the junk entries: checked before anything touches the device
-static bool junk_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
+// (model, env, query_shift) of the rollout entries: checked before anything touches the device
+static bool rollout_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
     return model->n_s == env->n_s && query_shift >= 0 && query_shift <= env->n_u && model->n_u == env->n_u + query_shift;
 }
-
-// the instantiated (n_s, n_u, shift > 0) of cem_rollout_kernel (sx_junk_ns*.hip); CALL(NS, NU, SH)
-#define SX_JUNK_DISPATCH(ns, nu, sh, CALL)                                    \
-    do {                                                                      \
-        if ((ns) == 2 && (nu) == 1 && (sh) == 1) return CALL(2, 1, 1);        \
-        if ((ns) == 4 && (nu) == 1 && (sh) == 1) return CALL(4, 1, 1);        \
-        if ((ns) == 3 && (nu) == 1 && (sh) == 1) return CALL(3, 1, 1);        \
-        if ((ns) == 2 && (nu) == 2 && (sh) == 1) return CALL(2, 2, 1);        \
-        if ((ns) == 2 && (nu) == 2 && (sh) == 2) return CALL(2, 2, 2);        \
-        if ((ns) == 3 && (nu) == 2 && (sh) == 1) return CALL(3, 2, 1);        \
-        if ((ns) == 1 && (nu) == 1 && (sh) == 1) return CALL(1, 1, 1);        \
-        return SX_ERR_UNSUPPORTED;                                            \
-    } while (0)
 
 int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H, const double* x0,
                         const double* q0, const double* mean, const double* std, const double* noise, double* actions,
@@ -1198,15 +1175,9 @@ int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_s
     if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
     if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
     if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (!junk_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
-    if (query_shift == 0)
-        return sx_cem_rollout(model, env, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status,
-                              workspace, workspace_bytes, stream);
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-#define CALL(NS, NU, SH) sx::launch_rollout_junk<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
-    SX_JUNK_DISPATCH(model->n_s, env->n_u, query_shift, CALL);
-#undef CALL
+    if (!rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::cem_rollout(model, env, query_shift, rp, workspace, workspace_bytes, stream);
 }
 
 int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
@@ -1215,19 +1186,13 @@ int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int 
                                int32_t* status, double* mean_out, double* std_out, void* stream) {
     if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
     if (E <= 0 || P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
-    if (!junk_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
-    if (query_shift == 0)
-        return sx_cem_rollout_elites(model, env, E, P, H, x0, q0, elite_rows, k, noise, actions, traj, sigma, obj_cost,
-                                     con_cost, status, mean_out, std_out, stream);
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    if (!rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
     rp.elite_rows = elite_rows;
     rp.elite_k = k;
     rp.mean_out = mean_out;
     rp.std_out = std_out;
-#define CALL(NS, NU, SH) sx::launch_rollout_junk<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
-    SX_JUNK_DISPATCH(model->n_s, env->n_u, query_shift, CALL);
-#undef CALL
+    return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
 }
 
 static bool feat_model_ok(const sx_feat_model* m) {

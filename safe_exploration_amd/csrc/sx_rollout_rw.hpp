@@ -34,9 +34,6 @@
 #include "sx_rw_launch.hpp"
 
 // build-time switches for A/B runs (defaults = the product)
-#ifndef SX_RW_PIPE
-#define SX_RW_PIPE 1       // software-pipelined Kstar phase (gp_kstar_phase_pipe)
-#endif
 #ifndef SX_RW_LDSCONST
 #define SX_RW_LDSCONST 1   // finish() reads its constants from LDS instead of (spilled) SGPRs
 #endif
@@ -51,20 +48,6 @@
 #endif
 #ifndef SX_RW_POLYFOLD
 #define SX_RW_POLYFOLD 0   // the cubic in w = r / u with the unit folded into its coefficients (one VALU instruction less per value)
-#endif
-#ifndef SX_RW_DIET
-#define SX_RW_DIET 1       // Kstar phase with the expanded exponent, the 2048-entry table and no all-padding pairs (rw_kstar_phase)
-#endif
-#if SX_RW_PIPE
-#define SX_RW_KSTAR gp_kstar_phase_pipe
-#else
-#define SX_RW_KSTAR gp_kstar_phase
-#endif
-
-#if SX_RW_DIET
-#define RW_KSTAR_CALL(qb, qe) rw_kstar_phase(gc, kl, lds.kfrag, qb, qe, zq)
-#else
-#define RW_KSTAR_CALL(qb, qe) SX_RW_KSTAR(gc, lds, qb, qe, zq)
 #endif
 
 namespace sx {
@@ -234,7 +217,7 @@ __device__ __forceinline__ void rw_mfma_phase(const GpConst<NS, D>& gc, GpTileLd
 // ---------------------------------------------------------------------------------------------------------------
 // The Kstar phase of the register-resident kernel.  A lone wave per SIMD issues an f64 VALU instruction every ~5.8
 // cycles however many independent chains it has (tools/valu_probe3.hip: 2.7 ns; two waves per SIMD: 2.4 ns) and the
-// pipelined loop of gp_kstar_phase_pipe already runs at that rate, so the phase only gets shorter with FEWER
+// software-pipelined form of gp_kstar_phase reaches that rate, so the phase only gets shorter with FEWER
 // instructions per kernel value (85 per 2 rows x 2 outputs there):
 //   * expanded exponent.  With the rows centred, x' = x - xbar, z' = z - xbar, and in table units (ln 2 / 2048):
 //         y_d(k) = L_d + sum_j kk_dj (z'_j - x'_kj)^2 = [L_d + sum_j kk_dj z'_j^2] + [sum_j kk_dj x'_kj^2] + sum_j (-2 kk_dj z'_j) x'_kj
@@ -522,15 +505,10 @@ void cem_rollout_rw_kernel(GpConst<NS, NS + NU> gc, ReachConst<NS, NU> rc, CostC
     // this wave's share of W: requested first, it travels while X, the exp table and the first tile's prologue are set up
     v2d wreg[MAXP];
     rw_load_w<NS, D, NRB>(gc, wave, lane, wreg);
-#if SX_RW_DIET
     RwKstarLds<NS, D> kl;
     kl.carve(pq + (((size_t)SX_TILE * PQS + 1) & ~(size_t)1), gc.n_pad);
     rw_kstar_setup(gc, kl, lds.kfrag);
     const int kstar_pairs = (gc.n_train + 7) >> 3;   // pairs of 8 rows with at least one training row
-#else
-    gp_load_xs(gc, lds);
-    const int kstar_pairs = gc.n_pad >> 3;
-#endif
 
     const bool owner = tid < SX_TILE;
     // Kstar shares (pairs of fragments).  Step 0: all waves alike.  From step 1 on wave 0 runs finish() meanwhile.
@@ -784,7 +762,7 @@ void cem_rollout_rw_kernel(GpConst<NS, NS + NU> gc, ReachConst<NS, NU> rc, CostC
                 if (t == 0) {
 #pragma unroll
                     for (int j = 0; j < D; ++j) zq[j] = zs_base[c * D + j];
-                    RW_KSTAR_CALL(q0_begin, q0_end);
+                    rw_kstar_phase(gc, kl, lds.kfrag, q0_begin, q0_end, zq);
                 } else {
                     double pc[NS];
                     next_centre(rc, c, zs_base + ((t - 1) & 1) * 16 * D + c * D, pc);
@@ -792,7 +770,7 @@ void cem_rollout_rw_kernel(GpConst<NS, NS + NU> gc, ReachConst<NS, NU> rc, CostC
                     for (int i = 0; i < NS; ++i) zq[i] = pc[i];
 #pragma unroll
                     for (int cidx = 0; cidx < NU; ++cidx) zq[NS + cidx] = acts[(c * H + t) * NU + cidx];
-                    RW_KSTAR_CALL(q_begin, q_end);
+                    rw_kstar_phase(gc, kl, lds.kfrag, q_begin, q_end, zq);
                 }
             } else {
                 if (owner) finish(t - 1);

@@ -2,16 +2,6 @@
 #include "sx_rw_impl.hpp"
 
 namespace sx {
-template int launch_rollout_rw<2, 1>(const GpConst<2, 3>&, const ReachConst<2, 1>&,
-                                      const CostConst<SX_MAX_M, 2, 1>&, const RolloutPtrs&, hipStream_t);
-template int launch_rollout_rh<2, 1>(const GpConst<2, 3>&, const ReachConst<2, 1>&,
-                                      const CostConst<SX_MAX_M, 2, 1>&, const RolloutPtrs&, hipStream_t);
-template int launch_rollout_rw<2, 2>(const GpConst<2, 4>&, const ReachConst<2, 2>&,
-                                      const CostConst<SX_MAX_M, 2, 2>&, const RolloutPtrs&, hipStream_t);
-template int launch_rollout_rh<2, 2>(const GpConst<2, 4>&, const ReachConst<2, 2>&,
-                                      const CostConst<SX_MAX_M, 2, 2>&, const RolloutPtrs&, hipStream_t);
-template bool rollout_rh_applies<2, 1>(int, int, int);
-template bool rollout_rw_applies<2, 1>(int, int, int);
-template bool rollout_rh_applies<2, 2>(int, int, int);
-template bool rollout_rw_applies<2, 2>(int, int, int);
+SX_RW_INSTANTIATE(2, 1)
+SX_RW_INSTANTIATE(2, 2)
 }  // namespace sx

@@ -1,0 +1,56 @@
+// The compiled shapes of the fused rollout, and the launcher of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
+// BYOUT, SH>).  The launcher's instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
+// sx_stream_ns34.hip, built in parallel with the rest); sx_kernels.hip sees the declaration.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/sx_amd.h"
+#include "sx_gp.hpp"
+#include "sx_reach.hpp"
+#include "sx_rollout.hpp"
+
+// (n_s, n_u, query shift) of every compiled fused rollout: X(NS, NU, SH, ...).  Shift 0 is sx_cem_rollout (and the shape
+// set of every other exact-GP entry point), shift > 0 sx_cem_rollout_junk (n_s + n_u + shift <= SX_MAX_D).  Each entry
+// has an instantiation of launch_rollout_stream in sx_stream_ns*.hip; ssm_cem.JUNK_FUSED_SHAPES is checked against it.
+#define SX_ROLLOUT_SHAPES(X, ...)                                                                                       \
+    X(2, 1, 0, __VA_ARGS__) X(4, 1, 0, __VA_ARGS__) X(2, 2, 0, __VA_ARGS__) X(4, 2, 0, __VA_ARGS__)                     \
+    X(3, 1, 0, __VA_ARGS__) X(1, 1, 0, __VA_ARGS__) X(2, 1, 1, __VA_ARGS__) X(4, 1, 1, __VA_ARGS__)                     \
+    X(3, 1, 1, __VA_ARGS__) X(2, 2, 1, __VA_ARGS__) X(2, 2, 2, __VA_ARGS__) X(3, 2, 1, __VA_ARGS__)                     \
+    X(1, 1, 1, __VA_ARGS__)
+
+// return CALL(NS, NU) for the shift-0 shape (ns, nu), SX_ERR_UNSUPPORTED for any other
+#define SX_SHIFT0_0(...) __VA_ARGS__
+#define SX_SHIFT0_1(...)
+#define SX_SHIFT0_2(...)
+#define SX_DISPATCH_ONE(NS, NU, SH, ns, nu, CALL) SX_SHIFT0_##SH(if ((ns) == NS && (nu) == NU) return CALL(NS, NU);)
+#define SX_DISPATCH(ns, nu, CALL)                               \
+    do {                                                        \
+        SX_ROLLOUT_SHAPES(SX_DISPATCH_ONE, ns, nu, CALL)        \
+        return SX_ERR_UNSUPPORTED;                              \
+    } while (0)
+
+// return CALL(NS, NU, SH) for the shape (ns, nu, sh), SX_ERR_UNSUPPORTED for any other
+#define SX_ROLLOUT_DISPATCH_ONE(NS, NU, SH, ns, nu, sh, CALL) \
+    if ((ns) == NS && (nu) == NU && (sh) == SH) return CALL(NS, NU, SH);
+#define SX_ROLLOUT_DISPATCH(ns, nu, sh, CALL)                               \
+    do {                                                                    \
+        SX_ROLLOUT_SHAPES(SX_ROLLOUT_DISPATCH_ONE, ns, nu, sh, CALL)        \
+        return SX_ERR_UNSUPPORTED;                                          \
+    } while (0)
+
+namespace sx {
+
+// Dynamic LDS bytes of cem_rollout_kernel: Kstar of all outputs (byout = false) or of one output at a time, for the GP
+// over ns + nu + sh columns and H steps of nu actions.
+inline size_t rollout_stream_lds_bytes(int ns, int nu, int sh, int n_train, int n_pad, int H, bool byout) {
+    return (gp_tile_lds_doubles(ns, ns + nu + sh, n_train, n_pad, kRolloutThreads / 64, byout ? 1 : ns) +
+            (size_t)SX_TILE * H * nu) * sizeof(double);
+}
+
+// Launches cem_rollout_kernel<NS, NU, byout, SH> with `lds` bytes (rollout_stream_lds_bytes) of dynamic LDS on `stream`.
+template <int NS, int NU, int SH>
+int launch_rollout_stream(const GpConst<NS, NS + NU + SH>& gc, const ReachConst<NS, NU>& rc,
+                          const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
+                          hipStream_t stream);
+
+}  // namespace sx

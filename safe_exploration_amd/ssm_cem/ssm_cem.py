@@ -12,7 +12,7 @@ from torch import Tensor
 from ..utils import assert_shape
 
 # (n_s, n_u, query shift) that sx_cem_rollout_junk rolls out in one launch per iteration: shift 0 is sx_cem_rollout's
-# shapes, shift > 0 the instantiations of csrc/sx_junk_ns*.hip (n_s + n_u + shift <= SX_MAX_D)
+# shapes, shift > 0 the query-shifted ones (n_s + n_u + shift <= SX_MAX_D): SX_ROLLOUT_SHAPES in csrc/sx_stream_launch.hpp
 JUNK_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1, 0), (1, 1, 0),
                                (2, 1, 1), (4, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1), (1, 1, 1)})
 
