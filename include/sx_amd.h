@@ -332,6 +332,41 @@ int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, i
 #define SX_FORM_BIG 4
 int sx_cem_rollout_form(const sx_gp_model* model, int H);
 
+/* ---- E problems with an exact GP each in one rollout launch (independent exploration runs) ----
+ * Every problem e of the launch has its own training set (its own N) and hyper-parameters; all models share (n_s, n_u),
+ * the sx_env and the buffer shapes of sx_cem_rollout.  The per-problem GP constants live in a device table that is built
+ * once per model change (the warm path); the rollout entries read it and copy nothing from the host.
+ *
+ * Bytes of the table for E models of shape (n_s, n_u); < 0 for bad arguments or a shape without a rollout kernel. */
+int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E);
+/* Packs the E models (host array, each built by sx_gp_fit + sx_gp_pack) into `table` (dev, sx_gp_model_table_bytes()
+ * bytes): their GP constants and the device pointers x_train, a_pack, stage_tab, which must stay valid while the table is
+ * used.  One host -> device copy on `stream`, and the call waits for it.  SX_ERR_ARG (before any device access) for a null
+ * pointer, E <= 0 or models of different (n_s, n_u); SX_ERR_UNSUPPORTED for a shape without a rollout kernel.
+ * Replaces: nothing in the reference, which runs its n_scenarios solvers one after another (episode_runner.py:40-123). */
+int sx_gp_model_table(const sx_gp_model* models, int E, void* table, void* stream);
+/* sx_cem_rollout over E problems with a GP each: `models` is the host array the table was built from (the launch plans
+ * from it: N of every model), `table` the device table.  Buffers as in sx_cem_rollout except
+ *   status  dev int32 [E]   one word per problem (OR of SX_STATUS_*): a NaN in one problem's model leaves the others clear
+ * The streaming kernel only: output by output for all problems where any model needs it, the LDS of the largest model.
+ * SX_ERR_ARG (before any device access) for null pointers, non-positive sizes or shapes that differ between the models or
+ * from env; SX_ERR_UNSUPPORTED where any model needs the workspace path (sx_cem_rollout_workspace_bytes() > 0) or the shape
+ * has no rollout kernel.  Replaces: the n_scenarios sequential solves' rollouts (episode_runner.py:40-123). */
+int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                         const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                         double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
+                         void* stream);
+/* sx_cem_rollout_elites over E problems with a GP each: the refit prologue from elite_rows [E x k x (2 + H n_u)], then
+ * sx_cem_rollout_multi.  Same limits as sx_cem_rollout_elites and sx_cem_rollout_multi; status dev int32 [E]. */
+int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                                double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                                int32_t* status, double* mean_out, double* std_out, void* stream);
+/* The form sx_cem_rollout_multi launches for these models and horizon (no launch, no device access): SX_FORM_STREAM or
+ * SX_FORM_BYOUT, or < 0 for bad arguments and wherever sx_cem_rollout_multi would answer SX_ERR_UNSUPPORTED.  The same
+ * contract as sx_cem_rollout_form. */
+int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -12,7 +12,7 @@ rollouts)``, an action-constraint cost of 3 per violating step, 10 per state out
 """
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -105,6 +105,98 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
                               _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj),
                               _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(workspace), ws_bytes,
                               _lib.stream_ptr(dev)), entry)
+    return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+
+
+class FusedMultiUnsupported(_lib.SxError):
+    """sx_cem_rollout_multi answered SX_ERR_UNSUPPORTED (before any launch): solve the problems one model at a time."""
+
+
+class GpModelTable:
+    """The device table of E exact-GP models (sx_gp_model_table), rebuilt only when one of the models changes (a GpCemSSM
+    builds a new sx_gp_model on every update).  `get` returns (the host array of the models, the device table)."""
+
+    def __init__(self):
+        self._models = None
+        self._array = None
+        self._table = None
+
+    def get(self, ssms: Sequence[GpCemSSM], dev):
+        models = [ssm.device_model for ssm in ssms]
+        if (self._models is not None and len(models) == len(self._models) and self._table.device == dev
+                and all(a is b for a, b in zip(models, self._models))):
+            return self._array, self._table
+        lib, E = _lib.lib(), len(models)
+        n_s, n_u = models[0].n_s, models[0].n_u
+        if any((m.n_s, m.n_u) != (n_s, n_u) for m in models):
+            raise ValueError(f'the models of a multi-model rollout must share (n_s, n_u); got '
+                             f'{[(m.n_s, m.n_u) for m in models]}')
+        nbytes = int(lib.sx_gp_model_table_bytes(n_s, n_u, E))
+        if nbytes < 0:
+            raise FusedMultiUnsupported(f'sx_gp_model_table_bytes: no rollout kernel for (n_s, n_u) = ({n_s}, {n_u})')
+        array = (_lib.SxGpModel * E)(*models)
+        table = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        _lib.check(lib.sx_gp_model_table(array, E, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_model_table')
+        self._models, self._array, self._table = models, array, table
+        return array, table
+
+
+def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, horizon: int, *,
+                      actions: Optional[Tensor] = None, mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
+                      noise: Optional[Tensor] = None, q0: Optional[Tensor] = None, want_traj: bool = False,
+                      want_sigma: bool = False, status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None,
+                      want_dist: bool = False, table: Optional[GpModelTable] = None):
+    """`cem_rollout` for E problems with an exact RBF GP each (ssms[e] for problem e), one launch: sx_cem_rollout_multi /
+    sx_cem_rollout_elites_multi.  Buffers as in `cem_rollout`; `status` is int32 [E], one word per problem.  `table` keeps
+    the device table of the models between calls (a fresh one is built otherwise).  Raises FusedMultiUnsupported where the
+    library has no single-launch form for the models (before any launch)."""
+    if any(getattr(ssm, 'kernel_family', 'rbf') != 'rbf' for ssm in ssms):
+        raise FusedMultiUnsupported('the multi-model rollout takes exact RBF GPs (kernel_family "rbf") only')
+    n_s, n_u = ssms[0].num_states, ssms[0].num_actions
+    _lib.require_gpu(x0, 'x0')
+    dev = x0.device
+    E = x0.size(0)
+    if len(ssms) != E:
+        raise ValueError(f'{len(ssms)} models for {E} problems')
+    models, tab = (table or GpModelTable()).get(ssms, dev)
+    if noise is not None:
+        P = noise.size(1)
+        actions = torch.empty((E, P, horizon, n_u), dtype=torch.float64, device=dev)
+    else:
+        P = actions.size(1)
+        actions = actions.contiguous()
+    S = n_s + n_s * n_s
+    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
+    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
+    con = torch.empty((E, P), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
+    if status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    lib = _lib.lib()
+
+    def check(code, what):
+        if code == _lib.SX_ERR_UNSUPPORTED:
+            raise FusedMultiUnsupported(f'{what}: no single-launch form for these models')
+        _lib.check(code, what)
+
+    if elite_rows is not None:
+        k = elite_rows.size(1)
+        if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
+            raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
+        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
+        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
+        check(lib.sx_cem_rollout_elites_multi(models, _lib.ptr(tab), ctypes.byref(env), E, P, horizon,
+                                              _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(elite_rows), k,
+                                              _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma),
+                                              _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(m_out),
+                                              _lib.ptr(s_out), _lib.stream_ptr(dev)), 'sx_cem_rollout_elites_multi')
+        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
+    check(lib.sx_cem_rollout_multi(models, _lib.ptr(tab), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
+                                   _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
+                                   _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                   _lib.stream_ptr(dev)), 'sx_cem_rollout_multi')
     return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
 
 
@@ -261,6 +353,27 @@ def cem_rank_refit_any(con: Tensor, obj: Tensor, actions: Tensor, k: int, **kw):
     flat = local['elite_rows'].reshape(-1)                       # [E x C k x (2 + L)] candidate rows
     return cem_rank_refit(flat, flat[1:], flat[2:], k, cost_stride=2 + L, act_stride=2 + L, row_len=L,
                           num_candidates=C * k, num_problems=E, **kw)
+
+
+def _hand_off(owner, best: Tensor, best_ok: Tensor, status: Tensor, q_block: Optional[Tensor]):
+    """The ONE device->host hand-off of a solve: one launch packs [status words | flags | point-state check | actions], one
+    copy into pinned memory (kept on `owner`) brings them over (sx_cem_pack_result).  Returns (status words int64 [G],
+    found bool [E], "q_block has a non-zero entry", best on the host)."""
+    G, E, L = status.numel(), best_ok.numel(), best[0].numel()
+    n = G + E + 1 + E * L
+    packed = torch.empty(n, dtype=torch.float64, device=best.device)
+    _lib.check(_lib.lib().sx_cem_pack_result(G, E, L, _lib.ptr(status), _lib.ptr(best_ok), _lib.ptr(q_block),
+                                             q_block.numel() if q_block is not None else 0,
+                                             _lib.ptr(best.contiguous()), _lib.ptr(packed),
+                                             _lib.stream_ptr(best.device)), 'sx_cem_pack_result')
+    host = getattr(owner, '_pinned', None)
+    if host is None or host.numel() < n:
+        owner._pinned = host = torch.empty(max(n, 256), dtype=torch.float64).pin_memory()
+    host[:n].copy_(packed, non_blocking=True)
+    torch.cuda.current_stream(best.device).synchronize()
+    out = host[:n].clone()
+    return (out[:G].to(torch.int64), out[G:G + E] != 0, bool(out[G + E] != 0),
+            out[G + E + 1:].view(best.shape))
 
 
 def fold_status(words) -> int:
@@ -575,23 +688,7 @@ class FusedCemMpc:
             q_block = q_block.contiguous()
 
         def hand_off(best, best_ok, status):
-            # one launch packs [status words | flags | point-state check | actions], one copy into pinned memory brings
-            # them over (sx_cem_pack_result)
-            G, E, L = status.numel(), best_ok.numel(), best[0].numel()
-            n = G + E + 1 + E * L
-            packed = torch.empty(n, dtype=torch.float64, device=best.device)
-            _lib.check(_lib.lib().sx_cem_pack_result(G, E, L, _lib.ptr(status), _lib.ptr(best_ok), _lib.ptr(q_block),
-                                                     q_block.numel() if q_block is not None else 0,
-                                                     _lib.ptr(best.contiguous()), _lib.ptr(packed),
-                                                     _lib.stream_ptr(best.device)), 'sx_cem_pack_result')
-            host = getattr(self, '_pinned', None)
-            if host is None or host.numel() < n:
-                self._pinned = host = torch.empty(max(n, 256), dtype=torch.float64).pin_memory()
-            host[:n].copy_(packed, non_blocking=True)
-            torch.cuda.current_stream(best.device).synchronize()
-            out = host[:n].clone()
-            return (out[:G].to(torch.int64), out[G:G + E] != 0, bool(out[G + E] != 0),
-                    out[G + E + 1:].view(best.shape))
+            return _hand_off(self, best, best_ok, status, q_block)
 
         best, best_ok, history, status = self.solve(x0)
         words, found, is_nonpoint, best_host = hand_off(best, best_ok, status)
@@ -637,3 +734,137 @@ class FusedCemMpc:
         if not bool(found[0]):
             return None, history
         return best[0], history
+
+
+class MultiModelCemMpc:
+    """E independent problems with an exact RBF GP each -- the reference's exploration scenarios, each with its own training
+    set and hyper-parameters -- solved together: one ``sx_cem_rollout_multi`` launch and one ``sx_cem_rank_refit`` launch per
+    CEM iteration for all of them, where ``FusedCemMpc`` needs one solve per model.
+
+    Problem e keeps a ``FusedCemMpc`` of its own (``solvers[e]``, built here from the same settings with seed ``seed + e``
+    unless given): it supplies the problem's noise draws and warm start, so a multi-model solve samples exactly what E
+    sequential ``get_actions`` calls would, and it takes over where the single launch does not apply -- a model that is not
+    an exact RBF GP, a training set that needs the workspace path (one solve per model then), and the per-problem
+    step-by-step repeat of ``FusedCemMpc._solve_checked``.  The problems share `env` and the CEM settings; sharded
+    (multi-GPU) multi-model solves are out of scope.
+    """
+
+    def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
+                 process_group=None, solvers: Optional[Sequence[FusedCemMpc]] = None):
+        if process_group is not None:
+            raise ValueError('MultiModelCemMpc solves on one GPU: sharded multi-model solves are not supported')
+        self._ssms = list(ssms)
+        if not self._ssms:
+            raise ValueError('MultiModelCemMpc needs at least one model')
+        if len({(s.num_states, s.num_actions) for s in self._ssms}) != 1:
+            raise ValueError('the models of a multi-model solve must share (n_s, n_u)')
+        if solvers is None:
+            solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
+                                   seed=seed + e, init_std=init_std, warm_start=warm_start)
+                       for e, ssm in enumerate(self._ssms)]
+        if len(solvers) != len(self._ssms):
+            raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models')
+        self._solvers = list(solvers)
+        self._env = env
+        self._horizon = time_horizon
+        self._num_rollouts = num_rollouts
+        self._num_elites = num_elites
+        self._num_iterations = num_iterations
+        self._device = self._solvers[0]._device
+        self._table = GpModelTable()
+        self._last_noise = None
+        self.last_status = [0] * len(self._ssms)
+        self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path
+        self.per_model_solves = 0       # solves that went one model at a time (single launch not applicable)
+
+    @property
+    def solvers(self) -> List[FusedCemMpc]:
+        return self._solvers
+
+    def set_env(self, env: _lib.SxEnv) -> None:
+        self._env = env
+        for s in self._solvers:
+            s.set_env(env)
+
+    def fused_applies(self) -> bool:
+        """Does one sx_cem_rollout_multi launch serve the models (exact RBF GPs, no workspace path)?  Host only."""
+        if any(getattr(ssm, 'kernel_family', 'rbf') != 'rbf' for ssm in self._ssms):
+            return False
+        models = (_lib.SxGpModel * len(self._ssms))(*[ssm.device_model for ssm in self._ssms])
+        return int(_lib.lib().sx_cem_rollout_multi_form(models, len(self._ssms), self._horizon)) >= 0
+
+    def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """E = len(models) solves from x0 [E x n_s] (points) in one launch per step of the loop.  Nothing synchronises.
+        noise: optional [iters x E x P x H x n_u] standard normals; by default problem e draws from solvers[e].
+        Returns (best [E x H x n_u], best_ok int32 [E], status int32 [E]: one word per problem).
+        Raises FusedMultiUnsupported (before any launch) where the single launch does not apply."""
+        E, H, n_u = len(self._ssms), self._horizon, self._ssms[0].num_actions
+        n_s = self._ssms[0].num_states
+        dev = x0.device
+        if x0.shape != (E, n_s):
+            raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
+        if noise is None:
+            noise = torch.stack([s._next_noise(1)[:, 0] for s in self._solvers], dim=1)
+        self._last_noise = noise
+        mean = torch.cat([s.safe_policy_plan(x0[e:e + 1]) if s._warm_start == 'safe_policy'
+                          else torch.zeros((1, H, n_u), dtype=torch.float64, device=dev)
+                          for e, s in enumerate(self._solvers)]).contiguous()
+        std = torch.stack([s._init_std.to(dev).expand(H, n_u) for s in self._solvers]).contiguous()
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
+        P = self._num_rollouts
+        chunks = rank_chunks(P)
+        in_prologue = (2 * H * n_u <= 256 * (1 + n_s)
+                       and int(_lib.lib().sx_cem_rank_counts(E, chunks * self._num_elites if chunks > 1 else P)) == 1)
+        rows, out = None, None
+        for it in range(self._num_iterations):
+            eps = noise[it].contiguous()
+            if rows is not None:
+                r = cem_rollout_multi(self._ssms, self._env, x0, H, elite_rows=rows, noise=eps, status=status,
+                                      table=self._table)
+            else:
+                r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, noise=eps, status=status,
+                                      table=self._table)
+            out = cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites,
+                                     want_rows=in_prologue, want_refit=not in_prologue)
+            if in_prologue:
+                rows = out['elite_rows']
+            else:
+                mean, std = out['mean'].view(E, H, n_u), out['std'].view(E, H, n_u)
+        return out['best'].view(E, H, n_u), out['best_ok'], status
+
+    def get_actions_multi(self, states: Tensor, where: str = 'get_actions_multi') -> Tuple[Tensor, Tensor]:
+        """Flat start states [E x (n_s + n_s^2)], all points, problem e for model e.  Returns (actions [E x H x n_u] on the
+        host, found bool [E] on the host); ``found[e] == False`` is the ``get_actions`` ``None`` of problem e.  Raises like
+        ``FusedCemMpc.get_actions`` if any problem hit a numerical failure; the step-by-step repeat of a solve that reports
+        both SX_STATUS_NAN and SX_STATUS_ZERO_FIX is made for that problem only."""
+        E, n_s = len(self._ssms), self._ssms[0].num_states
+        if states.dim() != 2 or states.shape != (E, n_s + n_s * n_s):
+            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(states.shape)}')
+        states = states.to(self._device, torch.float64)
+        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
+        if not self.fused_applies():
+            # one solve per model, each with its own checks (and its own step-by-step repeat)
+            self.per_model_solves += 1
+            per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1]) for e, s in enumerate(self._solvers)]
+            self.last_status = [s.last_status for s in self._solvers]
+            return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
+        best, best_ok, status = self.solve(x0)
+        words, found, is_nonpoint, best_host = _hand_off(self, best, best_ok, status, q_block)
+        if is_nonpoint:
+            raise NotImplementedError(f'{where} starts from point states (all-zero Q), as CemSafeMPC.get_action does')
+        self.last_status = [int(w) for w in words.tolist()]
+        both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
+        for e, s in enumerate(self._solvers):
+            if (self.last_status[e] & both) == both:
+                # FusedCemMpc._solve_checked's repeat, for this problem alone and with its own draws
+                self.stepwise_fallbacks += 1
+                b, ok, _, st = s.solve(x0[e:e + 1], noise=self._last_noise[:, e:e + 1].contiguous(), stepwise=True)
+                w, f, _, bh = _hand_off(self, b, ok, st, None)
+                self.last_status[e] = fold_status(w)
+                found[e], best_host[e] = f[0], bh[0]
+        for e, s in enumerate(self._solvers):
+            s.last_status = self.last_status[e]
+            raise_for_status(self.last_status[e], f'{where} (problem {e})',
+                             dump=lambda e=e: save_failure_state(self._ssms[e], x0[e:e + 1], None))
+        return best_host, found

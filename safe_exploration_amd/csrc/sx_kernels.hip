@@ -1,6 +1,7 @@
 // libsxamd: launchers + C ABI (include/sx_amd.h) over the kernels in sx_*.hpp.  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -646,7 +647,9 @@ static int resident_lds_bytes(int ns, int nu, int n_train, int n_pad, int H, siz
 }
 
 // `m` is the GP over ns + nu + sh columns (m->n_u = nu + sh), sh the query shift of sx_cem_rollout_junk.
-static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites) {
+// stream_only: the streaming kernel's answer (STREAM, BYOUT or BIG), never a resident form and no override -- the
+// multi-model rollout has only that kernel (plan_rollout_multi).
+static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites, bool stream_only = false) {
     const int ns = m->n_s, nu = m->n_u - sh, n_train = m->n_train, n_pad = m->n_pad;
     auto stream_lds = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, sh, n_train, n_pad, H, byout); };
     const bool all_at_once = n_pad <= 1024 && stream_lds(false) <= kMaxLdsBytes;
@@ -659,7 +662,7 @@ static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites
     if (by_output) return {SX_FORM_BYOUT, ok, stream_lds(true), 0};
     const RolloutPlan stream{SX_FORM_STREAM, ok, stream_lds(false), 0};
     const FormOverride& o = form_override();
-    if (!ok || sh > 0 || o.form == SX_FORM_STREAM) return stream;
+    if (!ok || sh > 0 || stream_only || o.form == SX_FORM_STREAM) return stream;
     // W partly resident on 8 waves (n_s <= 2), then all of W in the registers of 4 waves (smaller N), then W streamed from
     // L2: the 4-wave form loses to the streaming kernel only where the 8-wave form exists (n_s = 2, n_u = 1: 126.6
     // against 125.7 us at config 2), and beats it by 7 - 16 % on the shapes the 8-wave form does not cover (n_s = 3, 4;
@@ -700,6 +703,58 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
     }
     return launch_rollout_stream<NS, NU, SH>(make_gp_const<NS, NU + SH>(m, kRolloutThreads / 64), rc, cc, rps,
                                              plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
+// The multi-model rollout (sx_cem_rollout_multi[_elites]): one launch of the streaming kernel for E problems with a GP
+// each, so every model takes plan_rollout's streaming answer.  The launch is output by output where any model needs it,
+// with the LDS of the largest; a model without a single-launch form (BIG, or not ok) makes the whole launch unsupported.
+static RolloutPlan plan_rollout_multi(const sx_gp_model* models, int E, int H, bool elites) {
+    RolloutPlan out{SX_FORM_STREAM, true, 0, 0};
+    for (int i = 0; i < E; ++i) {
+        const RolloutPlan p = plan_rollout(&models[i], 0, H, elites, true);
+        if (p.form == SX_FORM_BIG || !p.ok) return {p.form, false, 0, 0};
+        if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
+    }
+    const sx_gp_model& m0 = models[0];
+    for (int i = 0; i < E; ++i)
+        out.lds = std::max(out.lds, rollout_stream_lds_bytes(m0.n_s, m0.n_u, 0, models[i].n_train, models[i].n_pad, H,
+                                                             out.form == SX_FORM_BYOUT));
+    return out;
+}
+
+// Bytes of one sx_gp_model_table entry: the GpConst the streaming kernel takes (SX_ERR_UNSUPPORTED for a shape without
+// a rollout kernel)
+template <int NS, int NU>
+static int64_t gp_table_entry_bytes() {
+    return (int64_t)sizeof(GpConst<NS, NS + NU>);
+}
+static int64_t gp_table_entry_bytes(int ns, int nu) {
+#define CALL(NS, NU) gp_table_entry_bytes<NS, NU>()
+    SX_DISPATCH(ns, nu, CALL);
+#undef CALL
+}
+
+template <int NS, int NU>
+static int build_gp_table(const sx_gp_model* models, int E, void* table, hipStream_t stream) {
+    std::vector<GpConst<NS, NS + NU>> host(E);
+    for (int i = 0; i < E; ++i) host[i] = make_gp_const<NS, NU>(&models[i], kRolloutThreads / 64);
+    if (hipMemcpyAsync(table, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return SX_ERR_LAUNCH;
+    // (the copy reads `host`, which ends with this call)
+    return hipStreamSynchronize(stream) == hipSuccess ? SX_OK : SX_ERR_LAUNCH;
+}
+
+template <int NS, int NU>
+static int launch_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const RolloutPtrs& rp,
+                                hipStream_t stream) {
+    const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    make_cost_const<NS, NU>(env, cc);
+    return launch_rollout_stream_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp,
+                                               plan.form == SX_FORM_BYOUT, plan.lds, stream);
 }
 
 // sx_cem_rollout[_elites][_junk] after their argument checks
@@ -1193,6 +1248,72 @@ int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int 
     rp.mean_out = mean_out;
     rp.std_out = std_out;
     return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
+}
+
+// E models of one (n_s, n_u) with a training set each: checked before anything touches the device
+static bool multi_models_ok(const sx_gp_model* models, int E) {
+    if (!models || E <= 0) return false;
+    const int ns = models[0].n_s, nu = models[0].n_u;
+    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || nu > SX_MAX_NU) return false;
+    for (int i = 0; i < E; ++i)
+        if (models[i].n_s != ns || models[i].n_u != nu || models[i].n_train <= 0 || models[i].n_pad <= 0) return false;
+    return true;
+}
+
+int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E) {
+    if (E <= 0 || n_s <= 0 || n_s > SX_MAX_NS || n_u <= 0 || n_u > SX_MAX_NU) return -1;
+    const int64_t entry = sx::gp_table_entry_bytes(n_s, n_u);
+    return entry == SX_ERR_UNSUPPORTED ? -1 : entry * E;
+}
+
+int sx_gp_model_table(const sx_gp_model* models, int E, void* table, void* stream) {
+    if (!table || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    for (int i = 0; i < E; ++i)
+        if (!models[i].x_train || !models[i].a_pack || !models[i].stage_tab) return SX_ERR_ARG;
+#define CALL(NS, NU) sx::build_gp_table<NS, NU>(models, E, table, (hipStream_t)stream)
+    SX_DISPATCH(models[0].n_s, models[0].n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H) {
+    if (!multi_models_ok(models, E) || H <= 0) return -1;
+    const sx::RolloutPlan plan = sx::plan_rollout_multi(models, E, H, false);
+    return plan.ok ? plan.form : -1;
+}
+
+static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx::RolloutPtrs& rp,
+                             void* stream) {
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+#define CALL(NS, NU) sx::launch_rollout_multi<NS, NU>(models, table, env, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                         const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                         double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
+                         void* stream) {
+    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
+    if (P <= 0 || H <= 0 || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (noise && (!mean || !std)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return cem_rollout_multi(models, table, env, rp, stream);
+}
+
+int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                                double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                                int32_t* status, double* mean_out, double* std_out, void* stream) {
+    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
+    if (P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
+    if (!multi_models_ok(models, E) || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    rp.elite_rows = elite_rows;
+    rp.elite_k = k;
+    rp.mean_out = mean_out;
+    rp.std_out = std_out;
+    return cem_rollout_multi(models, table, env, rp, stream);
 }
 
 static bool feat_model_ok(const sx_feat_model* m) {

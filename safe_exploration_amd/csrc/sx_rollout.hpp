@@ -60,14 +60,34 @@ struct RolloutPtrs {
 // SH > 0 (sx_cem_rollout_junk): the GP's inputs are D = NS + NU + SH columns -- training rows [x, u, 0_SH], queries
 // [p, 0_SH, u] -- while the reachability and the costs see (NS, NU) and the Jacobian's leading NS + NU columns (the
 // exact-GP form of JunkDimensionsSSM).  SH = 0 is the plain rollout.
-template <int NS, int NU, bool BYOUT = false, int SH = 0>
-__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS, NS + NU + SH> gc,
-                                                                      const int4* __restrict__ stage_tab,
-                                                                      ReachConst<NS, NU> rc,
-                                                                      CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp) {
+// MM = true (sx_cem_rollout_multi): every problem has a GP of its own.  The first argument is then the device table of
+// the E problems' GpConst (sx_gp_model_table), the workgroup reads its problem's entry with scalar loads (the pointer is
+// restrict-qualified and the kernel never writes it), `stage_tab` is unused (each entry carries its own), the LDS
+// carve-up follows the problem's n_train / n_pad inside the launch's allocation for the largest model, and `rp.status`
+// holds one word per problem.
+// (The problem index is derived inside `of`, so that the plain mode's statements keep their order and its ISA.)
+template <int NS, int D, bool MM>
+struct RolloutGpArg {
+    using type = GpConst<NS, D>;
+    __device__ static const GpConst<NS, D>& of(const type& gc, const RolloutPtrs&) { return gc; }
+};
+template <int NS, int D>
+struct RolloutGpArg<NS, D, true> {
+    using type = const GpConst<NS, D>* __restrict__;
+    __device__ static const GpConst<NS, D>& of(type table, const RolloutPtrs& rp) {
+        return table[blockIdx.x / ((rp.P + SX_TILE - 1) / SX_TILE)];
+    }
+};
+
+template <int NS, int NU, bool BYOUT = false, int SH = 0, bool MM = false>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
+    typename RolloutGpArg<NS, NS + NU + SH, MM>::type gc_arg, const int4* __restrict__ stage_tab_arg,
+    ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp) {
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
+    const GpConst<NS, D>& gc = RolloutGpArg<NS, D, MM>::of(gc_arg, rp);
+    const int4* __restrict__ const stage_tab = MM ? gc.stage_tab : stage_tab_arg;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     GpTileLds<NS, D> lds;
     const int nw = blockDim.x >> 6;
@@ -381,7 +401,7 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(GpConst<NS
         const int64_t g = (int64_t)e * rp.P + c0 + tid;
         rp.obj_cost[g] = obj;
         rp.con_cost[g] = con;
-        if (st) atomicOr(rp.status, st);
+        if (st) atomicOr(rp.status + (MM ? e : 0), st);
     }
 }
 

@@ -1,4 +1,5 @@
-// Body of launch_rollout_stream<NS, NU, SH>; included by sx_stream_ns*.hip, which instantiate it.
+// Bodies of launch_rollout_stream<NS, NU, SH> and launch_rollout_stream_multi<NS, NU>; included by sx_stream_ns*.hip and
+// sx_stream_multi.hip, which instantiate them.
 #pragma once
 #include "sx_launch.hpp"
 #include "sx_stream_launch.hpp"
@@ -29,7 +30,29 @@ int launch_rollout_stream(const GpConst<NS, NS + NU + SH>& gc, const ReachConst<
     return check_launch();
 }
 
+template <int NS, int NU>
+int launch_rollout_stream_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
+                                const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
+                                hipStream_t stream) {
+    const int tiles = (rp.P + SX_TILE - 1) / SX_TILE;
+    if (byout) {
+        if (int r = allow_lds(cem_rollout_kernel<NS, NU, true, 0, true>, lds)) return r;
+        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_kernel<NS, NU, true, 0, true>, dim3(rp.E * tiles), dim3(kRolloutThreads),
+               lds, stream, table, (const int4*)nullptr, rc, cc, rp);
+    } else {
+        if (int r = allow_lds(cem_rollout_kernel<NS, NU, false, 0, true>, lds)) return r;
+        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_kernel<NS, NU, false, 0, true>, dim3(rp.E * tiles), dim3(kRolloutThreads),
+               lds, stream, table, (const int4*)nullptr, rc, cc, rp);
+    }
+    return check_launch();
+}
+
 }  // namespace sx
+
+#define SX_STREAM_MULTI_INSTANTIATE(NS, NU)                                                                             \
+    template int sx::launch_rollout_stream_multi<NS, NU>(                                                              \
+        const sx::GpConst<NS, NS + NU>*, const sx::ReachConst<NS, NU>&, const sx::CostConst<SX_MAX_M, NS, NU>&,       \
+        const sx::RolloutPtrs&, bool, size_t, hipStream_t);
 
 #define SX_STREAM_INSTANTIATE(NS, NU, SH)                                                                            \
     template int sx::launch_rollout_stream<NS, NU, SH>(                                                               \

@@ -1,6 +1,7 @@
-// The compiled shapes of the fused rollout, and the launcher of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
-// BYOUT, SH>).  The launcher's instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
-// sx_stream_ns34.hip, built in parallel with the rest); sx_kernels.hip sees the declaration.
+// The compiled shapes of the fused rollout, and the launchers of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
+// BYOUT, SH, MM>).  The launchers' instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
+// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip; built in parallel with the rest); sx_kernels.hip sees
+// the declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,5 +53,12 @@ template <int NS, int NU, int SH>
 int launch_rollout_stream(const GpConst<NS, NS + NU + SH>& gc, const ReachConst<NS, NU>& rc,
                           const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
                           hipStream_t stream);
+
+// Launches cem_rollout_kernel<NS, NU, byout, 0, true> over E problems with a GP each: `table` is the device array of their
+// GpConst (sx_gp_model_table), `lds` the largest rollout_stream_lds_bytes over them.  rp.status holds E words.
+template <int NS, int NU>
+int launch_rollout_stream_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
+                                const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
+                                hipStream_t stream);
 
 }  // namespace sx

@@ -16,7 +16,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .safempc_cem import MpcResult
+from .safempc_cem import MpcResult, get_actions_multi
 
 
 @dataclass
@@ -47,10 +47,16 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
                      verbosity: int = 0) -> List[EpisodeResult]:
     """E episodes in lockstep.  `envs`: one environment per episode (``reset(mean, std)``, ``step(action) -> (action,
     next_state, observation, done, env_result)``, ``random_action()``, ``collect_metrics()``, ``n_s``, ``n_u``).
-    `solver`: a ``CemSafeMPC`` (``get_action_batch``) or None (random actions, exit code 5).  An episode whose
-    environment reports `done` stops (safety failure, reference :311-313); the others carry on.
+    `solver`: a ``CemSafeMPC`` (``get_action_batch``) or None (random actions, exit code 5), or a list of ``CemSafeMPC``,
+    one per episode: independent scenarios, each with its own model (the reference's n_scenarios solvers,
+    episode_runner.py:40-123), served by ``get_actions_multi`` -- one solve per step for the episodes still running, each
+    solver with its own ladder, episode e exactly as ``do_rollout`` with solver e.  An episode whose environment reports
+    `done` stops (safety failure, reference :311-313); the others carry on.
     """
     E = len(envs)
+    per_episode = isinstance(solver, (list, tuple))
+    if per_episode and len(solver) != E:
+        raise ValueError(f'{len(solver)} solvers for {E} episodes')
     ids = list(episode_ids) if episode_ids is not None else list(range(E))
     states = [np.asarray(env.reset(mean, std), dtype=np.float64) for env in envs]
     xx = [[np.zeros(envs[e].n_s + envs[e].n_u)] for e in range(E)]
@@ -63,8 +69,9 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
     failed = [False] * E
     solver_time = [0.0] * E
     active = list(range(E))
-    if solver is not None and hasattr(solver, 'reset_batch'):
-        solver.reset_batch()
+    for s in (solver if per_episode else [solver]):
+        if s is not None and hasattr(s, 'reset_batch'):
+            s.reset_batch()
     for i in range(n_steps):
         if not active:
             break
@@ -74,7 +81,10 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
         else:
             t0 = time.time()
             batch = np.stack([states[e] for e in active])
-            acts, step_results = solver.get_action_batch(batch, episode_ids=active, num_episodes=E)
+            if per_episode:
+                acts, step_results = get_actions_multi([solver[e] for e in active], batch)
+            else:
+                acts, step_results = solver.get_action_batch(batch, episode_ids=active, num_episodes=E)
             dt = time.time() - t0
             actions = [acts[k] for k in range(len(active))]
             for e in active:
@@ -110,7 +120,7 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
             metrics.log_scalar('env_result', env_result[e], ids[e])
             metrics.log_non_scalars(envs[e].collect_metrics(), ids[e])
             if solver is not None:
-                metrics.log_non_scalars(solver.collect_metrics(), ids[e])
+                metrics.log_non_scalars((solver[e] if per_episode else solver).collect_metrics(), ids[e])
         if n_successful[e] == 0:
             warnings.warn('Agent survived 0 steps, cannot collect data')
             res = EpisodeResult(np.empty((0, envs[e].n_s + envs[e].n_u)), np.empty((0, envs[e].n_s)), [], np.empty((0, 1)),

@@ -7,7 +7,7 @@ task runners work unchanged.  What differs is underneath: instead of handing Pyt
 the GP operands and the environment constants to ``FusedCemMpc`` (two kernel launches per CEM iteration).
 """
 from enum import Enum
-from typing import Callable, Dict, List, Optional, Tuple, Union
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -15,7 +15,7 @@ from numpy import ndarray
 from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
-from .cem_mpc import FusedCemMpc, Rollouts
+from .cem_mpc import FusedCemMpc, MultiModelCemMpc, Rollouts
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem.gp_ssm_cem import GpCemSSM
@@ -373,19 +373,23 @@ class CemSafeMPC(SafeMPC):
         actions: List[ndarray] = []
         results: List[MpcResult] = []
         for k, e in enumerate(ids):
-            if bool(found[k]):
-                self._batch_last_actions[e] = best[k]
-                self._batch_executed[e] = 1
-                actions.append(best[k][0])
-                results.append(MpcResult.FOUND_SOLUTION)
-            elif self._batch_executed[e] < self._batch_last_actions[e].shape[0]:
-                actions.append(self._batch_last_actions[e][self._batch_executed[e]])
-                self._batch_executed[e] += 1
-                results.append(MpcResult.PREVIOUS_SOLUTION)
-            else:
-                actions.append(np.asarray(self._safe_policy(states[k])))
-                results.append(MpcResult.SAFE_CONTROLLER)
+            action, result = self._batch_ladder(e, states[k], best[k], bool(found[k]))
+            actions.append(action)
+            results.append(result)
         return np.stack(actions), results
+
+    def _batch_ladder(self, e: int, state: ndarray, best: ndarray, found: bool) -> Tuple[ndarray, MpcResult]:
+        """Episode e's rung of the reference's ladder (safempc_cem.py:243-263) for a solve that returned `best` [H x n_u]
+        (`found`): fresh solution, else the rest of the previous one, else the safe controller."""
+        if found:
+            self._batch_last_actions[e] = best
+            self._batch_executed[e] = 1
+            return best[0], MpcResult.FOUND_SOLUTION
+        if self._batch_executed[e] < self._batch_last_actions[e].shape[0]:
+            action = self._batch_last_actions[e][self._batch_executed[e]]
+            self._batch_executed[e] += 1
+            return action, MpcResult.PREVIOUS_SOLUTION
+        return np.asarray(self._safe_policy(state)), MpcResult.SAFE_CONTROLLER
 
     def reset_batch(self) -> None:
         self._batch_last_actions = None
@@ -437,3 +441,67 @@ class CemSafeMPC(SafeMPC):
 
     def collect_metrics(self) -> Dict[str, float]:
         return self._ssm.collect_metrics()
+
+
+def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[ndarray, List[MpcResult]]:
+    """``get_action`` of several independent solvers at once -- the reference's exploration scenarios, each with its own
+    model and data (episode_runner.py:40-123) -- where solver e acts in states[e] ([E x n_s]).  Returns (actions
+    [E x n_u], one MpcResult per solver).
+
+    Over exact RBF GPs that is ONE solve for all of them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each
+    problem with its own GP); otherwise, and where the single launch does not apply, one solve per solver.  Either way
+    problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
+    ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
+    the CEM settings; ValueError otherwise."""
+    solvers = list(solvers)
+    states = np.asarray(states)
+    if not solvers:
+        raise ValueError('get_actions_multi needs at least one solver')
+    n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
+    if states.ndim != 2 or states.shape != (len(solvers), n_s):
+        raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')
+    for s in solvers:
+        if (s.state_dimen, s.action_dimen) != (n_s, n_u):
+            raise ValueError('the solvers of get_actions_multi must share (n_s, n_u)')
+        if s._batch_last_actions is None or len(s._batch_last_actions) != 1:
+            s._batch_last_actions = [np.empty((0, n_u))]
+            s._batch_executed = [0]
+    mpcs = [s._solver() for s in solvers]
+    def settings(m):
+        init = getattr(m, '_init_std', None)
+        return (type(m),) + tuple(getattr(m, a, None) for a in ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations',
+                                                                 '_warm_start', '_device', '_world')) + \
+            (None if init is None else tuple(init.reshape(-1).tolist()),)
+
+    first = settings(mpcs[0])
+    env_bytes = bytes(mpcs[0]._env) if getattr(mpcs[0], '_env', None) is not None else None
+    for m in mpcs[1:]:
+        if settings(m) != first:
+            raise ValueError('the solvers of get_actions_multi must share the CEM settings (horizon, rollouts, elites, '
+                             'iterations, initial distribution, device)')
+        if (bytes(m._env) if getattr(m, '_env', None) is not None else None) != env_bytes:
+            raise ValueError('the solvers of get_actions_multi must share the environment constants (sx_env)')
+    flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
+    if (all(isinstance(m, FusedCemMpc) and m._objective_hook is None and m._world == 1 for m in mpcs)
+            and all(getattr(m._ssm, 'kernel_family', None) == 'rbf' for m in mpcs)):
+        key = tuple(id(m) for m in mpcs)
+        cached = getattr(solvers[0], '_multi', None)
+        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1]._solvers, mpcs)):
+            multi = MultiModelCemMpc([m._ssm for m in mpcs], mpcs[0]._env, *first[1:5], solvers=mpcs)
+            solvers[0]._multi = cached = (key, multi)
+        multi = cached[1]
+        multi._env = mpcs[0]._env
+        best, found = multi.get_actions_multi(flat)
+        best = best.detach().cpu().numpy()
+    else:
+        per = [m.get_actions_batch(flat[e:e + 1]) for e, m in enumerate(mpcs)]
+        best = np.concatenate([p[0].detach().cpu().numpy() for p in per])
+        found = [bool(p[1][0]) for p in per]
+    actions: List[ndarray] = []
+    results: List[MpcResult] = []
+    for e, s in enumerate(solvers):
+        s.last_rollouts = []
+        action, result = s._batch_ladder(0, states[e], best[e], bool(found[e]))
+        actions.append(action)
+        results.append(result)
+    return np.stack(actions), results
