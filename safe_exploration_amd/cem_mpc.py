@@ -31,19 +31,12 @@ class Rollouts:
     constraint_costs: Tensor         # [P]
 
 
-def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, actions: Optional[Tensor] = None,
-                mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
-                q0: Optional[Tensor] = None, want_traj: bool = False, want_sigma: bool = False,
-                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False):
-    """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites (and their _junk, _feat and _mlp counterparts).
-
-    x0 [E x n_s]; either `actions` [E x P x H x n_u] (given), or (`mean`, `std` [E x H x n_u], `noise` [E x P x H x n_u]),
-    or (`elite_rows` [E x k x (2 + H n_u)], `noise`): the distribution is then refit from the previous iteration's elite
-    rows in the rollout kernel's prologue (`fused_refit_applies`); `want_dist` returns that refit as `mean` / `std`.
-    Returns dict(actions, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]).
-    """
-    n_s, n_u = ssm.num_states, ssm.num_actions
-    _lib.require_gpu(x0, 'x0')
+def _rollout(suffix: str, head: tuple, x0: Tensor, horizon: int, n_s: int, n_u: int, words: int, unsupported, *,
+             actions, mean, std, noise, q0, want_traj, want_sigma, status, elite_rows, want_dist, workspace=()):
+    """What `cem_rollout` and `cem_rollout_multi` share: the outputs, the `elite_rows` check and the launch of
+    sx_cem_rollout[_elites]<suffix>(*head, E, P, H, x0, q0, mean, std | elite_rows, k, noise, <outputs>, status,
+    *workspace | mean_out, std_out, stream).  `workspace`: (pointer, bytes) of the plain single-model entries; `words`: the
+    size of a fresh status; `unsupported`: what SX_ERR_UNSUPPORTED raises."""
     dev = x0.device
     E = x0.size(0)
     if noise is not None:
@@ -58,54 +51,69 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     obj = torch.empty((E, P), dtype=torch.float64, device=dev)
     con = torch.empty((E, P), dtype=torch.float64, device=dev)
     if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    lib = _lib.lib()
-    family = getattr(ssm, 'kernel_family', 'rbf')
-    if family in ('feature', 'mlp'):
-        # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
-        # 'mlp': MC-dropout ensembles over the frozen members, matrix cores for 1-2 hidden layers of <= 64 units
-        # (csrc/sx_mlp_mfma.hpp), one particle per lane otherwise (csrc/sx_mlp.hpp)
-        entry, model = ('sx_cem_rollout_feat', ssm.feat_model) if family == 'feature' else ('sx_cem_rollout_mlp', ssm.mlp_model)
-        _lib.check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
-                                       _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
-                                       _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                       _lib.stream_ptr(dev)), entry)
-        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
-    # exact RBF GP ('rbf') through sx_cem_rollout[_elites]; JunkDimensionsSSM over one ('rbf_junk') through the _junk entries:
-    # the real-output GP over the kept columns (`real_output_view`) with the query shift.  That GP also owns the workspace.
-    junk = family == 'rbf_junk'
-    owner = ssm.real_output_view() if junk else ssm
-    model, shift = owner.device_model, ssm.query_shift if junk else 0
-    suffix, shift_arg = ('_junk', (shift,)) if junk else ('', ())
-
-    def check(code, what):
-        if junk and code == _lib.SX_ERR_UNSUPPORTED:
-            raise FusedJunkUnsupported(f'{what}: no single-launch form for this model')
-        _lib.check(code, what)
-
+        status = torch.zeros(words, dtype=torch.int32, device=dev)
+    out = dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
     if elite_rows is not None:
         k = elite_rows.size(1)
         if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
             raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
         m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
         s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
-        entry = 'sx_cem_rollout_elites' + suffix
-        check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), *shift_arg, E, P, horizon, _lib.ptr(x0.contiguous()),
-                                  _lib.ptr(q0), _lib.ptr(elite_rows), k, _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj),
-                                  _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(m_out),
-                                  _lib.ptr(s_out), _lib.stream_ptr(dev)), entry)
-        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
-    # (a query shift > 0 never takes a workspace)
-    ws_bytes = int(lib.sx_cem_rollout_workspace_bytes(ctypes.byref(model), E, P, horizon)) if shift == 0 else 0
-    if ws_bytes < 0:
-        raise _lib.SxError('sx_cem_rollout_workspace_bytes: bad arguments')
-    workspace = owner.workspace(ws_bytes)   # None on the fused path; cached on the model otherwise
-    entry = 'sx_cem_rollout' + suffix
-    check(getattr(lib, entry)(ctypes.byref(model), ctypes.byref(env), *shift_arg, E, P, horizon, _lib.ptr(x0.contiguous()),
-                              _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj),
-                              _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(workspace), ws_bytes,
-                              _lib.stream_ptr(dev)), entry)
-    return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+        out.update(mean=m_out, std=s_out)
+        if workspace:
+            raise ValueError('the elite-row entries take no workspace')
+        entry, dist, tail = 'sx_cem_rollout_elites' + suffix, (_lib.ptr(elite_rows), k), (_lib.ptr(m_out), _lib.ptr(s_out))
+    else:
+        entry, dist, tail = 'sx_cem_rollout' + suffix, (_lib.ptr(mean), _lib.ptr(std)), workspace
+    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, _lib.ptr(x0.contiguous()), _lib.ptr(q0), *dist, _lib.ptr(noise),
+                                      _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con),
+                                      _lib.ptr(status), *tail, _lib.stream_ptr(dev))
+    if unsupported is not None and code == _lib.SX_ERR_UNSUPPORTED:
+        raise unsupported(f'{entry}: no single-launch form for the model')
+    _lib.check(code, entry)
+    return out
+
+
+def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, actions: Optional[Tensor] = None,
+                mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
+                q0: Optional[Tensor] = None, want_traj: bool = False, want_sigma: bool = False,
+                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False):
+    """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites (and their _junk, _feat and _mlp counterparts).
+
+    x0 [E x n_s]; either `actions` [E x P x H x n_u] (given), or (`mean`, `std` [E x H x n_u], `noise` [E x P x H x n_u]),
+    or (`elite_rows` [E x k x (2 + H n_u)], `noise`): the distribution is then refit from the previous iteration's elite
+    rows in the rollout kernel's prologue (`fused_refit_applies`), and `mean` / `std` are not read; `want_dist` returns
+    that refit as `mean` / `std`.
+    Returns dict(actions, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]).
+    """
+    _lib.require_gpu(x0, 'x0')
+    family = getattr(ssm, 'kernel_family', 'rbf')
+    workspace, unsupported = (), None
+    if family in ('feature', 'mlp'):
+        # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
+        # 'mlp': MC-dropout ensembles over the frozen members, matrix cores for 1-2 hidden layers of <= 64 units
+        # (csrc/sx_mlp_mfma.hpp), one particle per lane otherwise (csrc/sx_mlp.hpp).  Neither has an elite-row form.
+        suffix, model = ('_feat', ssm.feat_model) if family == 'feature' else ('_mlp', ssm.mlp_model)
+        head, elite_rows = (ctypes.byref(model), ctypes.byref(env)), None
+    else:
+        # exact RBF GP ('rbf'); JunkDimensionsSSM over one ('rbf_junk') through the _junk entries: the real-output GP over
+        # the kept columns (`real_output_view`) with the query shift.  That GP also owns the workspace.
+        junk = family == 'rbf_junk'
+        owner = ssm.real_output_view() if junk else ssm
+        model, shift = owner.device_model, ssm.query_shift if junk else 0
+        head = (ctypes.byref(model), ctypes.byref(env)) + ((shift,) if junk else ())
+        suffix, unsupported = ('_junk', FusedJunkUnsupported) if junk else ('', None)
+        if elite_rows is None:
+            # (a query shift > 0 never takes a workspace)
+            P = (actions if noise is None else noise).size(1)
+            ws_bytes = (int(_lib.lib().sx_cem_rollout_workspace_bytes(ctypes.byref(model), x0.size(0), P, horizon))
+                        if shift == 0 else 0)
+            if ws_bytes < 0:
+                raise _lib.SxError('sx_cem_rollout_workspace_bytes: bad arguments')
+            workspace = (_lib.ptr(owner.workspace(ws_bytes)), ws_bytes)   # None on the fused path; cached on the model else
+    return _rollout(suffix, head, x0, horizon, ssm.num_states, ssm.num_actions, 1, unsupported, actions=actions, mean=mean,
+                    std=std, noise=noise, q0=q0, want_traj=want_traj, want_sigma=want_sigma, status=status,
+                    elite_rows=elite_rows, want_dist=want_dist, workspace=workspace)
 
 
 class FusedMultiUnsupported(_lib.SxError):
@@ -152,52 +160,16 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
     library has no single-launch form for the models (before any launch)."""
     if any(getattr(ssm, 'kernel_family', 'rbf') != 'rbf' for ssm in ssms):
         raise FusedMultiUnsupported('the multi-model rollout takes exact RBF GPs (kernel_family "rbf") only')
-    n_s, n_u = ssms[0].num_states, ssms[0].num_actions
     _lib.require_gpu(x0, 'x0')
-    dev = x0.device
     E = x0.size(0)
     if len(ssms) != E:
         raise ValueError(f'{len(ssms)} models for {E} problems')
-    models, tab = (table or GpModelTable()).get(ssms, dev)
-    if noise is not None:
-        P = noise.size(1)
-        actions = torch.empty((E, P, horizon, n_u), dtype=torch.float64, device=dev)
-    else:
-        P = actions.size(1)
-        actions = actions.contiguous()
-    S = n_s + n_s * n_s
-    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
-    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
-    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
-    con = torch.empty((E, P), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.zeros(E, dtype=torch.int32, device=dev)
-    if status.numel() != E:
+    if status is not None and status.numel() != E:
         raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
-    lib = _lib.lib()
-
-    def check(code, what):
-        if code == _lib.SX_ERR_UNSUPPORTED:
-            raise FusedMultiUnsupported(f'{what}: no single-launch form for these models')
-        _lib.check(code, what)
-
-    if elite_rows is not None:
-        k = elite_rows.size(1)
-        if noise is None or tuple(elite_rows.shape) != (E, k, 2 + horizon * n_u) or not elite_rows.is_contiguous():
-            raise ValueError(f'elite_rows must be a contiguous [{E} x k x {2 + horizon * n_u}] tensor and come with noise')
-        m_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
-        s_out = torch.empty((E, horizon, n_u), dtype=torch.float64, device=dev) if want_dist else None
-        check(lib.sx_cem_rollout_elites_multi(models, _lib.ptr(tab), ctypes.byref(env), E, P, horizon,
-                                              _lib.ptr(x0.contiguous()), _lib.ptr(q0), _lib.ptr(elite_rows), k,
-                                              _lib.ptr(noise), _lib.ptr(actions), _lib.ptr(traj), _lib.ptr(sigma),
-                                              _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status), _lib.ptr(m_out),
-                                              _lib.ptr(s_out), _lib.stream_ptr(dev)), 'sx_cem_rollout_elites_multi')
-        return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status, mean=m_out, std=s_out)
-    check(lib.sx_cem_rollout_multi(models, _lib.ptr(tab), ctypes.byref(env), E, P, horizon, _lib.ptr(x0.contiguous()),
-                                   _lib.ptr(q0), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(actions),
-                                   _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                   _lib.stream_ptr(dev)), 'sx_cem_rollout_multi')
-    return dict(actions=actions, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+    models, tab = (table or GpModelTable()).get(ssms, x0.device)
+    return _rollout('_multi', (models, _lib.ptr(tab), ctypes.byref(env)), x0, horizon, ssms[0].num_states,
+                    ssms[0].num_actions, E, FusedMultiUnsupported, actions=actions, mean=mean, std=std, noise=noise, q0=q0,
+                    want_traj=want_traj, want_sigma=want_sigma, status=status, elite_rows=elite_rows, want_dist=want_dist)
 
 
 class FusedJunkUnsupported(_lib.SxError):
@@ -212,7 +184,7 @@ def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candid
     family = getattr(ssm, 'kernel_family', 'rbf')
     if family not in ('rbf', 'rbf_junk'):
         return False
-    if 2 * horizon * ssm.num_actions > 256 * (1 + ssm.num_states):
+    if 2 * horizon * ssm.num_actions > 256 * (1 + ssm.num_states):   # the bound of plan_rollout (csrc/sx_kernels.hip)
         return False
     lib = _lib.lib()
     model = ssm.real_output_view().device_model if family == 'rbf_junk' else ssm.device_model
@@ -384,6 +356,53 @@ def fold_status(words) -> int:
     return out
 
 
+def _cem_iterations(iterations: int, rollout, rank, mean: Tensor, std: Tensor):
+    """The CEM loop of a solve: per iteration `rollout(it, mean, std, rows)`, then `rank(it, rollout)`, whose elite rows
+    (where it skipped the refit: the next rollout refits in its prologue) or refit (mean, std) go to the next iteration.
+    Returns the last ranking (`best`, `best_ok`)."""
+    rows = out = None
+    for it in range(iterations):
+        out = rank(it, rollout(it, mean, std, rows))
+        if out['mean'] is None:
+            rows = out['elite_rows']
+        else:
+            mean, std = out['mean'].view(mean.shape), out['std'].view(std.shape)
+    return out
+
+
+def _check_solve(owner, x0: Tensor, q_block: Optional[Tensor], best: Tensor, best_ok: Tensor, status: Tensor, where: str,
+                 problems):
+    """What follows a FusedCemMpc or MultiModelCemMpc solve: the ONE device->host hand-off, the point-state check, the
+    step-by-step repeat (same draws) of a problem whose status has both SX_STATUS_NAN and SX_STATUS_ZERO_FIX set, and
+    raise_for_status with the failure dump.  `problems`: how the status words group -- (solver, rows) per problem, rows
+    indexing both the status words and the episodes: one problem over all G rank words and E episodes for a single-model
+    solve, (solvers[e], e:e+1) for a multi-model one.  Returns (best, found bool [E] on the host, "a problem repeated")."""
+    words, found, is_nonpoint, best_host = _hand_off(owner, best, best_ok, status, q_block)
+    if is_nonpoint:
+        raise NotImplementedError(f'{where} starts from point states (all-zero Q), as CemSafeMPC.get_action does')
+    statuses = [fold_status(words[r]) for _, r in problems]
+    both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
+    repeated = False
+    for i, (s, r) in enumerate(problems):
+        if (statuses[i] & both) == both and owner._last_noise is not None:
+            # The fused kernel lifts exact-zero variances per particle; the reference decides on the whole batch: with a
+            # zero present it lifts the NEGATIVE variances too and carries on, where the kernel went to sqrt -> NaN
+            # (gp_reachability_pytorch.py:234-243).  Both bits set is the only case in which that can matter: repeat
+            # the solve with the same draws through the step-by-step path, which follows the reference's rule.
+            owner.stepwise_fallbacks += 1
+            repeated = True
+            b, ok, _, st = s.solve(x0[r], noise=owner._last_noise[:, r].contiguous(), stepwise=True)
+            w, found[r], _, best_host[r] = _hand_off(owner, b, ok, st, None)
+            statuses[i] = fold_status(w)
+    for (s, _), st in zip(problems, statuses):
+        s.last_status = st
+    for i, ((s, r), st) in enumerate(zip(problems, statuses)):
+        # (a solver that did not run the checked solve itself holds none of its actions)
+        raise_for_status(st, where if len(problems) == 1 else f'{where} (problem {i})',
+                         dump=lambda s=s, r=r: save_failure_state(s._ssm, x0[r], s._last_actions if s is owner else None))
+    return best_host, found, repeated
+
+
 class FusedCemMpc:
     """Drop-in for ``ConstrainedCemMpc``: ``get_actions(flat_state [1 x S]) -> (actions [H x n_u] | None, rollouts)``.
 
@@ -444,7 +463,7 @@ class FusedCemMpc:
         # a CemSSM that only offers the predict_* surface (JunkDimensionsSSM over a HIP-backed model) is always rolled out
         # step by step: sx_gp_predict through the wrapper + sx_onestep_reach per step, the reference's own call pattern
         self._always_stepwise = getattr(ssm, 'kernel_family', None) == 'stepwise'
-        self.stepwise_fallbacks = 0     # solves repeated through the step-by-step path (see _solve_checked)
+        self.stepwise_fallbacks = 0     # solves repeated through the step-by-step path (see _check_solve)
         self._last_noise = self._last_actions = None
         self._objective_hook = None
         # bench.py sets this to a list: (start, end) torch.cuda.Event pairs are then recorded around every
@@ -546,6 +565,39 @@ class FusedCemMpc:
         return torch.randn((episodes, self._local_rollouts, self._horizon, self._ssm.num_actions), dtype=torch.float64,
                            device=self._device, generator=self._gen)
 
+    def start_distribution(self, x0: Tensor, init_mean: Optional[Tensor] = None,
+                           init_std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The first iteration's sampling distribution (mean, std) [E x H x n_u] from start states x0 [E x n_s]:
+        `init_mean` / `init_std` where given, else the warm start's mean and the constructor's init_std.  (The constant
+        ones are kept between solves: three small launches per solve otherwise, 2 % of a config-2 solve.)"""
+        E, dev, H, n_u = x0.size(0), x0.device, self._horizon, self._ssm.num_actions
+        if init_mean is not None:
+            mean = init_mean.to(dev).reshape(E, H, n_u).clone()
+        elif self._warm_start == 'safe_policy':
+            mean = self.safe_policy_plan(x0).contiguous()
+        else:
+            mean = self._constant('zero_mean', E, dev, lambda: torch.zeros((E, H, n_u), dtype=torch.float64, device=dev))
+        std = (init_std.to(dev).reshape(E, H, n_u).clone() if init_std is not None else
+               self._constant('init_std', E, dev, lambda: self._init_std.to(dev).expand(E, H, n_u).contiguous()))
+        return mean, std
+
+    def _refit_in_prologue(self, episodes: int) -> bool:
+        """`fused_refit_applies` for a solve of this solver's model, over the candidates of an iteration's last ranking
+        launch: the exchanged rows of a sharded solve, the chunks' elite rows of a two-level ranking, else the particles."""
+        chunks = rank_chunks(self._local_rollouts)
+        candidates = (self._world * (self._local_elites + (1 if episodes == 1 else 0)) if self._sharded
+                      else chunks * self._num_elites if chunks > 1 else self._local_rollouts)
+        return fused_refit_applies(self._ssm, episodes, self._local_rollouts, self._horizon, candidates)
+
+    def _rollout_stepwise(self, x0: Tensor, mean: Tensor, std: Tensor, eps: Tensor, status: Tensor):
+        """One iteration's rollout through `cem_rollout_stepwise`, problem by problem."""
+        acts = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x H x n_u]
+        per_e = [cem_rollout_stepwise(self._ssm, self._env, x0[e], acts[e], status=status,
+                                      group=self._group if self._world > 1 else None,
+                                      objective_hook=self._objective_hook) for e in range(x0.size(0))]
+        return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
+                    con_cost=torch.stack([q['con_cost'] for q in per_e]))
+
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None, init_mean: Optional[Tensor] = None,
               init_std: Optional[Tensor] = None, stepwise: bool = False) -> Tuple[Tensor, Tensor, List[Rollouts], Tensor]:
         """E independent solves from x0 [E x n_s] (points).  Nothing here synchronises with the host.
@@ -558,25 +610,11 @@ class FusedCemMpc:
         Returns (best [E x H x n_u], best_ok int32 [E], rollouts per iteration (if recorded), status int32 [G]: the
         status word of every rank, identical on all ranks; G = 1 without a process group -- OR them, `fold_status`).
         """
-        n_u, H = self._ssm.num_actions, self._horizon
-        E = x0.size(0)
-        dev = x0.device
+        n_u, H, E, dev = self._ssm.num_actions, self._horizon, x0.size(0), x0.device
         L = H * n_u
-        # (the constant start distribution and the zeroed status words are kept between solves: three small launches per
-        # solve otherwise, 2 % of a config-2 solve)
-        if init_mean is not None:
-            mean = init_mean.to(dev).reshape(E, H, n_u).clone()
-        elif self._warm_start == 'safe_policy':
-            mean = self.safe_policy_plan(x0).contiguous()
-        else:
-            mean = self._constant('zero_mean', E, dev, lambda: torch.zeros((E, H, n_u), dtype=torch.float64, device=dev))
-        if init_std is not None:
-            std = init_std.to(dev).reshape(E, H, n_u).clone()
-        else:
-            std = self._constant('init_std', E, dev, lambda: self._init_std.to(dev).expand(E, H, n_u).contiguous())
+        mean, std = self.start_distribution(x0, init_mean, init_std)
         status = self._fresh_status(dev)
         history: List[Rollouts] = []
-        out = None
         xch = None
         stepwise = stepwise or self._always_stepwise
         if noise is None and 'sample_noise' not in vars(self):
@@ -586,43 +624,30 @@ class FusedCemMpc:
         self._last_noise, self._last_actions = noise, None
         # From the second iteration on the refit happens in the rollout kernel's prologue, straight from the elite rows of
         # the ranking before it (sx_cem_rollout_elites): the ranking launches then skip their refit tail.
-        chunks = rank_chunks(self._local_rollouts)
-        final_candidates = (self._world * (self._local_elites + (1 if E == 1 else 0)) if self._sharded
-                            else chunks * self._num_elites if chunks > 1 else self._local_rollouts)
-        in_prologue = (not stepwise) and fused_refit_applies(self._ssm, E, self._local_rollouts, H, final_candidates)
-        rows = None
-        for it in range(self._num_iterations):
+        in_prologue = (not stepwise) and self._refit_in_prologue(E)
+        want_traj = self._record or self._objective_hook is not None
+
+        def rollout(it, mean, std, rows):
+            nonlocal stepwise, in_prologue
             eps = noise[it] if noise is not None else self.sample_noise(E)
             if noise is None:
                 self._last_noise = None      # per-iteration draws (a patched sample_noise): nothing to replay
             if self.rollout_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(torch.cuda.current_stream(dev))
-
-            def rollout_stepwise():
-                acts = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x H x n_u]
-                per_e = [cem_rollout_stepwise(self._ssm, self._env, x0[e], acts[e], status=status,
-                                              group=self._group if self._world > 1 else None,
-                                              objective_hook=self._objective_hook) for e in range(E)]
-                return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
-                            con_cost=torch.stack([q['con_cost'] for q in per_e]))
-
             if stepwise:
-                r = rollout_stepwise()
-            elif rows is not None:
-                r = cem_rollout(self._ssm, self._env, x0, H, elite_rows=rows, noise=eps.contiguous(),
-                                want_traj=self._record or self._objective_hook is not None, status=status)
+                r = self._rollout_stepwise(x0, mean, std, eps, status)
             else:
                 try:
-                    r = cem_rollout(self._ssm, self._env, x0, H, mean=mean, std=std, noise=eps.contiguous(),
-                                    want_traj=self._record or self._objective_hook is not None, status=status)
+                    r = cem_rollout(self._ssm, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
+                                    noise=eps.contiguous(), want_traj=want_traj, status=status)
                 except FusedJunkUnsupported:
                     # (answered before any launch) the junk-dimension model has no single-launch form for this training
                     # set: the whole solve goes step by step through the wrapper
                     if it != 0:
                         raise
                     stepwise, in_prologue = True, False
-                    r = rollout_stepwise()
+                    r = self._rollout_stepwise(x0, mean, std, eps, status)
             if self._objective_hook is not None and not stepwise:
                 n_s = self._ssm.num_states
                 centres = r['traj'][..., :n_s]                                   # [E x P x H x n_s]
@@ -633,81 +658,63 @@ class FusedCemMpc:
             if self.rollout_events is not None:
                 ev[1].record(torch.cuda.current_stream(dev))
                 self.rollout_events.append(ev)
-            if not self._sharded:
-                out = cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites,
-                                         want_rows=in_prologue, want_refit=not in_prologue)
-            else:
-                k = self._local_elites
-                if xch is None:
-                    xch = self._exchange(E, k, L, dev)
-                timed = self.exchange_events is not None and self._exchanges_seen % self.exchange_event_stride == 0
-                self._exchanges_seen += 1
-                if timed:   # four marks: before the local ranking | before the collective | after it | after the global ranking
-                    xev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-                    xev[0].record(torch.cuda.current_stream(dev))
-                if E == 1:
-                    # the local elite rows go straight into this rank's slot: no copy between the kernel and the collective
-                    cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], k, want_refit=False,
-                                       rows_out=xch.local_slot(it))
-                else:
-                    local = cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], k, want_rows=True, want_refit=False)
-                    xch.local_slot(it).copy_(local['elite_rows'])
-                last = it == self._num_iterations - 1
-                if timed:
-                    xev[1].record(torch.cuda.current_stream(dev))
-                # the ONE collective of the iteration; on the last one the status words of all ranks ride along
-                # (every rollout of this solve has been enqueued by then)
-                cand, words = xch.exchange(it, status if last else None)
-                if timed:
-                    xev[2].record(torch.cuda.current_stream(dev))
-                if last:
-                    status = words
-                flat = cand.reshape(-1)
-                out = cem_rank_refit(flat, flat[1:], flat[2:], self._num_elites, cost_stride=2 + L,
-                                     act_stride=2 + L, row_len=L, num_candidates=xch.candidates, num_problems=E,
-                                     want_rows=in_prologue, want_refit=not in_prologue)
-                if timed:
-                    xev[3].record(torch.cuda.current_stream(dev))
-                    self.exchange_events.append(xev)
-            if in_prologue:
-                rows = out['elite_rows']
-            else:
-                mean, std = out['mean'].view(E, H, n_u), out['std'].view(E, H, n_u)
             self._last_actions = r['actions']
             if self._record and r['traj'] is not None:
                 for e in range(E):
                     history.append(Rollouts(r['traj'][e], r['actions'][e], r['obj_cost'][e], r['con_cost'][e]))
+            return r
+
+        def rank(it, r):
+            nonlocal xch, status
+            if not self._sharded:
+                return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites,
+                                          want_rows=in_prologue, want_refit=not in_prologue)
+            k = self._local_elites
+            if xch is None:
+                xch = self._exchange(E, k, L, dev)
+            timed = self.exchange_events is not None and self._exchanges_seen % self.exchange_event_stride == 0
+            self._exchanges_seen += 1
+            if timed:   # four marks: before the local ranking | before the collective | after it | after the global ranking
+                xev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                xev[0].record(torch.cuda.current_stream(dev))
+            if E == 1:
+                # the local elite rows go straight into this rank's slot: no copy between the kernel and the collective
+                cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], k, want_refit=False,
+                                   rows_out=xch.local_slot(it))
+            else:
+                local = cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], k, want_rows=True, want_refit=False)
+                xch.local_slot(it).copy_(local['elite_rows'])
+            last = it == self._num_iterations - 1
+            if timed:
+                xev[1].record(torch.cuda.current_stream(dev))
+            # the ONE collective of the iteration; on the last one the status words of all ranks ride along
+            # (every rollout of this solve has been enqueued by then)
+            cand, words = xch.exchange(it, status if last else None)
+            if timed:
+                xev[2].record(torch.cuda.current_stream(dev))
+            if last:
+                status = words
+            flat = cand.reshape(-1)
+            out = cem_rank_refit(flat, flat[1:], flat[2:], self._num_elites, cost_stride=2 + L,
+                                 act_stride=2 + L, row_len=L, num_candidates=xch.candidates, num_problems=E,
+                                 want_rows=in_prologue, want_refit=not in_prologue)
+            if timed:
+                xev[3].record(torch.cuda.current_stream(dev))
+                self.exchange_events.append(xev)
+            return out
+
+        out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
         return out['best'].view(E, H, n_u), out['best_ok'], history, status
 
     def _solve_checked(self, x0: Tensor, where: str, q_block: Optional[Tensor] = None):
-        """`solve` + the ONE device->host hand-off of a solve + the reference's failure behaviour.  The hand-off carries the
-        status words, the feasibility flags, the selected actions and "is any entry of `q_block` non-zero" (the callers'
-        point-state check, evaluated on the device and read here instead of in a synchronisation of its own before the
-        solve).  Returns (best [E x H x n_u] ON THE HOST, found bool [E] on the host, rollouts)."""
+        """`solve` + `_check_solve`, whose one hand-off also carries "is any entry of `q_block` non-zero" (the callers'
+        point-state check, made on the device).  Returns (best [E x H x n_u] ON THE HOST, found bool [E] on the host,
+        rollouts)."""
         if q_block is not None and not q_block.is_contiguous():
             q_block = q_block.contiguous()
-
-        def hand_off(best, best_ok, status):
-            return _hand_off(self, best, best_ok, status, q_block)
-
         best, best_ok, history, status = self.solve(x0)
-        words, found, is_nonpoint, best_host = hand_off(best, best_ok, status)
-        if is_nonpoint:
-            raise NotImplementedError(f'{where} starts from point states (all-zero Q), as CemSafeMPC.get_action does')
-        self.last_status = fold_status(words)
-        both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
-        if (self.last_status & both) == both and self._last_noise is not None:
-            # The fused kernel lifts exact-zero variances per particle; the reference decides on the whole batch: with a
-            # zero present it lifts the NEGATIVE variances too and carries on, where the kernel went to sqrt -> NaN
-            # (gp_reachability_pytorch.py:234-243).  Both bits set is the only case in which that can matter: repeat
-            # the solve with the same draws through the step-by-step path, which follows the reference's rule.
-            self.stepwise_fallbacks += 1
-            best, best_ok, history, status = self.solve(x0, noise=self._last_noise, stepwise=True)
-            words, found, _, best_host = hand_off(best, best_ok, status)
-            self.last_status = fold_status(words)
-        raise_for_status(self.last_status, where,
-                         dump=lambda: save_failure_state(self._ssm, x0, self._last_actions))
-        return best_host, found, history
+        best_host, found, repeated = _check_solve(self, x0, q_block, best, best_ok, status, where, [(self, slice(None))])
+        return best_host, found, [] if repeated else history     # (a step-by-step solve records no rollouts)
 
     def get_actions_batch(self, states: Tensor) -> Tuple[Tensor, Tensor, List[Rollouts]]:
         """E independent episodes at once (BASELINE config 5): flat start states [E x (n_s + n_s^2)], all
@@ -745,7 +752,7 @@ class MultiModelCemMpc:
     unless given): it supplies the problem's noise draws and warm start, so a multi-model solve samples exactly what E
     sequential ``get_actions`` calls would, and it takes over where the single launch does not apply -- a model that is not
     an exact RBF GP, a training set that needs the workspace path (one solve per model then), and the per-problem
-    step-by-step repeat of ``FusedCemMpc._solve_checked``.  The problems share `env` and the CEM settings; sharded
+    step-by-step repeat of ``_check_solve``.  The problems share `env` and the CEM settings; sharded
     (multi-GPU) multi-model solves are out of scope.
     """
 
@@ -763,24 +770,56 @@ class MultiModelCemMpc:
             solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
                                    seed=seed + e, init_std=init_std, warm_start=warm_start)
                        for e, ssm in enumerate(self._ssms)]
-        if len(solvers) != len(self._ssms):
-            raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models')
+        if len(solvers) != len(self._ssms) or any(
+                (s._horizon, s._num_rollouts, s._num_elites, s._num_iterations, s._sharded)
+                != (time_horizon, num_rollouts, num_elites, num_iterations, False) for s in solvers):
+            raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: one per model, unsharded, with this '
+                             f'solve\'s horizon, particles, elites and iterations')
         self._solvers = list(solvers)
         self._env = env
         self._horizon = time_horizon
-        self._num_rollouts = num_rollouts
         self._num_elites = num_elites
         self._num_iterations = num_iterations
         self._device = self._solvers[0]._device
         self._table = GpModelTable()
         self._last_noise = None
-        self.last_status = [0] * len(self._ssms)
         self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path
         self.per_model_solves = 0       # solves that went one model at a time (single launch not applicable)
+
+    @classmethod
+    def from_solvers(cls, solvers: Sequence[FusedCemMpc]) -> 'MultiModelCemMpc':
+        """The multi-model solve over existing single-model solvers, solvers[e] for problem e, with their settings (which
+        `check_solvers` compares)."""
+        first = solvers[0]
+        return cls([s._ssm for s in solvers], first._env, first._horizon, first._num_rollouts, first._num_elites,
+                   first._num_iterations, device=first._device, solvers=solvers)
+
+    @staticmethod
+    def check_solvers(solvers: Sequence) -> None:
+        """ValueError unless the solvers share the CEM settings and the environment constants (sx_env).  (Read with
+        defaults: an injected optimiser need not be a FusedCemMpc.)"""
+        def settings(m):
+            init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
+            names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world')
+            return ((type(m),) + tuple(getattr(m, a, None) for a in names)
+                    + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
+
+        (cem0, env0), *rest = [settings(m) for m in solvers]
+        for cem, env in rest:
+            if cem != cem0:
+                raise ValueError('the solvers of a multi-model solve must share the CEM settings (horizon, rollouts, '
+                                 'elites, iterations, initial distribution, device)')
+            if env != env0:
+                raise ValueError('the solvers of a multi-model solve must share the environment constants (sx_env)')
 
     @property
     def solvers(self) -> List[FusedCemMpc]:
         return self._solvers
+
+    @property
+    def last_status(self) -> List[int]:
+        """The status word of every problem's last solve."""
+        return [s.last_status for s in self._solvers]
 
     def set_env(self, env: _lib.SxEnv) -> None:
         self._env = env
@@ -799,38 +838,28 @@ class MultiModelCemMpc:
         noise: optional [iters x E x P x H x n_u] standard normals; by default problem e draws from solvers[e].
         Returns (best [E x H x n_u], best_ok int32 [E], status int32 [E]: one word per problem).
         Raises FusedMultiUnsupported (before any launch) where the single launch does not apply."""
-        E, H, n_u = len(self._ssms), self._horizon, self._ssms[0].num_actions
-        n_s = self._ssms[0].num_states
-        dev = x0.device
+        E, H, n_s, n_u = len(self._ssms), self._horizon, self._ssms[0].num_states, self._ssms[0].num_actions
         if x0.shape != (E, n_s):
             raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
         if noise is None:
             noise = torch.stack([s._next_noise(1)[:, 0] for s in self._solvers], dim=1)
         self._last_noise = noise
-        mean = torch.cat([s.safe_policy_plan(x0[e:e + 1]) if s._warm_start == 'safe_policy'
-                          else torch.zeros((1, H, n_u), dtype=torch.float64, device=dev)
-                          for e, s in enumerate(self._solvers)]).contiguous()
-        std = torch.stack([s._init_std.to(dev).expand(H, n_u) for s in self._solvers]).contiguous()
-        status = torch.zeros(E, dtype=torch.int32, device=dev)
-        P = self._num_rollouts
-        chunks = rank_chunks(P)
-        in_prologue = (2 * H * n_u <= 256 * (1 + n_s)
-                       and int(_lib.lib().sx_cem_rank_counts(E, chunks * self._num_elites if chunks > 1 else P)) == 1)
-        rows, out = None, None
-        for it in range(self._num_iterations):
-            eps = noise[it].contiguous()
-            if rows is not None:
-                r = cem_rollout_multi(self._ssms, self._env, x0, H, elite_rows=rows, noise=eps, status=status,
-                                      table=self._table)
-            else:
-                r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, noise=eps, status=status,
-                                      table=self._table)
-            out = cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites,
-                                     want_rows=in_prologue, want_refit=not in_prologue)
-            if in_prologue:
-                rows = out['elite_rows']
-            else:
-                mean, std = out['mean'].view(E, H, n_u), out['std'].view(E, H, n_u)
+        starts = [s.start_distribution(x0[e:e + 1]) for e, s in enumerate(self._solvers)]
+        mean, std = torch.cat([m for m, _ in starts]), torch.cat([sd for _, sd in starts])
+        status = torch.zeros(E, dtype=torch.int32, device=x0.device)
+        # (solver 0 stands for all: the solvers share this solve's settings, and a model on the workspace path has no
+        # multi-model launch at all)
+        in_prologue = self._solvers[0]._refit_in_prologue(E)
+
+        def rollout(it, mean, std, rows):
+            return cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
+                                     noise=noise[it].contiguous(), status=status, table=self._table)
+
+        def rank(it, r):
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites, want_rows=in_prologue,
+                                      want_refit=not in_prologue)
+
+        out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
         return out['best'].view(E, H, n_u), out['best_ok'], status
 
     def get_actions_multi(self, states: Tensor, where: str = 'get_actions_multi') -> Tuple[Tensor, Tensor]:
@@ -847,24 +876,8 @@ class MultiModelCemMpc:
             # one solve per model, each with its own checks (and its own step-by-step repeat)
             self.per_model_solves += 1
             per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1]) for e, s in enumerate(self._solvers)]
-            self.last_status = [s.last_status for s in self._solvers]
             return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
         best, best_ok, status = self.solve(x0)
-        words, found, is_nonpoint, best_host = _hand_off(self, best, best_ok, status, q_block)
-        if is_nonpoint:
-            raise NotImplementedError(f'{where} starts from point states (all-zero Q), as CemSafeMPC.get_action does')
-        self.last_status = [int(w) for w in words.tolist()]
-        both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
-        for e, s in enumerate(self._solvers):
-            if (self.last_status[e] & both) == both:
-                # FusedCemMpc._solve_checked's repeat, for this problem alone and with its own draws
-                self.stepwise_fallbacks += 1
-                b, ok, _, st = s.solve(x0[e:e + 1], noise=self._last_noise[:, e:e + 1].contiguous(), stepwise=True)
-                w, f, _, bh = _hand_off(self, b, ok, st, None)
-                self.last_status[e] = fold_status(w)
-                found[e], best_host[e] = f[0], bh[0]
-        for e, s in enumerate(self._solvers):
-            s.last_status = self.last_status[e]
-            raise_for_status(self.last_status[e], f'{where} (problem {e})',
-                             dump=lambda e=e: save_failure_state(self._ssms[e], x0[e:e + 1], None))
+        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
+                                           [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
         return best_host, found

@@ -467,28 +467,14 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
             s._batch_last_actions = [np.empty((0, n_u))]
             s._batch_executed = [0]
     mpcs = [s._solver() for s in solvers]
-    def settings(m):
-        init = getattr(m, '_init_std', None)
-        return (type(m),) + tuple(getattr(m, a, None) for a in ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations',
-                                                                 '_warm_start', '_device', '_world')) + \
-            (None if init is None else tuple(init.reshape(-1).tolist()),)
-
-    first = settings(mpcs[0])
-    env_bytes = bytes(mpcs[0]._env) if getattr(mpcs[0], '_env', None) is not None else None
-    for m in mpcs[1:]:
-        if settings(m) != first:
-            raise ValueError('the solvers of get_actions_multi must share the CEM settings (horizon, rollouts, elites, '
-                             'iterations, initial distribution, device)')
-        if (bytes(m._env) if getattr(m, '_env', None) is not None else None) != env_bytes:
-            raise ValueError('the solvers of get_actions_multi must share the environment constants (sx_env)')
+    MultiModelCemMpc.check_solvers(mpcs)
     flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
     if (all(isinstance(m, FusedCemMpc) and m._objective_hook is None and m._world == 1 for m in mpcs)
             and all(getattr(m._ssm, 'kernel_family', None) == 'rbf' for m in mpcs)):
         key = tuple(id(m) for m in mpcs)
         cached = getattr(solvers[0], '_multi', None)
-        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1]._solvers, mpcs)):
-            multi = MultiModelCemMpc([m._ssm for m in mpcs], mpcs[0]._env, *first[1:5], solvers=mpcs)
-            solvers[0]._multi = cached = (key, multi)
+        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
+            solvers[0]._multi = cached = (key, MultiModelCemMpc.from_solvers(mpcs))
         multi = cached[1]
         multi._env = mpcs[0]._env
         best, found = multi.get_actions_multi(flat)
