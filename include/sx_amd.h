@@ -125,6 +125,23 @@ int sx_cem_rollout_feat(const sx_feat_model* model, const sx_env* env, int E, in
                         const double* mean, const double* std, const double* noise, double* actions, double* traj,
                         double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
 
+/* sx_cem_rollout_feat for a JunkDimensionsSSM over such a GP: as sx_cem_rollout_junk for the exact RBF GP.  The junk
+ * columns reach the features only through the network's first layer (phi = z for the linear kernel), so the padded GP's
+ * real outputs are those of the GP over the D = n_s + n_u + s kept columns (training rows [x, u, 0_s], queries [x, 0_s, u],
+ * s = query_shift = min(J_s, n_u)); for the linear kernel A_d splits into a kept and a junk block and the kept block is the
+ * fit on the kept features with the same lambda_d.  `model` is that GP (model->n_s == env->n_s, model->n_u == env->n_u +
+ * query_shift, fitted by sx_feat_fit on the kept columns); `env` and every buffer are shaped by (n_s, n_u) as in
+ * sx_cem_rollout_feat; the reachability step receives the Jacobian's leading n_s + n_u columns.
+ *   query_shift 0 .. env->n_u; 0 is sx_cem_rollout_feat itself.
+ * SX_ERR_ARG (before any device access) for null pointers, non-positive sizes, inconsistent shapes or a shift outside that
+ * range; SX_ERR_UNSUPPORTED for a shape that is not instantiated: (n_s, n_u, s) in (1,1,1) (2,1,1) (3,1,1) (2,2,1) (2,2,2)
+ * (3,2,1), the shapes a padded model with n_s + J_s <= SX_MAX_NS and n_u + J_a <= SX_MAX_NU has.
+ * sx_feat_features and sx_feat_fit take that model too (any n_u with n_s + n_u <= SX_MAX_D); sx_feat_predict does not. */
+int sx_cem_rollout_feat_junk(const sx_feat_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                             const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                             double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                             int32_t* status, void* stream);
+
 /* ---- MC-dropout state-space models: ssm_cem/dropout_ssm_cem.py, gal_concrete_dropout.py ----
  * An ensemble of S thinned ReLU networks: dropout masks drawn once per (re)training and held fixed, prediction = mean and
  * unbiased variance over the members, mean Jacobian by reverse sweeps.  One or two hidden layers of <= 64 units run on the
@@ -151,6 +168,16 @@ int sx_mlp_predict(const sx_mlp_model* model, const double* z, int P, double* me
 int sx_cem_rollout_mlp(const sx_mlp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                        const double* mean, const double* std, const double* noise, double* actions, double* traj,
                        double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
+
+/* sx_cem_rollout_mlp for a JunkDimensionsSSM over an MC-dropout model, as sx_cem_rollout_feat_junk: the junk columns reach
+ * the network only through its first layer, so `model` is the ensemble over the D = n_s + n_u + query_shift kept columns
+ * (first-layer weight columns and input-mask columns of those), with the mean rows [0, n_s) of the output layer and, with
+ * predict_std, the log-std rows [n_s + J_s, n_s + J_s + n_s) as rows [n_s, 2 n_s).  Same checks and shapes as
+ * sx_cem_rollout_feat_junk; query_shift 0 is sx_cem_rollout_mlp itself; SX_MLP_PATH=valu applies as there. */
+int sx_cem_rollout_mlp_junk(const sx_mlp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                            const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                            double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                            int32_t* status, void* stream);
 
 /* Optional kernel timer -- measurement support, not part of the reference's surface (it has no profiler: SURVEY.md 5).
  * While enabled, the launches of the path's kernels (every `sx_profile_stride`-th of each kind) carry a start and a stop HIP

@@ -80,6 +80,8 @@ SIGNATURES = {
     'sx_cem_rollout_feat': (c_int, [POINTER(SxFeatModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 12),
     'sx_mlp_predict': (c_int, [POINTER(SxMlpModel), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sx_cem_rollout_mlp': (c_int, [POINTER(SxMlpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 12),
+    'sx_cem_rollout_feat_junk': (c_int, [POINTER(SxFeatModel), POINTER(SxEnv), c_int, c_int, c_int, c_int] + [c_void_p] * 12),
+    'sx_cem_rollout_mlp_junk': (c_int, [POINTER(SxMlpModel), POINTER(SxEnv), c_int, c_int, c_int, c_int] + [c_void_p] * 12),
     'sx_onestep_reach': (c_int, [POINTER(SxEnv), c_int] + [c_void_p] * 11),
     'sx_polytope_distance': (c_int, [POINTER(SxEnv), c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                      c_void_p]),

@@ -89,12 +89,17 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     _lib.require_gpu(x0, 'x0')
     family = getattr(ssm, 'kernel_family', 'rbf')
     workspace, unsupported = (), None
-    if family in ('feature', 'mlp'):
+    if family in ('feature', 'mlp', 'feature_junk', 'mlp_junk'):
         # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
         # 'mlp': MC-dropout ensembles over the frozen members, matrix cores for 1-2 hidden layers of <= 64 units
         # (csrc/sx_mlp_mfma.hpp), one particle per lane otherwise (csrc/sx_mlp.hpp).  Neither has an elite-row form.
-        suffix, model = ('_feat', ssm.feat_model) if family == 'feature' else ('_mlp', ssm.mlp_model)
-        head, elite_rows = (ctypes.byref(model), ctypes.byref(env)), None
+        # JunkDimensionsSSM over one ('feature_junk', 'mlp_junk'): the _junk entries over the kept-column model
+        # (`real_output_view`) with the query shift.
+        junk = family.endswith('_junk')
+        owner = ssm.real_output_view() if junk else ssm
+        suffix, model = ('_feat', owner.feat_model) if family.startswith('feature') else ('_mlp', owner.mlp_model)
+        head, elite_rows = (ctypes.byref(model), ctypes.byref(env)) + ((ssm.query_shift,) if junk else ()), None
+        suffix += '_junk' if junk else ''
     else:
         # exact RBF GP ('rbf'); JunkDimensionsSSM over one ('rbf_junk') through the _junk entries: the real-output GP over
         # the kept columns (`real_output_view`) with the query shift.  That GP also owns the workspace.
@@ -180,7 +185,8 @@ def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candid
     """May the elite refit move from the ranking kernel's tail into the next rollout's prologue (sx_cem_rollout_elites)?
     Exact-GP models on the single-launch path whose H n_u means and standard deviations fit the prologue's scratch, where
     the ranking that produces the rows (over `candidates` rows per problem; default: the particles) is the counting one.
-    (JunkDimensionsSSM over an exact GP, 'rbf_junk': the same for its real-output GP, sx_cem_rollout_elites_junk.)"""
+    (JunkDimensionsSSM over an exact GP, 'rbf_junk': the same for its real-output GP, sx_cem_rollout_elites_junk.)
+    The feature-GP and MC-dropout families, 'feature_junk' and 'mlp_junk' included, have no elite-row form: False."""
     family = getattr(ssm, 'kernel_family', 'rbf')
     if family not in ('rbf', 'rbf_junk'):
         return False

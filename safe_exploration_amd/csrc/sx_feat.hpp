@@ -337,10 +337,15 @@ struct FeatRolloutPtrs {
     int E, P, H;
 };
 
-template <int NS, int NU>
+// SH > 0 (sx_cem_rollout_feat_junk): the GP's inputs are D = NS + NU + SH columns -- training rows [x, u, 0_SH], queries
+// [p, 0_SH, u] -- while the reachability and the costs see (NS, NU) and the Jacobian's leading NS + NU columns (the
+// feature-GP form of JunkDimensionsSSM).  SH = 0 is the plain rollout.
+template <int NS, int NU, int SH = 0>
 __global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(FeatConst fc, ReachConst<NS, NU> rc,
                                                                      CostConst<SX_MAX_M, NS, NU> cc, FeatRolloutPtrs rp) {
-    constexpr int D = NS + NU;
+    constexpr int D = NS + NU + SH;
+    constexpr int UC = NS + SH;   // first action column of a query row
+    static_assert(D <= SX_MAX_D, "the feature network's first layer holds at most SX_MAX_D inputs");
     constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double feat_smem[];
     const int lane = threadIdx.x;
@@ -377,10 +382,22 @@ __global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(FeatConst f
 #pragma unroll
         for (int j = 0; j < NS; ++j) z[j] = p[j];
 #pragma unroll
-        for (int c = 0; c < NU; ++c) z[NS + c] = u[c];
+        for (int j = NS; j < UC; ++j) z[j] = 0.0;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) z[UC + c] = u[c];
         if (have_q) {
             feat_gp_predict<NS, D, true>(fc, z, feat_smem, lane, mean, var, jac);
-            reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+            if constexpr (SH == 0) {
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+            } else {
+                // [A | B]: the derivatives by the TRAINING rows' state and action columns (the reference's padding)
+                double jab[NS][NS + NU];
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+#pragma unroll
+                    for (int j = 0; j < NS + NU; ++j) jab[i][j] = jac[i][j];
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jab, p1, Q1, st);
+            }
         } else {
             feat_gp_predict<NS, D, false>(fc, z, feat_smem, lane, mean, var, jac);
             reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);

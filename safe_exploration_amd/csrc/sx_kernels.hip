@@ -780,7 +780,25 @@ static int launch_feat_predict(const sx_feat_model* m, const double* z, int P, d
     return check_launch();
 }
 
-template <int NS, int NU>
+// (n_s, n_u, query shift > 0) of sx_cem_rollout_feat_junk and sx_cem_rollout_mlp_junk: X(NS, NU, SH, ...) for every shape a
+// padded feature-GP or MC-dropout model can be built for (n_s + J_s <= SX_MAX_NS, n_u + J_a <= SX_MAX_NU, SH = min(J_s, n_u));
+// shift 0 is the shapes of sx_cem_rollout_feat / sx_cem_rollout_mlp.  ssm_cem.JUNK_MODEL_FUSED_SHAPES mirrors this list.
+#define SX_MODEL_JUNK_SHAPES(X, ...)                                                                                    \
+    X(1, 1, 1, __VA_ARGS__) X(2, 1, 1, __VA_ARGS__) X(3, 1, 1, __VA_ARGS__) X(2, 2, 1, __VA_ARGS__)                     \
+    X(2, 2, 2, __VA_ARGS__) X(3, 2, 1, __VA_ARGS__)
+// return CALL(NS, NU, SH) for the shape (ns, nu, sh): SX_DISPATCH's shapes with SH = 0 for sh = 0, the list above else
+#define SX_MODEL_JUNK_ONE(NS, NU, SH, ns, nu, sh, CALL) \
+    if ((ns) == NS && (nu) == NU && (sh) == SH) return CALL(NS, NU, SH);
+#define SX_MODEL_JUNK_DISPATCH(ns, nu, sh, CALL)                             \
+    do {                                                                     \
+        if ((sh) == 0) {                                                     \
+            SX_DISPATCH(ns, nu, CALL##_0);                                   \
+        }                                                                    \
+        SX_MODEL_JUNK_SHAPES(SX_MODEL_JUNK_ONE, ns, nu, sh, CALL)            \
+        return SX_ERR_UNSUPPORTED;                                           \
+    } while (0)
+
+template <int NS, int NU, int SH = 0>
 static int launch_rollout_feat(const sx_feat_model* m, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
     const FeatConst fc = make_feat_const(m);
     ReachConst<NS, NU> rc;
@@ -788,9 +806,9 @@ static int launch_rollout_feat(const sx_feat_model* m, const sx_env* env, const 
     CostConst<SX_MAX_M, NS, NU> cc;
     make_cost_const<NS, NU>(env, cc);
     const size_t lds = kFeatLdsDoubles * sizeof(double);
-    if (int r = allow_lds(cem_rollout_feat_kernel<NS, NU>, lds)) return r;
+    if (int r = allow_lds(cem_rollout_feat_kernel<NS, NU, SH>, lds)) return r;
     const int64_t total = (int64_t)rp.E * rp.P;
-    launch(SX_PROF_ROLLOUT_FEAT, cem_rollout_feat_kernel<NS, NU>, dim3((unsigned)((total + kFeatWave - 1) / kFeatWave)),
+    launch(SX_PROF_ROLLOUT_FEAT, cem_rollout_feat_kernel<NS, NU, SH>, dim3((unsigned)((total + kFeatWave - 1) / kFeatWave)),
            dim3(kFeatWave), lds, stream, fc, rc, cc, rp);
     return check_launch();
 }
@@ -833,18 +851,19 @@ static int launch_mlp_predict(const sx_mlp_model* m, const double* z, int P, dou
     return check_launch();
 }
 
-template <int NS, int NU, int L, bool FULL>
+template <int NS, int NU, int L, bool FULL, int SH>
 static int launch_rollout_mlp_mfma(const MlpConst& mc, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
                                    const FeatRolloutPtrs& rp, hipStream_t stream) {
-    const size_t lds = (size_t)MmLds<NS, NS + NU>::total * sizeof(double);
-    if (int r = allow_lds(cem_rollout_mlp_mfma_kernel<NS, NU, L, FULL>, lds)) return r;
+    const size_t lds = (size_t)MmLds<NS, NS + NU + SH>::total * sizeof(double);
+    if (int r = allow_lds(cem_rollout_mlp_mfma_kernel<NS, NU, L, FULL, SH>, lds)) return r;
     const int64_t total = (int64_t)rp.E * rp.P;
-    launch(SX_PROF_ROLLOUT_MLP, cem_rollout_mlp_mfma_kernel<NS, NU, L, FULL>, dim3((unsigned)((total + kMmTile - 1) / kMmTile)),
+    launch(SX_PROF_ROLLOUT_MLP, cem_rollout_mlp_mfma_kernel<NS, NU, L, FULL, SH>,
+           dim3((unsigned)((total + kMmTile - 1) / kMmTile)),
            dim3(kMmThreads), lds, stream, mc, rc, cc, rp);
     return check_launch();
 }
 
-template <int NS, int NU>
+template <int NS, int NU, int SH = 0>
 static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
     const MlpConst mc = make_mlp_const(m);
     ReachConst<NS, NU> rc;
@@ -854,15 +873,15 @@ static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const Fe
     if (mlp_use_mfma(mc)) {
         const bool full = mlp_mfma_full(mc);
         if (mc.n_hidden == 1)
-            return full ? launch_rollout_mlp_mfma<NS, NU, 1, true>(mc, rc, cc, rp, stream)
-                        : launch_rollout_mlp_mfma<NS, NU, 1, false>(mc, rc, cc, rp, stream);
-        return full ? launch_rollout_mlp_mfma<NS, NU, 2, true>(mc, rc, cc, rp, stream)
-                    : launch_rollout_mlp_mfma<NS, NU, 2, false>(mc, rc, cc, rp, stream);
+            return full ? launch_rollout_mlp_mfma<NS, NU, 1, true, SH>(mc, rc, cc, rp, stream)
+                        : launch_rollout_mlp_mfma<NS, NU, 1, false, SH>(mc, rc, cc, rp, stream);
+        return full ? launch_rollout_mlp_mfma<NS, NU, 2, true, SH>(mc, rc, cc, rp, stream)
+                    : launch_rollout_mlp_mfma<NS, NU, 2, false, SH>(mc, rc, cc, rp, stream);
     }
     const size_t lds = mlp_lds_doubles(mc.n_hidden, mc.wmax) * sizeof(double);
-    if (int r = allow_lds(cem_rollout_mlp_kernel<NS, NU>, lds)) return r;
+    if (int r = allow_lds(cem_rollout_mlp_kernel<NS, NU, SH>, lds)) return r;
     const int64_t total = (int64_t)rp.E * rp.P;
-    launch(SX_PROF_ROLLOUT_MLP, cem_rollout_mlp_kernel<NS, NU>, dim3((unsigned)((total + kMlpLanes - 1) / kMlpLanes)),
+    launch(SX_PROF_ROLLOUT_MLP, cem_rollout_mlp_kernel<NS, NU, SH>, dim3((unsigned)((total + kMlpLanes - 1) / kMlpLanes)),
            dim3(kMlpLanes), lds, stream, mc, rc, cc, rp);
     return check_launch();
 }
@@ -1316,8 +1335,10 @@ int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, co
     return cem_rollout_multi(models, table, env, rp, stream);
 }
 
-static bool feat_model_ok(const sx_feat_model* m) {
-    if (!m || m->n_s <= 0 || m->n_s > SX_MAX_NS || m->n_u <= 0 || m->n_u > SX_MAX_NU) return false;
+// wide: the kept-column model of sx_cem_rollout_feat_junk, n_u = real actions + query shift, n_s + n_u <= SX_MAX_D
+static bool feat_model_ok(const sx_feat_model* m, bool wide = false) {
+    if (!m || m->n_s <= 0 || m->n_s > SX_MAX_NS || m->n_u <= 0) return false;
+    if (m->n_u > (wide ? SX_MAX_D - m->n_s : SX_MAX_NU)) return false;
     if (m->n_layers < 0 || m->n_layers > SX_FEAT_MAX_LAYERS || m->n_feat <= 0 || m->n_feat > SX_FEAT_MAX_WIDTH) return false;
     if (m->width[0] != m->n_s + m->n_u) return false;
     for (int l = 1; l <= m->n_layers; ++l)
@@ -1327,7 +1348,7 @@ static bool feat_model_ok(const sx_feat_model* m) {
 }
 
 int sx_feat_features(const sx_feat_model* model, const double* x, int N, double* phi, void* stream) {
-    if (!feat_model_ok(model) || N < 0) return SX_ERR_ARG;
+    if (!feat_model_ok(model, true) || N < 0) return SX_ERR_ARG;
     if (N == 0) return SX_OK;
     if (!x || !phi) return SX_ERR_ARG;
     const sx::FeatConst fc = sx::make_feat_const(model);
@@ -1346,7 +1367,7 @@ int sx_feat_features(const sx_feat_model* model, const double* x, int N, double*
 
 int sx_feat_fit(const sx_feat_model* model, const double* phi, const double* y, int N, const double* lambda, double* wbar,
                 double* minv, double* stats, int32_t* status, void* stream) {
-    if (!feat_model_ok(model) || !phi || !y || N <= 0 || !lambda || !wbar || !minv || !stats || !status) return SX_ERR_ARG;
+    if (!feat_model_ok(model, true) || !phi || !y || N <= 0 || !lambda || !wbar || !minv || !stats || !status) return SX_ERR_ARG;
     sx::FeatFitArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.phi = phi;
@@ -1375,19 +1396,38 @@ int sx_feat_predict(const sx_feat_model* model, const double* z, int P, double* 
 int sx_cem_rollout_feat(const sx_feat_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                         const double* mean, const double* std, const double* noise, double* actions, double* traj,
                         double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
-    if (!feat_model_ok(model) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
+    return sx_cem_rollout_feat_junk(model, env, 0, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost,
+                                    status, stream);
+}
+
+// query shift 0 .. env->n_u; the model over n_s + n_u + shift columns (the plain model for shift 0)
+static bool junk_env_ok(const sx_env* env, int model_ns, int model_nu, int query_shift) {
+    if (!env || env->n_s <= 0 || env->n_s > SX_MAX_NS || env->n_u <= 0 || env->n_u > SX_MAX_NU) return false;
+    if (query_shift < 0 || query_shift > env->n_u) return false;
+    return model_ns == env->n_s && model_nu == env->n_u + query_shift;
+}
+
+int sx_cem_rollout_feat_junk(const sx_feat_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                             const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                             double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                             int32_t* status, void* stream) {
+    if (!feat_model_ok(model, query_shift > 0) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
     if (!model->wbar || !model->minv || E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
     if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
+    if (!junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
     if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
     sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-#define CALL(NS, NU) sx::launch_rollout_feat<NS, NU>(model, env, rp, (hipStream_t)stream)
-    SX_DISPATCH(model->n_s, model->n_u, CALL);
+#define CALL(NS, NU, SH) sx::launch_rollout_feat<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
+#define CALL_0(NS, NU) CALL(NS, NU, 0)
+    SX_MODEL_JUNK_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
+#undef CALL_0
 #undef CALL
 }
 
-static bool mlp_model_ok(const sx_mlp_model* m) {
-    if (!m || m->n_s <= 0 || m->n_s > SX_MAX_NS || m->n_u <= 0 || m->n_u > SX_MAX_NU) return false;
+// wide: the kept-column model of sx_cem_rollout_mlp_junk, n_u = real actions + query shift, n_s + n_u <= SX_MAX_D
+static bool mlp_model_ok(const sx_mlp_model* m, bool wide = false) {
+    if (!m || m->n_s <= 0 || m->n_s > SX_MAX_NS || m->n_u <= 0) return false;
+    if (m->n_u > (wide ? SX_MAX_D - m->n_s : SX_MAX_NU)) return false;
     if (m->n_hidden < 0 || m->n_hidden > SX_MLP_MAX_HIDDEN || m->n_out < m->n_s || m->n_samples <= 0) return false;
     if (m->predict_std && m->n_out < 2 * m->n_s) return false;
     if (m->width[0] != m->n_s + m->n_u || !m->net || !m->masks) return false;
@@ -1408,14 +1448,24 @@ int sx_mlp_predict(const sx_mlp_model* model, const double* z, int P, double* me
 int sx_cem_rollout_mlp(const sx_mlp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
                        const double* mean, const double* std, const double* noise, double* actions, double* traj,
                        double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
-    if (!mlp_model_ok(model) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
+    return sx_cem_rollout_mlp_junk(model, env, 0, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost,
+                                   status, stream);
+}
+
+int sx_cem_rollout_mlp_junk(const sx_mlp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                            const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                            double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                            int32_t* status, void* stream) {
+    if (!mlp_model_ok(model, query_shift > 0) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
     if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
     if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
+    if (!junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
     if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
     sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-#define CALL(NS, NU) sx::launch_rollout_mlp<NS, NU>(model, env, rp, (hipStream_t)stream)
-    SX_DISPATCH(model->n_s, model->n_u, CALL);
+#define CALL(NS, NU, SH) sx::launch_rollout_mlp<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
+#define CALL_0(NS, NU) CALL(NS, NU, 0)
+    SX_MODEL_JUNK_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
+#undef CALL_0
 #undef CALL
 }
 

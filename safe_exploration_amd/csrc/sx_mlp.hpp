@@ -234,11 +234,15 @@ __global__ __launch_bounds__(kMlpLanes) void mlp_predict_kernel(MlpConst mc, con
     }
 }
 
-// the CEM particle rollout over the ensemble: one particle per lane for all H steps (arguments as FeatRolloutPtrs)
-template <int NS, int NU>
+// the CEM particle rollout over the ensemble: one particle per lane for all H steps (arguments as FeatRolloutPtrs).
+// SH > 0 (sx_cem_rollout_mlp_junk): the network's inputs are D = NS + NU + SH columns, queries [p, 0_SH, u], the
+// reachability step takes the Jacobian's leading NS + NU columns -- as cem_rollout_feat_kernel.
+template <int NS, int NU, int SH = 0>
 __global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(MlpConst mc, ReachConst<NS, NU> rc,
                                                                     CostConst<SX_MAX_M, NS, NU> cc, FeatRolloutPtrs rp) {
-    constexpr int D = NS + NU;
+    constexpr int D = NS + NU + SH;
+    constexpr int UC = NS + SH;   // first action column of a query row
+    static_assert(D <= SX_MAX_D, "the network's first layer holds at most SX_MAX_D inputs");
     constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double mlp_smem[];
     const int lane = threadIdx.x;
@@ -275,10 +279,21 @@ __global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(MlpConst mc,
 #pragma unroll
         for (int j = 0; j < NS; ++j) z[j] = p[j];
 #pragma unroll
-        for (int c = 0; c < NU; ++c) z[NS + c] = u[c];
+        for (int j = NS; j < UC; ++j) z[j] = 0.0;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) z[UC + c] = u[c];
         if (have_q) {
             mlp_ensemble_predict<NS, D, true>(mc, z, mlp_smem, lane, mean, var, jac);
-            reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+            if constexpr (SH == 0) {
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+            } else {
+                double jab[NS][NS + NU];   // [A | B]: the training rows' state and action columns
+#pragma unroll
+                for (int i = 0; i < NS; ++i)
+#pragma unroll
+                    for (int j = 0; j < NS + NU; ++j) jab[i][j] = jac[i][j];
+                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jab, p1, Q1, st);
+            }
         } else {
             mlp_ensemble_predict<NS, D, false>(mc, z, mlp_smem, lane, mean, var, jac);
             reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);

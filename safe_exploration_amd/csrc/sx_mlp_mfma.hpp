@@ -615,12 +615,17 @@ __global__ __launch_bounds__(kMmThreads) void mlp_predict_mfma_kernel(MlpConst m
     }
 }
 
-// the CEM particle rollout over the ensemble (arguments as FeatRolloutPtrs; results as cem_rollout_mlp_kernel)
-template <int NS, int NU, int L, bool FULL>
+// the CEM particle rollout over the ensemble (arguments as FeatRolloutPtrs; results as cem_rollout_mlp_kernel).
+// SH > 0 (sx_cem_rollout_mlp_junk): D = NS + NU + SH inputs, queries [p, 0_SH, u], the Jacobian's leading NS + NU columns
+// to the reachability step.  A query and the bias column share one 8-wide operand (zin of mm_member_*, zbuf rows here):
+// D + 1 <= 8, which D <= SX_MAX_D = 6 keeps.
+template <int NS, int NU, int L, bool FULL, int SH = 0>
 __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpConst mc, ReachConst<NS, NU> rc,
                                                                           CostConst<SX_MAX_M, NS, NU> cc,
                                                                           FeatRolloutPtrs rp) {
-    constexpr int D = NS + NU;
+    constexpr int D = NS + NU + SH;
+    constexpr int UC = NS + SH;   // first action column of a query row
+    static_assert(D <= SX_MAX_D && D + 1 <= 8, "a query and the bias column fill at most one 8-wide operand");
     constexpr int S = NS + NS * NS;
     using M = MmLds<NS, D>;
     extern __shared__ __attribute__((aligned(16))) double mm_smem[];
@@ -652,10 +657,12 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpCon
             } else {
                 a = rp.actions[gi];
             }
-            zbuf[tid * 8 + NS + c] = a;
+            zbuf[tid * 8 + UC + c] = a;
         }
 #pragma unroll
         for (int j = 0; j < NS; ++j) zbuf[tid * 8 + j] = p[j];
+#pragma unroll
+        for (int j = NS; j < UC; ++j) zbuf[tid * 8 + j] = 0.0;
     };
     if (owner) {
         double p[NS];
@@ -689,11 +696,20 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpCon
                 for (int j = 0; j < NS; ++j) Q[i][j] = sbuf[i * NS + j];
             }
 #pragma unroll
-            for (int c = 0; c < NU; ++c) u[c] = zbuf[tid * 8 + NS + c];
+            for (int c = 0; c < NU; ++c) u[c] = zbuf[tid * 8 + UC + c];
             double obj = sbuf[NS * NS], con = sbuf[NS * NS + 1];
             if (have_q) {
                 mm_merge<NS, D, true>(dm, mm_smem, tid, mean, var, jac);
-                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+                if constexpr (SH == 0) {
+                    reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
+                } else {
+                    double jab[NS][NS + NU];   // [A | B]: the training rows' state and action columns
+#pragma unroll
+                    for (int i = 0; i < NS; ++i)
+#pragma unroll
+                        for (int j = 0; j < NS + NU; ++j) jab[i][j] = jac[i][j];
+                    reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jab, p1, Q1, st);
+                }
             } else {
                 mm_merge<NS, D, false>(dm, mm_smem, tid, mean, var, jac);
                 reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);

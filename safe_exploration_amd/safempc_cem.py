@@ -296,7 +296,8 @@ class CemSafeMPC(SafeMPC):
     def _solver(self):
         if self._injected_mpc:
             return self._mpc
-        if getattr(self._ssm, 'kernel_family', None) not in ('rbf', 'feature', 'mlp', 'stepwise', 'rbf_junk'):
+        if getattr(self._ssm, 'kernel_family', None) not in ('rbf', 'feature', 'mlp', 'stepwise', 'rbf_junk',
+                                                                'feature_junk', 'mlp_junk'):
             raise NotImplementedError('the fused CEM solver needs a HIP-backed CemSSM (GpCemSSM, McDropoutSSM, '
                                       'GalConcreteDropoutSSM, or JunkDimensionsSSM over one of them); other CemSSMs are outside '
                                       'the accelerated path')

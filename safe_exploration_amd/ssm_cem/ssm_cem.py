@@ -15,6 +15,11 @@ from ..utils import assert_shape
 # shapes, shift > 0 the query-shifted ones (n_s + n_u + shift <= SX_MAX_D): SX_ROLLOUT_SHAPES in csrc/sx_stream_launch.hpp
 JUNK_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1, 0), (1, 1, 0),
                                (2, 1, 1), (4, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1), (1, 1, 1)})
+# (n_s, n_u, query shift) that sx_cem_rollout_feat_junk / sx_cem_rollout_mlp_junk roll out in one launch per iteration: shift
+# 0 is sx_cem_rollout_feat's / sx_cem_rollout_mlp's shapes, shift > 0 every shape a padded feature-GP or MC-dropout model
+# can be built for (n_s + J_s <= 4, n_u + J_a <= 2): SX_MODEL_JUNK_SHAPES in csrc/sx_kernels.hip
+JUNK_MODEL_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1, 0), (1, 1, 0),
+                                     (1, 1, 1), (2, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1)})
 
 
 class CemSSM(ABC):
@@ -103,9 +108,11 @@ class JunkDimensionsSSM(CemSSM):
     derivatives with respect to junk STATE inputs -- but over an exact RBF GP it is an exact GP over the columns that are
     ever non-zero, [0, n_s + n_u) and [n_s + J_s, n_s + J_s + n_u): training rows [x, u, 0_s], queries [x, 0_s, u],
     s = `query_shift` = min(J_s, n_u), real outputs only.  That model (`real_output_view`) is what the fused rollout
-    sx_cem_rollout_junk takes (`kernel_family = 'rbf_junk'`, one launch per CEM iteration).  Every other inner model, and
-    shapes the kernel is not instantiated for (n_s + n_u + s > 6), are rolled out STEP BY STEP (`kernel_family =
-    'stepwise'`: H x (predict through this wrapper + sx_onestep_reach) per CEM iteration, the way the reference's optimiser
+    sx_cem_rollout_junk takes (`kernel_family = 'rbf_junk'`, one launch per CEM iteration).  The same reduction holds for
+    a feature-space GP ('linear', 'nn') and an MC-dropout model, whose inputs meet the junk only in the first linear layer:
+    `kernel_family = 'feature_junk'` / 'mlp_junk' (sx_cem_rollout_feat_junk / sx_cem_rollout_mlp_junk,
+    ssm_cem/kept_columns.py).  Every other inner model, and shapes the kernels are not instantiated for, are rolled out
+    STEP BY STEP (`kernel_family = 'stepwise'`: H x (predict through this wrapper + sx_onestep_reach) per CEM iteration, the way the reference's optimiser
     drives its dynamics callback).  Both reproduce the reference's numbers, the Jacobian's "action" block included.
     """
 
@@ -152,24 +159,42 @@ class JunkDimensionsSSM(CemSSM):
         n_s, n_u, js = self.num_states, self.num_actions, self._junk_states
         return tuple(sorted(set(range(n_s + n_u)) | set(range(n_s + js, n_s + js + n_u))))
 
+    def _model_junk_family(self) -> Optional[str]:
+        """'feature_junk' / 'mlp_junk' for an inner model that IS a FeatureGpCemSSM / McDropoutSSM (GalConcreteDropoutSSM
+        included): decided on the class, since only these classes' device models are known to reduce to the kept columns."""
+        from .dropout_ssm_cem import McDropoutSSM
+        from .feature_gp_ssm_cem import FeatureGpCemSSM
+        if isinstance(self._ssm, FeatureGpCemSSM):
+            return 'feature_junk'
+        if isinstance(self._ssm, McDropoutSSM):
+            return 'mlp_junk'
+        return None
+
     @property
     def kernel_family(self) -> str:
-        """'rbf_junk' (fused rollout, sx_cem_rollout_junk) over an RBF exact GP where the kernel is instantiated for
-        (n_s, n_u, query_shift); 'stepwise' otherwise."""
-        if getattr(self._ssm, 'kernel_family', None) != 'rbf':
+        """'rbf_junk' (fused rollout, sx_cem_rollout_junk) over an RBF exact GP, 'feature_junk' (sx_cem_rollout_feat_junk)
+        over a feature-space GP and 'mlp_junk' (sx_cem_rollout_mlp_junk) over an MC-dropout model, where the kernel is
+        instantiated for (n_s, n_u, query_shift); 'stepwise' otherwise."""
+        shape = (self.num_states, self.num_actions, self.query_shift)
+        if getattr(self._ssm, 'kernel_family', None) == 'rbf':
+            return 'rbf_junk' if shape in JUNK_FUSED_SHAPES else 'stepwise'
+        family = self._model_junk_family()
+        if family is None or shape not in JUNK_MODEL_FUSED_SHAPES:
             return 'stepwise'
-        if (self.num_states, self.num_actions, self.query_shift) not in JUNK_FUSED_SHAPES:
-            return 'stepwise'
-        return 'rbf_junk'
+        return family
 
     def real_output_view(self) -> CemSSM:
         """The exact GP over the kept columns with the n_s real outputs (n_s states, n_u + query_shift "actions"): the
         model sx_cem_rollout_junk takes.  Folded wrappers: the inner model itself.  Otherwise a GpCemSSM built through the
         wrapper's constructor on first use, with the inner model's hyper-parameters of the first n_s outputs at the kept
         columns (K over the kept columns is K over the padded ones entry for entry), rebuilt whenever the inner model's
-        device model changes (new training data or hyper-parameters)."""
+        device model changes (new training data or hyper-parameters).  Over a feature-space GP or an MC-dropout model: a
+        `kept_columns.KeptColumnView` (`_model_view`)."""
         if self._cols is not None:
             return self._ssm
+        family = self._model_junk_family()
+        if family is not None:
+            return self._model_view(family)
         inner_model = self._ssm.device_model
         if self._view is None or self._view_of is not inner_model:
             n_s, cols = self.num_states, list(self._kept_columns())
@@ -182,6 +207,24 @@ class JunkDimensionsSSM(CemSSM):
             x = self._x_train
             view.update_model(torch.cat((x, x.new_zeros((x.size(0), self.query_shift))), dim=1), self._y_train,
                               opt_hyp=False, replace_old=True)
+            self._view, self._view_of = view, inner_model
+        return self._view
+
+    def _model_view(self, family: str) -> CemSSM:
+        """real_output_view over a feature-space GP or an MC-dropout model (ssm_cem/kept_columns.py): the inner model's
+        current parameters at the kept columns, rebuilt whenever its device model changes (new data, training, a
+        re-initialised or re-frozen ensemble)."""
+        from . import kept_columns
+        inner_model = self._ssm.feat_model if family == 'feature_junk' else self._ssm.mlp_model
+        if self._view is None or self._view_of is not inner_model:
+            n_s, cols = self.num_states, list(self._kept_columns())
+            if family == 'feature_junk':
+                x = self._x_train
+                view = kept_columns.feature_view(self._ssm, cols, n_s,
+                                                 torch.cat((x, x.new_zeros((x.size(0), self.query_shift))), dim=1),
+                                                 self._y_train)
+            else:
+                view = kept_columns.mlp_view(self._ssm, cols, n_s)
             self._view, self._view_of = view, inner_model
         return self._view
 
