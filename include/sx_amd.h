@@ -394,6 +394,40 @@ int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, co
  * contract as sx_cem_rollout_form. */
 int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H);
 
+/* ---- E problems with a feature GP / an MC-dropout ensemble each in one rollout launch ----
+ * As sx_cem_rollout_multi for the exact GP: every problem e has its own model (its own training data, hyper-parameters,
+ * network weights and masks); the models share (n_s, n_u), the sx_env, the buffer shapes of sx_cem_rollout_feat /
+ * sx_cem_rollout_mlp and their ARCHITECTURE, which fixes the kernel and its LDS for the whole launch:
+ *   feature GP:  n_layers, width[0 .. n_layers], normalise, n_feat
+ *   MC-dropout:  n_hidden, width[0 .. n_hidden], n_out, n_samples, predict_std   (SX_MLP_PATH=valu applies as for one model)
+ * The per-problem constants live in a device table built once per model change.
+ *
+ * Bytes of the table for these E models; < 0 for bad arguments, models whose (n_s, n_u) or architecture differ, or a shape
+ * without a rollout kernel: the host-only answer to "does one launch serve these models". */
+int64_t sx_feat_model_table_bytes(const sx_feat_model* models, int E);
+/* Packs the E models (host array) into `table` (dev, sx_feat_model_table_bytes() bytes): their constants and the device
+ * pointers net, wbar, minv, which must stay valid while the table is used.  One host -> device copy on `stream`, and the
+ * call waits for it.  SX_ERR_ARG (before any device access) for a null pointer, E <= 0 or models of different (n_s, n_u);
+ * SX_ERR_UNSUPPORTED for differing architectures or a shape without a rollout kernel. */
+int sx_feat_model_table(const sx_feat_model* models, int E, void* table, void* stream);
+/* sx_cem_rollout_feat over E problems with a feature GP each: `models` is the host array the table was built from,
+ * `table` the device table.  Buffers as in sx_cem_rollout_feat except
+ *   status  dev int32 [E]   one word per problem (OR of SX_STATUS_*): a NaN in one problem's model leaves the others clear
+ * SX_ERR_ARG (before any device access) for null pointers, E <= 0, non-positive sizes or shapes that differ between the
+ * models or from env; SX_ERR_UNSUPPORTED (before any launch) for differing architectures or a shape without a kernel.
+ * No elite-row form.  Replaces: the n_scenarios sequential solves' rollouts (episode_runner.py:40-123). */
+int sx_cem_rollout_feat_multi(const sx_feat_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                              const double* x0, const double* q0, const double* mean, const double* std,
+                              const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                              double* con_cost, int32_t* status, void* stream);
+/* The same three for MC-dropout ensembles: the table carries the device pointers net and masks. */
+int64_t sx_mlp_model_table_bytes(const sx_mlp_model* models, int E);
+int sx_mlp_model_table(const sx_mlp_model* models, int E, void* table, void* stream);
+int sx_cem_rollout_mlp_multi(const sx_mlp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                             const double* x0, const double* q0, const double* mean, const double* std,
+                             const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                             double* con_cost, int32_t* status, void* stream);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

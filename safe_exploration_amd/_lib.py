@@ -100,6 +100,14 @@ SIGNATURES = {
     'sx_cem_rollout_elites_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p, c_int] + [c_void_p] * 10),
     'sx_cem_rollout_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
+    'sx_feat_model_table_bytes': (c_int64, [POINTER(SxFeatModel), c_int]),
+    'sx_feat_model_table': (c_int, [POINTER(SxFeatModel), c_int, c_void_p, c_void_p]),
+    'sx_cem_rollout_feat_multi': (c_int, [POINTER(SxFeatModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int]
+                                  + [c_void_p] * 12),
+    'sx_mlp_model_table_bytes': (c_int64, [POINTER(SxMlpModel), c_int]),
+    'sx_mlp_model_table': (c_int, [POINTER(SxMlpModel), c_int, c_void_p, c_void_p]),
+    'sx_cem_rollout_mlp_multi': (c_int, [POINTER(SxMlpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int]
+                                 + [c_void_p] * 12),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -125,17 +125,54 @@ class FusedMultiUnsupported(_lib.SxError):
     """sx_cem_rollout_multi answered SX_ERR_UNSUPPORTED (before any launch): solve the problems one model at a time."""
 
 
-class GpModelTable:
-    """The device table of E exact-GP models (sx_gp_model_table), rebuilt only when one of the models changes (a GpCemSSM
-    builds a new sx_gp_model on every update).  `get` returns (the host array of the models, the device table)."""
+# the families with a multi-model rollout: kernel_family -> (the model's struct attribute, its ctypes type, the C prefix of
+# the table entries, the suffix of the rollout entry)
+MULTI_FAMILIES = {'rbf': ('device_model', _lib.SxGpModel, 'sx_gp_model', '_multi'),
+                  'feature': ('feat_model', _lib.SxFeatModel, 'sx_feat_model', '_feat_multi'),
+                  'mlp': ('mlp_model', _lib.SxMlpModel, 'sx_mlp_model', '_mlp_multi')}
 
-    def __init__(self):
+
+def multi_family(ssms: Sequence) -> Optional[str]:
+    """The kernel_family all `ssms` share if it has a multi-model rollout ('rbf', 'feature', 'mlp'); None for mixed
+    families, JunkDimensionsSSM ('*_junk') and 'stepwise' models."""
+    families = {getattr(ssm, 'kernel_family', 'rbf') for ssm in ssms}
+    family = families.pop() if len(families) == 1 else None
+    return family if family in MULTI_FAMILIES else None
+
+
+def model_array(ssms: Sequence, family: str):
+    """The host array of the models' structs (sx_gp_model / sx_feat_model / sx_mlp_model) for the multi-model entries."""
+    attr, ctype = MULTI_FAMILIES[family][:2]
+    return (ctype * len(ssms))(*[getattr(ssm, attr) for ssm in ssms])
+
+
+def model_table_bytes(array, family: str) -> int:
+    """Bytes of the device table of these models; < 0 where one launch does not serve them (host only).  The exact GP's
+    size depends on the shape alone; the feature-GP and MC-dropout tables also require one architecture."""
+    lib, E = _lib.lib(), len(array)
+    if family == 'rbf':
+        n_s, n_u = array[0].n_s, array[0].n_u
+        return int(lib.sx_gp_model_table_bytes(n_s, n_u, E))
+    return int(getattr(lib, MULTI_FAMILIES[family][2] + '_table_bytes')(array, E))
+
+
+class GpModelTable:
+    """The device table of E models of one family (`family`: 'rbf' -- sx_gp_model_table, the default --, 'feature' --
+    sx_feat_model_table -- or 'mlp' -- sx_mlp_model_table), rebuilt only when one of the models changes (the models build
+    a new device_model / feat_model / mlp_model struct on every update).  `get` returns (the host array of the models,
+    the device table)."""
+
+    def __init__(self, family: str = 'rbf'):
+        if family not in MULTI_FAMILIES:
+            raise ValueError(f'no multi-model table for kernel_family {family!r}')
+        self.family = family
         self._models = None
         self._array = None
         self._table = None
 
     def get(self, ssms: Sequence[GpCemSSM], dev):
-        models = [ssm.device_model for ssm in ssms]
+        attr = MULTI_FAMILIES[self.family][0]
+        models = [getattr(ssm, attr) for ssm in ssms]
         if (self._models is not None and len(models) == len(self._models) and self._table.device == dev
                 and all(a is b for a, b in zip(models, self._models))):
             return self._array, self._table
@@ -144,12 +181,15 @@ class GpModelTable:
         if any((m.n_s, m.n_u) != (n_s, n_u) for m in models):
             raise ValueError(f'the models of a multi-model rollout must share (n_s, n_u); got '
                              f'{[(m.n_s, m.n_u) for m in models]}')
-        nbytes = int(lib.sx_gp_model_table_bytes(n_s, n_u, E))
+        array = model_array(ssms, self.family)
+        nbytes = model_table_bytes(array, self.family)
         if nbytes < 0:
-            raise FusedMultiUnsupported(f'sx_gp_model_table_bytes: no rollout kernel for (n_s, n_u) = ({n_s}, {n_u})')
-        array = (_lib.SxGpModel * E)(*models)
+            raise FusedMultiUnsupported(f'{MULTI_FAMILIES[self.family][2]}_table_bytes: no single launch for these models '
+                                        f'((n_s, n_u) = ({n_s}, {n_u}) without a rollout kernel, or differing '
+                                        f'architectures)')
         table = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        _lib.check(lib.sx_gp_model_table(array, E, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_model_table')
+        entry = MULTI_FAMILIES[self.family][2] + '_table'
+        _lib.check(getattr(lib, entry)(array, E, _lib.ptr(table), _lib.stream_ptr(dev)), entry)
         self._models, self._array, self._table = models, array, table
         return array, table
 
@@ -159,22 +199,32 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
                       noise: Optional[Tensor] = None, q0: Optional[Tensor] = None, want_traj: bool = False,
                       want_sigma: bool = False, status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None,
                       want_dist: bool = False, table: Optional[GpModelTable] = None):
-    """`cem_rollout` for E problems with an exact RBF GP each (ssms[e] for problem e), one launch: sx_cem_rollout_multi /
-    sx_cem_rollout_elites_multi.  Buffers as in `cem_rollout`; `status` is int32 [E], one word per problem.  `table` keeps
-    the device table of the models between calls (a fresh one is built otherwise).  Raises FusedMultiUnsupported where the
-    library has no single-launch form for the models (before any launch)."""
-    if any(getattr(ssm, 'kernel_family', 'rbf') != 'rbf' for ssm in ssms):
-        raise FusedMultiUnsupported('the multi-model rollout takes exact RBF GPs (kernel_family "rbf") only')
+    """`cem_rollout` for E problems with a model each (ssms[e] for problem e), one launch.  The models share one
+    kernel_family: exact RBF GPs ('rbf': sx_cem_rollout_multi / sx_cem_rollout_elites_multi), feature-space GPs
+    ('feature': sx_cem_rollout_feat_multi) or MC-dropout ensembles ('mlp': sx_cem_rollout_mlp_multi; neither of the last
+    two has an elite-row form).  Buffers as in `cem_rollout`; `status` is int32 [E], one word per problem.  `table` keeps
+    the device table of the models between calls (a fresh one is built otherwise, as where it belongs to another family).
+    Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch): mixed
+    families, JunkDimensionsSSM and step-by-step models, differing architectures, a shape without a kernel."""
+    family = multi_family(ssms)
+    if family is None:
+        raise FusedMultiUnsupported('the multi-model rollout takes models of one kernel_family: "rbf", "feature" or "mlp"; '
+                                    f'got {[getattr(ssm, "kernel_family", "rbf") for ssm in ssms]}')
+    if family != 'rbf' and elite_rows is not None:
+        raise ValueError(f'the {family!r} family has no elite-row form of the multi-model rollout')
     _lib.require_gpu(x0, 'x0')
     E = x0.size(0)
     if len(ssms) != E:
         raise ValueError(f'{len(ssms)} models for {E} problems')
     if status is not None and status.numel() != E:
         raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
-    models, tab = (table or GpModelTable()).get(ssms, x0.device)
-    return _rollout('_multi', (models, _lib.ptr(tab), ctypes.byref(env)), x0, horizon, ssms[0].num_states,
-                    ssms[0].num_actions, E, FusedMultiUnsupported, actions=actions, mean=mean, std=std, noise=noise, q0=q0,
-                    want_traj=want_traj, want_sigma=want_sigma, status=status, elite_rows=elite_rows, want_dist=want_dist)
+    if table is None or table.family != family:
+        table = GpModelTable(family)
+    models, tab = table.get(ssms, x0.device)
+    return _rollout(MULTI_FAMILIES[family][3], (models, _lib.ptr(tab), ctypes.byref(env)), x0, horizon,
+                    ssms[0].num_states, ssms[0].num_actions, E, FusedMultiUnsupported, actions=actions, mean=mean, std=std,
+                    noise=noise, q0=q0, want_traj=want_traj, want_sigma=want_sigma, status=status, elite_rows=elite_rows,
+                    want_dist=want_dist)
 
 
 class FusedJunkUnsupported(_lib.SxError):
@@ -750,16 +800,19 @@ class FusedCemMpc:
 
 
 class MultiModelCemMpc:
-    """E independent problems with an exact RBF GP each -- the reference's exploration scenarios, each with its own training
-    set and hyper-parameters -- solved together: one ``sx_cem_rollout_multi`` launch and one ``sx_cem_rank_refit`` launch per
-    CEM iteration for all of them, where ``FusedCemMpc`` needs one solve per model.
+    """E independent problems with a model each -- the reference's exploration scenarios, each with its own training set,
+    hyper-parameters or network -- solved together: one multi-model rollout launch and one ``sx_cem_rank_refit`` launch per
+    CEM iteration for all of them, where ``FusedCemMpc`` needs one solve per model.  The models share one kernel_family:
+    exact RBF GPs (``sx_cem_rollout_multi``), feature-space GPs, 'linear' / 'nn' (``sx_cem_rollout_feat_multi``), or
+    MC-dropout ensembles (``sx_cem_rollout_mlp_multi``); the last two share their architecture too, and have no elite-row
+    form (the ranking kernel refits).
 
     Problem e keeps a ``FusedCemMpc`` of its own (``solvers[e]``, built here from the same settings with seed ``seed + e``
     unless given): it supplies the problem's noise draws and warm start, so a multi-model solve samples exactly what E
-    sequential ``get_actions`` calls would, and it takes over where the single launch does not apply -- a model that is not
-    an exact RBF GP, a training set that needs the workspace path (one solve per model then), and the per-problem
-    step-by-step repeat of ``_check_solve``.  The problems share `env` and the CEM settings; sharded
-    (multi-GPU) multi-model solves are out of scope.
+    sequential ``get_actions`` calls would, and it takes over where the single launch does not apply -- mixed families,
+    JunkDimensionsSSM and step-by-step models, differing architectures, an exact-GP training set that needs the workspace
+    path (one solve per model then), and the per-problem step-by-step repeat of ``_check_solve``.  The problems share
+    `env` and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
     """
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
@@ -787,7 +840,8 @@ class MultiModelCemMpc:
         self._num_elites = num_elites
         self._num_iterations = num_iterations
         self._device = self._solvers[0]._device
-        self._table = GpModelTable()
+        family = multi_family(self._ssms)
+        self._table = GpModelTable(family) if family is not None else None
         self._last_noise = None
         self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path
         self.per_model_solves = 0       # solves that went one model at a time (single launch not applicable)
@@ -833,11 +887,16 @@ class MultiModelCemMpc:
             s.set_env(env)
 
     def fused_applies(self) -> bool:
-        """Does one sx_cem_rollout_multi launch serve the models (exact RBF GPs, no workspace path)?  Host only."""
-        if any(getattr(ssm, 'kernel_family', 'rbf') != 'rbf' for ssm in self._ssms):
+        """Does one multi-model launch serve the models?  Exact RBF GPs without the workspace path
+        (sx_cem_rollout_multi_form); feature-space GPs or MC-dropout ensembles of one shape and architecture (the sign of
+        sx_feat_model_table_bytes / sx_mlp_model_table_bytes).  Host only."""
+        family = multi_family(self._ssms)
+        if family is None:
             return False
-        models = (_lib.SxGpModel * len(self._ssms))(*[ssm.device_model for ssm in self._ssms])
-        return int(_lib.lib().sx_cem_rollout_multi_form(models, len(self._ssms), self._horizon)) >= 0
+        models = model_array(self._ssms, family)
+        if family == 'rbf':
+            return int(_lib.lib().sx_cem_rollout_multi_form(models, len(self._ssms), self._horizon)) >= 0
+        return model_table_bytes(models, family) >= 0
 
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """E = len(models) solves from x0 [E x n_s] (points) in one launch per step of the loop.  Nothing synchronises.

@@ -226,101 +226,6 @@ __global__ __launch_bounds__(kFeatWave) void feat_predict_kernel(FeatConst fc, c
     }
 }
 
-// ---- sx_feat_fit: A_d = Phi^T Phi + lambda_d I, M_d = chol(A_d)^-1, wbar_d = M_d^T M_d Phi^T y_d ------------------------
-// One workgroup of 1024 threads per output; F <= 32, so A (F x F) has one thread per entry and lives in LDS.
-// stats[d] = { y_d^T y_d, |M_d Phi^T y_d|^2, sum log diag chol(A_d) }: what the exact marginal likelihood needs.
-struct FeatFitArgs {
-    const double* phi;   // [N x F]
-    const double* y;     // [N x n_s]
-    double lambda[SX_MAX_NS];
-    double* wbar;        // [n_s x F]
-    double* minv;        // [n_s x F x F]
-    double* stats;       // [n_s x 3]
-    int* status;
-    int n, F, n_s;
-};
-
-__global__ __launch_bounds__(1024) void feat_fit_kernel(FeatFitArgs a) {
-    __shared__ double A[SX_FEAT_MAX_WIDTH][SX_FEAT_MAX_WIDTH + 1];
-    __shared__ double Li[SX_FEAT_MAX_WIDTH][SX_FEAT_MAX_WIDTH + 1];
-    __shared__ double b[SX_FEAT_MAX_WIDTH], t[SX_FEAT_MAX_WIDTH];
-    __shared__ double yy_part[16];
-    const int d = blockIdx.x, tid = threadIdx.x;
-    const int F = a.F, n = a.n;
-    const int r = tid / SX_FEAT_MAX_WIDTH, c = tid % SX_FEAT_MAX_WIDTH;
-    if (r < F && c <= r) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s = fma(a.phi[(size_t)i * F + r], a.phi[(size_t)i * F + c], s);
-        if (r == c) s += a.lambda[d];
-        A[r][c] = s;
-        A[c][r] = s;
-    }
-    if (tid < F) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s = fma(a.phi[(size_t)i * F + tid], a.y[(size_t)i * a.n_s + d], s);
-        b[tid] = s;
-    }
-    {
-        double s = 0.0;
-        for (int i = tid; i < n; i += 1024) {
-            const double v = a.y[(size_t)i * a.n_s + d];
-            s = fma(v, v, s);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if ((tid & 63) == 0) yy_part[tid >> 6] = s;
-    }
-    __syncthreads();
-    // Cholesky A = L L^T in place (lower), column by column; F <= 32: one wave's worth of rows
-    bool bad = false;
-    for (int j = 0; j < F; ++j) {
-        if (tid == 0) {
-            const double p = A[j][j];
-            if (!(p > 0.0)) bad = true;
-            A[j][j] = sqrt(p);
-        }
-        __syncthreads();
-        if (tid > j && tid < F) A[tid][j] /= A[j][j];
-        __syncthreads();
-        if (r > j && r < F && c > j && c <= r) A[r][c] -= A[r][j] * A[c][j];
-        __syncthreads();
-    }
-    // M = L^-1 by forward substitution, one column per thread
-    if (tid < F) {
-        const int col = tid;
-        for (int i = 0; i < F; ++i) {
-            double s = (i == col) ? 1.0 : 0.0;
-            for (int k = col; k < i; ++k) s -= A[i][k] * Li[k][col];
-            Li[i][col] = (i >= col) ? s / A[i][i] : 0.0;
-        }
-    }
-    __syncthreads();
-    if (tid < F) {   // t = M b
-        double s = 0.0;
-        for (int k = 0; k <= tid; ++k) s = fma(Li[tid][k], b[k], s);
-        t[tid] = s;
-    }
-    __syncthreads();
-    if (tid < F) {   // wbar = M^T t
-        double s = 0.0;
-        for (int k = tid; k < F; ++k) s = fma(Li[k][tid], t[k], s);
-        a.wbar[(size_t)d * F + tid] = s;
-    }
-    if (r < F && c < F) a.minv[((size_t)d * F + r) * F + c] = (c <= r) ? Li[r][c] : 0.0;
-    if (tid == 0) {
-        double yy = 0.0, tt = 0.0, ld = 0.0;
-        for (int w = 0; w < 16; ++w) yy += yy_part[w];
-        for (int k = 0; k < F; ++k) {
-            tt = fma(t[k], t[k], tt);
-            ld += log(A[k][k]);
-        }
-        a.stats[d * 3 + 0] = yy;
-        a.stats[d * 3 + 1] = tt;
-        a.stats[d * 3 + 2] = ld;
-        if (bad) atomicOr(a.status, SX_STATUS_NOT_PD);
-    }
-}
-
 // ---- sx_cem_rollout_feat: the CEM particle rollout over a feature-space GP, one particle per lane for all H steps ----------
 struct FeatRolloutPtrs {
     const double* x0;
@@ -337,23 +242,75 @@ struct FeatRolloutPtrs {
     int E, P, H;
 };
 
+// The model argument of the rollout kernels of the feature-GP and MC-dropout families: the constants C themselves, or
+// with MM = true (sx_cem_rollout_feat_multi / sx_cem_rollout_mlp_multi) the device table of the E problems' constants
+// (sx_feat_model_table / sx_mlp_model_table), of which the workgroup binds its problem's entry.  The pointer is
+// restrict-qualified and never written, and the index is uniform: the fields come through scalar loads.  The entry is
+// read through the constant address space, which the table is for the launch: the compiler then takes the device
+// pointers it holds (weights, masks) to be global, as it does for those of a kernel argument, and reads through them
+// with global loads rather than flat ones.
+template <typename C, bool MM>
+struct ModelArg {
+    using type = C;
+    __device__ static const C& of(const type& c, int) { return c; }
+};
+template <typename C>
+struct ModelArg<C, true> {
+    using type = const C* __restrict__;
+    __device__ static const C& of(type table, int e) {
+        using ConstC = __attribute__((address_space(4))) const C;
+        return *(const C*)((ConstC*)table + e);
+    }
+};
+
+// MM: the problem of this workgroup.  A multi-model launch covers every problem with ceil(P / TILE) workgroups of its own
+// (TILE particles each), so the problem follows from blockIdx alone and is uniform.
+template <int TILE>
+__device__ __forceinline__ int tile_problem(int P) {
+    return (int)blockIdx.x / ((P + TILE - 1) / TILE);
+}
+
+// Particle index of this lane within its problem's tiles (MM): `lane` of the workgroup's tile of TILE particles.
+template <int TILE>
+__device__ __forceinline__ int tile_particle(int e, int P, int lane) {
+    return ((int)blockIdx.x - e * ((P + TILE - 1) / TILE)) * TILE + lane;
+}
+
 // SH > 0 (sx_cem_rollout_feat_junk): the GP's inputs are D = NS + NU + SH columns -- training rows [x, u, 0_SH], queries
 // [p, 0_SH, u] -- while the reachability and the costs see (NS, NU) and the Jacobian's leading NS + NU columns (the
 // feature-GP form of JunkDimensionsSSM).  SH = 0 is the plain rollout.
-template <int NS, int NU, int SH = 0>
-__global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(FeatConst fc, ReachConst<NS, NU> rc,
-                                                                     CostConst<SX_MAX_M, NS, NU> cc, FeatRolloutPtrs rp) {
+// MM = true (sx_cem_rollout_feat_multi, SH = 0): every problem has a GP of its own, `fc_arg` is the device table of their
+// FeatConst (ModelArg), the workgroups are problem-aligned (tile_problem; lanes past P are masked like those past E P in
+// the plain mode: they compute on the problem's first particle and write nothing), particle (e, i) keeps its [E x P ...]
+// buffer index, and `rp.status` holds one word per problem.
+template <int NS, int NU, int SH = 0, bool MM = false>
+__global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(typename ModelArg<FeatConst, MM>::type fc_arg,
+                                                                     ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc,
+                                                                     FeatRolloutPtrs rp) {
+    static_assert(!MM || SH == 0, "the multi-model rollout has no query shift");
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     static_assert(D <= SX_MAX_D, "the feature network's first layer holds at most SX_MAX_D inputs");
     constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double feat_smem[];
     const int lane = threadIdx.x;
-    const int64_t g = blockIdx.x * (int64_t)kFeatWave + lane;
-    const int64_t total = (int64_t)rp.E * rp.P;
-    const bool valid = g < total;
-    const int64_t gg = valid ? g : 0;
-    const int e = (int)(gg / rp.P);
+    int64_t g, gg;
+    bool valid;
+    int e;
+    if constexpr (MM) {
+        e = tile_problem<kFeatWave>(rp.P);
+        const int i = tile_particle<kFeatWave>(e, rp.P, lane);
+        valid = i < rp.P;
+        g = (int64_t)e * rp.P + i;
+        gg = valid ? g : (int64_t)e * rp.P;
+    } else {
+        g = blockIdx.x * (int64_t)kFeatWave + lane;
+        const int64_t total = (int64_t)rp.E * rp.P;
+        valid = g < total;
+        gg = valid ? g : 0;
+        e = (int)(gg / rp.P);
+    }
+    const FeatConst& fc = ModelArg<FeatConst, MM>::of(fc_arg, e);
     const int H = rp.H;
     double p[NS], Q[NS][NS];
     bool have_q = rp.q0 != nullptr;
@@ -434,7 +391,7 @@ __global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(FeatConst f
     if (valid) {
         rp.obj_cost[g] = obj;
         rp.con_cost[g] = con;
-        if (st) atomicOr(rp.status, st);
+        if (st) atomicOr(rp.status + (MM ? e : 0), st);
     }
 }
 

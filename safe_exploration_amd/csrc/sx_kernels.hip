@@ -25,8 +25,10 @@
 #include "sx_rank.hpp"
 #include "sx_rank_count.hpp"
 #include "sx_feat.hpp"
+#include "sx_feat_fit.hpp"
 #include "sx_mlp.hpp"
 #include "sx_mlp_mfma.hpp"
+#include "sx_model_multi.hpp"
 
 namespace sx {
 
@@ -887,6 +889,37 @@ static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const Fe
 }
 }  // namespace sx
 
+namespace sx {
+// sx_feat_model_table / sx_mlp_model_table: one host -> device copy of the E entries on `stream`, waited for
+template <typename C>
+static int copy_model_table(const std::vector<C>& host, void* table, hipStream_t stream) {
+    if (hipMemcpyAsync(table, host.data(), host.size() * sizeof(C), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return SX_ERR_LAUNCH;
+    // (the copy reads `host`, which ends with the caller)
+    return hipStreamSynchronize(stream) == hipSuccess ? SX_OK : SX_ERR_LAUNCH;
+}
+
+// sx_cem_rollout_feat_multi / _mlp_multi after their checks: the problems' shared constants, then the launch
+template <int NS, int NU>
+static int feat_multi_launch(const FeatConst* table, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
+    ReachConst<NS, NU> rc;
+    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    make_cost_const<NS, NU>(env, cc);
+    return launch_rollout_feat_multi<NS, NU>(table, rc, cc, rp, stream);
+}
+
+template <int NS, int NU>
+static int mlp_multi_launch(const MlpConst* table, const MlpConst& arch, bool mfma, const sx_env* env,
+                            const FeatRolloutPtrs& rp, hipStream_t stream) {
+    ReachConst<NS, NU> rc;
+    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    make_cost_const<NS, NU>(env, cc);
+    return launch_rollout_mlp_multi<NS, NU>(table, arch, mfma, rc, cc, rp, stream);
+}
+}  // namespace sx
+
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
@@ -1466,6 +1499,113 @@ int sx_cem_rollout_mlp_junk(const sx_mlp_model* model, const sx_env* env, int qu
 #define CALL_0(NS, NU) CALL(NS, NU, 0)
     SX_MODEL_JUNK_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
 #undef CALL_0
+#undef CALL
+}
+
+// ---- E problems with a feature GP / an MC-dropout ensemble each in one launch (sx_*_model_table, sx_cem_rollout_*_multi)
+// The models share (n_s, n_u), checked with the arguments (SX_ERR_ARG), and their architecture, which fixes the kernel and
+// its LDS for the whole launch (SX_ERR_UNSUPPORTED otherwise, like a shape without a kernel).
+static int feat_models_check(const sx_feat_model* models, int E) {
+    if (!models || E <= 0) return SX_ERR_ARG;
+    const sx_feat_model& a = models[0];
+    for (int i = 0; i < E; ++i) {
+        const sx_feat_model& m = models[i];
+        if (!feat_model_ok(&m) || m.n_s != a.n_s || m.n_u != a.n_u) return SX_ERR_ARG;
+    }
+    for (int i = 1; i < E; ++i) {
+        const sx_feat_model& m = models[i];
+        if (m.n_layers != a.n_layers || m.normalise != a.normalise || m.n_feat != a.n_feat) return SX_ERR_UNSUPPORTED;
+        for (int l = 0; l <= a.n_layers; ++l)
+            if (m.width[l] != a.width[l]) return SX_ERR_UNSUPPORTED;
+    }
+    if (!sx::rollout_compiled(a.n_s, a.n_u, 0)) return SX_ERR_UNSUPPORTED;
+    return SX_OK;
+}
+
+static int mlp_models_check(const sx_mlp_model* models, int E) {
+    if (!models || E <= 0) return SX_ERR_ARG;
+    const sx_mlp_model& a = models[0];
+    for (int i = 0; i < E; ++i) {
+        const sx_mlp_model& m = models[i];
+        if (!mlp_model_ok(&m) || m.n_s != a.n_s || m.n_u != a.n_u) return SX_ERR_ARG;
+    }
+    for (int i = 1; i < E; ++i) {
+        const sx_mlp_model& m = models[i];
+        if (m.n_hidden != a.n_hidden || m.n_out != a.n_out || m.n_samples != a.n_samples || m.predict_std != a.predict_std)
+            return SX_ERR_UNSUPPORTED;
+        for (int l = 0; l <= a.n_hidden; ++l)
+            if (m.width[l] != a.width[l]) return SX_ERR_UNSUPPORTED;
+    }
+    if (!sx::rollout_compiled(a.n_s, a.n_u, 0)) return SX_ERR_UNSUPPORTED;
+    return SX_OK;
+}
+
+int64_t sx_feat_model_table_bytes(const sx_feat_model* models, int E) {
+    return feat_models_check(models, E) == SX_OK ? (int64_t)E * (int64_t)sizeof(sx::FeatConst) : -1;
+}
+
+int64_t sx_mlp_model_table_bytes(const sx_mlp_model* models, int E) {
+    return mlp_models_check(models, E) == SX_OK ? (int64_t)E * (int64_t)sizeof(sx::MlpConst) : -1;
+}
+
+int sx_feat_model_table(const sx_feat_model* models, int E, void* table, void* stream) {
+    if (!table) return SX_ERR_ARG;
+    if (int r = feat_models_check(models, E)) return r;
+    for (int i = 0; i < E; ++i)
+        if (!models[i].wbar || !models[i].minv) return SX_ERR_ARG;
+    std::vector<sx::FeatConst> host(E);
+    for (int i = 0; i < E; ++i) host[i] = sx::make_feat_const(&models[i]);
+    return sx::copy_model_table(host, table, (hipStream_t)stream);
+}
+
+int sx_mlp_model_table(const sx_mlp_model* models, int E, void* table, void* stream) {
+    if (!table) return SX_ERR_ARG;
+    if (int r = mlp_models_check(models, E)) return r;
+    std::vector<sx::MlpConst> host(E);
+    for (int i = 0; i < E; ++i) host[i] = sx::make_mlp_const(&models[i]);
+    return sx::copy_model_table(host, table, (hipStream_t)stream);
+}
+
+// the buffer checks the multi-model entries share with sx_cem_rollout_multi
+static bool multi_buffers_ok(const void* table, const sx_env* env, int P, int H, const double* x0, const double* mean,
+                             const double* std, const double* noise, const double* actions, const double* obj_cost,
+                             const double* con_cost, const int32_t* status) {
+    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return false;
+    if (P <= 0 || H <= 0) return false;
+    return !noise || (mean && std);
+}
+
+int sx_cem_rollout_feat_multi(const sx_feat_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                              const double* x0, const double* q0, const double* mean, const double* std,
+                              const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                              double* con_cost, int32_t* status, void* stream) {
+    if (!multi_buffers_ok(table, env, P, H, x0, mean, std, noise, actions, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    const int check = feat_models_check(models, E);
+    if (check == SX_ERR_ARG || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    if (check != SX_OK) return check;
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    const auto* tab = static_cast<const sx::FeatConst*>(table);
+#define CALL(NS, NU) sx::feat_multi_launch<NS, NU>(tab, env, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_mlp_multi(const sx_mlp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                             const double* x0, const double* q0, const double* mean, const double* std,
+                             const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                             double* con_cost, int32_t* status, void* stream) {
+    if (!multi_buffers_ok(table, env, P, H, x0, mean, std, noise, actions, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    const int check = mlp_models_check(models, E);
+    if (check == SX_ERR_ARG || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    if (check != SX_OK) return check;
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    const auto* tab = static_cast<const sx::MlpConst*>(table);
+    const sx::MlpConst arch = sx::make_mlp_const(&models[0]);
+    const bool mfma = sx::mlp_use_mfma(arch);   // (the same answer for every model: they share the architecture)
+#define CALL(NS, NU) sx::mlp_multi_launch<NS, NU>(tab, arch, mfma, env, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
 #undef CALL
 }
 

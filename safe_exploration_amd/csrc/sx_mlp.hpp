@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sx_amd.h"
+#include "sx_feat.hpp"   // FeatRolloutPtrs, ModelArg
 #include "sx_reach.hpp"
 
 namespace sx {
@@ -237,20 +238,36 @@ __global__ __launch_bounds__(kMlpLanes) void mlp_predict_kernel(MlpConst mc, con
 // the CEM particle rollout over the ensemble: one particle per lane for all H steps (arguments as FeatRolloutPtrs).
 // SH > 0 (sx_cem_rollout_mlp_junk): the network's inputs are D = NS + NU + SH columns, queries [p, 0_SH, u], the
 // reachability step takes the Jacobian's leading NS + NU columns -- as cem_rollout_feat_kernel.
-template <int NS, int NU, int SH = 0>
-__global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(MlpConst mc, ReachConst<NS, NU> rc,
-                                                                    CostConst<SX_MAX_M, NS, NU> cc, FeatRolloutPtrs rp) {
+// MM = true (sx_cem_rollout_mlp_multi, SH = 0): a network and masks per problem, `mc_arg` the device table of their
+// MlpConst; problem-aligned workgroups and one status word per problem, as cem_rollout_feat_kernel's MM mode.
+template <int NS, int NU, int SH = 0, bool MM = false>
+__global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(typename ModelArg<MlpConst, MM>::type mc_arg,
+                                                                    ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc,
+                                                                    FeatRolloutPtrs rp) {
+    static_assert(!MM || SH == 0, "the multi-model rollout has no query shift");
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     static_assert(D <= SX_MAX_D, "the network's first layer holds at most SX_MAX_D inputs");
     constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double mlp_smem[];
     const int lane = threadIdx.x;
-    const int64_t g = blockIdx.x * (int64_t)kMlpLanes + lane;
-    const int64_t total = (int64_t)rp.E * rp.P;
-    const bool valid = g < total;
-    const int64_t gg = valid ? g : 0;
-    const int e = (int)(gg / rp.P);
+    int64_t g, gg;
+    bool valid;
+    int e;
+    if constexpr (MM) {
+        e = tile_problem<kMlpLanes>(rp.P);
+        const int i = tile_particle<kMlpLanes>(e, rp.P, lane);
+        valid = i < rp.P;
+        g = (int64_t)e * rp.P + i;
+        gg = valid ? g : (int64_t)e * rp.P;
+    } else {
+        g = blockIdx.x * (int64_t)kMlpLanes + lane;
+        const int64_t total = (int64_t)rp.E * rp.P;
+        valid = g < total;
+        gg = valid ? g : 0;
+        e = (int)(gg / rp.P);
+    }
+    const MlpConst& mc = ModelArg<MlpConst, MM>::of(mc_arg, e);
     const int H = rp.H;
     double p[NS], Q[NS][NS];
     bool have_q = rp.q0 != nullptr;
@@ -330,7 +347,7 @@ __global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(MlpConst mc,
     if (valid) {
         rp.obj_cost[g] = obj;
         rp.con_cost[g] = con;
-        if (st) atomicOr(rp.status, st);
+        if (st) atomicOr(rp.status + (MM ? e : 0), st);
     }
 }
 

@@ -619,10 +619,16 @@ __global__ __launch_bounds__(kMmThreads) void mlp_predict_mfma_kernel(MlpConst m
 // SH > 0 (sx_cem_rollout_mlp_junk): D = NS + NU + SH inputs, queries [p, 0_SH, u], the Jacobian's leading NS + NU columns
 // to the reachability step.  A query and the bias column share one 8-wide operand (zin of mm_member_*, zbuf rows here):
 // D + 1 <= 8, which D <= SX_MAX_D = 6 keeps.
-template <int NS, int NU, int L, bool FULL, int SH = 0>
-__global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpConst mc, ReachConst<NS, NU> rc,
+// MM = true (sx_cem_rollout_mlp_multi, SH = 0): a network and masks per problem, `mc_arg` the device table of their
+// MlpConst (ModelArg); every problem has ceil(P / 16) tiles of its own, so a tile never straddles two problems, the
+// workgroup packs its problem's weights in the prologue, and `rp.status` holds one word per problem.  Particles past P in
+// a problem's last tile compute on the problem's first particle and write nothing.
+template <int NS, int NU, int L, bool FULL, int SH = 0, bool MM = false>
+__global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(typename ModelArg<MlpConst, MM>::type mc_arg,
+                                                                          ReachConst<NS, NU> rc,
                                                                           CostConst<SX_MAX_M, NS, NU> cc,
                                                                           FeatRolloutPtrs rp) {
+    static_assert(!MM || SH == 0, "the multi-model rollout has no query shift");
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     static_assert(D <= SX_MAX_D && D + 1 <= 8, "a query and the bias column fill at most one 8-wide operand");
@@ -630,17 +636,30 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpCon
     using M = MmLds<NS, D>;
     extern __shared__ __attribute__((aligned(16))) double mm_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pe = MM ? tile_problem<kMmTile>(rp.P) : 0;   // (MM) the workgroup's problem
+    const MlpConst& mc = ModelArg<MlpConst, MM>::of(mc_arg, pe);
     const MmDims dm = mm_dims(mc);
     mm_pack<NS, D>(mc, dm, mm_smem, tid);
 
     // Particle state: owned by lanes 0-15 of wave 0, but kept in LDS between the steps (the centre and the action in the
     // query-point buffer, Q and the two costs beside it), so that no register is held across the members' matrix work.
     const bool owner = tid < kMmTile;
-    const int64_t total = (int64_t)rp.E * rp.P;
-    const int64_t g = (int64_t)blockIdx.x * kMmTile + (tid & 15);
-    const bool valid = owner && g < total;
-    const int64_t gg = g < total ? g : 0;
-    const int e = (int)(gg / rp.P);
+    int64_t g, gg;
+    bool valid;
+    int e;
+    if constexpr (MM) {
+        e = pe;
+        const int i = tile_particle<kMmTile>(e, rp.P, tid & 15);
+        valid = owner && i < rp.P;
+        g = (int64_t)e * rp.P + i;
+        gg = i < rp.P ? g : (int64_t)e * rp.P;
+    } else {
+        const int64_t total = (int64_t)rp.E * rp.P;
+        g = (int64_t)blockIdx.x * kMmTile + (tid & 15);
+        valid = owner && g < total;
+        gg = g < total ? g : 0;
+        e = (int)(gg / rp.P);
+    }
     const int H = rp.H;
     bool have_q = rp.q0 != nullptr;    // (uniform)
     int st = 0;
@@ -749,7 +768,7 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(MlpCon
     if (valid) {
         rp.obj_cost[g] = sbuf[NS * NS];
         rp.con_cost[g] = sbuf[NS * NS + 1];
-        if (st) atomicOr(rp.status, st);
+        if (st) atomicOr(rp.status + (MM ? e : 0), st);
     }
 }
 

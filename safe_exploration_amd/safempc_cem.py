@@ -15,7 +15,7 @@ from numpy import ndarray
 from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
-from .cem_mpc import FusedCemMpc, MultiModelCemMpc, Rollouts
+from .cem_mpc import FusedCemMpc, MultiModelCemMpc, Rollouts, multi_family
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem.gp_ssm_cem import GpCemSSM
@@ -444,13 +444,23 @@ class CemSafeMPC(SafeMPC):
         return self._ssm.collect_metrics()
 
 
+def multi_solve_applies(mpcs: Sequence) -> bool:
+    """Do these single-model optimisers go through one MultiModelCemMpc (get_actions_multi)?  Unsharded FusedCemMpc
+    instances without an objective hook whose models share one kernel_family with a multi-model rollout: exact RBF GPs,
+    feature-space GPs ('linear', 'nn') or MC-dropout ensembles.  (Whether one launch then serves the models -- no workspace
+    path, one architecture -- is MultiModelCemMpc.fused_applies: a solve per model otherwise.)"""
+    return (all(isinstance(m, FusedCemMpc) and m._objective_hook is None and m._world == 1 for m in mpcs)
+            and multi_family([m._ssm for m in mpcs]) is not None)
+
+
 def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[ndarray, List[MpcResult]]:
     """``get_action`` of several independent solvers at once -- the reference's exploration scenarios, each with its own
     model and data (episode_runner.py:40-123) -- where solver e acts in states[e] ([E x n_s]).  Returns (actions
     [E x n_u], one MpcResult per solver).
 
-    Over exact RBF GPs that is ONE solve for all of them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each
-    problem with its own GP); otherwise, and where the single launch does not apply, one solve per solver.  Either way
+    Over models of one family -- exact RBF GPs, feature-space GPs or MC-dropout ensembles -- that is ONE solve for all of
+    them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model); otherwise (mixed
+    families, JunkDimensionsSSM, ...), and where the single launch does not apply, one solve per solver.  Either way
     problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
     ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
     the CEM settings; ValueError otherwise."""
@@ -470,8 +480,7 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     mpcs = [s._solver() for s in solvers]
     MultiModelCemMpc.check_solvers(mpcs)
     flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
-    if (all(isinstance(m, FusedCemMpc) and m._objective_hook is None and m._world == 1 for m in mpcs)
-            and all(getattr(m._ssm, 'kernel_family', None) == 'rbf' for m in mpcs)):
+    if multi_solve_applies(mpcs):
         key = tuple(id(m) for m in mpcs)
         cached = getattr(solvers[0], '_multi', None)
         if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
