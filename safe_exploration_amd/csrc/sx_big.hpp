@@ -11,6 +11,7 @@
 
 #include "sx_gp.hpp"
 #include "sx_reach.hpp"
+#include "sx_step.hpp"
 
 namespace sx {
 
@@ -366,7 +367,6 @@ template <int NS, int NU>
 __global__ void step_big_kernel(GpConst<NS, NS + NU> gc, ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc,
                                 BigStep bs, BigWs ws, int64_t total, int64_t p128) {
     constexpr int D = NS + NU;
-    constexpr int S = NS + NS * NS;
     const int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (g >= total) return;
     double p[NS], Q[NS][NS], z[D], u[NU], mean[NS], var[NS], jac[NS][D], p1[NS], Q1[NS][NS];
@@ -407,28 +407,10 @@ __global__ void step_big_kernel(GpConst<NS, NS + NU> gc, ReachConst<NS, NU> rc, 
         reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);
     double obj = bs.obj[g] + objective_cost<SX_MAX_M, NS, NU>(cc, p1, var);
     double con = bs.con[g];
-    bool uviol = false;
-#pragma unroll
-    for (int c = 0; c < NU; ++c) uviol = uviol || (u[c] < cc.u_min[c]) || (u[c] > cc.u_max[c]);
-    if (uviol) con += SX_ACTION_VIOLATION_COST;
-    if (cc.con_mode == SX_CON_ALL_STATES || bs.t == bs.H - 1) {
-        if (polytope_violated<SX_MAX_M, NS>(cc.h_mat, cc.h_vec, cc.m, 1.0, p1, Q1, nullptr)) con += SX_STATE_VIOLATION_COST;
-    }
+    constraint_costs<NS, NU>(cc, u, p1, Q1, bs.t, bs.H, con);
     bs.obj[g] = obj;
     bs.con[g] = con;
-    if (bs.traj) {
-        double* tr = bs.traj + (g * bs.H + bs.t) * S;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            tr[i] = p1[i];
-#pragma unroll
-            for (int j = 0; j < NS; ++j) tr[NS + i * NS + j] = Q1[i][j];
-        }
-    }
-    if (bs.sigma) {
-#pragma unroll
-        for (int i = 0; i < NS; ++i) bs.sigma[(g * bs.H + bs.t) * NS + i] = var[i];
-    }
+    store_step<NS>(bs.traj, bs.sigma, true, g, bs.H, bs.t, p1, Q1, var);
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
         ws.pst[g * NS + i] = p1[i];

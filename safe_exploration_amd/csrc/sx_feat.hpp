@@ -14,6 +14,7 @@
 
 #include "../../include/sx_amd.h"
 #include "sx_reach.hpp"
+#include "sx_step.hpp"
 
 namespace sx {
 
@@ -227,172 +228,17 @@ __global__ __launch_bounds__(kFeatWave) void feat_predict_kernel(FeatConst fc, c
 }
 
 // ---- sx_cem_rollout_feat: the CEM particle rollout over a feature-space GP, one particle per lane for all H steps ----------
-struct FeatRolloutPtrs {
-    const double* x0;
-    const double* q0;
-    const double* mean;
-    const double* std;
-    const double* noise;
-    double* actions;
-    double* traj;
-    double* sigma;
-    double* obj_cost;
-    double* con_cost;
-    int* status;
-    int E, P, H;
-};
-
-// The model argument of the rollout kernels of the feature-GP and MC-dropout families: the constants C themselves, or
-// with MM = true (sx_cem_rollout_feat_multi / sx_cem_rollout_mlp_multi) the device table of the E problems' constants
-// (sx_feat_model_table / sx_mlp_model_table), of which the workgroup binds its problem's entry.  The pointer is
-// restrict-qualified and never written, and the index is uniform: the fields come through scalar loads.  The entry is
-// read through the constant address space, which the table is for the launch: the compiler then takes the device
-// pointers it holds (weights, masks) to be global, as it does for those of a kernel argument, and reads through them
-// with global loads rather than flat ones.
-template <typename C, bool MM>
-struct ModelArg {
-    using type = C;
-    __device__ static const C& of(const type& c, int) { return c; }
-};
-template <typename C>
-struct ModelArg<C, true> {
-    using type = const C* __restrict__;
-    __device__ static const C& of(type table, int e) {
-        using ConstC = __attribute__((address_space(4))) const C;
-        return *(const C*)((ConstC*)table + e);
-    }
-};
-
-// MM: the problem of this workgroup.  A multi-model launch covers every problem with ceil(P / TILE) workgroups of its own
-// (TILE particles each), so the problem follows from blockIdx alone and is uniform.
-template <int TILE>
-__device__ __forceinline__ int tile_problem(int P) {
-    return (int)blockIdx.x / ((P + TILE - 1) / TILE);
-}
-
-// Particle index of this lane within its problem's tiles (MM): `lane` of the workgroup's tile of TILE particles.
-template <int TILE>
-__device__ __forceinline__ int tile_particle(int e, int P, int lane) {
-    return ((int)blockIdx.x - e * ((P + TILE - 1) / TILE)) * TILE + lane;
-}
-
-// SH > 0 (sx_cem_rollout_feat_junk): the GP's inputs are D = NS + NU + SH columns -- training rows [x, u, 0_SH], queries
-// [p, 0_SH, u] -- while the reachability and the costs see (NS, NU) and the Jacobian's leading NS + NU columns (the
-// feature-GP form of JunkDimensionsSSM).  SH = 0 is the plain rollout.
-// MM = true (sx_cem_rollout_feat_multi, SH = 0): every problem has a GP of its own, `fc_arg` is the device table of their
-// FeatConst (ModelArg), the workgroups are problem-aligned (tile_problem; lanes past P are masked like those past E P in
-// the plain mode: they compute on the problem's first particle and write nothing), particle (e, i) keeps its [E x P ...]
-// buffer index, and `rp.status` holds one word per problem.
+// (cem_rollout_lanes, sx_step.hpp, with the GP's prediction; the modes SH and MM are described there)
 template <int NS, int NU, int SH = 0, bool MM = false>
 __global__ __launch_bounds__(kFeatWave) void cem_rollout_feat_kernel(typename ModelArg<FeatConst, MM>::type fc_arg,
                                                                      ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc,
                                                                      FeatRolloutPtrs rp) {
-    static_assert(!MM || SH == 0, "the multi-model rollout has no query shift");
     constexpr int D = NS + NU + SH;
-    constexpr int UC = NS + SH;   // first action column of a query row
-    static_assert(D <= SX_MAX_D, "the feature network's first layer holds at most SX_MAX_D inputs");
-    constexpr int S = NS + NS * NS;
     extern __shared__ __attribute__((aligned(16))) double feat_smem[];
-    const int lane = threadIdx.x;
-    int64_t g, gg;
-    bool valid;
-    int e;
-    if constexpr (MM) {
-        e = tile_problem<kFeatWave>(rp.P);
-        const int i = tile_particle<kFeatWave>(e, rp.P, lane);
-        valid = i < rp.P;
-        g = (int64_t)e * rp.P + i;
-        gg = valid ? g : (int64_t)e * rp.P;
-    } else {
-        g = blockIdx.x * (int64_t)kFeatWave + lane;
-        const int64_t total = (int64_t)rp.E * rp.P;
-        valid = g < total;
-        gg = valid ? g : 0;
-        e = (int)(gg / rp.P);
-    }
-    const FeatConst& fc = ModelArg<FeatConst, MM>::of(fc_arg, e);
-    const int H = rp.H;
-    double p[NS], Q[NS][NS];
-    bool have_q = rp.q0 != nullptr;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        p[i] = rp.x0[(int64_t)e * NS + i];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) Q[i][j] = have_q ? rp.q0[((int64_t)e * NS + i) * NS + j] : 0.0;
-    }
-    double obj = 0.0, con = 0.0;
-    int st = 0;
-    for (int t = 0; t < H; ++t) {
-        double z[D], u[NU], mean[NS], var[NS], jac[NS][D], p1[NS], Q1[NS][NS];
-#pragma unroll
-        for (int c = 0; c < NU; ++c) {
-            const int64_t gi = (gg * H + t) * NU + c;
-            double a;
-            if (rp.noise) {
-                a = rp.mean[((int64_t)e * H + t) * NU + c] + rp.std[((int64_t)e * H + t) * NU + c] * rp.noise[gi];
-                if (valid) rp.actions[gi] = a;
-            } else {
-                a = rp.actions[gi];
-            }
-            u[c] = a;
-        }
-#pragma unroll
-        for (int j = 0; j < NS; ++j) z[j] = p[j];
-#pragma unroll
-        for (int j = NS; j < UC; ++j) z[j] = 0.0;
-#pragma unroll
-        for (int c = 0; c < NU; ++c) z[UC + c] = u[c];
-        if (have_q) {
-            feat_gp_predict<NS, D, true>(fc, z, feat_smem, lane, mean, var, jac);
-            if constexpr (SH == 0) {
-                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st);
-            } else {
-                // [A | B]: the derivatives by the TRAINING rows' state and action columns (the reference's padding)
-                double jab[NS][NS + NU];
-#pragma unroll
-                for (int i = 0; i < NS; ++i)
-#pragma unroll
-                    for (int j = 0; j < NS + NU; ++j) jab[i][j] = jac[i][j];
-                reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jab, p1, Q1, st);
-            }
-        } else {
-            feat_gp_predict<NS, D, false>(fc, z, feat_smem, lane, mean, var, jac);
-            reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);
-        }
-        have_q = true;
-        obj += objective_cost<SX_MAX_M, NS, NU>(cc, p1, var);
-        bool uviol = false;
-#pragma unroll
-        for (int c = 0; c < NU; ++c) uviol = uviol || (u[c] < cc.u_min[c]) || (u[c] > cc.u_max[c]);
-        if (uviol) con += SX_ACTION_VIOLATION_COST;
-        if (cc.con_mode == SX_CON_ALL_STATES || t == H - 1) {
-            if (polytope_violated<SX_MAX_M, NS>(cc.h_mat, cc.h_vec, cc.m, 1.0, p1, Q1, nullptr)) con += SX_STATE_VIOLATION_COST;
-        }
-        if (valid && rp.traj) {
-            double* tr = rp.traj + (g * H + t) * S;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                tr[i] = p1[i];
-#pragma unroll
-                for (int j = 0; j < NS; ++j) tr[NS + i * NS + j] = Q1[i][j];
-            }
-        }
-        if (valid && rp.sigma) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) rp.sigma[(g * H + t) * NS + i] = var[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            p[i] = p1[i];
-#pragma unroll
-            for (int j = 0; j < NS; ++j) Q[i][j] = Q1[i][j];
-        }
-    }
-    if (valid) {
-        rp.obj_cost[g] = obj;
-        rp.con_cost[g] = con;
-        if (st) atomicOr(rp.status + (MM ? e : 0), st);
-    }
+    cem_rollout_lanes<NS, NU, SH, MM, kFeatWave, FeatConst>(
+        fc_arg, rc, cc, rp,
+        [&](auto with_jac, const FeatConst& fc, const double (&z)[D], int lane, double (&mean)[NS], double (&var)[NS],
+            double (&jac)[NS][D]) { feat_gp_predict<NS, D, decltype(with_jac)::value>(fc, z, feat_smem, lane, mean, var, jac); });
 }
 
 }  // namespace sx

@@ -286,6 +286,29 @@ static void make_cost_const(const sx_env* env, CostConst<SX_MAX_M, NS, NU>& cc) 
     cc.con_mode = env->con_mode;
 }
 
+// The reachability and cost constants of a rollout launch: SX_ERR_UNSUPPORTED for a constraint count outside
+// 1 .. SX_MAX_M, SX_ERR_ARG where B = I + kfb^T kfb has no Cholesky factor
+template <int NS, int NU>
+static int env_consts(const sx_env* env, ReachConst<NS, NU>& rc, CostConst<SX_MAX_M, NS, NU>& cc) {
+    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
+    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
+    make_cost_const<NS, NU>(env, cc);
+    return SX_OK;
+}
+
+// The arguments every rollout entry checks alike, before anything touches the device (SX_ERR_ARG where false): env, the
+// buffers, E, P, H, and what the actions come from -- with noise, the sampling distribution (mean, std) or, in the elite
+// row form (rp.elite_rows), k elite rows and both or neither of the refit's outputs.
+template <typename Ptrs>
+static bool rollout_args_ok(const sx_env* env, const Ptrs& rp) {
+    if (!env || !rp.x0 || !rp.actions || !rp.obj_cost || !rp.con_cost || !rp.status) return false;
+    if (rp.E <= 0 || rp.P <= 0 || rp.H <= 0) return false;
+    if constexpr (std::is_same<Ptrs, RolloutPtrs>::value) {
+        if (rp.elite_rows) return rp.noise && rp.elite_k > 0 && (rp.mean_out == nullptr) == (rp.std_out == nullptr);
+    }
+    return !rp.noise || (rp.mean && rp.std);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Optional kernel timer (sx_profile_*): while enabled, every n-th launch of each of the path's kernel classes carries a
 // pair of HIP events on the stream the kernel is launched on (sx_launch.hpp); sx_profile_collect adds the elapsed times up
@@ -576,9 +599,8 @@ static int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const Rol
     constexpr int D = NS + NU;
     auto gc = make_gp_const<NS, NU>(m, kRolloutThreads / 64);
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     const int64_t total = (int64_t)rp.E * rp.P;
     const int64_t p128 = (total + kBigTile - 1) / kBigTile * kBigTile;
     BigWs ws = big_ws_layout(workspace, NS, D, m->n_pad, total);
@@ -686,9 +708,8 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
         if (plan.form == SX_FORM_BIG) return launch_rollout_big<NS, NU>(m, env, rp, workspace, workspace_bytes, stream);
     }
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     RolloutPtrs rps = rp;
 #ifdef SX_STAMPS
     rps.stamps = g_stamp_host;
@@ -736,14 +757,21 @@ static int64_t gp_table_entry_bytes(int ns, int nu) {
 #undef CALL
 }
 
+// sx_gp_model_table / sx_feat_model_table / sx_mlp_model_table: one host -> device copy of the E entries on `stream`,
+// waited for
+template <typename C>
+static int copy_model_table(const std::vector<C>& host, void* table, hipStream_t stream) {
+    if (hipMemcpyAsync(table, host.data(), host.size() * sizeof(C), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return SX_ERR_LAUNCH;
+    // (the copy reads `host`, which ends with the caller)
+    return hipStreamSynchronize(stream) == hipSuccess ? SX_OK : SX_ERR_LAUNCH;
+}
+
 template <int NS, int NU>
 static int build_gp_table(const sx_gp_model* models, int E, void* table, hipStream_t stream) {
     std::vector<GpConst<NS, NS + NU>> host(E);
     for (int i = 0; i < E; ++i) host[i] = make_gp_const<NS, NU>(&models[i], kRolloutThreads / 64);
-    if (hipMemcpyAsync(table, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return SX_ERR_LAUNCH;
-    // (the copy reads `host`, which ends with this call)
-    return hipStreamSynchronize(stream) == hipSuccess ? SX_OK : SX_ERR_LAUNCH;
+    return copy_model_table(host, table, stream);
 }
 
 template <int NS, int NU>
@@ -752,9 +780,8 @@ static int launch_rollout_multi(const sx_gp_model* models, const void* table, co
     const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
     if (!plan.ok) return SX_ERR_UNSUPPORTED;
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     return launch_rollout_stream_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp,
                                                plan.form == SX_FORM_BYOUT, plan.lds, stream);
 }
@@ -762,7 +789,6 @@ static int launch_rollout_multi(const sx_gp_model* models, const void* table, co
 // sx_cem_rollout[_elites][_junk] after their argument checks
 static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
 #define CALL(NS, NU, SH) launch_rollout<NS, NU, SH>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
     SX_ROLLOUT_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
 #undef CALL
@@ -804,9 +830,8 @@ template <int NS, int NU, int SH = 0>
 static int launch_rollout_feat(const sx_feat_model* m, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
     const FeatConst fc = make_feat_const(m);
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     const size_t lds = kFeatLdsDoubles * sizeof(double);
     if (int r = allow_lds(cem_rollout_feat_kernel<NS, NU, SH>, lds)) return r;
     const int64_t total = (int64_t)rp.E * rp.P;
@@ -839,12 +864,9 @@ static int launch_mlp_predict(const sx_mlp_model* m, const double* z, int P, dou
                               hipStream_t stream) {
     const MlpConst mc = make_mlp_const(m);
     if (mlp_use_mfma(mc)) {
-        const bool full = mlp_mfma_full(mc);
-        if (mc.n_hidden == 1)
-            return full ? launch_mlp_predict_mfma<NS, NU, 1, true>(mc, z, P, mean, var, jac, stream)
-                        : launch_mlp_predict_mfma<NS, NU, 1, false>(mc, z, P, mean, var, jac, stream);
-        return full ? launch_mlp_predict_mfma<NS, NU, 2, true>(mc, z, P, mean, var, jac, stream)
-                    : launch_mlp_predict_mfma<NS, NU, 2, false>(mc, z, P, mean, var, jac, stream);
+        return mlp_mfma_form(mc, [&](auto l, auto full) {
+            return launch_mlp_predict_mfma<NS, NU, decltype(l)::value, decltype(full)::value>(mc, z, P, mean, var, jac, stream);
+        });
     }
     const size_t lds = mlp_lds_doubles(mc.n_hidden, mc.wmax) * sizeof(double);
     if (int rc = allow_lds(mlp_predict_kernel<NS, NU>, lds)) return rc;
@@ -869,16 +891,12 @@ template <int NS, int NU, int SH = 0>
 static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
     const MlpConst mc = make_mlp_const(m);
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     if (mlp_use_mfma(mc)) {
-        const bool full = mlp_mfma_full(mc);
-        if (mc.n_hidden == 1)
-            return full ? launch_rollout_mlp_mfma<NS, NU, 1, true, SH>(mc, rc, cc, rp, stream)
-                        : launch_rollout_mlp_mfma<NS, NU, 1, false, SH>(mc, rc, cc, rp, stream);
-        return full ? launch_rollout_mlp_mfma<NS, NU, 2, true, SH>(mc, rc, cc, rp, stream)
-                    : launch_rollout_mlp_mfma<NS, NU, 2, false, SH>(mc, rc, cc, rp, stream);
+        return mlp_mfma_form(mc, [&](auto l, auto full) {
+            return launch_rollout_mlp_mfma<NS, NU, decltype(l)::value, decltype(full)::value, SH>(mc, rc, cc, rp, stream);
+        });
     }
     const size_t lds = mlp_lds_doubles(mc.n_hidden, mc.wmax) * sizeof(double);
     if (int r = allow_lds(cem_rollout_mlp_kernel<NS, NU, SH>, lds)) return r;
@@ -890,22 +908,12 @@ static int launch_rollout_mlp(const sx_mlp_model* m, const sx_env* env, const Fe
 }  // namespace sx
 
 namespace sx {
-// sx_feat_model_table / sx_mlp_model_table: one host -> device copy of the E entries on `stream`, waited for
-template <typename C>
-static int copy_model_table(const std::vector<C>& host, void* table, hipStream_t stream) {
-    if (hipMemcpyAsync(table, host.data(), host.size() * sizeof(C), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return SX_ERR_LAUNCH;
-    // (the copy reads `host`, which ends with the caller)
-    return hipStreamSynchronize(stream) == hipSuccess ? SX_OK : SX_ERR_LAUNCH;
-}
-
 // sx_cem_rollout_feat_multi / _mlp_multi after their checks: the problems' shared constants, then the launch
 template <int NS, int NU>
 static int feat_multi_launch(const FeatConst* table, const sx_env* env, const FeatRolloutPtrs& rp, hipStream_t stream) {
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     return launch_rollout_feat_multi<NS, NU>(table, rc, cc, rp, stream);
 }
 
@@ -913,9 +921,8 @@ template <int NS, int NU>
 static int mlp_multi_launch(const MlpConst* table, const MlpConst& arch, bool mfma, const sx_env* env,
                             const FeatRolloutPtrs& rp, hipStream_t stream) {
     ReachConst<NS, NU> rc;
-    if (!make_reach_const<NS, NU>(env, rc)) return SX_ERR_ARG;
     CostConst<SX_MAX_M, NS, NU> cc;
-    make_cost_const<NS, NU>(env, cc);
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
     return launch_rollout_mlp_multi<NS, NU>(table, arch, mfma, rc, cc, rp, stream);
 }
 }  // namespace sx
@@ -1279,11 +1286,8 @@ int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_s
                         const double* q0, const double* mean, const double* std, const double* noise, double* actions,
                         double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
                         int64_t workspace_bytes, void* stream) {
-    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
-    if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (!rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!model || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     return sx::cem_rollout(model, env, query_shift, rp, workspace, workspace_bytes, stream);
 }
 
@@ -1291,14 +1295,12 @@ int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int 
                                const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
                                double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                                int32_t* status, double* mean_out, double* std_out, void* stream) {
-    if (!model || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
-    if (!rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
     rp.elite_rows = elite_rows;
     rp.elite_k = k;
     rp.mean_out = mean_out;
     rp.std_out = std_out;
+    if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
 }
 
@@ -1335,7 +1337,6 @@ int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H) {
 
 static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx::RolloutPtrs& rp,
                              void* stream) {
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
 #define CALL(NS, NU) sx::launch_rollout_multi<NS, NU>(models, table, env, rp, (hipStream_t)stream)
     SX_DISPATCH(env->n_s, env->n_u, CALL);
 #undef CALL
@@ -1345,11 +1346,9 @@ int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_
                          const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
                          double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
                          void* stream) {
-    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (P <= 0 || H <= 0 || !multi_models_ok(models, E)) return SX_ERR_ARG;
-    if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!table || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     return cem_rollout_multi(models, table, env, rp, stream);
 }
 
@@ -1357,14 +1356,13 @@ int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, co
                                 const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
                                 double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                                 int32_t* status, double* mean_out, double* std_out, void* stream) {
-    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status || !elite_rows || !noise) return SX_ERR_ARG;
-    if (P <= 0 || H <= 0 || k <= 0 || (mean_out == nullptr) != (std_out == nullptr)) return SX_ERR_ARG;
-    if (!multi_models_ok(models, E) || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     sx::RolloutPtrs rp{x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
     rp.elite_rows = elite_rows;
     rp.elite_k = k;
     rp.mean_out = mean_out;
     rp.std_out = std_out;
+    if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     return cem_rollout_multi(models, table, env, rp, stream);
 }
 
@@ -1444,12 +1442,9 @@ int sx_cem_rollout_feat_junk(const sx_feat_model* model, const sx_env* env, int 
                              const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
                              double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                              int32_t* status, void* stream) {
-    if (!feat_model_ok(model, query_shift > 0) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (!model->wbar || !model->minv || E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
-    if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (!junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!feat_model_ok(model, query_shift > 0) || !model->wbar || !model->minv) return SX_ERR_ARG;
+    if (!sx::rollout_args_ok(env, rp) || !junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
 #define CALL(NS, NU, SH) sx::launch_rollout_feat<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
 #define CALL_0(NS, NU) CALL(NS, NU, 0)
     SX_MODEL_JUNK_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
@@ -1489,12 +1484,9 @@ int sx_cem_rollout_mlp_junk(const sx_mlp_model* model, const sx_env* env, int qu
                             const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
                             double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                             int32_t* status, void* stream) {
-    if (!mlp_model_ok(model, query_shift > 0) || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
-    if (noise && (!mean || !std)) return SX_ERR_ARG;
-    if (!junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!mlp_model_ok(model, query_shift > 0)) return SX_ERR_ARG;
+    if (!sx::rollout_args_ok(env, rp) || !junk_env_ok(env, model->n_s, model->n_u, query_shift)) return SX_ERR_ARG;
 #define CALL(NS, NU, SH) sx::launch_rollout_mlp<NS, NU, SH>(model, env, rp, (hipStream_t)stream)
 #define CALL_0(NS, NU) CALL(NS, NU, 0)
     SX_MODEL_JUNK_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
@@ -1566,25 +1558,15 @@ int sx_mlp_model_table(const sx_mlp_model* models, int E, void* table, void* str
     return sx::copy_model_table(host, table, (hipStream_t)stream);
 }
 
-// the buffer checks the multi-model entries share with sx_cem_rollout_multi
-static bool multi_buffers_ok(const void* table, const sx_env* env, int P, int H, const double* x0, const double* mean,
-                             const double* std, const double* noise, const double* actions, const double* obj_cost,
-                             const double* con_cost, const int32_t* status) {
-    if (!table || !env || !x0 || !actions || !obj_cost || !con_cost || !status) return false;
-    if (P <= 0 || H <= 0) return false;
-    return !noise || (mean && std);
-}
-
 int sx_cem_rollout_feat_multi(const sx_feat_model* models, const void* table, const sx_env* env, int E, int P, int H,
                               const double* x0, const double* q0, const double* mean, const double* std,
                               const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
                               double* con_cost, int32_t* status, void* stream) {
-    if (!multi_buffers_ok(table, env, P, H, x0, mean, std, noise, actions, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!table || !sx::rollout_args_ok(env, rp)) return SX_ERR_ARG;
     const int check = feat_models_check(models, E);
     if (check == SX_ERR_ARG || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     if (check != SX_OK) return check;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
     const auto* tab = static_cast<const sx::FeatConst*>(table);
 #define CALL(NS, NU) sx::feat_multi_launch<NS, NU>(tab, env, rp, (hipStream_t)stream)
     SX_DISPATCH(env->n_s, env->n_u, CALL);
@@ -1595,12 +1577,11 @@ int sx_cem_rollout_mlp_multi(const sx_mlp_model* models, const void* table, cons
                              const double* x0, const double* q0, const double* mean, const double* std,
                              const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
                              double* con_cost, int32_t* status, void* stream) {
-    if (!multi_buffers_ok(table, env, P, H, x0, mean, std, noise, actions, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!table || !sx::rollout_args_ok(env, rp)) return SX_ERR_ARG;
     const int check = mlp_models_check(models, E);
     if (check == SX_ERR_ARG || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     if (check != SX_OK) return check;
-    if (env->m <= 0 || env->m > SX_MAX_M) return SX_ERR_UNSUPPORTED;
-    const sx::FeatRolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
     const auto* tab = static_cast<const sx::MlpConst*>(table);
     const sx::MlpConst arch = sx::make_mlp_const(&models[0]);
     const bool mfma = sx::mlp_use_mfma(arch);   // (the same answer for every model: they share the architecture)

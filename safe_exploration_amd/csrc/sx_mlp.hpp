@@ -16,8 +16,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sx_amd.h"
-#include "sx_feat.hpp"   // FeatRolloutPtrs, ModelArg
 #include "sx_reach.hpp"
+#include "sx_step.hpp"
 
 namespace sx {
 
@@ -235,11 +235,10 @@ __global__ __launch_bounds__(kMlpLanes) void mlp_predict_kernel(MlpConst mc, con
     }
 }
 
-// the CEM particle rollout over the ensemble: one particle per lane for all H steps (arguments as FeatRolloutPtrs).
-// SH > 0 (sx_cem_rollout_mlp_junk): the network's inputs are D = NS + NU + SH columns, queries [p, 0_SH, u], the
-// reachability step takes the Jacobian's leading NS + NU columns -- as cem_rollout_feat_kernel.
-// MM = true (sx_cem_rollout_mlp_multi, SH = 0): a network and masks per problem, `mc_arg` the device table of their
-// MlpConst; problem-aligned workgroups and one status word per problem, as cem_rollout_feat_kernel's MM mode.
+// the CEM particle rollout over the ensemble: one particle per lane for all H steps, cem_rollout_lanes (sx_step.hpp) with
+// the ensemble's prediction, where the modes SH and MM are described.  Spelled out here, step included: compiled through
+// cem_rollout_lanes, or on the step helpers of sx_step.hpp, this kernel runs 2-4 % slower (SX_MLP_PATH=valu, bench.py
+// --ssm mc_dropout).
 template <int NS, int NU, int SH = 0, bool MM = false>
 __global__ __launch_bounds__(kMlpLanes) void cem_rollout_mlp_kernel(typename ModelArg<MlpConst, MM>::type mc_arg,
                                                                     ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc,

@@ -90,6 +90,17 @@ __host__ __device__ inline bool mlp_mfma_full(const MlpConst& mc) {
     return true;
 }
 
+// The matrix-core form of an ensemble mlp_mfma_ok() admits: f(L, FULL) for L = n_hidden (1 or 2) and FULL = mlp_mfma_full,
+// both as std::integral_constant, so that f can name the kernel instantiation of the form.
+template <typename F>
+inline int mlp_mfma_form(const MlpConst& mc, F&& f) {
+    using L1 = std::integral_constant<int, 1>;
+    using L2 = std::integral_constant<int, 2>;
+    const bool full = mlp_mfma_full(mc);
+    if (mc.n_hidden == 1) return full ? f(L1{}, std::true_type{}) : f(L1{}, std::false_type{});
+    return full ? f(L2{}, std::true_type{}) : f(L2{}, std::false_type{});
+}
+
 // element (row, k) of a fragment-pair matrix with `npairs` pairs per row-block -> index in doubles
 __device__ __forceinline__ void mm_frag_decode(int idx, int npairs, int& row, int& k) {
     const int slot = idx & 1, lane = (idx >> 1) & 63, pair = idx >> 7;
@@ -632,7 +643,6 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(typena
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     static_assert(D <= SX_MAX_D && D + 1 <= 8, "a query and the bias column fill at most one 8-wide operand");
-    constexpr int S = NS + NS * NS;
     using M = MmLds<NS, D>;
     extern __shared__ __attribute__((aligned(16))) double mm_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -647,19 +657,8 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(typena
     int64_t g, gg;
     bool valid;
     int e;
-    if constexpr (MM) {
-        e = pe;
-        const int i = tile_particle<kMmTile>(e, rp.P, tid & 15);
-        valid = owner && i < rp.P;
-        g = (int64_t)e * rp.P + i;
-        gg = i < rp.P ? g : (int64_t)e * rp.P;
-    } else {
-        const int64_t total = (int64_t)rp.E * rp.P;
-        g = (int64_t)blockIdx.x * kMmTile + (tid & 15);
-        valid = owner && g < total;
-        gg = g < total ? g : 0;
-        e = (int)(gg / rp.P);
-    }
+    particle_slot<kMmTile, MM>(rp, tid & 15, g, gg, e, valid);
+    valid = owner && valid;   // (lanes 0-15 of wave 0 own the particles)
     const int H = rp.H;
     bool have_q = rp.q0 != nullptr;    // (uniform)
     int st = 0;
@@ -667,17 +666,7 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(typena
     double* sbuf = mm_smem + M::state + (tid & 15) * (NS * NS + 2);
     auto publish = [&](int t, const double (&p)[NS]) {        // the action of step t and the query point (p, u) -> LDS
 #pragma unroll
-        for (int c = 0; c < NU; ++c) {
-            const int64_t gi = (gg * H + t) * NU + c;
-            double a;
-            if (rp.noise) {
-                a = rp.mean[((int64_t)e * H + t) * NU + c] + rp.std[((int64_t)e * H + t) * NU + c] * rp.noise[gi];
-                if (valid) rp.actions[gi] = a;
-            } else {
-                a = rp.actions[gi];
-            }
-            zbuf[tid * 8 + UC + c] = a;
-        }
+        for (int c = 0; c < NU; ++c) zbuf[tid * 8 + UC + c] = step_action<NU>(rp, e, gg, H, t, c, valid);
 #pragma unroll
         for (int j = 0; j < NS; ++j) zbuf[tid * 8 + j] = p[j];
 #pragma unroll
@@ -734,27 +723,8 @@ __global__ __launch_bounds__(kMmThreads) void cem_rollout_mlp_mfma_kernel(typena
                 reach_point<NS, NU>(rc, p, u, mean, var, p1, Q1, st);
             }
             obj += objective_cost<SX_MAX_M, NS, NU>(cc, p1, var);
-            bool uviol = false;
-#pragma unroll
-            for (int c = 0; c < NU; ++c) uviol = uviol || (u[c] < cc.u_min[c]) || (u[c] > cc.u_max[c]);
-            if (uviol) con += SX_ACTION_VIOLATION_COST;
-            if (cc.con_mode == SX_CON_ALL_STATES || t == H - 1) {
-                if (polytope_violated<SX_MAX_M, NS>(cc.h_mat, cc.h_vec, cc.m, 1.0, p1, Q1, nullptr))
-                    con += SX_STATE_VIOLATION_COST;
-            }
-            if (valid && rp.traj) {
-                double* tr = rp.traj + (g * H + t) * S;
-#pragma unroll
-                for (int i = 0; i < NS; ++i) {
-                    tr[i] = p1[i];
-#pragma unroll
-                    for (int j = 0; j < NS; ++j) tr[NS + i * NS + j] = Q1[i][j];
-                }
-            }
-            if (valid && rp.sigma) {
-#pragma unroll
-                for (int i = 0; i < NS; ++i) rp.sigma[(g * H + t) * NS + i] = var[i];
-            }
+            constraint_costs<NS, NU>(cc, u, p1, Q1, t, H, con);
+            store_step<NS>(rp.traj, rp.sigma, valid, g, H, t, p1, Q1, var);
 #pragma unroll
             for (int i = 0; i < NS; ++i)
 #pragma unroll

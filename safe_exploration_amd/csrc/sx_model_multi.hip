@@ -46,12 +46,9 @@ template <int NS, int NU>
 int launch_rollout_mlp_multi(const MlpConst* table, const MlpConst& arch, bool mfma, const ReachConst<NS, NU>& rc,
                              const CostConst<SX_MAX_M, NS, NU>& cc, const FeatRolloutPtrs& rp, hipStream_t stream) {
     if (mfma) {
-        const bool full = mlp_mfma_full(arch);
-        if (arch.n_hidden == 1)
-            return full ? launch_rollout_mlp_mfma_multi<NS, NU, 1, true>(table, rc, cc, rp, stream)
-                        : launch_rollout_mlp_mfma_multi<NS, NU, 1, false>(table, rc, cc, rp, stream);
-        return full ? launch_rollout_mlp_mfma_multi<NS, NU, 2, true>(table, rc, cc, rp, stream)
-                    : launch_rollout_mlp_mfma_multi<NS, NU, 2, false>(table, rc, cc, rp, stream);
+        return mlp_mfma_form(arch, [&](auto l, auto full) {
+            return launch_rollout_mlp_mfma_multi<NS, NU, decltype(l)::value, decltype(full)::value>(table, rc, cc, rp, stream);
+        });
     }
     const unsigned grid = multi_grid(rp, kMlpLanes);
     if (grid == 0) return SX_ERR_UNSUPPORTED;

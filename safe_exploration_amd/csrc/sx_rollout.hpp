@@ -261,7 +261,8 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
             }
         }
         if (valid) st |= st_step;
-        // costs (safempc_cem.py:102-132,304-312; action constraint: test_safempc_cem.py:59-71)
+        // costs (safempc_cem.py:102-132,304-312; action constraint: test_safempc_cem.py:59-71) and stores, as
+        // constraint_costs / store_step of sx_step.hpp (which move this kernel's multi-model form by 2 %)
         obj += objective_cost<SX_MAX_M, NS, NU>(cc, p1, var);
         bool uviol = false;
 #pragma unroll

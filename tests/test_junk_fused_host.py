@@ -71,6 +71,35 @@ def test_junk_entries_refuse_null_buffers_without_a_gpu():
     assert _elites(model, env, 1, noise=None) == _lib.SX_ERR_ARG
 
 
+def test_junk_entries_refuse_bad_sizes_and_answer_the_constraint_count_last_without_a_gpu():
+    model, env = _structs(2, 2, 1)
+    lib, m, e = _lib.lib(), ctypes.byref(model), ctypes.byref(env)
+
+    def roll(E=1, P=16, H=3, x0=_P, mean=None, std=None, noise=None, con=_P):
+        return lib.sx_cem_rollout_junk(m, e, 1, E, P, H, x0, None, mean, std, noise, _P, None, None, _P, con, _P, None, 0,
+                                       None)
+
+    def elites(E=1, P=16, H=3, x0=_P, k=4, mean_out=None, std_out=None):
+        return lib.sx_cem_rollout_elites_junk(m, e, 1, E, P, H, x0, None, _P, k, _P, _P, None, None, _P, _P, _P, mean_out,
+                                              std_out, None)
+
+    for call in (roll, elites):
+        assert call(E=0) == _lib.SX_ERR_ARG
+        assert call(P=0) == _lib.SX_ERR_ARG
+        assert call(H=-1) == _lib.SX_ERR_ARG
+    assert roll(con=None) == _lib.SX_ERR_ARG
+    assert roll(noise=_P, mean=_P) == _lib.SX_ERR_ARG                   # noise without a whole distribution
+    assert roll(noise=_P, std=_P) == _lib.SX_ERR_ARG
+    assert elites(k=0) == _lib.SX_ERR_ARG
+    assert elites(mean_out=_P) == _lib.SX_ERR_ARG                       # one refit output without the other
+    for m_bad in (0, _lib.SX_MAX_M + 1):                                # constraint rows outside 1 .. SX_MAX_M
+        env.m = m_bad
+        assert roll() == _lib.SX_ERR_UNSUPPORTED
+        assert elites() == _lib.SX_ERR_UNSUPPORTED
+        assert roll(x0=None) == _lib.SX_ERR_ARG                         # argument errors answer first
+        assert elites(k=0) == _lib.SX_ERR_ARG
+
+
 def _inner(family):
     inner = mock.Mock()
     inner.kernel_family = family

@@ -103,6 +103,30 @@ def test_model_junk_entries_refuse_null_buffers_without_a_gpu(entry, make):
     assert _call(entry, bad, env, 1) == _lib.SX_ERR_ARG
 
 
+@pytest.mark.parametrize('entry,make', [('sx_cem_rollout_feat_junk', _feat), ('sx_cem_rollout_mlp_junk', _mlp)])
+def test_model_junk_entries_refuse_bad_sizes_and_answer_the_constraint_count_last_without_a_gpu(entry, make):
+    model, env = make(2, 2), _env(2, 1)
+    fn = getattr(_lib.lib(), entry)
+
+    def call(P=16, H=3, x0=_P, mean=None, std=None, noise=None, con=_P):
+        return fn(ctypes.byref(model), ctypes.byref(env), 1, 1, P, H, x0, None, mean, std, noise, _P, None, None, _P, con, _P,
+                  None)
+
+    assert call(P=0) == _lib.SX_ERR_ARG
+    assert call(H=0) == _lib.SX_ERR_ARG
+    assert call(con=None) == _lib.SX_ERR_ARG
+    assert call(noise=_P, mean=_P) == _lib.SX_ERR_ARG                   # noise without a whole distribution
+    if entry == 'sx_cem_rollout_feat_junk':
+        model.minv = None
+        assert call() == _lib.SX_ERR_ARG
+        model.minv = 16
+    for m_bad in (0, _lib.SX_MAX_M + 1):                                # constraint rows outside 1 .. SX_MAX_M
+        env.m = m_bad
+        assert call() == _lib.SX_ERR_UNSUPPORTED
+        assert call(x0=None) == _lib.SX_ERR_ARG                         # argument errors answer first
+        assert call(noise=_P) == _lib.SX_ERR_ARG
+
+
 class FeatConf:
     exact_gp_training_iterations = 0
     nn_kernel_layers = [6, 5]

@@ -142,6 +142,22 @@ def test_rollout_entry_rejects_bad_arguments_before_any_device_access(family):
     assert _rollout(fn, array([make(3, 2)]), 1, env(3, 2)) == _lib.SX_ERR_UNSUPPORTED   # no kernel for (3, 2)
 
 
+@pytest.mark.parametrize('family', sorted(FAMILIES))
+def test_rollout_entry_answers_argument_errors_before_unsupported_cases(family):
+    make, _, _, rollout, variants = FAMILIES[family]
+    fn = getattr(_lib.lib(), rollout)
+    ok, mixed = array([make(), make(), make()]), array([make(), make(**variants[0]), make()])
+    assert _rollout(fn, mixed, 3, env(), x0=None) == _lib.SX_ERR_ARG
+    assert _rollout(fn, mixed, 3, env(), noise=FAKE, mean=FAKE) == _lib.SX_ERR_ARG
+    assert _rollout(fn, array([make(3, 2)]), 1, env(3, 2), P=0) == _lib.SX_ERR_ARG
+    for m_bad in (0, _lib.SX_MAX_M + 1):                                # constraint rows outside 1 .. SX_MAX_M
+        e = env()
+        e.m = m_bad
+        assert _rollout(fn, ok, 3, e) == _lib.SX_ERR_UNSUPPORTED
+        assert _rollout(fn, ok, 3, e, status=None) == _lib.SX_ERR_ARG
+        assert _rollout(fn, mixed, 3, e) == _lib.SX_ERR_UNSUPPORTED
+
+
 class Model:
     """A stand-in for a model of the given kernel_family with a fixed struct (what fused_applies reads)."""
 

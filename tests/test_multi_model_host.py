@@ -88,6 +88,23 @@ def test_rollout_entries_reject_bad_arguments_before_any_device_access():
                                     FAKE, FAKE, FAKE, None) == _lib.SX_ERR_ARG
 
 
+def test_rollout_entries_answer_the_constraint_count_after_the_arguments():
+    lib = _lib.lib()
+    ok, env = _models([(2, 1, 60)] * 3), _env(2, 1)
+    assert lib.sx_cem_rollout_multi(ok, FAKE, ctypes.byref(env), 3, 32, 5, None, None, None, None, None, FAKE, None, None,
+                                    FAKE, FAKE, FAKE, None) == _lib.SX_ERR_ARG                    # null x0
+    assert lib.sx_cem_rollout_multi(ok, FAKE, ctypes.byref(env), 3, 32, 5, FAKE, None, None, None, None, FAKE, None, None,
+                                    None, FAKE, FAKE, None) == _lib.SX_ERR_ARG                    # null objective costs
+    assert lib.sx_cem_rollout_elites_multi(ok, FAKE, ctypes.byref(env), 3, 32, 5, FAKE, None, FAKE, 3, FAKE, FAKE, None,
+                                           None, FAKE, FAKE, FAKE, FAKE, None, None) == _lib.SX_ERR_ARG   # mean_out alone
+    for m_bad in (0, _lib.SX_MAX_M + 1):                                # constraint rows outside 1 .. SX_MAX_M
+        env.m = m_bad
+        assert _rollout(lib, ok, 3, env) == _lib.SX_ERR_UNSUPPORTED
+        assert _elites(lib, ok, 3, env) == _lib.SX_ERR_UNSUPPORTED
+        assert _rollout(lib, ok, 3, env, status=None) == _lib.SX_ERR_ARG   # argument errors answer first
+        assert _elites(lib, ok, 3, env, k=0) == _lib.SX_ERR_ARG
+
+
 @pytest.mark.skipif(bool(os.environ.get('SX_ROLLOUT')), reason='SX_ROLLOUT forces a form')
 def test_workspace_path_models_make_the_multi_form_negative():
     """The multi form is negative exactly where some model needs the workspace path (sx_cem_rollout_workspace_bytes > 0);
