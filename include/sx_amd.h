@@ -229,6 +229,34 @@ int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, dou
 int sx_gp_mll_grad(const sx_gp_model* model, const double* y_train, const double* linv, const double* alpha,
                    const double* logdet, double* work, double* mll, double* grad, void* stream);
 
+/* ---- E exact GPs' fit and MLL gradient in one launch sequence (batched hyper-parameter training) ----
+ * Every problem e has its own training set (its own N <= 4096) and hyper-parameters; all share (n_s, n_u).  Problem e's
+ * linv, alpha, logdet, mll and gradient are bit-identical to what sx_gp_fit / sx_gp_mll_grad give for that model alone.
+ * The per-problem constants and buffers live in a table of SX_GP_FIT_ENTRY_BYTES per problem, which sx_gp_fit_table
+ * writes to HOST memory: the caller copies it to the device (from pinned memory that needs no wait) and passes the
+ * device copy to the two launchers, which read it and copy nothing from the host.
+ *
+ * Bytes of the table for E problems (E * SX_GP_FIT_ENTRY_BYTES); < 0 for E <= 0. */
+#define SX_GP_FIT_ENTRY_BYTES 360
+int64_t sx_gp_fit_table_bytes(int E);
+/* Lays the E models (host array: {n_s, n_u, n_train, inv_ls2, outputscale, noise, x_train} set as for sx_gp_fit) out in
+ * `table` (HOST memory, sx_gp_fit_table_bytes() bytes) with problem e's device buffers (host arrays of E device
+ * pointers): y_train[e] dev [N_e x n_s], work[e] dev [n_s x N_e x N_e] (scratch), linv[e] dev [n_s x N_e x N_e],
+ * alpha[e] dev [n_s x N_e], logdet[e] dev [n_s]; and the shared outputs status dev int32 [E] (one word per problem,
+ * SX_STATUS_NOT_PD), mll dev [E x n_s], grad dev [E x n_s x (D + 2)].  No device access.
+ * SX_ERR_ARG for a null pointer, E <= 0, models of different (n_s, n_u) or n_s + n_u > SX_MAX_D; SX_ERR_UNSUPPORTED for
+ * N > 4096. */
+int sx_gp_fit_table(const sx_gp_model* models, int E, const double* const* y_train, double* const* work,
+                    double* const* linv, double* const* alpha, double* const* logdet, int32_t* status, double* mll,
+                    double* grad, void* table);
+/* sx_gp_fit for the E problems of `table` (dev, the device copy of sx_gp_fit_table's output for the same `models`): one
+ * launch of the one-workgroup kernel for every problem with N <= 96 and one blocked launch sequence, sized by the
+ * largest N, for the others.  The argument checks of sx_gp_fit_table (before any device access). */
+int sx_gp_fit_multi(const sx_gp_model* models, int E, const void* table, void* stream);
+/* sx_gp_mll_grad for the E problems of `table`, after sx_gp_fit_multi: mll and grad into the table's [E x ...] outputs.
+ * Replaces: the autograd pass of the n_scenarios GpCemSSM._train_model runs (episode_runner.py:55,123). */
+int sx_gp_mll_grad_multi(const sx_gp_model* models, int E, const void* table, void* stream);
+
 /* Lays W_d = L_d^-1 (dev [n_s x N x N], lower triangular) and alpha (dev [n_s x N]) out in fragment order.
  * model->{n_s,n_u,n_train,inv_ls2,x_train,a_pack,stage_tab} must be set; n_pad is filled in.
  * Replaces: GpCemSSM._update_model (ssm_cem/gp_ssm_cem.py:96-101) -- where the prediction operands are (re)built. */

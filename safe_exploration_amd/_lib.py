@@ -11,6 +11,7 @@ SX_MAX_NU = 2
 SX_MAX_D = SX_MAX_NS + SX_MAX_NU
 SX_MAX_M = 16
 SX_TILE = 16
+SX_GP_FIT_ENTRY_BYTES = 360
 SX_FEAT_MAX_WIDTH = 32
 SX_FEAT_MAX_LAYERS = 3
 SX_MLP_MAX_HIDDEN = 4
@@ -68,6 +69,10 @@ SIGNATURES = {
     'sx_gp_pack_sizes': (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     'sx_gp_fit': (c_int, [POINTER(SxGpModel)] + [c_void_p] * 7),
     'sx_gp_mll_grad': (c_int, [POINTER(SxGpModel)] + [c_void_p] * 8),
+    'sx_gp_fit_table_bytes': (c_int64, [c_int]),
+    'sx_gp_fit_table': (c_int, [POINTER(SxGpModel), c_int] + [POINTER(c_void_p)] * 5 + [c_void_p] * 4),
+    'sx_gp_fit_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),
+    'sx_gp_mll_grad_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),
     'sx_gp_pack': (c_int, [POINTER(SxGpModel), c_void_p, c_void_p, c_void_p]),
     'sx_gp_predict': (c_int, [POINTER(SxGpModel), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                               c_void_p]),

@@ -70,11 +70,70 @@ struct FitArgs {
     int n, D, n_s, panel_cols;
 };
 
-__global__ __launch_bounds__(kFitThreads) void gp_fit_kernel(FitArgs fa) {
+// One problem of a multi-model warm-path launch (sx_gp_fit_multi / sx_gp_mll_grad_multi): an entry of the device table
+// sx_gp_fit_table lays out.  It carries the fields of every Args struct the fit and MLL kernels take, under the same
+// names, so that one kernel body serves both modes.
+struct GpFitEntry {
+    double inv_ls2[SX_MAX_NS * SX_MAX_D];
+    double outputscale[SX_MAX_NS];
+    double noise[SX_MAX_NS];
+    const double* x;   // [N x D]
+    const double* y;   // [N x n_s]
+    double* lmat;      // [n_s x N x N]  the problem's `work`: K then L
+    double* scratch;   // the same `work`: the blocked MLL kernels' partial sums
+    double* linv;      // [n_s x N x N]
+    double* alpha;     // [n_s x N]
+    double* logdet;    // [n_s]
+    int* status;       // the problem's own word
+    double* mll;       // [n_s]            (the problem's rows of the caller's [E x n_s])
+    double* grad;      // [n_s x (D + 2)]  (the problem's rows of the caller's [E x n_s x (D + 2)])
+    int n, D, n_s;
+    int nblk;          // 0: N <= kBlockedFitMinN, the one-workgroup kernels serve the problem; else ceil(N / 64)
+    int panel_cols;    // the one-workgroup fit's panel width
+    int pad_;
+};
+static_assert(sizeof(GpFitEntry) == SX_GP_FIT_ENTRY_BYTES, "include/sx_amd.h: SX_GP_FIT_ENTRY_BYTES");
+
+// The argument of the warm-path kernels: the Args struct A itself (one model, the grid's output index is the output d),
+// or with MM = true the device table of E problems' GpFitEntry, of which the workgroup binds the entry of its problem:
+// the grid's output index is then e n_s + d (n_s is shared by the problems).  The pointer is restrict-qualified and
+// never written and the index is uniform, so the entry is read through the constant address space (scalar loads, and
+// the device pointers it holds are taken to be global, as those of a kernel argument are).
+// (d is derived inside `of`, so that the plain mode's statements keep their order and its ISA.)
+template <typename A, bool MM>
+struct FitArg {
+    using type = A;
+    using entry = A;
+    __device__ static const A& of(const type& a, int idx, int& d) {
+        d = idx;
+        return a;
+    }
+};
+template <typename A>
+struct FitArg<A, true> {
+    using type = const GpFitEntry* __restrict__;
+    using entry = GpFitEntry;
+    __device__ static const GpFitEntry& of(type table, int idx, int& d) {
+        using ConstE = __attribute__((address_space(4))) const GpFitEntry;
+        const ConstE* t = (const ConstE*)table;
+        const int ns = t[0].n_s;
+        const int e = idx / ns;
+        d = idx - e * ns;
+        return *(const GpFitEntry*)(t + e);
+    }
+};
+
+template <bool MM = false>
+__global__ __launch_bounds__(kFitThreads) void gp_fit_kernel(typename FitArg<FitArgs, MM>::type fa_arg) {
     __shared__ double vec[kFitMaxN];
     __shared__ double red[kFitThreads];
     extern __shared__ __attribute__((aligned(16))) double panel[];   // [n x panel_cols]
-    const int d = blockIdx.x, tid = threadIdx.x, n = fa.n, D = fa.D;
+    int d;
+    const auto& fa = FitArg<FitArgs, MM>::of(fa_arg, blockIdx.x, d);
+    if constexpr (MM) {
+        if (fa.nblk > 0) return;   // a problem of the blocked path
+    }
+    const int tid = threadIdx.x, n = fa.n, D = fa.D;
     double* A = fa.lmat + (size_t)d * n * n;
     double* W = fa.linv + (size_t)d * n * n;
     // 1. kernel matrix (lower triangle)
@@ -207,9 +266,23 @@ struct MllArgs {
     int n, D, n_s;
 };
 
-__global__ __launch_bounds__(kFitThreads) void gp_mll_grad_kernel(MllArgs ma) {
+// (the argument is bound through a pointer set in `if constexpr`, not through a call: a call that takes the plain
+// mode's by-value argument by reference, even one inlined, changed that mode's ISA -- 8 more VGPRs, signed 64-bit
+// address arithmetic)
+template <bool MM = false>
+__global__ __launch_bounds__(kFitThreads) void gp_mll_grad_kernel(typename FitArg<MllArgs, MM>::type ma_arg) {
     __shared__ double red[kFitThreads];
-    const int d = blockIdx.x, tid = threadIdx.x, n = ma.n, D = ma.D;
+    const typename FitArg<MllArgs, MM>::entry* pma;
+    int d_mm = 0;
+    if constexpr (MM)
+        pma = &FitArg<MllArgs, MM>::of(ma_arg, blockIdx.x, d_mm);
+    else
+        pma = &ma_arg;
+    const auto& ma = *pma;
+    if constexpr (MM) {
+        if (ma.nblk > 0) return;   // a problem of the blocked path
+    }
+    const int d = MM ? d_mm : (int)blockIdx.x, tid = threadIdx.x, n = ma.n, D = ma.D;
     const double* W = ma.linv + (size_t)d * n * n;
     const double* al = ma.alpha + (size_t)d * n;
     double acc[SX_MAX_D + 2];

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sx_amd.h"
+#include "sx_fit.hpp"
 #include "sx_gp.hpp"
 
 namespace sx {
@@ -91,8 +92,14 @@ __device__ __forceinline__ void for_each_result(const v4d (&acc)[4], F&& f) {
         for (int r = 0; r < 4; ++r) f(16 * wave + (lane >> 4) + 4 * r, 16 * c + (lane & 15), acc[c][r]);
 }
 
-__global__ __launch_bounds__(kFThreads) void fit_kmat_kernel(BlockedFitArgs fa) {
-    const int d = blockIdx.z, bi = blockIdx.y, bj = blockIdx.x, n = fa.n, D = fa.D;
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void fit_kmat_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg) {
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.z, d);
+    const int bi = blockIdx.y, bj = blockIdx.x, n = fa.n, D = fa.D;
+    if constexpr (MM) {
+        if (bi >= fa.nblk || bj >= fa.nblk) return;   // past this problem's blocks (all of them: nblk = 0)
+    }
     double* A = fa.lmat + (size_t)d * n * n;
     double* W = fa.linv + (size_t)d * n * n;
     for (int idx = threadIdx.x; idx < kFB * kFB; idx += kFThreads) {
@@ -112,10 +119,16 @@ __global__ __launch_bounds__(kFThreads) void fit_kmat_kernel(BlockedFitArgs fa) 
 }
 
 // one workgroup per output: factor the 64 x 64 diagonal block p in LDS, invert the factor
-__global__ __launch_bounds__(kFThreads) void fit_potrf_diag_kernel(BlockedFitArgs fa, int p) {
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void fit_potrf_diag_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg, int p) {
     __shared__ double L[kFB * kFLd];
     __shared__ double Wd[kFB * kFLd];
-    const int d = blockIdx.x, tid = threadIdx.x, n = fa.n;
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.x, d);
+    const int tid = threadIdx.x, n = fa.n;
+    if constexpr (MM) {
+        if (p >= fa.nblk) return;
+    }
     double* A = fa.lmat + (size_t)d * n * n;
     double* W = fa.linv + (size_t)d * n * n;
     load_block(L, A, n, p, p, true);
@@ -162,10 +175,16 @@ __global__ __launch_bounds__(kFThreads) void fit_potrf_diag_kernel(BlockedFitArg
 }
 
 // L_tp = A_tp W_pp^T for block rows t = p + 1 + blockIdx.x
-__global__ __launch_bounds__(kFThreads) void fit_trsm_kernel(BlockedFitArgs fa, int p) {
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void fit_trsm_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg, int p) {
     __shared__ double As[kFB * kFLd];
     __shared__ double Bs[kFB * kFLd];
-    const int d = blockIdx.y, t = p + 1 + blockIdx.x, n = fa.n;
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.y, d);
+    const int t = p + 1 + blockIdx.x, n = fa.n;
+    if constexpr (MM) {
+        if (t >= fa.nblk) return;
+    }
     double* A = fa.lmat + (size_t)d * n * n;
     const double* W = fa.linv + (size_t)d * n * n;
     load_block(As, A, n, t, p, false);
@@ -180,11 +199,17 @@ __global__ __launch_bounds__(kFThreads) void fit_trsm_kernel(BlockedFitArgs fa, 
 }
 
 // A_ts -= L_tp L_sp^T for the trailing block pairs t >= s > p
-__global__ __launch_bounds__(kFThreads) void fit_syrk_kernel(BlockedFitArgs fa, int p) {
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void fit_syrk_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg, int p) {
     __shared__ double As[kFB * kFLd];
     __shared__ double Bs[kFB * kFLd];
-    const int d = blockIdx.z, t = p + 1 + blockIdx.y, s = p + 1 + blockIdx.x, n = fa.n;
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.z, d);
+    const int t = p + 1 + blockIdx.y, s = p + 1 + blockIdx.x, n = fa.n;
     if (s > t) return;
+    if constexpr (MM) {
+        if (t >= fa.nblk) return;   // (s <= t)
+    }
     double* A = fa.lmat + (size_t)d * n * n;
     load_block(As, A, n, t, p, false);
     load_block(Bs, A, n, s, p, false);
@@ -227,10 +252,16 @@ __device__ __forceinline__ void strip_mma(v4d& acc, const double* As, const doub
     for (int k0 = 0; k0 < kFB; k0 += 4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(arow[k0], bcol[k0 * kFLd], acc, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(kFThreads) void fit_trtri_kernel(BlockedFitArgs fa) {
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void fit_trtri_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg) {
     __shared__ double As[kFB * kFLd];
     __shared__ double Bs[kFB * kFLd];
-    const int d = blockIdx.y, j = blockIdx.x, strip = blockIdx.z, n = fa.n;
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.y, d);
+    const int j = blockIdx.x, strip = blockIdx.z, n = fa.n;
+    if constexpr (MM) {
+        if (j >= fa.nblk) return;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double* A = fa.lmat + (size_t)d * n * n;
     double* W = fa.linv + (size_t)d * n * n;
@@ -261,10 +292,16 @@ __global__ __launch_bounds__(kFThreads) void fit_trtri_kernel(BlockedFitArgs fa)
 
 // alpha = W^T (W y) and sum log diag L: one 1024-thread workgroup per output, t = W y kept in LDS (N <= 4096).
 // Memory-bound on one CU (W is read twice: 64 MB per output at N = 2000, ~0.5 ms) -- a warm-path tail.
-__global__ __launch_bounds__(1024) void fit_alpha_logdet_kernel(BlockedFitArgs fa) {
+template <bool MM = false>
+__global__ __launch_bounds__(1024) void fit_alpha_logdet_kernel(typename FitArg<BlockedFitArgs, MM>::type fa_arg) {
     extern __shared__ __attribute__((aligned(16))) double tvec[];  // [n]
     __shared__ double red[1024];
-    const int d = blockIdx.x, tid = threadIdx.x, n = fa.n;
+    int d;
+    const auto& fa = FitArg<BlockedFitArgs, MM>::of(fa_arg, blockIdx.x, d);
+    if constexpr (MM) {
+        if (fa.nblk == 0) return;   // a problem of the one-workgroup path
+    }
+    const int tid = threadIdx.x, n = fa.n;
     const int lane = tid & 63, wave = tid >> 6;
     const double* A = fa.lmat + (size_t)d * n * n;
     const double* W = fa.linv + (size_t)d * n * n;
@@ -321,12 +358,18 @@ struct BlockedMllArgs {
     int n, D, n_s, nblk;
 };
 
-__global__ __launch_bounds__(kFThreads) void mll_pairs_kernel(BlockedMllArgs ma) {
+template <bool MM = false>
+__global__ __launch_bounds__(kFThreads) void mll_pairs_kernel(typename FitArg<BlockedMllArgs, MM>::type ma_arg) {
     __shared__ double As[kFB * kFLd];
     __shared__ double Bs[kFB * kFLd];
     __shared__ double red[kFThreads / 64][SX_MAX_D + 2];
-    const int d = blockIdx.z, bi = blockIdx.y, bj = blockIdx.x, n = ma.n, D = ma.D;
+    int d;
+    const auto& ma = FitArg<BlockedMllArgs, MM>::of(ma_arg, blockIdx.z, d);
+    const int bi = blockIdx.y, bj = blockIdx.x, n = ma.n, D = ma.D;
     if (bj > bi) return;
+    if constexpr (MM) {
+        if (bi >= ma.nblk) return;   // (bj <= bi)
+    }
     const double* W = ma.linv + (size_t)d * n * n;
     const double* al = ma.alpha + (size_t)d * n;
     v4d acc[4] = {};
@@ -372,9 +415,15 @@ __global__ __launch_bounds__(kFThreads) void mll_pairs_kernel(BlockedMllArgs ma)
     }
 }
 
-__global__ __launch_bounds__(256) void mll_reduce_kernel(BlockedMllArgs ma) {
+template <bool MM = false>
+__global__ __launch_bounds__(256) void mll_reduce_kernel(typename FitArg<BlockedMllArgs, MM>::type ma_arg) {
     __shared__ double red[256];
-    const int d = blockIdx.x, tid = threadIdx.x, n = ma.n, D = ma.D;
+    int d;
+    const auto& ma = FitArg<BlockedMllArgs, MM>::of(ma_arg, blockIdx.x, d);
+    if constexpr (MM) {
+        if (ma.nblk == 0) return;   // a problem of the one-workgroup path
+    }
+    const int tid = threadIdx.x, n = ma.n, D = ma.D;
     const int npairs = ma.nblk * (ma.nblk + 1) / 2;
     const double* part = ma.scratch + (size_t)d * n * n;
     for (int c = 0; c < D + 3; ++c) {

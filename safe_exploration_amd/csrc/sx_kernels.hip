@@ -1008,6 +1008,14 @@ int sx_gp_pack_sizes(int n_s, int n_u, int n_train, int64_t* a_doubles, int64_t*
     return SX_OK;
 }
 
+// the one-workgroup fit's panel width for N points (sx_gp_fit): as wide as the LDS left beside the static arrays allows
+// (vec 32 KB + red 8 KB), at most 32
+static int fit_panel_cols(int n) {
+    const size_t lds_budget = 112 * 1024;
+    const int nb = (int)(lds_budget / (sizeof(double) * (size_t)n));
+    return nb > 32 ? 32 : (nb < 1 ? 1 : nb);
+}
+
 int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, double* linv, double* alpha,
               double* logdet, int32_t* status, void* stream) {
     if (!model || !model->x_train || !y_train || !work || !linv || !alpha || !logdet || !status) return SX_ERR_ARG;
@@ -1042,17 +1050,17 @@ int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, dou
         ba.nblk = (ba.n + sx::kFB - 1) / sx::kFB;
         hipStream_t s = (hipStream_t)stream;
         const int nb = ba.nblk, ns = ba.n_s;
-        hipLaunchKernelGGL(sx::fit_kmat_kernel, dim3(nb, nb, ns), dim3(sx::kFThreads), 0, s, ba);
+        hipLaunchKernelGGL(sx::fit_kmat_kernel<false>, dim3(nb, nb, ns), dim3(sx::kFThreads), 0, s, ba);
         for (int p = 0; p < nb; ++p) {
-            hipLaunchKernelGGL(sx::fit_potrf_diag_kernel, dim3(ns), dim3(sx::kFThreads), 0, s, ba, p);
+            hipLaunchKernelGGL(sx::fit_potrf_diag_kernel<false>, dim3(ns), dim3(sx::kFThreads), 0, s, ba, p);
             const int m = nb - p - 1;
             if (m > 0) {
-                hipLaunchKernelGGL(sx::fit_trsm_kernel, dim3(m, ns), dim3(sx::kFThreads), 0, s, ba, p);
-                hipLaunchKernelGGL(sx::fit_syrk_kernel, dim3(m, m, ns), dim3(sx::kFThreads), 0, s, ba, p);
+                hipLaunchKernelGGL(sx::fit_trsm_kernel<false>, dim3(m, ns), dim3(sx::kFThreads), 0, s, ba, p);
+                hipLaunchKernelGGL(sx::fit_syrk_kernel<false>, dim3(m, m, ns), dim3(sx::kFThreads), 0, s, ba, p);
             }
         }
-        hipLaunchKernelGGL(sx::fit_trtri_kernel, dim3(nb, ns, sx::kFB / 16), dim3(sx::kFThreads), 0, s, ba);
-        hipLaunchKernelGGL(sx::fit_alpha_logdet_kernel, dim3(ns), dim3(1024), sizeof(double) * (size_t)ba.n, s, ba);
+        hipLaunchKernelGGL(sx::fit_trtri_kernel<false>, dim3(nb, ns, sx::kFB / 16), dim3(sx::kFThreads), 0, s, ba);
+        hipLaunchKernelGGL(sx::fit_alpha_logdet_kernel<false>, dim3(ns), dim3(1024), sizeof(double) * (size_t)ba.n, s, ba);
         return sx::check_launch();
     }
     fa.x = model->x_train;
@@ -1065,19 +1073,16 @@ int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, dou
     fa.n = model->n_train;
     fa.D = D;
     fa.n_s = model->n_s;
-    // panel width: as wide as the LDS left beside the static arrays allows (vec 32 KB + red 8 KB), at most 32
-    const size_t lds_budget = 112 * 1024;
-    int nb = (int)(lds_budget / (sizeof(double) * (size_t)fa.n));
-    nb = nb > 32 ? 32 : (nb < 1 ? 1 : nb);
+    const int nb = fit_panel_cols(fa.n);
     fa.panel_cols = nb;
     const size_t lds = sizeof(double) * (size_t)fa.n * nb;
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(sx::gp_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(sx::gp_fit_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         return SX_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(sx::gp_fit_kernel, dim3(model->n_s), dim3(sx::kFitThreads), lds, (hipStream_t)stream, fa);
+    hipLaunchKernelGGL(sx::gp_fit_kernel<false>, dim3(model->n_s), dim3(sx::kFitThreads), lds, (hipStream_t)stream, fa);
     return sx::check_launch();
 }
 
@@ -1104,8 +1109,8 @@ int sx_gp_mll_grad(const sx_gp_model* model, const double* y_train, const double
         ba.D = Db;
         ba.n_s = model->n_s;
         ba.nblk = (ba.n + sx::kFB - 1) / sx::kFB;
-        hipLaunchKernelGGL(sx::mll_pairs_kernel, dim3(ba.nblk, ba.nblk, ba.n_s), dim3(sx::kFThreads), 0, (hipStream_t)stream, ba);
-        hipLaunchKernelGGL(sx::mll_reduce_kernel, dim3(ba.n_s), dim3(256), 0, (hipStream_t)stream, ba);
+        hipLaunchKernelGGL(sx::mll_pairs_kernel<false>, dim3(ba.nblk, ba.nblk, ba.n_s), dim3(sx::kFThreads), 0, (hipStream_t)stream, ba);
+        hipLaunchKernelGGL(sx::mll_reduce_kernel<false>, dim3(ba.n_s), dim3(256), 0, (hipStream_t)stream, ba);
         return sx::check_launch();
     }
     sx::MllArgs ma;
@@ -1126,7 +1131,129 @@ int sx_gp_mll_grad(const sx_gp_model* model, const double* y_train, const double
     ma.n = model->n_train;
     ma.D = D;
     ma.n_s = model->n_s;
-    hipLaunchKernelGGL(sx::gp_mll_grad_kernel, dim3(model->n_s), dim3(sx::kFitThreads), 0, (hipStream_t)stream, ma);
+    hipLaunchKernelGGL(sx::gp_mll_grad_kernel<false>, dim3(model->n_s), dim3(sx::kFitThreads), 0, (hipStream_t)stream, ma);
+    return sx::check_launch();
+}
+
+// ---- E exact GPs' fit and MLL gradient in one launch sequence (sx_gp_fit_table, sx_gp_fit_multi, sx_gp_mll_grad_multi)
+
+// the E models of a multi-model fit: one (n_s, n_u), a training set each; SX_OK, or the code to answer
+static int fit_models_check(const sx_gp_model* models, int E) {
+    if (!models || E <= 0) return SX_ERR_ARG;
+    const int ns = models[0].n_s, nu = models[0].n_u;
+    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || ns + nu > SX_MAX_D) return SX_ERR_ARG;
+    for (int e = 0; e < E; ++e)
+        if (models[e].n_s != ns || models[e].n_u != nu || models[e].n_train <= 0 || !models[e].x_train) return SX_ERR_ARG;
+    for (int e = 0; e < E; ++e)
+        if (models[e].n_train > sx::kFitMaxN) return SX_ERR_UNSUPPORTED;
+    return SX_OK;
+}
+
+// what one multi-model launch sequence needs: the largest block count of the blocked problems (0: none), the largest N of
+// the one-workgroup problems (0: none)
+struct FitMultiPlan {
+    int nb_max = 0, small_n_max = 0;
+};
+static FitMultiPlan plan_fit_multi(const sx_gp_model* models, int E) {
+    FitMultiPlan plan;
+    for (int e = 0; e < E; ++e) {
+        const int n = models[e].n_train;
+        if (n > sx::kBlockedFitMinN)
+            plan.nb_max = std::max(plan.nb_max, (n + sx::kFB - 1) / sx::kFB);
+        else
+            plan.small_n_max = std::max(plan.small_n_max, n);
+    }
+    return plan;
+}
+
+int64_t sx_gp_fit_table_bytes(int E) {
+    if (E <= 0) return -1;
+    return (int64_t)E * (int64_t)sizeof(sx::GpFitEntry);
+}
+
+int sx_gp_fit_table(const sx_gp_model* models, int E, const double* const* y_train, double* const* work,
+                    double* const* linv, double* const* alpha, double* const* logdet, int32_t* status, double* mll,
+                    double* grad, void* table) {
+    if (!y_train || !work || !linv || !alpha || !logdet || !status || !mll || !grad || !table) return SX_ERR_ARG;
+    if (int r = fit_models_check(models, E)) return r;
+    for (int e = 0; e < E; ++e)
+        if (!y_train[e] || !work[e] || !linv[e] || !alpha[e] || !logdet[e]) return SX_ERR_ARG;
+    const int ns = models[0].n_s, D = ns + models[0].n_u;
+    sx::GpFitEntry* out = static_cast<sx::GpFitEntry*>(table);
+    for (int e = 0; e < E; ++e) {
+        const sx_gp_model& m = models[e];
+        sx::GpFitEntry t;
+        std::memset(&t, 0, sizeof(t));
+        for (int i = 0; i < ns * D; ++i) t.inv_ls2[i] = m.inv_ls2[i];
+        for (int i = 0; i < ns; ++i) {
+            t.outputscale[i] = m.outputscale[i];
+            t.noise[i] = m.noise[i];
+        }
+        t.x = m.x_train;
+        t.y = y_train[e];
+        t.lmat = t.scratch = work[e];
+        t.linv = linv[e];
+        t.alpha = alpha[e];
+        t.logdet = logdet[e];
+        t.status = status + e;
+        t.mll = mll + (size_t)e * ns;
+        t.grad = grad + (size_t)e * ns * (D + 2);
+        t.n = m.n_train;
+        t.D = D;
+        t.n_s = ns;
+        t.nblk = m.n_train > sx::kBlockedFitMinN ? (m.n_train + sx::kFB - 1) / sx::kFB : 0;
+        t.panel_cols = fit_panel_cols(m.n_train);
+        std::memcpy(out + e, &t, sizeof(t));
+    }
+    return SX_OK;
+}
+
+int sx_gp_fit_multi(const sx_gp_model* models, int E, const void* table, void* stream) {
+    if (!table) return SX_ERR_ARG;
+    if (int r = fit_models_check(models, E)) return r;
+    const FitMultiPlan plan = plan_fit_multi(models, E);
+    const sx::GpFitEntry* tab = static_cast<const sx::GpFitEntry*>(table);
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = E * models[0].n_s;   // the (problem, output) grid dimension
+    if (plan.small_n_max > 0) {
+        // N <= 96: the panel is 32 columns wide for every such problem, at most 24 KB of LDS
+        const size_t lds = sizeof(double) * (size_t)plan.small_n_max * fit_panel_cols(plan.small_n_max);
+        hipLaunchKernelGGL(sx::gp_fit_kernel<true>, dim3(rows), dim3(sx::kFitThreads), lds, s, tab);
+    }
+    if (plan.nb_max > 0) {
+        const int nb = plan.nb_max;
+        int n_max = 0;
+        for (int e = 0; e < E; ++e) n_max = std::max(n_max, (int)models[e].n_train);
+        hipLaunchKernelGGL(sx::fit_kmat_kernel<true>, dim3(nb, nb, rows), dim3(sx::kFThreads), 0, s, tab);
+        for (int p = 0; p < nb; ++p) {
+            hipLaunchKernelGGL(sx::fit_potrf_diag_kernel<true>, dim3(rows), dim3(sx::kFThreads), 0, s, tab, p);
+            const int m = nb - p - 1;
+            if (m > 0) {
+                hipLaunchKernelGGL(sx::fit_trsm_kernel<true>, dim3(m, rows), dim3(sx::kFThreads), 0, s, tab, p);
+                hipLaunchKernelGGL(sx::fit_syrk_kernel<true>, dim3(m, m, rows), dim3(sx::kFThreads), 0, s, tab, p);
+            }
+        }
+        hipLaunchKernelGGL(sx::fit_trtri_kernel<true>, dim3(nb, rows, sx::kFB / 16), dim3(sx::kFThreads), 0, s, tab);
+        hipLaunchKernelGGL(sx::fit_alpha_logdet_kernel<true>, dim3(rows), dim3(1024), sizeof(double) * (size_t)n_max, s,
+                           tab);
+    }
+    return sx::check_launch();
+}
+
+int sx_gp_mll_grad_multi(const sx_gp_model* models, int E, const void* table, void* stream) {
+    if (!table) return SX_ERR_ARG;
+    if (int r = fit_models_check(models, E)) return r;
+    const FitMultiPlan plan = plan_fit_multi(models, E);
+    const sx::GpFitEntry* tab = static_cast<const sx::GpFitEntry*>(table);
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = E * models[0].n_s;
+    if (plan.small_n_max > 0)
+        hipLaunchKernelGGL(sx::gp_mll_grad_kernel<true>, dim3(rows), dim3(sx::kFitThreads), 0, s, tab);
+    if (plan.nb_max > 0) {
+        const int nb = plan.nb_max;
+        hipLaunchKernelGGL(sx::mll_pairs_kernel<true>, dim3(nb, nb, rows), dim3(sx::kFThreads), 0, s, tab);
+        hipLaunchKernelGGL(sx::mll_reduce_kernel<true>, dim3(rows), dim3(256), 0, s, tab);
+    }
     return sx::check_launch();
 }
 

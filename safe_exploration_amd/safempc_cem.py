@@ -18,6 +18,7 @@ from . import _lib, gp_reachability_pytorch
 from .cem_mpc import FusedCemMpc, MultiModelCemMpc, Rollouts, multi_family
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
+from .ssm_cem import gp_ssm_cem
 from .ssm_cem.gp_ssm_cem import GpCemSSM
 from .ssm_cem.ssm_cem import CemSSM
 from .utils import assert_shape, dlqr, get_device
@@ -501,3 +502,22 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
         actions.append(action)
         results.append(result)
     return np.stack(actions), results
+
+
+def update_models_multi(solvers: Sequence[CemSafeMPC], xs: Sequence[ndarray], ys: Sequence[ndarray], opt_hyp=False,
+                        replace_old=True) -> None:
+    """``update_model`` of several independent solvers at once -- the counterpart of ``get_actions_multi`` for the
+    reference's retraining of every scenario's model after an episode (episode_runner.py:55,123): solver e's model learns
+    the error of (xs[e], ys[e]) to its linear prior, as ``CemSafeMPC.update_model``.  Exact RBF GPs of one shape train in
+    lockstep (``gp_ssm_cem.update_models_multi``: one fit and one MLL-gradient launch sequence per Adam step for all of
+    them), with the results of one update_model per solver; other models are updated one at a time."""
+    solvers, xs, ys = list(solvers), list(xs), list(ys)
+    if not len(solvers) == len(xs) == len(ys):
+        raise ValueError(f'{len(solvers)} solvers, {len(xs)} input sets, {len(ys)} target sets')
+    xs_t, ys_t = [], []
+    for s, x, y in zip(solvers, xs, ys):
+        x_s, x_u = x[:, :s.state_dimen], x[:, s.state_dimen:]
+        y_error = y - s.eval_prior(x_s, x_u) if s._use_prior_model else y
+        xs_t.append(torch.tensor(x, device=s._device))
+        ys_t.append(torch.tensor(y_error, device=s._device))
+    gp_ssm_cem.update_models_multi([s._ssm for s in solvers], xs_t, ys_t, opt_hyp, replace_old)

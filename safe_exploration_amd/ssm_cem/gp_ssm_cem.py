@@ -13,7 +13,7 @@ Hyper-parameters follow gpytorch's parameterisation (softplus of a raw parameter
 1e-4 floor).  gpytorch is not available to check these defaults against: "parity unpinned" (DESIGN.md).
 """
 import ctypes
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -119,23 +119,35 @@ class GpCemSSM(CemSSM):
             self._update_model(self._x_train, self._y_train)
 
     # ---- model (re)build: the warm path ------------------------------------------------------------------------
+    def _fit_struct(self, x: Tensor, raw: Optional[Tuple[Tensor, Tensor, Tensor]] = None) -> _lib.SxGpModel:
+        """The sx_gp_model sx_gp_fit takes: training inputs x (device, contiguous) and the hyper-parameters of the raw
+        parameters `raw` = (lengthscale, outputscale, noise), the model's own by default."""
+        raw_ls, raw_os, raw_noise = raw if raw is not None else (self._raw_lengthscale, self._raw_outputscale,
+                                                                 self._raw_noise)
+        m = _lib.SxGpModel()
+        m.n_s, m.n_u, m.n_train = self.num_states, self.num_actions, x.size(0)
+        _lib.fill(m.inv_ls2, (1.0 / F.softplus(raw_ls) ** 2).numpy())
+        _lib.fill(m.outputscale, F.softplus(raw_os).numpy())
+        _lib.fill(m.noise, (F.softplus(raw_noise) + self._noise_floor).numpy())
+        m.x_train = x.data_ptr()
+        return m
+
+    def _fit_workspace(self, n: int, dev) -> Tuple[Tensor, Tensor]:
+        """(work, linv) of sx_gp_fit for N = n, reused across fits of one size."""
+        if self._fit_ws is None or self._fit_ws[0].size(1) != n or self._fit_ws[0].device != dev:
+            self._fit_ws = (torch.empty((self.num_states, n, n), dtype=torch.float64, device=dev),
+                            torch.empty((self.num_states, n, n), dtype=torch.float64, device=dev))
+        self._linv_current = False   # (set again by _update_model, whose fit is the model's)
+        return self._fit_ws
+
     def _fit(self, x: Tensor, y: Tensor):
         """sx_gp_fit for the current hyper-parameters.  Returns (model struct, linv, alpha, logdet); raises if the
         kernel matrix is not positive definite."""
         lib = _lib.lib()
         dev = x.device
-        n_s, n_u, n = self.num_states, self.num_actions, x.size(0)
-        m = _lib.SxGpModel()
-        m.n_s, m.n_u, m.n_train = n_s, n_u, n
-        _lib.fill(m.inv_ls2, (1.0 / self.lengthscale ** 2).numpy())
-        _lib.fill(m.outputscale, self.outputscale.numpy())
-        _lib.fill(m.noise, self.noise.numpy())
-        m.x_train = x.data_ptr()
-        if self._fit_ws is None or self._fit_ws[0].size(1) != n or self._fit_ws[0].device != dev:
-            self._fit_ws = (torch.empty((n_s, n, n), dtype=torch.float64, device=dev),
-                            torch.empty((n_s, n, n), dtype=torch.float64, device=dev))
-        work, linv = self._fit_ws
-        self._linv_current = False   # (set again by _update_model, whose fit is the model's)
+        n_s, n = self.num_states, x.size(0)
+        m = self._fit_struct(x)
+        work, linv = self._fit_workspace(n, dev)
         alpha = torch.empty((n_s, n), dtype=torch.float64, device=dev)
         logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -144,32 +156,41 @@ class GpCemSSM(CemSSM):
         return m, linv, alpha, logdet, status
 
     def _update_model(self, x_train: Tensor, y_train: Tensor) -> None:
-        n_s, n_u, n = self.num_states, self.num_actions, x_train.size(0)
+        n = x_train.size(0)
         if n > MAX_TRAINING_POINTS:
             raise ValueError(f'{n} training points: the exact-GP kernels hold up to {MAX_TRAINING_POINTS} (sx_gp_fit); keep the '
                              f'most recent / most informative ones (update_model(..., replace_old=True))')
         _lib.require_gpu(x_train, 'train_x')
         _lib.require_gpu(y_train, 'train_y')
-        lib = _lib.lib()
-        dev = x_train.device
         x = x_train.detach().contiguous()
         y = y_train.detach().contiguous()
-        a_n, t_n = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(lib.sx_gp_pack_sizes(n_s, n_u, n, ctypes.byref(a_n), ctypes.byref(t_n)), 'sx_gp_pack_sizes')
-        a_pack = torch.empty(a_n.value, dtype=torch.float64, device=dev)
-        stage_tab = torch.empty(t_n.value, dtype=torch.int32, device=dev)
         # factorise on the device (sx_gp_fit), then lay the operands out for the matrix cores (sx_gp_pack)
         m, linv, alpha, logdet, status = self._fit(x, y)
-        m.a_pack, m.stage_tab = a_pack.data_ptr(), stage_tab.data_ptr()
-        _lib.check(lib.sx_gp_pack(ctypes.byref(m), _lib.ptr(linv), _lib.ptr(alpha), _lib.stream_ptr(dev)), 'sx_gp_pack')
+        packed = self._pack(m, linv, alpha)
         if int(status.item()) & _lib.SX_STATUS_NOT_PD:
             raise RuntimeError('the kernel matrix K + noise I is not positive definite for the current hyper-parameters')
+        self._install(x, m, packed, alpha, logdet.cpu())
+
+    def _pack(self, m: _lib.SxGpModel, linv: Tensor, alpha: Tensor) -> Tuple[Tensor, Tensor]:
+        """sx_gp_pack of a fitted model into new buffers: (a_pack, stage_tab), which `m` then points at."""
+        lib = _lib.lib()
+        dev = linv.device
+        a_n, t_n = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(lib.sx_gp_pack_sizes(m.n_s, m.n_u, m.n_train, ctypes.byref(a_n), ctypes.byref(t_n)), 'sx_gp_pack_sizes')
+        a_pack = torch.empty(a_n.value, dtype=torch.float64, device=dev)
+        stage_tab = torch.empty(t_n.value, dtype=torch.int32, device=dev)
+        m.a_pack, m.stage_tab = a_pack.data_ptr(), stage_tab.data_ptr()
+        _lib.check(lib.sx_gp_pack(ctypes.byref(m), _lib.ptr(linv), _lib.ptr(alpha), _lib.stream_ptr(dev)), 'sx_gp_pack')
+        return a_pack, stage_tab
+
+    def _install(self, x: Tensor, m: _lib.SxGpModel, packed: Tuple[Tensor, Tensor], alpha: Tensor, logdet: Tensor) -> None:
+        """Makes the packed fit of x the model's (logdet: host [n_s]); the fit workspace holds its W."""
         self._model = m
-        self._buffers = (x, a_pack, stage_tab)
+        self._buffers = (x,) + tuple(packed)
         self._alpha = alpha
         self._linv_current = True
         # 1/2 log det(I + K_d / noise_d) = sum log diag L_d - N/2 log noise_d
-        self._info_gain = (logdet.cpu() - 0.5 * n * torch.log(self.noise)).numpy()
+        self._info_gain = (logdet - 0.5 * x.size(0) * torch.log(self.noise)).numpy()
 
     def mll_and_grad(self, x_train: Tensor, y_train: Tensor):
         """Exact marginal log likelihood per output [n_s] and its gradient [n_s x (D + 2)] w.r.t.
@@ -310,3 +331,143 @@ class GpCemSSM(CemSSM):
     @property
     def parametric(self) -> bool:
         return False
+
+
+# ---- E exact GPs trained in lockstep: the reference's n_scenarios models (episode_runner.py:55,123) -----------------------
+def _multi_fit_applies(ssms: Sequence[CemSSM], xs: Sequence[Tensor]) -> bool:
+    """Do these models train together (update_models_multi)?  Exact RBF GPs of one (n_s, n_u) and one training-iteration
+    count, with their data on one device."""
+    first = ssms[0]
+    return (all(isinstance(m, GpCemSSM) and m.kernel_family == 'rbf' for m in ssms)
+            and all((m.num_states, m.num_actions, m._training_iterations)
+                    == (first.num_states, first.num_actions, first._training_iterations) for m in ssms)
+            and all(x.device == xs[0].device for x in xs)
+            and len({id(m) for m in ssms}) == len(ssms))
+
+
+class _MultiFit:
+    """The device side of a multi-model fit: problem e's fit buffers (its model's fit workspace, alpha, logdet), the
+    stacked outputs (status [E], mll [E x n_s], grad [E x n_s x (D + 2)]) and the problem table, written by
+    sx_gp_fit_table into pinned host memory and copied to the device on the stream without a wait."""
+
+    def __init__(self, ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor]):
+        lib = _lib.lib()
+        dev = xs[0].device
+        self.ssms, self.xs, self.ys, self.E = ssms, xs, ys, len(ssms)
+        n_s, d_in = ssms[0].num_states, ssms[0].num_states + ssms[0].num_actions
+        self.ws = [m._fit_workspace(x.size(0), dev) for m, x in zip(ssms, xs)]
+        self.alpha = [torch.empty((n_s, x.size(0)), dtype=torch.float64, device=dev) for x in xs]
+        self.logdet = torch.empty((self.E, n_s), dtype=torch.float64, device=dev)
+        self.status = torch.zeros(self.E, dtype=torch.int32, device=dev)
+        self.mll = torch.empty((self.E, n_s), dtype=torch.float64, device=dev)
+        self.grad = torch.empty((self.E, n_s, d_in + 2), dtype=torch.float64, device=dev)
+        nbytes = int(lib.sx_gp_fit_table_bytes(self.E))
+        self.host_table = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        self.table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.stream = _lib.stream_ptr(dev)
+
+    def new_alpha(self) -> None:
+        """Fresh alpha buffers: the final fit's become the models' own."""
+        self.alpha = [torch.empty_like(a) for a in self.alpha]
+
+    def launch(self, raws: List[Tuple[Tensor, Tensor, Tensor]], mll: bool):
+        """sx_gp_fit_multi (and sx_gp_mll_grad_multi) at the raw hyper-parameters raws[e]; returns the E model structs."""
+        lib = _lib.lib()
+        E = self.E
+        models = (_lib.SxGpModel * E)(*[m._fit_struct(x, raw) for m, x, raw in zip(self.ssms, self.xs, raws)])
+        arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
+        _lib.check(lib.sx_gp_fit_table(models, E, arr(self.ys), arr([w[0] for w in self.ws]), arr([w[1] for w in self.ws]),
+                                       arr(self.alpha), arr(list(self.logdet)), _lib.ptr(self.status), _lib.ptr(self.mll),
+                                       _lib.ptr(self.grad), ctypes.c_void_p(self.host_table.data_ptr())), 'sx_gp_fit_table')
+        # (the previous step's copy has completed: every step ends in a host read of its results)
+        self.table.copy_(self.host_table, non_blocking=True)
+        self.status.zero_()
+        _lib.check(lib.sx_gp_fit_multi(models, E, _lib.ptr(self.table), self.stream), 'sx_gp_fit_multi')
+        if mll:
+            _lib.check(lib.sx_gp_mll_grad_multi(models, E, _lib.ptr(self.table), self.stream), 'sx_gp_mll_grad_multi')
+        return models
+
+    def check_status(self, status: Tensor) -> None:
+        """Raises for the first problem whose kernel matrix is not positive definite (status: host [E])."""
+        for e in range(self.E):
+            if int(status[e]) & _lib.SX_STATUS_NOT_PD:
+                raise RuntimeError(f'problem {e}: the kernel matrix K + noise I is not positive definite for the current '
+                                   f'hyper-parameters')
+
+
+def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequence[Tensor], opt_hyp=False,
+                        replace_old=False) -> None:
+    """``m.update_model(x, y, opt_hyp, replace_old)`` for every (m, x, y) at once: the reference's n_scenarios models, each
+    retrained on its own data after every episode (episode_runner.py:55,123).
+
+    Exact RBF GPs of one (n_s, n_u) and one iteration count train in lockstep: per Adam step ONE sx_gp_fit_multi and ONE
+    sx_gp_mll_grad_multi launch sequence for all of them and one host read, then one batched fit and an sx_gp_pack per
+    model.  Adam is the recipe of GpCemSSM._train_model, one optimizer over every model's raw parameters; its update is
+    elementwise, and each model keeps its own parameter tensors, so each follows the trajectory it would follow alone:
+    the hyper-parameters, loss curves (``_last_training_losses``) and predictions equal those of per-model
+    ``update_model`` bit for bit.  A kernel matrix that is not positive definite in problem e raises RuntimeError naming
+    e, and then no model's data, hyper-parameters or predictions have changed.  (Each model's fit workspace serves the
+    batch from the start, so after such a call its cached W = L^-1 is marked stale, and its next
+    predict_variance_jacobian factorises once more -- as after a failed single-model update.)  Any other list of models (other families,
+    JunkDimensionsSSM, differing shapes or iteration counts) is updated one model at a time."""
+    ssms, xs, ys = list(ssms), list(xs), list(ys)
+    if not len(ssms) == len(xs) == len(ys):
+        raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
+    if not ssms:
+        return
+    if not _multi_fit_applies(ssms, xs):
+        for m, x, y in zip(ssms, xs, ys):
+            m.update_model(x, y, opt_hyp, replace_old)
+        return
+    # the merged training sets, checked before anything changes
+    merged = []
+    for m, x, y in zip(ssms, xs, ys):
+        n = x.size(0)
+        assert_shape(x, (n, m.num_states + m.num_actions))
+        assert_shape(y, (n, m.num_states))
+        if not replace_old and m._x_train is not None and m._y_train is not None:
+            x, y = torch.cat((m._x_train, x), dim=0), torch.cat((m._y_train, y), dim=0)
+        if x.size(0) > MAX_TRAINING_POINTS:
+            raise ValueError(f'{x.size(0)} training points: the exact-GP kernels hold up to {MAX_TRAINING_POINTS}')
+        _lib.require_gpu(x, 'train_x')
+        _lib.require_gpu(y, 'train_y')
+        merged.append((x, y))
+    fit = _MultiFit(ssms, [x.detach().contiguous() for x, _ in merged], [y.detach().contiguous() for _, y in merged])
+    E, n_s, d_in = len(ssms), ssms[0].num_states, ssms[0].num_states + ssms[0].num_actions
+    raws = [(m._raw_lengthscale, m._raw_outputscale, m._raw_noise) for m in ssms]
+    losses: Optional[List[List[float]]] = None
+    iterations = ssms[0]._training_iterations
+    if (opt_hyp or ssms[0].parametric) and iterations > 0:
+        params = [[t.clone().requires_grad_(True) for t in raw] for raw in raws]
+        opt = torch.optim.Adam([t for p in params for t in p], lr=0.01)
+        losses = [[] for _ in ssms]
+        for _ in range(iterations):
+            step = [tuple(t.detach() for t in p) for p in params]
+            fit.launch(step, mll=True)
+            host = torch.cat((fit.mll.reshape(-1), fit.grad.reshape(-1), fit.status.double())).cpu()   # the step's one sync
+            fit.check_status(host[-E:])
+            grads = host[E * n_s:-E].reshape(E, n_s, d_in + 2)
+            for e, (x, p) in enumerate(zip(fit.xs, params)):
+                n = x.size(0)
+                mll, grad = host[e * n_s:(e + 1) * n_s].clone(), grads[e]
+                losses[e].append(float(-(mll / n).sum()))
+                # d loss / d raw = -(1/N) d mll / d theta * sigmoid(raw), as GpCemSSM._train_model
+                p[0].grad = -(grad[:, :d_in] / n) * torch.sigmoid(p[0].detach())
+                p[1].grad = -(grad[:, d_in] / n) * torch.sigmoid(p[1].detach())
+                p[2].grad = -(grad[:, d_in + 1] / n) * torch.sigmoid(p[2].detach())
+            opt.step()
+        raws = [tuple(t.detach().clone() for t in p) for p in params]
+    # the final fit at the trained hyper-parameters; nothing is committed before it has succeeded everywhere
+    fit.new_alpha()
+    models = fit.launch(raws, mll=False)
+    host = torch.cat((fit.status.double(), fit.logdet.reshape(-1))).cpu()
+    fit.check_status(host[:E])
+    logdets = host[E:].reshape(E, n_s)
+    for e, m in enumerate(ssms):
+        m._x_train, m._y_train = merged[e]
+        m._raw_lengthscale, m._raw_outputscale, m._raw_noise = raws[e]
+        if losses is not None:
+            m._last_training_losses = losses[e]
+        model = _lib.SxGpModel.from_buffer_copy(models[e])
+        packed = m._pack(model, fit.ws[e][1], fit.alpha[e])
+        m._install(fit.xs[e], model, packed, fit.alpha[e], logdets[e].clone())
