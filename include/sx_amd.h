@@ -456,6 +456,40 @@ int sx_cem_rollout_mlp_multi(const sx_mlp_model* models, const void* table, cons
                              const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
                              double* con_cost, int32_t* status, void* stream);
 
+/* ---- The performance trajectory of the CEM solver ----
+ * A SafeMPC plans two trajectories: the safety trajectory (sx_cem_rollout: H steps of ellipsoids, the constraints) and
+ * the performance trajectory, n_perf steps of plain mean predictions that share their first r actions with the safety
+ * trajectory and carry the objective.  One launch per CEM iteration, after the safety rollout, for E problems x P particles:
+ *   v_t = safe_actions[t] (t < r), tail[t - r] (t >= r);   mu_0 = x0,   mu_{t+1} = a mu_t + b v_t + mean_GP([mu_t, v_t])
+ * (one_step_mean_equivalent with sigma_x = None, chained as mean_equivalent_multistep: no feedback term, no variance).
+ *   model        {n_s, n_u, n_train, inv_ls2, outputscale, x_train} of the exact RBF GP
+ *   alpha        dev [n_s x N]                 as sx_gp_fit wrote it
+ *   env          {n_s, n_u, a, b, u_min, u_max, obj_mode, obj_w_abs, obj_target, obj_w_lin}
+ *   H, n_perf, r 1 <= r <= H, n_perf > r; T = n_perf - r tail steps
+ *   x0           dev [E x n_s]
+ *   safe_actions dev [E x P x H x n_u]         what the safety rollout wrote (the shared actions are then bit-identical)
+ *   tail_mean, tail_std dev [E x T x n_u]      sampling distribution of the tail (ignored when tail_noise == NULL)
+ *   tail_noise   dev [E x P x T x n_u] | NULL  standard-normal draws; NULL = the tail of `rows` is an INPUT
+ *   rows         dev [E x P x (H + T) x n_u]   out: [safe_actions | tail], tail = tail_mean + tail_std * tail_noise: the rows
+ *                                              sx_cem_rank_refit ranks and refits (row_len = (H + T) n_u)
+ *   obj_cost     dev [E x P]                   OVERWRITTEN with sum_{t = 1..n_perf} cost(mu_t), cost = SX_OBJ_AFFINE_ABS
+ *   con_cost     dev [E x P]                   ADDED TO: SX_ACTION_VIOLATION_COST per tail step whose action leaves
+ *                                              [u_min, u_max] (the safety rollout has counted the shared steps; the
+ *                                              performance trajectory has no state constraint)
+ *   perf_traj    dev [E x P x n_perf x n_s] | NULL   mu_1 .. mu_n_perf
+ *   status       dev int32                     OR-ed with SX_STATUS_NAN on a non-finite mu_t
+ * A particle's numbers do not depend on P or on the launch's grid.
+ * SX_ERR_ARG (before any device access) for null pointers, non-positive sizes, r outside 1 .. H, n_perf <= r, tail_noise
+ * without tail_mean / tail_std, or shapes that differ between model and env; SX_ERR_UNSUPPORTED for env->obj_mode ==
+ * SX_OBJ_NEG_VARIANCE (the variance needs the safety kernels' N x N product), a shape sx_cem_rollout is not instantiated
+ * for, or a training set beyond the kernel's LDS ((2 n_s + n_u) N doubles: N <= 2016 at the widest shape).
+ * Replaces: nothing in the reference's CEM solver, which has no performance trajectory (safempc_cem.py:212-215); its casadi
+ * solver builds one in safempc_simple.py:398-490. */
+int sx_cem_perf_rollout(const sx_gp_model* model, const double* alpha, const sx_env* env, int E, int P, int H, int n_perf,
+                        int r, const double* x0, const double* safe_actions, const double* tail_mean,
+                        const double* tail_std, const double* tail_noise, double* rows, double* obj_cost, double* con_cost,
+                        double* perf_traj, int32_t* status, void* stream);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

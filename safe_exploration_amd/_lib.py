@@ -113,6 +113,8 @@ SIGNATURES = {
     'sx_mlp_model_table': (c_int, [POINTER(SxMlpModel), c_int, c_void_p, c_void_p]),
     'sx_cem_rollout_mlp_multi': (c_int, [POINTER(SxMlpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int]
                                  + [c_void_p] * 12),
+    'sx_cem_perf_rollout': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int, c_int, c_int]
+                            + [c_void_p] * 11),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -231,6 +231,38 @@ class FusedJunkUnsupported(_lib.SxError):
     """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
 
 
+def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
+                     safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                     tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                     tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False):
+    """Thin wrapper over sx_cem_perf_rollout: the performance trajectory of the particles of a safety rollout (exact RBF
+    GPs only).  x0 [E x n_s]; `safe_actions` [E x P x H x n_u], `obj_cost` (overwritten) and `con_cost` (added to) [E x P]
+    as `cem_rollout` returned them; the tail either drawn (`tail_mean`, `tail_std` [E x T x n_u], `tail_noise`
+    [E x P x T x n_u], T = n_perf - r) or given as the tail of `rows` [E x P x (H + T) x n_u].
+    Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, status)."""
+    _lib.require_gpu(x0, 'x0')
+    if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
+        raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
+                                  f'{getattr(ssm, "kernel_family", None)!r}')
+    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
+    E, P = safe_actions.size(0), safe_actions.size(1)
+    T = n_perf - r
+    if tail_noise is not None:
+        if rows is not None:
+            raise ValueError('either tail_noise (the tail is drawn) or rows (the tail is given), not both')
+        rows = torch.empty((E, P, horizon + T, n_u), dtype=torch.float64, device=dev)
+    elif rows is None or tuple(rows.shape) != (E, P, horizon + T, n_u) or not rows.is_contiguous():
+        raise ValueError(f'without tail_noise, rows must be a contiguous [{E} x {P} x {horizon + T} x {n_u}] tensor')
+    traj = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_traj else None
+    code = _lib.lib().sx_cem_perf_rollout(ctypes.byref(ssm.device_model), _lib.ptr(ssm._alpha), ctypes.byref(env), E, P,
+                                          horizon, n_perf, r, _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions),
+                                          _lib.ptr(tail_mean), _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows),
+                                          _lib.ptr(obj_cost), _lib.ptr(con_cost), _lib.ptr(traj), _lib.ptr(status),
+                                          _lib.stream_ptr(dev))
+    _lib.check(code, 'sx_cem_perf_rollout')
+    return dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, status=status)
+
+
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
     """May the elite refit move from the ranking kernel's tail into the next rollout's prologue (sx_cem_rollout_elites)?
     Exact-GP models on the single-launch path whose H n_u means and standard deviations fit the prologue's scratch, where
@@ -465,14 +497,37 @@ class FusedCemMpc:
     With a process group of G > 1 ranks the particles are sharded (``num_rollouts`` is the GLOBAL count): every rank
     rolls out its share, keeps its local top-k rows, ONE all-gather per iteration assembles the G*(k+1) candidate rows, and
     every rank redundantly ranks them and refits -- bit-identical on all ranks.
+
+    ``n_perf > 0`` adds the performance trajectory of a SafeMPC (exact RBF GPs, one GPU): n_perf
+    mean-equivalent steps that share their first ``perf_r`` actions with the safety trajectory and carry the objective,
+    while the safety trajectory keeps the constraints.  The CEM distribution then covers the row [safety actions | tail] of
+    H + n_perf - perf_r steps; an iteration is the safety rollout, ``sx_cem_perf_rollout`` and the ranking over those rows.
+    ``get_actions*`` still return the H safety actions of the best row; its tail is ``last_perf_actions``.
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
-                 record_rollouts: bool = False, process_group=None, force_exchange: bool = False):
+                 record_rollouts: bool = False, process_group=None, force_exchange: bool = False, n_perf: int = 0,
+                 perf_r: int = 1):
         self._ssm = ssm
         self._env = env
         self._horizon = time_horizon
+        # the performance trajectory (off with n_perf = 0): T tail steps behind the H safety steps of a row
+        self._n_perf, self._perf_r = int(n_perf), int(perf_r)
+        if self._n_perf < 0 or (self._n_perf > 0 and not (1 <= self._perf_r <= time_horizon and self._n_perf > self._perf_r)):
+            raise ValueError(f'a performance trajectory needs 1 <= perf_r <= time_horizon and n_perf > perf_r, got '
+                             f'n_perf={n_perf}, perf_r={perf_r}, time_horizon={time_horizon}')
+        self._tail = self._n_perf - self._perf_r if self._n_perf > 0 else 0
+        self._row_steps = time_horizon + self._tail
+        if self._n_perf > 0:
+            family = getattr(ssm, 'kernel_family', 'rbf')
+            if family != 'rbf':
+                raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
+                                          f'{family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+            if process_group is not None:
+                raise NotImplementedError('the performance trajectory is not built for sharded particles (a process group)')
+            self._check_perf_objective(env)
+        self.last_perf_actions = None     # [E x T x n_u] on the host: the tail of the last checked solve's best rows
         self._num_iterations = num_iterations
         self._record = record_rollouts
         # the first iteration's sampling distribution: std is a scalar or one value per step [H] / [H x n_u];
@@ -481,6 +536,8 @@ class FusedCemMpc:
         self._init_std = torch.as_tensor(init_std, dtype=torch.float64).cpu()
         if self._init_std.dim() > 0:
             self._init_std = self._init_std.reshape(time_horizon, -1).expand(time_horizon, ssm.num_actions).clone()
+            if self._tail:      # the tail steps start from the last safety step's value
+                self._init_std = torch.cat([self._init_std, self._init_std[-1:].expand(self._tail, -1)])
         if warm_start not in ('zero', 'safe_policy'):
             raise ValueError(f"warm_start must be 'zero' or 'safe_policy', got {warm_start!r}")
         self._warm_start = warm_start
@@ -540,9 +597,17 @@ class FusedCemMpc:
         """New problem constants (the pendulum's objective target moves between calls).  `objective_hook`, if given, is
         an ``Environment.objective_cost_function`` this module has no kernel form for: it is then evaluated with torch
         on the recorded trajectory centres, H small launches per iteration instead of none."""
+        if self._n_perf > 0 and objective_hook is None:
+            self._check_perf_objective(env)
         self._env = env
         self._objective_hook = objective_hook
         self._prior_tensors = None
+
+    @staticmethod
+    def _check_perf_objective(env: _lib.SxEnv) -> None:
+        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE:
+            raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
+                             '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function')
 
     def _prior(self):
         """(a [n_s x n_s], b [n_s x n_u], k_fb [n_u x n_s]) of the current sx_env as device tensors."""
@@ -552,8 +617,8 @@ class FusedCemMpc:
             self._prior_tensors = (t(self._env.a, n_s, n_s), t(self._env.b, n_s, n_u), t(self._env.k_fb, n_u, n_s))
         return self._prior_tensors
 
-    def safe_policy_plan(self, x0: Tensor) -> Tensor:
-        """[E x H x n_u]: the safe controller u_t = k_fb x_t (reference safempc_cem.py:259-262, the last rung of the
+    def safe_policy_plan(self, x0: Tensor, steps: Optional[int] = None) -> Tensor:
+        """[E x H x n_u] ([E x steps x n_u] where given): the safe controller u_t = k_fb x_t (reference safempc_cem.py:259-262, the last rung of the
         fallback ladder) rolled through the model's MEAN dynamics x_{t+1} = a x_t + b u_t + mu(x_t, u_t) from x0
         [E x n_s] -- H one-point-per-episode sx_gp_predict launches, nothing synchronises.  It is the warm start of
         workloads whose open-loop instability (cart-pole: 1.77 per step, 9e4 over H = 20) leaves a zero-mean start no
@@ -561,7 +626,7 @@ class FusedCemMpc:
         a, b, k_fb = self._prior()
         x = x0.to(self._device, torch.float64)
         plan = []
-        for _ in range(self._horizon):
+        for _ in range(self._horizon if steps is None else steps):
             u = x @ k_fb.t()
             mean, _ = self._ssm.predict_without_jacobians(x.contiguous(), u.contiguous())
             plan.append(u)
@@ -600,10 +665,11 @@ class FusedCemMpc:
         return cache[key]
 
     def _next_noise(self, episodes: int) -> Tensor:
-        """[iters x E x P_local x H x n_u] standard normals for one solve, from this solver's generator.  They are drawn for
+        """[iters x E x P_local x H x n_u] standard normals for one solve (H + T steps with a performance trajectory), from
+        this solver's generator.  They are drawn for
         up to 8 solves per generator launch (at most 256 MB): one launch per solve is 8 us + a 6 us gap in front of the first
         rollout, 1.2 % of a config-2 solve."""
-        shape = (self._num_iterations, episodes, self._local_rollouts, self._horizon, self._ssm.num_actions)
+        shape = (self._num_iterations, episodes, self._local_rollouts, self._row_steps, self._ssm.num_actions)
         pool = getattr(self, '_noise_pool', None)
         if pool is None or tuple(pool.shape[1:]) != shape or self._noise_next >= pool.size(0):
             per_solve = 8
@@ -618,17 +684,22 @@ class FusedCemMpc:
         return out
 
     def sample_noise(self, episodes: int = 1) -> Tensor:
-        return torch.randn((episodes, self._local_rollouts, self._horizon, self._ssm.num_actions), dtype=torch.float64,
+        return torch.randn((episodes, self._local_rollouts, self._row_steps, self._ssm.num_actions), dtype=torch.float64,
                            device=self._device, generator=self._gen)
 
     def start_distribution(self, x0: Tensor, init_mean: Optional[Tensor] = None,
                            init_std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The first iteration's sampling distribution (mean, std) [E x H x n_u] from start states x0 [E x n_s]:
-        `init_mean` / `init_std` where given, else the warm start's mean and the constructor's init_std.  (The constant
+        `init_mean` / `init_std` where given, else the warm start's mean and the constructor's init_std; with a performance
+        trajectory H + T steps, the tail behind the safety steps (zero mean, or the safe policy's plan continued).  (The constant
         ones are kept between solves: three small launches per solve otherwise, 2 % of a config-2 solve.)"""
-        E, dev, H, n_u = x0.size(0), x0.device, self._horizon, self._ssm.num_actions
+        E, dev, H, n_u = x0.size(0), x0.device, self._row_steps, self._ssm.num_actions
         if init_mean is not None:
             mean = init_mean.to(dev).reshape(E, H, n_u).clone()
+        elif self._warm_start == 'safe_policy' and self._n_perf > 0:
+            # the plan continued for n_perf steps: its first H steps, then the steps perf_r .. n_perf - 1 as the tail
+            plan = self.safe_policy_plan(x0, max(self._horizon, self._n_perf))
+            mean = torch.cat([plan[:, :self._horizon], plan[:, self._perf_r:self._n_perf]], dim=1).contiguous()
         elif self._warm_start == 'safe_policy':
             mean = self.safe_policy_plan(x0).contiguous()
         else:
@@ -665,9 +736,14 @@ class FusedCemMpc:
         noise: optional [iters x E x P_local x H x n_u] pre-drawn standard normals (parity tests inject them).
         Returns (best [E x H x n_u], best_ok int32 [E], rollouts per iteration (if recorded), status int32 [G]: the
         status word of every rank, identical on all ranks; G = 1 without a process group -- OR them, `fold_status`).
+
+        With a performance trajectory (n_perf > 0) the rows are H + T steps long, T = n_perf - perf_r: `noise`,
+        `init_mean`, `init_std` and the returned best rows have H + T where the above says H, the tail behind the safety
+        actions.
         """
         n_u, H, E, dev = self._ssm.num_actions, self._horizon, x0.size(0), x0.device
-        L = H * n_u
+        perf, rows_steps = self._n_perf > 0, self._row_steps
+        L = rows_steps * n_u
         mean, std = self.start_distribution(x0, init_mean, init_std)
         status = self._fresh_status(dev)
         history: List[Rollouts] = []
@@ -680,8 +756,12 @@ class FusedCemMpc:
         self._last_noise, self._last_actions = noise, None
         # From the second iteration on the refit happens in the rollout kernel's prologue, straight from the elite rows of
         # the ranking before it (sx_cem_rollout_elites): the ranking launches then skip their refit tail.
-        in_prologue = (not stepwise) and self._refit_in_prologue(E)
-        want_traj = self._record or self._objective_hook is not None
+        # (not with a performance trajectory: the prologue reads rows of 2 + H n_u, the ranking launch refits the long rows)
+        in_prologue = (not stepwise) and (not perf) and self._refit_in_prologue(E)
+        want_traj = self._record or (self._objective_hook is not None and not perf)
+        if perf and noise is not None:
+            # the draws of the safety steps and of the tail, each contiguous: two copies per solve
+            noise_safe, noise_tail = noise[:, :, :, :H].contiguous(), noise[:, :, :, H:].contiguous()
 
         def rollout(it, mean, std, rows):
             nonlocal stepwise, in_prologue
@@ -691,6 +771,12 @@ class FusedCemMpc:
             if self.rollout_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(torch.cuda.current_stream(dev))
+            if perf:
+                # the safety rollout runs over the first H steps of the row's distribution and draws
+                full_mean, full_std = mean, std
+                mean, std = mean[:, :H].contiguous(), std[:, :H].contiguous()
+                eps, eps_tail = ((noise_safe[it], noise_tail[it]) if noise is not None
+                                 else (eps[:, :, :H].contiguous(), eps[:, :, H:].contiguous()))
             if stepwise:
                 r = self._rollout_stepwise(x0, mean, std, eps, status)
             else:
@@ -704,7 +790,22 @@ class FusedCemMpc:
                         raise
                     stepwise, in_prologue = True, False
                     r = self._rollout_stepwise(x0, mean, std, eps, status)
-            if self._objective_hook is not None and not stepwise:
+            if perf:
+                # the performance trajectory: its objective replaces the safety trajectory's, the tail's action box adds to
+                # the constraint cost, and the rows [safety actions | tail] are what the ranking sees
+                hook, n_s = self._objective_hook, self._ssm.num_states
+                pr = cem_perf_rollout(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, safe_actions=r['actions'],
+                                      obj_cost=r['obj_cost'].contiguous(), con_cost=r['con_cost'].contiguous(),
+                                      status=status, tail_mean=full_mean[:, H:].contiguous(),
+                                      tail_std=full_std[:, H:].contiguous(), tail_noise=eps_tail,
+                                      want_traj=hook is not None)
+                r.update(safe_actions=r['actions'], actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
+                if hook is not None:
+                    obj = torch.zeros_like(pr['obj_cost'])
+                    for t in range(self._n_perf):
+                        obj += hook(pr['perf_traj'][:, :, t].reshape(-1, n_s)).reshape(obj.shape)
+                    r['obj_cost'] = obj.contiguous()
+            elif self._objective_hook is not None and not stepwise:
                 n_s = self._ssm.num_states
                 centres = r['traj'][..., :n_s]                                   # [E x P x H x n_s]
                 obj = torch.zeros_like(r['obj_cost'])
@@ -717,7 +818,8 @@ class FusedCemMpc:
             self._last_actions = r['actions']
             if self._record and r['traj'] is not None:
                 for e in range(E):
-                    history.append(Rollouts(r['traj'][e], r['actions'][e], r['obj_cost'][e], r['con_cost'][e]))
+                    history.append(Rollouts(r['traj'][e], r.get('safe_actions', r['actions'])[e], r['obj_cost'][e],
+                                            r['con_cost'][e]))
             return r
 
         def rank(it, r):
@@ -760,7 +862,7 @@ class FusedCemMpc:
             return out
 
         out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
-        return out['best'].view(E, H, n_u), out['best_ok'], history, status
+        return out['best'].view(E, rows_steps, n_u), out['best_ok'], history, status
 
     def _solve_checked(self, x0: Tensor, where: str, q_block: Optional[Tensor] = None):
         """`solve` + `_check_solve`, whose one hand-off also carries "is any entry of `q_block` non-zero" (the callers'
@@ -770,6 +872,10 @@ class FusedCemMpc:
             q_block = q_block.contiguous()
         best, best_ok, history, status = self.solve(x0)
         best_host, found, repeated = _check_solve(self, x0, q_block, best, best_ok, status, where, [(self, slice(None))])
+        if self._n_perf > 0:
+            # the callers' plan is the safety actions of the best row; its tail stays readable
+            self.last_perf_actions = best_host[:, self._horizon:]
+            best_host = best_host[:, :self._horizon]
         return best_host, found, [] if repeated else history     # (a step-by-step solve records no rollouts)
 
     def get_actions_batch(self, states: Tensor) -> Tuple[Tensor, Tensor, List[Rollouts]]:
@@ -834,6 +940,8 @@ class MultiModelCemMpc:
                 != (time_horizon, num_rollouts, num_elites, num_iterations, False) for s in solvers):
             raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: one per model, unsharded, with this '
                              f'solve\'s horizon, particles, elites and iterations')
+        if any(getattr(s, '_n_perf', 0) > 0 for s in solvers):
+            raise NotImplementedError('multi-model solves have no performance trajectory (solvers with n_perf > 0)')
         self._solvers = list(solvers)
         self._env = env
         self._horizon = time_horizon

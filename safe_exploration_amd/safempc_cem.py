@@ -222,6 +222,22 @@ class CemSafeMPC(SafeMPC):
         self._env_objective_cost_func = env.objective_cost_function
         self._record_rollouts = bool(getattr(conf, 'plot_cem_optimisation', False)
                                      or getattr(conf, 'plot_cem_terminal_states', False))
+        # The performance trajectory (FusedCemMpc): cem_n_perf steps (0 = off) sharing their first
+        # cem_perf_r actions with the safety trajectory.  Settings of their own: the reference's CEM configs inherit
+        # n_perf / r / type_perf_traj from the casadi defaults and must keep solving without one.
+        self._cem_n_perf = int(getattr(conf, 'cem_n_perf', 0) or 0)
+        self._cem_perf_r = int(getattr(conf, 'cem_perf_r', 1))
+        if self._cem_n_perf:
+            if not (1 <= self._cem_perf_r <= self._mpc_time_horizon and self._cem_n_perf > self._cem_perf_r):
+                raise ValueError(f'cem_n_perf={self._cem_n_perf} needs 1 <= cem_perf_r <= mpc_time_horizon and cem_n_perf > '
+                                 f'cem_perf_r, got cem_perf_r={self._cem_perf_r}, mpc_time_horizon={self._mpc_time_horizon}')
+            family = getattr(ssm, 'kernel_family', None)
+            if mpc is None and family != 'rbf':
+                raise NotImplementedError(f'cem_n_perf > 0 needs an exact RBF GP (GpCemSSM); kernel_family {family!r} has no '
+                                          f'performance trajectory')
+            if env.objective_cost_function(torch.zeros((1, env.n_s), dtype=torch.float64)) is None:
+                raise ValueError('cem_n_perf > 0 needs an environment objective: the performance trajectory propagates '
+                                 'means only and cannot carry the variance objective')
 
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
@@ -261,7 +277,8 @@ class CemSafeMPC(SafeMPC):
 
     @property
     def performance_trajectory_length(self) -> int:
-        return 0  # no performance trajectory in the CEM solver (reference safempc_cem.py:212-215)
+        """conf.cem_n_perf: 0 (the reference's CEM solver has none, safempc_cem.py:212-215) unless that setting asks."""
+        return self._cem_n_perf
 
     @property
     def x_train(self) -> ndarray:
@@ -288,6 +305,10 @@ class CemSafeMPC(SafeMPC):
         state_c = next(c for c in self._constraints if hasattr(c, 'polytope_a'))
         spec = objective_spec(self._env)
         mode, w_abs, target, w_lin = spec if spec is not None else (_lib.SX_OBJ_NEG_VARIANCE, None, None, None)
+        if spec is None and self._cem_n_perf:
+            # the hook is evaluated on the performance trajectory's recorded means; the kernels' own objective (all-zero
+            # weights here) is overwritten
+            mode = _lib.SX_OBJ_AFFINE_ABS
         env = make_env(self._state_dimen, self._action_dimen, a=a, b=b, k_fb=self._lqr.get_control_matrix(),
                        l_mu=self._l_mu.cpu().numpy(), l_sigma=self._l_sigma.cpu().numpy(), beta=self._beta_safety,
                        h_mat=state_c.polytope_a, h_vec=state_c.polytope_b, u_min=action_c.u_min, u_max=action_c.u_max,
@@ -317,7 +338,8 @@ class CemSafeMPC(SafeMPC):
                                     seed=int(getattr(self._conf, 'cem_seed', 0)),
                                     init_std=getattr(self._conf, 'cem_init_std', 1.0),
                                     warm_start=getattr(self._conf, 'cem_warm_start', None) or 'zero',
-                                    record_rollouts=self._record_rollouts)
+                                    record_rollouts=self._record_rollouts, n_perf=self._cem_n_perf,
+                                    perf_r=self._cem_perf_r)
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
         self._env_key = key
         return self._mpc
@@ -469,6 +491,9 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     states = np.asarray(states)
     if not solvers:
         raise ValueError('get_actions_multi needs at least one solver')
+    if any(getattr(s, '_cem_n_perf', 0) > 0 for s in solvers):
+        raise NotImplementedError('get_actions_multi has no performance trajectory: solvers with cem_n_perf > 0 act one at '
+                                  'a time (get_action)')
     n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
     if states.ndim != 2 or states.shape != (len(solvers), n_s):
         raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')
