@@ -272,7 +272,7 @@ def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candid
     family = getattr(ssm, 'kernel_family', 'rbf')
     if family not in ('rbf', 'rbf_junk'):
         return False
-    if 2 * horizon * ssm.num_actions > 256 * (1 + ssm.num_states):   # the bound of plan_rollout (csrc/sx_kernels.hip)
+    if 2 * horizon * ssm.num_actions > 256 * (1 + ssm.num_states):   # the bound of plan_rollout (csrc/sx_gp_rollout.hip)
         return False
     lib = _lib.lib()
     model = ssm.real_output_view().device_model if family == 'rbf_junk' else ssm.device_model

@@ -1,0 +1,172 @@
+// The large-N path: the kernels of sx_big.hpp and the two predict helpers, launch_predict_big and launch_rollout_big
+// (sx_big_launch.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES.
+#include <cstdlib>
+#include <vector>
+
+#include "sx_big.hpp"
+#include "sx_big_launch.hpp"
+#include "sx_host.hpp"
+#include "sx_launch.hpp"
+#include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES
+
+namespace sx {
+
+// trmm_reduce_kernel variants, selectable for A/B measurements (tools/cfg4_probe.py):
+//   SX_TRMM_ORDER   = tile order bits: 16 paired tiles (default for small grids), 8 longest-first (default otherwise),
+//                     1 XCD-contiguous with the row tile fastest, 0 plain;
+//                     + 2 / + 4: timing-only diagnostics (every workgroup reads the same Kstar / W tile: no fabric traffic)
+//   SX_TRMM_VARIANT = <pairs per chunk><LDS buffers>: 13 (default), 12, 22, 23
+// Measured at config 4 (N = 2000, 16 384 particles), per launch: plain order 7.2 ms, XCD-contiguous 4.73 ms, longest-first
+// 3.92 ms -- whatever the variant, and the same with the fabric traffic removed (order + 6): the kernel was never
+// memory-bound, its tiles differ 16-fold in work and the tail of the launch was what it lost.
+static const int g_trmm_order = std::getenv("SX_TRMM_ORDER") ? std::atoi(std::getenv("SX_TRMM_ORDER")) : -1;
+static const int g_trmm_variant = std::getenv("SX_TRMM_VARIANT") ? std::atoi(std::getenv("SX_TRMM_VARIANT")) : 13;
+//   SX_TRMM_PT      = particle tiles per workgroup: 8 | 4 (default: 4 where 8 would leave a compute unit with at most two
+//                     workgroups, see launch_trmm)
+static const int g_trmm_pt = std::getenv("SX_TRMM_PT") ? std::atoi(std::getenv("SX_TRMM_PT")) : 0;
+
+template <int NS, int D, int PPC, int NBUF, int PT>
+static void launch_trmm_v(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, int row_tiles, hipStream_t stream) {
+    constexpr int lds = big_lds_bytes<PPC, NBUF, PT>();
+    (void)allow_lds(trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, lds);
+    const int64_t pgroups = p128 / (PT * 16);
+    const int64_t tiles = pgroups * row_tiles * NS;
+    // Tile order.  A large grid runs longest tile first.  A grid of a few rounds is all quantisation: it runs PAIRED tiles
+    // (row tile rt and row_tiles - 1 - rt in one workgroup: equal work) when that deals the work out more evenly than
+    // longest-first does -- judged by dealing the workgroups round-robin onto the 256 CUs and comparing the fullest CU.
+    // SX_TRMM_ORDER overrides.
+    int order = g_trmm_order;
+    if (order < 0) {
+        order = 8;
+        if (tiles <= 3 * 768 && row_tiles > 1) {
+            const int nrb = gc.n_pad >> 4, groups = (int)pgroups * NS;
+            std::vector<double> work(row_tiles);
+            for (int rt = 0; rt < row_tiles; ++rt) {
+                const int rb0 = rt * kBigRb, rb_end = rb0 + kBigRb < nrb ? rb0 + kBigRb : nrb;
+                double w = 0.0;
+                for (int rb = rb0; rb < rb0 + kBigRb; ++rb) w += 2 * (rb + 1) < 2 * rb_end ? 2 * (rb + 1) : 2 * rb_end;
+                work[rt] = w;
+            }
+            auto fullest = [&](const std::vector<double>& per_wg) {     // per_wg: work of the workgroups in dispatch order
+                double cu[256] = {0.0};
+                for (size_t i = 0; i < per_wg.size(); ++i) cu[i & 255] += per_wg[i];
+                double m = 0.0;
+                for (double v : cu) m = v > m ? v : m;
+                return m;
+            };
+            std::vector<double> plain, paired;
+            for (int rt = row_tiles - 1; rt >= 0; --rt) plain.insert(plain.end(), groups, work[rt]);
+            for (int j = 0; j < (row_tiles + 1) / 2; ++j)
+                paired.insert(paired.end(), groups, work[row_tiles - 1 - j] + (j != row_tiles - 1 - j ? work[j] : 0.0));
+            if (fullest(paired) < fullest(plain)) order = 16;
+        }
+    }
+    const dim3 grid((unsigned)((order & 16) ? pgroups * ((row_tiles + 1) / 2) * NS : tiles));
+    if (kind >= 0)
+        launch(kind, trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, grid, dim3(kBigThreads), lds, stream, gc, ws, p128, row_tiles, order);
+    else
+        hipLaunchKernelGGL((trmm_reduce_kernel<NS, D, PPC, NBUF, PT>), grid, dim3(kBigThreads), lds, stream, gc, ws, p128, row_tiles,
+                           order);
+}
+
+template <int NS, int D>
+static void launch_trmm(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, int row_tiles, hipStream_t stream) {
+    // Small grids take 128 x 64 tiles: with 128 x 128 a grid of up to two workgroups per compute unit (N ~ 1000 .. 1400 at
+    // 4096 particles) leaves each SIMD one or two waves that idle through every barrier and DMA wait; twice the workgroups
+    // at half the size fill those gaps (tools/n_sweep.sh: the step at the path switch).
+    const int64_t wgs8 = (p128 / kBigTile) * row_tiles * NS;
+    const bool half = g_trmm_pt ? g_trmm_pt == 4 : wgs8 <= 2 * 768;
+    if (half) return launch_trmm_v<NS, D, 1, 3, 4>(kind, gc, ws, p128, row_tiles, stream);
+    switch (g_trmm_variant) {
+        case 12: return launch_trmm_v<NS, D, 1, 2, 8>(kind, gc, ws, p128, row_tiles, stream);
+        case 22: return launch_trmm_v<NS, D, 2, 2, 8>(kind, gc, ws, p128, row_tiles, stream);
+        case 23: return launch_trmm_v<NS, D, 2, 3, 8>(kind, gc, ws, p128, row_tiles, stream);
+        default: return launch_trmm_v<NS, D, 1, 3, 8>(kind, gc, ws, p128, row_tiles, stream);
+    }
+}
+
+// ---- sx_gp_predict for training sets beyond the LDS budget: the same Kstar / triangular-product kernels, then collect ----
+template <int NS, int D>
+__global__ void predict_init_big_kernel(const double* __restrict__ z, int64_t P, int64_t p128, BigWs ws) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= p128 * D) return;
+    ws.zs[i] = (i < P * D) ? z[i] : 0.0;
+}
+
+template <int NS, int D>
+__global__ void predict_collect_big_kernel(GpConst<NS, D> gc, BigWs ws, int64_t P, int64_t p128, int row_parts,
+                                           double* __restrict__ mean, double* __restrict__ var, double* __restrict__ jac) {
+    const int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (g >= P) return;
+#pragma unroll
+    for (int d = 0; d < NS; ++d) {
+        double q = 0.0;
+        for (int r = 0; r < row_parts; ++r) q += ws.part[((int64_t)d * row_parts + r) * p128 + g];
+        var[g * NS + d] = (gc.outputscale[d] - q) + gc.noise[d];
+        const double m = ws.mj[((int64_t)d * (D + 1)) * p128 + g];
+        mean[g * NS + d] = m;
+        if (jac) {
+#pragma unroll
+            for (int j = 0; j < D; ++j)
+                jac[(g * NS + d) * D + j] =
+                    ws.mj[((int64_t)d * (D + 1) + 1 + j) * p128 + g] - ws.zs[g * D + j] * gc.inv_ls2[d * D + j] * m;
+        }
+    }
+}
+
+template <int NS, int NU>
+int launch_predict_big(const sx_gp_model* m, const double* z, int P, double* mean, double* var, double* jac,
+                       double* workspace, int64_t workspace_bytes, hipStream_t stream) {
+    constexpr int D = NS + NU;
+    auto gc = make_gp_const<NS, NU>(m, kPredictThreads / 64);
+    const int64_t p128 = ((int64_t)P + kBigTile - 1) / kBigTile * kBigTile;
+    BigWs ws = big_ws_layout(workspace, NS, D, m->n_pad, P);
+    if (!workspace || workspace_bytes < ws.total * (int64_t)sizeof(double)) return SX_ERR_ARG;
+    const int row_tiles = (m->n_pad + kBigTile - 1) / kBigTile;
+    hipLaunchKernelGGL((predict_init_big_kernel<NS, D>), dim3((unsigned)((p128 * D + 255) / 256)), dim3(256), 0, stream, z,
+                       (int64_t)P, p128, ws);
+    hipLaunchKernelGGL((kstar_big_kernel<NS, D>), dim3((unsigned)(p128 / 16), (unsigned)((m->n_pad + 255) / 256)), dim3(256),
+                       0, stream, gc, ws);
+    launch_trmm<NS, D>(-1, gc, ws, p128, row_tiles, stream);
+    hipLaunchKernelGGL((predict_collect_big_kernel<NS, D>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, stream, gc, ws,
+                       (int64_t)P, p128, row_tiles * 2, mean, var, jac);
+    return check_launch();
+}
+
+template <int NS, int NU>
+int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, double* workspace,
+                       int64_t workspace_bytes, hipStream_t stream) {
+    constexpr int D = NS + NU;
+    auto gc = make_gp_const<NS, NU>(m, kRolloutThreads / 64);
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    const int64_t total = (int64_t)rp.E * rp.P;
+    const int64_t p128 = (total + kBigTile - 1) / kBigTile * kBigTile;
+    BigWs ws = big_ws_layout(workspace, NS, D, m->n_pad, total);
+    if (!workspace || workspace_bytes < ws.total * (int64_t)sizeof(double)) return SX_ERR_ARG;
+    const int row_tiles = (m->n_pad + kBigTile - 1) / kBigTile;
+    BigInit bi{rp.x0, rp.q0, rp.mean, rp.std, rp.noise, rp.actions, rp.obj_cost, rp.con_cost, rp.P, rp.H};
+    hipLaunchKernelGGL((init_big_kernel<NS, NU>), dim3((unsigned)((p128 + 255) / 256)), dim3(256), 0, stream, bi, ws, total,
+                       p128);
+    for (int t = 0; t < rp.H; ++t) {
+        launch(SX_PROF_KSTAR_BIG, kstar_big_kernel<NS, D>, dim3((unsigned)(p128 / 16), (unsigned)((m->n_pad + 255) / 256)),
+               dim3(256), 0, stream, gc, ws);
+        launch_trmm<NS, D>(SX_PROF_TRMM_BIG, gc, ws, p128, row_tiles, stream);
+        BigStep bs{rp.actions, rp.traj, rp.sigma, rp.obj_cost, rp.con_cost, rp.status, rp.H, t, row_tiles * 2,
+                   (t > 0 || rp.q0 != nullptr) ? 1 : 0};
+        launch(SX_PROF_STEP_BIG, step_big_kernel<NS, NU>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, gc, rc, cc,
+               bs, ws, total, p128);
+    }
+    return check_launch();
+}
+
+}  // namespace sx
+
+#define SX_BIG_INSTANTIATE(NS, NU)                                                                                      \
+    template int sx::launch_predict_big<NS, NU>(const sx_gp_model*, const double*, int, double*, double*, double*,     \
+                                                double*, int64_t, hipStream_t);                                        \
+    template int sx::launch_rollout_big<NS, NU>(const sx_gp_model*, const sx_env*, const sx::RolloutPtrs&, double*,    \
+                                                int64_t, hipStream_t);
+#define SX_BIG_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_BIG_INSTANTIATE(NS, NU))
+SX_ROLLOUT_SHAPES(SX_BIG_ONE, 0)

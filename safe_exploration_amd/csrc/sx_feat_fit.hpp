@@ -1,5 +1,5 @@
 // sx_feat_fit: the weight-space fit of the degenerate-kernel GPs of sx_feat.hpp.  A non-template kernel, so that only
-// sx_kernels.hip includes it (sx_feat.hpp itself is included by more than one translation unit).
+// sx_feat.hip includes it (sx_feat.hpp itself is included by more than one translation unit).
 #pragma once
 #include <hip/hip_runtime.h>
 

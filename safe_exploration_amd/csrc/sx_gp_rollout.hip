@@ -1,0 +1,307 @@
+// The exact-GP rollout entries: which form a model's rollout takes (plan_rollout), the launch in
+// that form through the launchers of sx_rw_launch.hpp, sx_stream_launch.hpp and sx_big_launch.hpp, the GP model table, and
+// sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi, sx_cem_rollout_form, sx_cem_rollout_multi_form,
+// sx_cem_rollout_workspace_bytes.  No kernel is compiled here.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/sx_amd.h"
+#include "sx_big.hpp"   // big_ws_layout
+#include "sx_big_launch.hpp"
+#include "sx_host.hpp"
+#include "sx_launch.hpp"
+#include "sx_rw_launch.hpp"
+#include "sx_stream_launch.hpp"
+
+namespace sx {
+
+#ifdef SX_STAMPS
+extern unsigned long long* g_stamp_host;   // diagnostic build: the phase-stamp buffer (sx_debug_set_stamps, sx_rank.hip)
+#endif
+
+// The rollout form of a model, decided here only: sx_cem_rollout[_elites][_junk] launch it,
+// sx_cem_rollout_form reports it, sx_cem_rollout_workspace_bytes sizes the workspace path by it.  No HIP call.
+struct RolloutPlan {
+    int form;     // SX_FORM_*
+    bool ok;      // false: sx_cem_rollout answers SX_ERR_UNSUPPORTED
+    size_t lds;   // dynamic LDS bytes of the form's kernel (not SX_FORM_BIG)
+    int nrb;      // SX_FORM_RH / SX_FORM_RW: n_pad / 16, the kernel's instantiation
+};
+
+// SX_ROLLOUT=rh|rw|stream forces one form of the single-launch kernel (A/B runs); where it does not apply the rollout
+// takes the streaming kernel, or answers SX_ERR_UNSUPPORTED with SX_ROLLOUT_STRICT set (so that a run knows what it timed).
+struct FormOverride {
+    int form;   // SX_FORM_RH / SX_FORM_RW / SX_FORM_STREAM, or -1: none
+    bool strict;
+    bool refuses() const { return strict && form >= 0; }
+};
+static const FormOverride& form_override() {
+    static const FormOverride o = [] {
+        const char* e = std::getenv("SX_ROLLOUT");
+        const int form = !e                            ? -1
+                         : std::strcmp(e, "stream") == 0 ? SX_FORM_STREAM
+                         : std::strcmp(e, "rw") == 0     ? SX_FORM_RW
+                         : std::strcmp(e, "rh") == 0     ? SX_FORM_RH
+                                                         : -1;
+        return FormOverride{form, std::getenv("SX_ROLLOUT_STRICT") != nullptr};
+    }();
+    return o;
+}
+
+template <int NS, int NU>
+static int resident_lds_bytes(int n_train, int n_pad, int H, size_t* rh, size_t* rw) {
+    *rh = rollout_rh_lds_bytes<NS, NU>(n_train, n_pad, H);
+    *rw = rollout_rw_lds_bytes<NS, NU>(n_train, n_pad, H);
+    return SX_OK;
+}
+// LDS bytes of the 8-wave and the 4-wave form for a plain rollout of a compiled shape (~0: that form has no instantiation)
+static int resident_lds_bytes(int ns, int nu, int n_train, int n_pad, int H, size_t* rh, size_t* rw) {
+#define CALL(NS, NU) resident_lds_bytes<NS, NU>(n_train, n_pad, H, rh, rw)
+    SX_DISPATCH(ns, nu, CALL);
+#undef CALL
+}
+
+// `m` is the GP over ns + nu + sh columns (m->n_u = nu + sh), sh the query shift of sx_cem_rollout_junk.
+// stream_only: the streaming kernel's answer (STREAM, BYOUT or BIG), never a resident form and no override -- the
+// multi-model rollout has only that kernel (plan_rollout_multi).
+static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites, bool stream_only = false) {
+    const int ns = m->n_s, nu = m->n_u - sh, n_train = m->n_train, n_pad = m->n_pad;
+    auto stream_lds = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, sh, n_train, n_pad, H, byout); };
+    const bool all_at_once = n_pad <= 1024 && stream_lds(false) <= kMaxLdsBytes;
+    const bool by_output = !all_at_once && ns > 1 && n_pad <= 1024 && stream_lds(true) <= kMaxLdsBytes;
+    bool ok = rollout_compiled(ns, nu, sh);
+    // Kstar in HBM: plain rollouts only, without elite rows (the refit prologue belongs to the single-launch kernel)
+    if (!all_at_once && !by_output) return {SX_FORM_BIG, ok && sh == 0 && !elites, 0, 0};
+    // (the refit prologue keeps 2 H n_u doubles in the Kstar / mean-row buffers: at least 256 + 256 n_s of them)
+    if (elites && 2 * H * nu > 256 + 256 * ns) ok = false;
+    if (by_output) return {SX_FORM_BYOUT, ok, stream_lds(true), 0};
+    const RolloutPlan stream{SX_FORM_STREAM, ok, stream_lds(false), 0};
+    const FormOverride& o = form_override();
+    if (!ok || sh > 0 || stream_only || o.form == SX_FORM_STREAM) return stream;
+    // W partly resident on 8 waves (n_s <= 2), then all of W in the registers of 4 waves (smaller N), then W streamed from
+    // L2: the 4-wave form loses to the streaming kernel only where the 8-wave form exists (n_s = 2, n_u = 1: 126.6
+    // against 125.7 us at config 2), and beats it by 7 - 16 % on the shapes the 8-wave form does not cover (n_s = 3, 4;
+    // n_s = n_u = 2 beyond N = 128).
+    size_t rh, rw;
+    resident_lds_bytes(ns, nu, n_train, n_pad, H, &rh, &rw);
+    if (o.form != SX_FORM_RW && rh <= kMaxLdsBytes) return {SX_FORM_RH, true, rh, n_pad >> 4};
+    if (o.form != SX_FORM_RH && rw <= kMaxLdsBytes) return {SX_FORM_RW, true, rw, n_pad >> 4};
+    return {SX_FORM_STREAM, !o.refuses(), stream.lds, 0};
+}
+
+// The rollout of a GP over NS + NU + SH columns (SH: the query shift of sx_cem_rollout_junk) in the form plan_rollout picks.
+template <int NS, int NU, int SH>
+static int launch_rollout(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, double* workspace,
+                          int64_t workspace_bytes, hipStream_t stream) {
+    RolloutPlan plan = plan_rollout(m, SH, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    if constexpr (SH == 0) {
+        if (plan.form == SX_FORM_BIG) return launch_rollout_big<NS, NU>(m, env, rp, workspace, workspace_bytes, stream);
+    }
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    RolloutPtrs rps = rp;
+#ifdef SX_STAMPS
+    rps.stamps = g_stamp_host;
+#endif
+    if constexpr (SH == 0) {
+        if (plan.form == SX_FORM_RH || plan.form == SX_FORM_RW) {
+            const int r = plan.form == SX_FORM_RH
+                              ? launch_rollout_rh<NS, NU>(make_gp_const<NS, NU>(m, 8), rc, cc, rps, plan.nrb, plan.lds, stream)
+                              : launch_rollout_rw<NS, NU>(make_gp_const<NS, NU>(m, kRwWaves), rc, cc, rps, plan.nrb, plan.lds,
+                                                          stream);
+            if (r != SX_ERR_UNSUPPORTED || form_override().refuses()) return r;
+            plan = {SX_FORM_STREAM, true, rollout_stream_lds_bytes(NS, NU, SH, m->n_train, m->n_pad, rp.H, false), 0};
+        }
+    }
+    return launch_rollout_stream<NS, NU, SH>(make_gp_const<NS, NU + SH>(m, kRolloutThreads / 64), rc, cc, rps,
+                                             plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
+// The multi-model rollout (sx_cem_rollout_multi[_elites]): one launch of the streaming kernel for E problems with a GP
+// each, so every model takes plan_rollout's streaming answer.  The launch is output by output where any model needs it,
+// with the LDS of the largest; a model without a single-launch form (BIG, or not ok) makes the whole launch unsupported.
+static RolloutPlan plan_rollout_multi(const sx_gp_model* models, int E, int H, bool elites) {
+    RolloutPlan out{SX_FORM_STREAM, true, 0, 0};
+    for (int i = 0; i < E; ++i) {
+        const RolloutPlan p = plan_rollout(&models[i], 0, H, elites, true);
+        if (p.form == SX_FORM_BIG || !p.ok) return {p.form, false, 0, 0};
+        if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
+    }
+    const sx_gp_model& m0 = models[0];
+    for (int i = 0; i < E; ++i)
+        out.lds = std::max(out.lds, rollout_stream_lds_bytes(m0.n_s, m0.n_u, 0, models[i].n_train, models[i].n_pad, H,
+                                                             out.form == SX_FORM_BYOUT));
+    return out;
+}
+
+// Bytes of one sx_gp_model_table entry: the GpConst the streaming kernel takes (SX_ERR_UNSUPPORTED for a shape without
+// a rollout kernel)
+template <int NS, int NU>
+static int64_t gp_table_entry_bytes() {
+    return (int64_t)sizeof(GpConst<NS, NS + NU>);
+}
+static int64_t gp_table_entry_bytes(int ns, int nu) {
+#define CALL(NS, NU) gp_table_entry_bytes<NS, NU>()
+    SX_DISPATCH(ns, nu, CALL);
+#undef CALL
+}
+
+template <int NS, int NU>
+static int build_gp_table(const sx_gp_model* models, int E, void* table, hipStream_t stream) {
+    std::vector<GpConst<NS, NS + NU>> host(E);
+    for (int i = 0; i < E; ++i) host[i] = make_gp_const<NS, NU>(&models[i], kRolloutThreads / 64);
+    return copy_model_table(host, table, stream);
+}
+
+template <int NS, int NU>
+static int launch_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const RolloutPtrs& rp,
+                                hipStream_t stream) {
+    const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    return launch_rollout_stream_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp,
+                                               plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
+// sx_cem_rollout[_elites][_junk] after their argument checks
+static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+#define CALL(NS, NU, SH) launch_rollout<NS, NU, SH>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
+    SX_ROLLOUT_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
+#undef CALL
+}
+
+}  // namespace sx
+
+extern "C" {
+
+int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, int H) {
+    if (!model || E <= 0 || P <= 0 || H <= 0) return -1;
+    if (sx::plan_rollout(model, 0, H, false).form != SX_FORM_BIG) return 0;
+    return sx::big_ws_layout(nullptr, model->n_s, model->n_s + model->n_u, model->n_pad, (int64_t)E * P).total *
+           (int64_t)sizeof(double);
+}
+
+int sx_cem_rollout_form(const sx_gp_model* model, int H) {
+    if (!model || H <= 0) return -1;
+    const sx::RolloutPlan plan = sx::plan_rollout(model, 0, H, false);
+    return plan.ok ? plan.form : -1;
+}
+
+int sx_cem_rollout(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
+                   const double* mean, const double* std, const double* noise, double* actions, double* traj,
+                   double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
+                   int64_t workspace_bytes, void* stream) {
+    return sx_cem_rollout_junk(model, env, 0, E, P, H, x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost,
+                               status, workspace, workspace_bytes, stream);
+}
+
+int sx_cem_rollout_elites(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* x0, const double* q0,
+                          const double* elite_rows, int k, const double* noise, double* actions, double* traj, double* sigma,
+                          double* obj_cost, double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream) {
+    return sx_cem_rollout_elites_junk(model, env, 0, E, P, H, x0, q0, elite_rows, k, noise, actions, traj, sigma, obj_cost,
+                                      con_cost, status, mean_out, std_out, stream);
+}
+
+// The elite-row form of a rollout's actions: the refit prologue derives the sampling distribution from k sorted elite
+// rows and, where mean_out and std_out are given, writes it out
+static sx::RolloutPtrs with_elites(sx::RolloutPtrs rp, const double* elite_rows, int k, double* mean_out, double* std_out) {
+    rp.elite_rows = elite_rows;
+    rp.elite_k = k;
+    rp.mean_out = mean_out;
+    rp.std_out = std_out;
+    return rp;
+}
+
+// (model, env, query_shift) of the rollout entries: checked before anything touches the device
+static bool rollout_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
+    return model->n_s == env->n_s && query_shift >= 0 && query_shift <= env->n_u && model->n_u == env->n_u + query_shift;
+}
+
+int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H, const double* x0,
+                        const double* q0, const double* mean, const double* std, const double* noise, double* actions,
+                        double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!model || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
+    return sx::cem_rollout(model, env, query_shift, rp, workspace, workspace_bytes, stream);
+}
+
+int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
+                               const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                               double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                               int32_t* status, double* mean_out, double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
+                                            E, P, H}, elite_rows, k, mean_out, std_out);
+    if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
+    return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
+}
+
+// E models of one (n_s, n_u) with a training set each: checked before anything touches the device
+static bool multi_models_ok(const sx_gp_model* models, int E) {
+    if (!models || E <= 0) return false;
+    const int ns = models[0].n_s, nu = models[0].n_u;
+    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || nu > SX_MAX_NU) return false;
+    for (int i = 0; i < E; ++i)
+        if (models[i].n_s != ns || models[i].n_u != nu || models[i].n_train <= 0 || models[i].n_pad <= 0) return false;
+    return true;
+}
+
+int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E) {
+    if (E <= 0 || n_s <= 0 || n_s > SX_MAX_NS || n_u <= 0 || n_u > SX_MAX_NU) return -1;
+    const int64_t entry = sx::gp_table_entry_bytes(n_s, n_u);
+    return entry == SX_ERR_UNSUPPORTED ? -1 : entry * E;
+}
+
+int sx_gp_model_table(const sx_gp_model* models, int E, void* table, void* stream) {
+    if (!table || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    for (int i = 0; i < E; ++i)
+        if (!models[i].x_train || !models[i].a_pack || !models[i].stage_tab) return SX_ERR_ARG;
+#define CALL(NS, NU) sx::build_gp_table<NS, NU>(models, E, table, (hipStream_t)stream)
+    SX_DISPATCH(models[0].n_s, models[0].n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H) {
+    if (!multi_models_ok(models, E) || H <= 0) return -1;
+    const sx::RolloutPlan plan = sx::plan_rollout_multi(models, E, H, false);
+    return plan.ok ? plan.form : -1;
+}
+
+static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx::RolloutPtrs& rp,
+                             void* stream) {
+#define CALL(NS, NU) sx::launch_rollout_multi<NS, NU>(models, table, env, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                         const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                         double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
+                         void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!table || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    return cem_rollout_multi(models, table, env, rp, stream);
+}
+
+int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                                double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                                int32_t* status, double* mean_out, double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
+                                            E, P, H}, elite_rows, k, mean_out, std_out);
+    if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    return cem_rollout_multi(models, table, env, rp, stream);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Launch plumbing shared by the translation units of libsxamd: the sampled kernel timer (sx_profile_*), the dynamic-LDS
-// grant and the launch check.  Defined in sx_kernels.hip.
+// grant and the launch check.  Defined in sx_runtime.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -1,6 +1,6 @@
 // Launchers of the feature-GP and MC-dropout rollout kernels in the multi-model mode (MM = true: a model per problem,
 // sx_cem_rollout_feat_multi / sx_cem_rollout_mlp_multi).  Their instantiations are compiled in a translation unit of
-// their own (sx_model_multi.hip, every shift-0 shape of SX_ROLLOUT_SHAPES); sx_kernels.hip sees the declarations.
+// their own (sx_model_multi.hip, every shift-0 shape of SX_ROLLOUT_SHAPES); sx_feat.hip and sx_mlp.hip see the declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 

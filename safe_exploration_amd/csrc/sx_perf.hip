@@ -1,9 +1,9 @@
 // sx_cem_perf_rollout: the performance-trajectory kernel (sx_perf.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES, its
 // launcher and the entry point.  A translation unit of its own: nothing the other objects compile changes with it.
 #include <climits>
-#include <cmath>
 #include <cstring>
 
+#include "sx_host.hpp"
 #include "sx_launch.hpp"
 #include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES, SX_DISPATCH
 #include "sx_perf.hpp"
@@ -23,14 +23,9 @@ int launch_perf_rollout(const PerfConst<NS, NU>& pc, const PerfPtrs& pp, hipStre
 template <int NS, int NU>
 static int perf_rollout(const sx_gp_model* m, const double* alpha, const sx_env* env, const PerfPtrs& pp,
                         hipStream_t stream) {
-    constexpr int D = NS + NU;
     PerfConst<NS, NU> pc;
     std::memset(&pc, 0, sizeof(pc));
-    for (int d = 0; d < NS; ++d) {
-        // (the constants of make_gp_const, sx_kernels.hip: the safety kernels' exponent)
-        for (int j = 0; j < D; ++j) pc.k_nh_ils2[d * D + j] = -0.5 * m->inv_ls2[d * D + j] * kExpScale;
-        pc.k_log_os[d] = std::log(m->outputscale[d]) * kExpScale;
-    }
+    exp_hyper(*m, pc.k_nh_ils2, pc.k_log_os);
     for (int i = 0; i < NS * NS; ++i) pc.step.a[i] = env->a[i];
     for (int i = 0; i < NS * NU; ++i) pc.step.b[i] = env->b[i];
     for (int c = 0; c < NU; ++c) {

@@ -1,5 +1,5 @@
 // Launcher of the register-resident rollout kernels (sx_rollout_rw.hpp).  Its instantiations are compiled in translation
-// units of their own (sx_rw_ns{1..4}.hip: one per state dimension, built in parallel); sx_kernels.hip sees the declaration.
+// units of their own (sx_rw_ns{1..4}.hip: one per state dimension, built in parallel); sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // The compiled shapes of the fused rollout, and the launchers of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
 // BYOUT, SH, MM>).  The launchers' instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
-// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip; built in parallel with the rest); sx_kernels.hip sees
-// the declarations.
+// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip; built in parallel with the rest); sx_gp_rollout.hip
+// sees the declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +40,14 @@
     } while (0)
 
 namespace sx {
+
+// is (ns, nu, sh) one of SX_ROLLOUT_SHAPES?
+inline bool rollout_compiled(int ns, int nu, int sh) {
+#define SX_COMPILED(NS, NU, SH, unused) if (ns == NS && nu == NU && sh == SH) return true;
+    SX_ROLLOUT_SHAPES(SX_COMPILED, 0)
+#undef SX_COMPILED
+    return false;
+}
 
 // Dynamic LDS bytes of cem_rollout_kernel: Kstar of all outputs (byout = false) or of one output at a time, for the GP
 // over ns + nu + sh columns and H steps of nu actions.

@@ -17,7 +17,7 @@ JUNK_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1
                                (2, 1, 1), (4, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1), (1, 1, 1)})
 # (n_s, n_u, query shift) that sx_cem_rollout_feat_junk / sx_cem_rollout_mlp_junk roll out in one launch per iteration: shift
 # 0 is sx_cem_rollout_feat's / sx_cem_rollout_mlp's shapes, shift > 0 every shape a padded feature-GP or MC-dropout model
-# can be built for (n_s + J_s <= 4, n_u + J_a <= 2): SX_MODEL_JUNK_SHAPES in csrc/sx_kernels.hip
+# can be built for (n_s + J_s <= 4, n_u + J_a <= 2): SX_MODEL_JUNK_SHAPES in csrc/sx_model_shapes.hpp
 JUNK_MODEL_FUSED_SHAPES = frozenset({(2, 1, 0), (4, 1, 0), (2, 2, 0), (4, 2, 0), (3, 1, 0), (1, 1, 0),
                                      (1, 1, 1), (2, 1, 1), (3, 1, 1), (2, 2, 1), (2, 2, 2), (3, 2, 1)})
 

@@ -298,7 +298,7 @@ def test_refit_scratch_at_its_bound_in_forced_forms(form, n_s, n_u):
 def test_gp_predict_past_4096_workgroups(n_s, n_u, N, n_pad, kernel):
     """sx_gp_predict (predict_with_jacobians, predict_without_jacobians) of P = 4096 16 + 37 points: 4099 tiles on a grid
     capped at 4096 workgroups, so tiles 4096 .. 4098 run on a second trip of the tile loop.  Which kernel runs follows
-    from predict_fits (csrc/sx_kernels.hip), the LDS of gp_tile_lds_doubles on 8 waves against 160 KiB:
+    from predict_fits (csrc/sx_gp_predict.hip), the LDS of gp_tile_lds_doubles on 8 waves against 160 KiB:
     (2, 1), N = 77, n_pad = 96: 4736 doubles (37 KiB) with every output resident, gp_predict_kernel<2, 1, false>;
     (3, 1), N = 500, n_pad = 512: 28416 doubles (222 KiB) do not fit, 12032 (94 KiB) one output at a time do,
     gp_predict_kernel<3, 1, true>.  The rows of tiles 0, 4095, 4096 and the ragged last tile equal a small launch of those

@@ -31,7 +31,7 @@ def test_model_junk_entries_are_declared_and_exported():
 
 def test_model_junk_shapes_match_the_instantiations():
     from safe_exploration_amd.ssm_cem.ssm_cem import JUNK_FUSED_SHAPES, JUNK_MODEL_FUSED_SHAPES
-    src = open(os.path.join(ROOT, 'safe_exploration_amd', 'csrc', 'sx_kernels.hip')).read()
+    src = open(os.path.join(ROOT, 'safe_exploration_amd', 'csrc', 'sx_model_shapes.hpp')).read()
     block = src[src.index('#define SX_MODEL_JUNK_SHAPES'):]
     block = block[:block.index('\n\n') if '\n\n' in block else len(block)]
     block = block[:block.index('//')]

@@ -1,6 +1,6 @@
 """Times the config-4 shape (cart-pole, N_train=2000, P=16384, H=20) through the large-training-set path: one rollout
 = 20 x (kstar_big_kernel, trmm_reduce_kernel, step_big_kernel).  Refuses to report a throughput on a non-zero status.
-Environment: N, P, H override the shape; SX_TRMM_VARIANT / SX_TRMM_ORDER select trmm_reduce_kernel variants (csrc/sx_kernels.hip)."""
+Environment: N, P, H override the shape; SX_TRMM_VARIANT / SX_TRMM_ORDER select trmm_reduce_kernel variants (csrc/sx_big.hip)."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
