@@ -490,6 +490,32 @@ int sx_cem_perf_rollout(const sx_gp_model* model, const double* alpha, const sx_
                         const double* tail_std, const double* tail_noise, double* rows, double* obj_cost, double* con_cost,
                         double* perf_traj, int32_t* status, void* stream);
 
+/* The performance trajectory WITH the GP's posterior variance ("variance form"): what an
+ * exploration run plans with.  Per particle, with v_t and mu_0 as above,
+ *   (mean_t, var_t) = GP posterior at [mu_t, v_t] (noise included, as sx_gp_predict)
+ *   mu_{t+1} = a mu_t + b v_t + mean_t;   obj += cost(mu_{t+1}, var_t)       t = 0 .. n_perf - 1
+ * cost = -sum_d var_t[d] for SX_OBJ_NEG_VARIANCE (the CEM solver's exploration objective, safempc_cem.py:304-312, moved
+ * onto the performance trajectory), the separable objective on mu_{t+1} for SX_OBJ_AFFINE_ABS (sx_cem_perf_rollout's
+ * objective; the variances are then an extra output).  No zero / negative fix-up of var_t (nothing takes its square root),
+ * no variance propagation, no feedback term, no state constraint.
+ * Arguments as sx_cem_perf_rollout, except:
+ *   model        the PACKED exact-GP model sx_cem_rollout takes (x_train, a_pack, stage_tab, n_pad of sx_gp_pack): the
+ *                variance needs W and the stage table, not alpha
+ *   perf_sigma   dev [E x P x n_perf x n_s] | NULL   var_0 .. var_{n_perf - 1}
+ *   status       OR-ed with SX_STATUS_NAN on a non-finite mu_t or var_t (that particle's objective is NaN: it never ranks)
+ * One workgroup of SX_WAVES waves per tile of 16 particles, the Kstar and matrix phases of the streaming safety kernel per
+ * step; a tile's numbers do not depend on P or on the launch's grid.
+ * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout, and for a model without a_pack / stage_tab / a valid n_pad
+ * or an obj_mode that is neither of the two; SX_ERR_UNSUPPORTED for a shape sx_cem_rollout is not instantiated for and for
+ * training sets outside the two forms built: Kstar of all outputs in LDS beside the tile's n_perf actions (N up to ~ 524
+ * at (n_s, n_u) = (2, 1)), else output by output (n_s > 1, n_pad <= 1024).  No resident-W form, no workspace path.
+ * Replaces: nothing in the reference's CEM solver; its casadi solver sums gp_sigma_pred of mean_equivalent_multistep
+ * (safempc_simple.py:292-321, 398-490). */
+int sx_cem_perf_rollout_var(const sx_gp_model* model, const sx_env* env, int E, int P, int H, int n_perf, int r,
+                            const double* x0, const double* safe_actions, const double* tail_mean, const double* tail_std,
+                            const double* tail_noise, double* rows, double* obj_cost, double* con_cost, double* perf_traj,
+                            double* perf_sigma, int32_t* status, void* stream);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

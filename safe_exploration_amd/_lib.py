@@ -115,6 +115,8 @@ SIGNATURES = {
                                  + [c_void_p] * 12),
     'sx_cem_perf_rollout': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int, c_int, c_int]
                             + [c_void_p] * 11),
+    'sx_cem_perf_rollout_var': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int, c_int, c_int]
+                                + [c_void_p] * 12),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

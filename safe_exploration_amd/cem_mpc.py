@@ -29,6 +29,9 @@ class Rollouts:
     actions: Tensor                  # [P x H x n_u]
     objective_costs: Tensor          # [P]
     constraint_costs: Tensor         # [P]
+    # with FusedCemMpc(perf_variance=True): the performance trajectory's means and posterior variances [P x n_perf x n_s]
+    perf_trajectories: Optional[Tensor] = None
+    perf_sigma: Optional[Tensor] = None
 
 
 def _rollout(suffix: str, head: tuple, x0: Tensor, horizon: int, n_s: int, n_u: int, words: int, unsupported, *,
@@ -261,6 +264,44 @@ def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n
                                           _lib.stream_ptr(dev))
     _lib.check(code, 'sx_cem_perf_rollout')
     return dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, status=status)
+
+
+def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
+                         safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                         tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                         tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False,
+                         want_sigma: bool = False):
+    """Thin wrapper over sx_cem_perf_rollout_var: `cem_perf_rollout` with the GP's posterior variance at every step (the
+    N x N product of the safety kernels), for both objective modes -- SX_OBJ_NEG_VARIANCE sums -var_t over the performance
+    trajectory.  Arguments as `cem_perf_rollout`; `want_sigma` also returns the variances.
+    Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, perf_sigma (same shape) | None,
+    status)."""
+    _lib.require_gpu(x0, 'x0')
+    if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
+        raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
+                                  f'{getattr(ssm, "kernel_family", None)!r}')
+    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
+    E, P = safe_actions.size(0), safe_actions.size(1)
+    T = n_perf - r
+    if tail_noise is not None:
+        if rows is not None:
+            raise ValueError('either tail_noise (the tail is drawn) or rows (the tail is given), not both')
+        rows = torch.empty((E, P, horizon + T, n_u), dtype=torch.float64, device=dev)
+    elif rows is None or tuple(rows.shape) != (E, P, horizon + T, n_u) or not rows.is_contiguous():
+        raise ValueError(f'without tail_noise, rows must be a contiguous [{E} x {P} x {horizon + T} x {n_u}] tensor')
+    traj = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_traj else None
+    sigma = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    code = _lib.lib().sx_cem_perf_rollout_var(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, horizon, n_perf, r,
+                                              _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions), _lib.ptr(tail_mean),
+                                              _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows), _lib.ptr(obj_cost),
+                                              _lib.ptr(con_cost), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(status),
+                                              _lib.stream_ptr(dev))
+    if code == _lib.SX_ERR_UNSUPPORTED:
+        raise _lib.SxError(f'sx_cem_perf_rollout_var: no form of the variance performance rollout for this model '
+                           f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
+                           f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
+    _lib.check(code, 'sx_cem_perf_rollout_var')
+    return dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, perf_sigma=sigma, status=status)
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
@@ -503,12 +544,17 @@ class FusedCemMpc:
     while the safety trajectory keeps the constraints.  The CEM distribution then covers the row [safety actions | tail] of
     H + n_perf - perf_r steps; an iteration is the safety rollout, ``sx_cem_perf_rollout`` and the ranking over those rows.
     ``get_actions*`` still return the H safety actions of the best row; its tail is ``last_perf_actions``.
+
+    ``perf_variance=True`` (with ``n_perf > 0``) runs ``sx_cem_perf_rollout_var`` in place of ``sx_cem_perf_rollout``: the
+    performance trajectory then carries the GP's posterior variance at every step, and with it the variance objective
+    (SX_OBJ_NEG_VARIANCE: an exploration run looks n_perf steps ahead for where the model is uncertain).  Recorded rollouts
+    keep the performance means and variances.
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
                  record_rollouts: bool = False, process_group=None, force_exchange: bool = False, n_perf: int = 0,
-                 perf_r: int = 1):
+                 perf_r: int = 1, perf_variance: bool = False):
         self._ssm = ssm
         self._env = env
         self._horizon = time_horizon
@@ -519,6 +565,9 @@ class FusedCemMpc:
                              f'n_perf={n_perf}, perf_r={perf_r}, time_horizon={time_horizon}')
         self._tail = self._n_perf - self._perf_r if self._n_perf > 0 else 0
         self._row_steps = time_horizon + self._tail
+        self._perf_variance = bool(perf_variance)
+        if self._perf_variance and self._n_perf <= 0:
+            raise ValueError('perf_variance=True needs a performance trajectory (n_perf > 0)')
         if self._n_perf > 0:
             family = getattr(ssm, 'kernel_family', 'rbf')
             if family != 'rbf':
@@ -603,11 +652,11 @@ class FusedCemMpc:
         self._objective_hook = objective_hook
         self._prior_tensors = None
 
-    @staticmethod
-    def _check_perf_objective(env: _lib.SxEnv) -> None:
-        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE:
+    def _check_perf_objective(self, env: _lib.SxEnv) -> None:
+        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and not self._perf_variance:
             raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
-                             '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function')
+                             '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function, or pass '
+                             'perf_variance=True')
 
     def _prior(self):
         """(a [n_s x n_s], b [n_s x n_u], k_fb [n_u x n_s]) of the current sx_env as device tensors."""
@@ -794,11 +843,16 @@ class FusedCemMpc:
                 # the performance trajectory: its objective replaces the safety trajectory's, the tail's action box adds to
                 # the constraint cost, and the rows [safety actions | tail] are what the ranking sees
                 hook, n_s = self._objective_hook, self._ssm.num_states
-                pr = cem_perf_rollout(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, safe_actions=r['actions'],
-                                      obj_cost=r['obj_cost'].contiguous(), con_cost=r['con_cost'].contiguous(),
-                                      status=status, tail_mean=full_mean[:, H:].contiguous(),
-                                      tail_std=full_std[:, H:].contiguous(), tail_noise=eps_tail,
-                                      want_traj=hook is not None)
+                kw = dict(safe_actions=r['actions'], obj_cost=r['obj_cost'].contiguous(),
+                          con_cost=r['con_cost'].contiguous(), status=status, tail_mean=full_mean[:, H:].contiguous(),
+                          tail_std=full_std[:, H:].contiguous(), tail_noise=eps_tail)
+                if self._perf_variance:
+                    pr = cem_perf_rollout_var(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
+                                              want_traj=hook is not None or self._record, want_sigma=self._record)
+                    r.update(perf_traj=pr['perf_traj'], perf_sigma=pr['perf_sigma'])
+                else:
+                    pr = cem_perf_rollout(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
+                                          want_traj=hook is not None)
                 r.update(safe_actions=r['actions'], actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
                 if hook is not None:
                     obj = torch.zeros_like(pr['obj_cost'])
@@ -820,6 +874,8 @@ class FusedCemMpc:
                 for e in range(E):
                     history.append(Rollouts(r['traj'][e], r.get('safe_actions', r['actions'])[e], r['obj_cost'][e],
                                             r['con_cost'][e]))
+                    if r.get('perf_sigma') is not None:
+                        history[-1].perf_trajectories, history[-1].perf_sigma = r['perf_traj'][e], r['perf_sigma'][e]
             return r
 
         def rank(it, r):

@@ -227,6 +227,11 @@ class CemSafeMPC(SafeMPC):
         # n_perf / r / type_perf_traj from the casadi defaults and must keep solving without one.
         self._cem_n_perf = int(getattr(conf, 'cem_n_perf', 0) or 0)
         self._cem_perf_r = int(getattr(conf, 'cem_perf_r', 1))
+        # cem_perf_variance: the performance trajectory carries the GP's posterior variance (sx_cem_perf_rollout_var), and
+        # with it the exploration objective of an environment without an objective_cost_function
+        self._cem_perf_variance = bool(getattr(conf, 'cem_perf_variance', False))
+        if self._cem_perf_variance and not self._cem_n_perf:
+            raise ValueError('cem_perf_variance needs a performance trajectory (cem_n_perf > 0)')
         if self._cem_n_perf:
             if not (1 <= self._cem_perf_r <= self._mpc_time_horizon and self._cem_n_perf > self._cem_perf_r):
                 raise ValueError(f'cem_n_perf={self._cem_n_perf} needs 1 <= cem_perf_r <= mpc_time_horizon and cem_n_perf > '
@@ -235,9 +240,11 @@ class CemSafeMPC(SafeMPC):
             if mpc is None and family != 'rbf':
                 raise NotImplementedError(f'cem_n_perf > 0 needs an exact RBF GP (GpCemSSM); kernel_family {family!r} has no '
                                           f'performance trajectory')
-            if env.objective_cost_function(torch.zeros((1, env.n_s), dtype=torch.float64)) is None:
+            if (not self._cem_perf_variance
+                    and env.objective_cost_function(torch.zeros((1, env.n_s), dtype=torch.float64)) is None):
                 raise ValueError('cem_n_perf > 0 needs an environment objective: the performance trajectory propagates '
-                                 'means only and cannot carry the variance objective')
+                                 'means only and cannot carry the variance objective (set cem_perf_variance for one that '
+                                 'does)')
 
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
@@ -339,7 +346,7 @@ class CemSafeMPC(SafeMPC):
                                     init_std=getattr(self._conf, 'cem_init_std', 1.0),
                                     warm_start=getattr(self._conf, 'cem_warm_start', None) or 'zero',
                                     record_rollouts=self._record_rollouts, n_perf=self._cem_n_perf,
-                                    perf_r=self._cem_perf_r)
+                                    perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}))
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
         self._env_key = key
         return self._mpc

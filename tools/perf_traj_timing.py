@@ -1,7 +1,8 @@
 """Solve time with and without the performance trajectory, on this build: config 2 (pendulum, N = 200, 4096 particles,
 H = 15, 8 CEM iterations, 409 elites).
 
-    python tools/perf_traj_timing.py [--n-perf 15,30,45] [--solves 200] [--warmup 20] [--off-only] [--label L] [--out F]
+    python tools/perf_traj_timing.py [--n-perf 15,30,45] [--solves 200] [--warmup 20] [--off-only] [--variance] [--label L]
+                                     [--out F]
 
 Rows (one JSON line each: median and p95 in ms of synchronous solves -- FusedCemMpc.solve + device synchronise on the host
 clock -- `--solves` times after `--warmup` untimed ones; printed and, with `--out`, appended to that jsonl file):
@@ -12,6 +13,9 @@ clock -- `--solves` times after `--warmup` untimed ones; printed and, with `--ou
                   difference to `off`
   launch_safety, launch_perf_K   one launch alone (sx_cem_rollout at H = 15; sx_cem_perf_rollout at n_perf = K): 200
                   launches back to back between two synchronisations, per launch, in us
+`--variance` adds, for every K: `n_perf=K var_affine` (perf_variance=True with the same objective: the cost of the variance
+kernel alone), `n_perf=K var` (perf_variance=True over config 2's own variance objective; `extra_ms` against off_cfg2) and
+`launch_perf_var_K` (sx_cem_perf_rollout_var alone).
 `--off-only` stops after off_H30 and uses nothing the parent commit lacks: run the same file from a checkout of the parent for
 the same-session comparison (`--label` names the build in the rows).  Needs the GPU.
 """
@@ -62,6 +66,7 @@ def main():
     ap.add_argument('--solves', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--off-only', action='store_true')
+    ap.add_argument('--variance', action='store_true')
     ap.add_argument('--label', default='this')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -82,9 +87,9 @@ def main():
     def solver(ssm, env, H, **kw):
         return FusedCemMpc(ssm, env, H, wl.particles, wl.elites, wl.iterations, device=DEV, init_std=wl.init_std, **kw)
 
-    ssm, env = problems.build(wl.spec, device=DEV)
-    med, p95 = time_solves(solver(ssm, env, wl.horizon), x0, args.warmup, args.solves)
-    row(row='off_cfg2', H=wl.horizon, n_perf=0, median_ms=med, p95_ms=p95)
+    ssm, env_var = problems.build(wl.spec, device=DEV)
+    off_cfg2, p95 = time_solves(solver(ssm, env_var, wl.horizon), x0, args.warmup, args.solves)
+    row(row='off_cfg2', H=wl.horizon, n_perf=0, median_ms=off_cfg2, p95_ms=p95)
     spec = problems.pendulum(wl.spec.X.shape[0], seed=0, obj_mode=_lib.SX_OBJ_AFFINE_ABS)
     ssm, env = problems.build(spec, device=DEV)
     off, p95 = time_solves(solver(ssm, env, wl.horizon), x0, args.warmup, args.solves)
@@ -99,6 +104,11 @@ def main():
         med, p95 = time_solves(solver(ssm, env, H, n_perf=k, perf_r=1), x0, args.warmup, args.solves)
         row(row=f'n_perf={k}', H=H, n_perf=k, r=1, median_ms=med, p95_ms=p95, extra_ms=med - off,
             extra_per_iteration_us=(med - off) * 1e3 / wl.iterations)
+        if args.variance:
+            for name, e, base in (('var_affine', env, off), ('var', env_var, off_cfg2)):
+                med, p95 = time_solves(solver(ssm, e, H, n_perf=k, perf_r=1, perf_variance=True), x0, args.warmup, args.solves)
+                row(row=f'n_perf={k} {name}', H=H, n_perf=k, r=1, median_ms=med, p95_ms=p95, extra_ms=med - base,
+                    extra_per_iteration_us=(med - base) * 1e3 / wl.iterations)
     # the launches alone
     gen = torch.Generator(device=DEV)
     gen.manual_seed(0)
@@ -117,6 +127,11 @@ def main():
             lambda: cem_mpc.cem_perf_rollout(ssm, env, x0, H, k, 1, safe_actions=safety['actions'],
                                              obj_cost=safety['obj_cost'], con_cost=safety['con_cost'], status=status,
                                              tail_mean=t_mean, tail_std=t_std, tail_noise=t_noise)))
+        if args.variance:
+            row(row=f'launch_perf_var_{k}', H=H, n_perf=k, r=1, us=time_launches(
+                lambda: cem_mpc.cem_perf_rollout_var(ssm, env_var, x0, H, k, 1, safe_actions=safety['actions'],
+                                                     obj_cost=safety['obj_cost'], con_cost=safety['con_cost'], status=status,
+                                                     tail_mean=t_mean, tail_std=t_std, tail_noise=t_noise)))
 
 
 if __name__ == '__main__':
