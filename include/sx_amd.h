@@ -516,6 +516,58 @@ int sx_cem_perf_rollout_var(const sx_gp_model* model, const sx_env* env, int E, 
                             const double* tail_noise, double* rows, double* obj_cost, double* con_cost, double* perf_traj,
                             double* perf_sigma, int32_t* status, void* stream);
 
+/* ---- The performance trajectory for E problems with an exact GP each ("multi-model form") ----
+ * One performance-rollout launch per CEM iteration for E exploration scenarios, after sx_cem_rollout_multi: every problem
+ * e has its own model; all models share (n_s, n_u), the sx_env and the buffer shapes of sx_cem_perf_rollout[_var], per
+ * problem.  `models` is the host array the launch plans from (N of every model), the device table carries the constants.
+ *
+ * The mean-only form reads alpha, which the packed sx_gp_model does not carry: a table of its own, built once per model
+ * change.  Bytes of it for E models of shape (n_s, n_u); < 0 for bad arguments or a shape without a kernel. */
+int64_t sx_cem_perf_table_bytes(int n_s, int n_u, int E);
+/* Packs, for each of the E models (host array), the kernel constants, the device pointers x_train and alphas[e] (host
+ * array of E device pointers, dev [n_s x N_e] as sx_gp_fit wrote them) and N_e into `table` (dev,
+ * sx_cem_perf_table_bytes() bytes); the pointers must stay valid while the table is used.  One host -> device copy on
+ * `stream`, and the call waits for it.  SX_ERR_ARG (before any device access) for a null pointer (a null alphas[e]
+ * included), E <= 0, models of different (n_s, n_u) or without x_train / n_train; SX_ERR_UNSUPPORTED for a shape without a
+ * kernel. */
+int sx_cem_perf_table(const sx_gp_model* models, const double* const* alphas, int E, void* table, void* stream);
+/* sx_cem_perf_rollout over E problems with a GP each: problem e's numbers are those of sx_cem_perf_rollout on model e
+ * alone, bit for bit (the lanes per particle and every model's padding are the single-model kernel's).  Arguments as
+ * sx_cem_perf_rollout except
+ *   models      host array of the E models the table was built from
+ *   perf_table  dev, built by sx_cem_perf_table
+ *   status      dev int32 [E]   one word per problem: a NaN in one problem's model leaves the others clear
+ * The grid is problem-aligned, E x ceil(P / 16) workgroups: a workgroup stages its own problem's training inputs and alpha
+ * in LDS, inside the launch's allocation for the largest model.
+ * SX_ERR_ARG (before any device access) for null pointers, non-positive sizes, r outside 1 .. H, n_perf <= r, tail_noise
+ * without tail_mean / tail_std, shapes that differ between the models or from env, or an obj_mode that is none of the two;
+ * SX_ERR_UNSUPPORTED (before any launch) for SX_OBJ_NEG_VARIANCE, a shape without a kernel or a model beyond the kernel's
+ * LDS, as sx_cem_perf_rollout.  Replaces: nothing in the reference's CEM solver; its n_scenarios casadi solvers each build
+ * a performance trajectory and run one after another (episode_runner.py:40-123, safempc_simple.py:398-490). */
+int sx_cem_perf_rollout_multi(const sx_gp_model* models, const void* perf_table, const sx_env* env, int E, int P, int H,
+                              int n_perf, int r, const double* x0, const double* safe_actions, const double* tail_mean,
+                              const double* tail_std, const double* tail_noise, double* rows, double* obj_cost,
+                              double* con_cost, double* perf_traj, int32_t* status, void* stream);
+/* sx_cem_perf_rollout_var over E problems with a GP each.  Arguments as sx_cem_perf_rollout_var except
+ *   models  host array of the E PACKED models
+ *   table   dev, the table sx_gp_model_table built from them (the one sx_cem_rollout_multi reads)
+ *   status  dev int32 [E]   one word per problem
+ * Output by output for every problem where any model needs it, with the LDS of the largest model
+ * (sx_cem_perf_rollout_var_multi_form); where that form is model e's own (sx_cem_perf_rollout_var_form) problem e's numbers
+ * are those of sx_cem_perf_rollout_var on model e alone, bit for bit.
+ * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout_var, for every model, and for shapes that differ between
+ * the models or from env; SX_ERR_UNSUPPORTED (before any launch) where any model has no form or the shape no kernel. */
+int sx_cem_perf_rollout_var_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                  int n_perf, int r, const double* x0, const double* safe_actions, const double* tail_mean,
+                                  const double* tail_std, const double* tail_noise, double* rows, double* obj_cost,
+                                  double* con_cost, double* perf_traj, double* perf_sigma, int32_t* status, void* stream);
+/* The form sx_cem_perf_rollout_var / sx_cem_perf_rollout_var_multi launch for this model / these models and n_perf (no
+ * launch, no device access): SX_FORM_STREAM (Kstar of all outputs in LDS) or SX_FORM_BYOUT, or < 0 for bad arguments (a
+ * null pointer, n_perf <= 1, an unpacked model, models of different shapes) and wherever the entry would answer
+ * SX_ERR_UNSUPPORTED.  The same contract as sx_cem_rollout_form / sx_cem_rollout_multi_form. */
+int sx_cem_perf_rollout_var_form(const sx_gp_model* model, int n_perf);
+int sx_cem_perf_rollout_var_multi_form(const sx_gp_model* models, int E, int n_perf);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -234,20 +234,22 @@ class FusedJunkUnsupported(_lib.SxError):
     """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
 
 
-def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
-                     safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
-                     tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
-                     tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False):
-    """Thin wrapper over sx_cem_perf_rollout: the performance trajectory of the particles of a safety rollout (exact RBF
-    GPs only).  x0 [E x n_s]; `safe_actions` [E x P x H x n_u], `obj_cost` (overwritten) and `con_cost` (added to) [E x P]
-    as `cem_rollout` returned them; the tail either drawn (`tail_mean`, `tail_std` [E x T x n_u], `tail_noise`
-    [E x P x T x n_u], T = n_perf - r) or given as the tail of `rows` [E x P x (H + T) x n_u].
-    Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, status)."""
+def _require_rbf(ssms: Sequence, x0: Tensor) -> None:
     _lib.require_gpu(x0, 'x0')
-    if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
-        raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
-                                  f'{getattr(ssm, "kernel_family", None)!r}')
-    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
+    for ssm in ssms:
+        if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
+            raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
+                                      f'{getattr(ssm, "kernel_family", None)!r}')
+
+
+def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: int, n_perf: int, r: int, *, safe_actions,
+                  obj_cost, con_cost, status, tail_mean, tail_std, tail_noise, rows, want_traj, want_sigma=None,
+                  unsupported=None):
+    """What `cem_perf_rollout`, `cem_perf_rollout_var` and `cem_perf_rollout_multi` share (after `_require_rbf`): the
+    buffers and the launch of `entry`(*head, E, P, H, n_perf, r, x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost,
+    con_cost, perf_traj[, perf_sigma], status, stream).  `want_sigma` is None for the mean-only entries (no perf_sigma
+    argument); `unsupported(n_s, n_u)`: what SX_ERR_UNSUPPORTED raises, where the entry has a message of its own."""
+    dev, n_s, n_u = x0.device, ssms[0].num_states, ssms[0].num_actions
     E, P = safe_actions.size(0), safe_actions.size(1)
     T = n_perf - r
     if tail_noise is not None:
@@ -257,13 +259,34 @@ def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n
     elif rows is None or tuple(rows.shape) != (E, P, horizon + T, n_u) or not rows.is_contiguous():
         raise ValueError(f'without tail_noise, rows must be a contiguous [{E} x {P} x {horizon + T} x {n_u}] tensor')
     traj = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_traj else None
-    code = _lib.lib().sx_cem_perf_rollout(ctypes.byref(ssm.device_model), _lib.ptr(ssm._alpha), ctypes.byref(env), E, P,
-                                          horizon, n_perf, r, _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions),
-                                          _lib.ptr(tail_mean), _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows),
-                                          _lib.ptr(obj_cost), _lib.ptr(con_cost), _lib.ptr(traj), _lib.ptr(status),
-                                          _lib.stream_ptr(dev))
-    _lib.check(code, 'sx_cem_perf_rollout')
-    return dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, status=status)
+    sigma = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    outs = (_lib.ptr(traj),) + (() if want_sigma is None else (_lib.ptr(sigma),))
+    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, n_perf, r, _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions),
+                                      _lib.ptr(tail_mean), _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows),
+                                      _lib.ptr(obj_cost), _lib.ptr(con_cost), *outs, _lib.ptr(status), _lib.stream_ptr(dev))
+    if unsupported is not None and code == _lib.SX_ERR_UNSUPPORTED:
+        raise unsupported(n_s, n_u)
+    _lib.check(code, entry)
+    out = dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, status=status)
+    if want_sigma is not None:
+        out['perf_sigma'] = sigma
+    return out
+
+
+def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
+                     safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                     tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                     tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False):
+    """Thin wrapper over sx_cem_perf_rollout: the performance trajectory of the particles of a safety rollout (exact RBF
+    GPs only).  x0 [E x n_s]; `safe_actions` [E x P x H x n_u], `obj_cost` (overwritten) and `con_cost` (added to) [E x P]
+    as `cem_rollout` returned them; the tail either drawn (`tail_mean`, `tail_std` [E x T x n_u], `tail_noise`
+    [E x P x T x n_u], T = n_perf - r) or given as the tail of `rows` [E x P x (H + T) x n_u].
+    Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, status)."""
+    _require_rbf([ssm], x0)
+    head = (ctypes.byref(ssm.device_model), _lib.ptr(ssm._alpha), ctypes.byref(env))
+    return _perf_rollout('sx_cem_perf_rollout', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
+                         obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
+                         tail_noise=tail_noise, rows=rows, want_traj=want_traj)
 
 
 def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
@@ -276,32 +299,83 @@ def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: in
     trajectory.  Arguments as `cem_perf_rollout`; `want_sigma` also returns the variances.
     Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, perf_sigma (same shape) | None,
     status)."""
-    _lib.require_gpu(x0, 'x0')
-    if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
-        raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
-                                  f'{getattr(ssm, "kernel_family", None)!r}')
-    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
-    E, P = safe_actions.size(0), safe_actions.size(1)
-    T = n_perf - r
-    if tail_noise is not None:
-        if rows is not None:
-            raise ValueError('either tail_noise (the tail is drawn) or rows (the tail is given), not both')
-        rows = torch.empty((E, P, horizon + T, n_u), dtype=torch.float64, device=dev)
-    elif rows is None or tuple(rows.shape) != (E, P, horizon + T, n_u) or not rows.is_contiguous():
-        raise ValueError(f'without tail_noise, rows must be a contiguous [{E} x {P} x {horizon + T} x {n_u}] tensor')
-    traj = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_traj else None
-    sigma = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_sigma else None
-    code = _lib.lib().sx_cem_perf_rollout_var(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, horizon, n_perf, r,
-                                              _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions), _lib.ptr(tail_mean),
-                                              _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows), _lib.ptr(obj_cost),
-                                              _lib.ptr(con_cost), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(status),
-                                              _lib.stream_ptr(dev))
-    if code == _lib.SX_ERR_UNSUPPORTED:
-        raise _lib.SxError(f'sx_cem_perf_rollout_var: no form of the variance performance rollout for this model '
-                           f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
-                           f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
-    _lib.check(code, 'sx_cem_perf_rollout_var')
-    return dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, perf_sigma=sigma, status=status)
+    _require_rbf([ssm], x0)
+
+    def unsupported(n_s, n_u):
+        return _lib.SxError(f'sx_cem_perf_rollout_var: no form of the variance performance rollout for this model '
+                            f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
+                            f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
+    head = (ctypes.byref(ssm.device_model), ctypes.byref(env))
+    return _perf_rollout('sx_cem_perf_rollout_var', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
+                         obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
+                         tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
+                         unsupported=unsupported)
+
+
+class PerfModelTable:
+    """The device table of sx_cem_perf_table for E exact GPs -- their kernel constants, training inputs and alpha, what the
+    mean-only performance rollout reads --, kept like `GpModelTable` and rebuilt only when one of the models changes (a
+    model builds a new device_model struct, and a new alpha, on every update).  `get` returns (the host array of the
+    models, the device table)."""
+
+    def __init__(self):
+        self._models = None
+        self._alphas = None
+        self._array = None
+        self._table = None
+
+    def get(self, ssms: Sequence[GpCemSSM], dev):
+        models, alphas = [ssm.device_model for ssm in ssms], [ssm._alpha for ssm in ssms]
+        if (self._models is not None and len(models) == len(self._models) and self._table.device == dev
+                and all(a is b for a, b in zip(models, self._models))
+                and all(a is b for a, b in zip(alphas, self._alphas))):
+            return self._array, self._table
+        lib, E = _lib.lib(), len(models)
+        n_s, n_u = models[0].n_s, models[0].n_u
+        if any((m.n_s, m.n_u) != (n_s, n_u) for m in models):
+            raise ValueError(f'the models of a multi-model rollout must share (n_s, n_u); got '
+                             f'{[(m.n_s, m.n_u) for m in models]}')
+        array = model_array(ssms, 'rbf')
+        nbytes = int(lib.sx_cem_perf_table_bytes(n_s, n_u, E))
+        if nbytes < 0:
+            raise FusedMultiUnsupported(f'sx_cem_perf_table_bytes: (n_s, n_u) = ({n_s}, {n_u}) has no performance rollout')
+        table = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        ptrs = (ctypes.c_void_p * E)(*[_lib.ptr(a) for a in alphas])
+        _lib.check(lib.sx_cem_perf_table(array, ptrs, E, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_cem_perf_table')
+        self._models, self._alphas, self._array, self._table = models, alphas, array, table
+        return array, table
+
+
+def cem_perf_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
+                           variance: bool = False, safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                           tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                           tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False,
+                           want_sigma: bool = False, table=None):
+    """`cem_perf_rollout` (`variance=False`: sx_cem_perf_rollout_multi) or `cem_perf_rollout_var` (`variance=True`:
+    sx_cem_perf_rollout_var_multi) for E problems with an exact GP each (ssms[e] for problem e) in one launch.  Buffers as
+    in the single-model wrappers, per problem; `status` is int32 [E], one word per problem.  `table` keeps the device table
+    between calls: a `PerfModelTable` for the mean-only form, the `GpModelTable` of `cem_rollout_multi` for the variance
+    form (a fresh one is built otherwise).  Raises FusedMultiUnsupported where the library has no single launch for the
+    models (before any launch)."""
+    _require_rbf(ssms, x0)
+    E = x0.size(0)
+    if len(ssms) != E:
+        raise ValueError(f'{len(ssms)} models for {E} problems')
+    if status is not None and status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    entry = 'sx_cem_perf_rollout_var_multi' if variance else 'sx_cem_perf_rollout_multi'
+    want = GpModelTable if variance else PerfModelTable
+    if not isinstance(table, want) or getattr(table, 'family', 'rbf') != 'rbf':
+        table = want()
+    models, dev_table = table.get(ssms, x0.device)
+
+    def unsupported(n_s, n_u):
+        return FusedMultiUnsupported(f'{entry}: no single launch of the performance rollout for these models ((n_s, n_u) = '
+                                     f'({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, n_perf = {n_perf})')
+    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r, safe_actions=safe_actions, obj_cost=obj_cost,
+                         con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std, tail_noise=tail_noise,
+                         rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma) if variance else None,
+                         unsupported=unsupported)
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
@@ -977,6 +1051,8 @@ class MultiModelCemMpc:
     `env` and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
     """
 
+    _perf_solvers = False   # MultiModelPerfCemMpc: the solvers carry a performance trajectory
+
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
                  process_group=None, solvers: Optional[Sequence[FusedCemMpc]] = None):
@@ -996,8 +1072,9 @@ class MultiModelCemMpc:
                 != (time_horizon, num_rollouts, num_elites, num_iterations, False) for s in solvers):
             raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: one per model, unsharded, with this '
                              f'solve\'s horizon, particles, elites and iterations')
-        if any(getattr(s, '_n_perf', 0) > 0 for s in solvers):
-            raise NotImplementedError('multi-model solves have no performance trajectory (solvers with n_perf > 0)')
+        if not self._perf_solvers and any(getattr(s, '_n_perf', 0) > 0 for s in solvers):
+            raise NotImplementedError('MultiModelCemMpc solves have no performance trajectory (solvers with n_perf > 0): '
+                                      'MultiModelPerfCemMpc solves those')
         self._solvers = list(solvers)
         self._env = env
         self._horizon = time_horizon
@@ -1024,7 +1101,8 @@ class MultiModelCemMpc:
         defaults: an injected optimiser need not be a FusedCemMpc.)"""
         def settings(m):
             init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
-            names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world')
+            names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world',
+                     '_n_perf', '_perf_r', '_perf_variance')
             return ((type(m),) + tuple(getattr(m, a, None) for a in names)
                     + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
 
@@ -1032,7 +1110,8 @@ class MultiModelCemMpc:
         for cem, env in rest:
             if cem != cem0:
                 raise ValueError('the solvers of a multi-model solve must share the CEM settings (horizon, rollouts, '
-                                 'elites, iterations, initial distribution, device)')
+                                 'elites, iterations, initial distribution, device, and the performance trajectory\'s '
+                                 'n_perf, perf_r, perf_variance)')
             if env != env0:
                 raise ValueError('the solvers of a multi-model solve must share the environment constants (sx_env)')
 
@@ -1110,3 +1189,113 @@ class MultiModelCemMpc:
         best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
                                            [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
         return best_host, found
+
+
+class MultiModelPerfCemMpc(MultiModelCemMpc):
+    """``MultiModelCemMpc`` over solvers with a performance trajectory (``FusedCemMpc(n_perf > 0)``, DESIGN.md section
+    3.9): E exact RBF GPs whose solvers share ``n_perf``, ``perf_r`` and ``perf_variance``.  An iteration is
+    ``sx_cem_rollout_multi`` over the first H steps of the rows, ONE performance-rollout launch for all problems
+    (``sx_cem_perf_rollout_multi``, or ``sx_cem_perf_rollout_var_multi`` with ``perf_variance``) and the ranking over the
+    rows of H + T steps, T = n_perf - perf_r; the ranking launch refits (no prologue refit, as in ``FusedCemMpc.solve``
+    with a performance trajectory).  Problem e draws solvers[e]'s noise and start distribution, which have row length.
+    ``get_actions_multi`` returns the H safety actions and leaves the tail in every solver's ``last_perf_actions``.
+    Where either launch has no form for the models the problems are solved one model at a time (``per_model_solves``).
+    """
+    _perf_solvers = True
+
+    def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, n_perf: Optional[int] = None, perf_r: int = 1, perf_variance: bool = False,
+                 device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero', process_group=None,
+                 solvers: Optional[Sequence[FusedCemMpc]] = None):
+        if process_group is not None:
+            raise NotImplementedError('the performance trajectory is not built for sharded particles (a process group)')
+        if solvers is None:
+            if not n_perf or n_perf <= 0:
+                raise ValueError('MultiModelPerfCemMpc needs a performance trajectory (n_perf > 0); MultiModelCemMpc solves '
+                                 'without one')
+            solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
+                                   seed=seed + e, init_std=init_std, warm_start=warm_start, n_perf=n_perf, perf_r=perf_r,
+                                   perf_variance=perf_variance) for e, ssm in enumerate(ssms)]
+        solvers = list(solvers)
+        settings = {(getattr(s, '_n_perf', 0), getattr(s, '_perf_r', 1), getattr(s, '_perf_variance', False))
+                    for s in solvers}
+        if len(settings) != 1:
+            raise ValueError(f'the solvers of a multi-model solve with a performance trajectory must share (n_perf, perf_r, '
+                             f'perf_variance), got {sorted(settings)}')
+        (self._n_perf, self._perf_r, self._perf_variance), = settings
+        if self._n_perf <= 0:
+            raise ValueError('MultiModelPerfCemMpc needs solvers with a performance trajectory (n_perf > 0); '
+                             'MultiModelCemMpc solves the others')
+        if n_perf is not None and (int(n_perf), int(perf_r), bool(perf_variance)) != (self._n_perf, self._perf_r,
+                                                                                      self._perf_variance):
+            raise ValueError(f'the solvers have (n_perf, perf_r, perf_variance) = {(self._n_perf, self._perf_r, self._perf_variance)}'
+                             f', not {(n_perf, perf_r, perf_variance)}')
+        if any(getattr(s, '_objective_hook', None) is not None for s in solvers):
+            raise NotImplementedError('a multi-model solve with a performance trajectory has no objective hook: solvers '
+                                      'with one act one at a time (get_actions)')
+        super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
+                         init_std=init_std, warm_start=warm_start, solvers=solvers)
+        if multi_family(self._ssms) != 'rbf':
+            raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
+                                      f'{[getattr(s, "kernel_family", None) for s in self._ssms]}')
+        self._tail = self._n_perf - self._perf_r
+        self._perf_table = PerfModelTable() if not self._perf_variance else None
+
+    def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
+        if objective_hook is not None:
+            raise NotImplementedError('a multi-model solve with a performance trajectory has no objective hook')
+        super().set_env(env)
+
+    def fused_applies(self) -> bool:
+        """Does one launch of each kind serve the models?  The safety rollout as in `MultiModelCemMpc`, and the variance
+        form of the performance rollout where its form query answers (sx_cem_perf_rollout_var_multi_form).  The mean-only
+        form adds no condition: it stages (2 n_s + n_u) N doubles in LDS, which holds every training set the multi-model
+        safety rollout takes (n_pad <= 1024).  Host only."""
+        if not super().fused_applies():
+            return False
+        if self._perf_variance:
+            models = model_array(self._ssms, 'rbf')
+            return int(_lib.lib().sx_cem_perf_rollout_var_multi_form(models, len(self._ssms), self._n_perf)) >= 0
+        return True
+
+    def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """As `MultiModelCemMpc.solve` with rows of H + T steps: noise [iters x E x P x (H + T) x n_u], and the returned
+        best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
+        E, H, T = len(self._ssms), self._horizon, self._tail
+        n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
+        if x0.shape != (E, n_s):
+            raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
+        if noise is None:
+            noise = torch.stack([s._next_noise(1)[:, 0] for s in self._solvers], dim=1)
+        self._last_noise = noise
+        noise_safe, noise_tail = noise[:, :, :, :H].contiguous(), noise[:, :, :, H:].contiguous()
+        starts = [s.start_distribution(x0[e:e + 1]) for e, s in enumerate(self._solvers)]
+        mean, std = torch.cat([m for m, _ in starts]), torch.cat([sd for _, sd in starts])
+        status = torch.zeros(E, dtype=torch.int32, device=x0.device)
+
+        def rollout(it, mean, std, rows):
+            r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean[:, :H].contiguous(), std=std[:, :H].contiguous(),
+                                  noise=noise_safe[it], status=status, table=self._table)
+            pr = cem_perf_rollout_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r,
+                                        variance=self._perf_variance, safe_actions=r['actions'],
+                                        obj_cost=r['obj_cost'], con_cost=r['con_cost'], status=status,
+                                        tail_mean=mean[:, H:].contiguous(), tail_std=std[:, H:].contiguous(),
+                                        tail_noise=noise_tail[it],
+                                        table=self._table if self._perf_variance else self._perf_table)
+            return dict(actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
+
+        def rank(it, r):
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites)
+
+        out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
+        return out['best'].view(E, H + T, n_u), out['best_ok'], status
+
+    def get_actions_multi(self, states: Tensor, where: str = 'get_actions_multi') -> Tuple[Tensor, Tensor]:
+        """As `MultiModelCemMpc.get_actions_multi`: the H safety actions of every problem's best row; the row's tail
+        [1 x T x n_u] becomes solvers[e].last_perf_actions."""
+        best, found = super().get_actions_multi(states, where)
+        if best.size(1) != self._horizon:      # (a solve per model has cut its rows already)
+            for e, s in enumerate(self._solvers):
+                s.last_perf_actions = best[e:e + 1, self._horizon:]
+            best = best[:, :self._horizon]
+        return best, found

@@ -1,0 +1,54 @@
+// The performance-trajectory kernels in the multi-model mode (sx_cem_perf_rollout_multi, sx_cem_perf_rollout_var_multi):
+// every shift-0 shape of SX_ROLLOUT_SHAPES, and their launchers.  A translation unit of its own: nothing the other
+// objects compile changes with it.
+#include <climits>
+
+#include "sx_launch.hpp"
+#include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES
+#include "sx_perf.hpp"
+#include "sx_perf_launch.hpp"
+
+namespace sx {
+
+static_assert(kPerfVarThreads == kRolloutThreads, "the stage table of sx_gp_pack is cut for the safety kernel's waves");
+
+template <int NS, int NU>
+int launch_perf_rollout_multi(const PerfGpEntry<NS, NU>* table, const PerfStepConst<NS, NU>& step, const PerfPtrs& pp,
+                              size_t lds, hipStream_t stream) {
+    const int64_t blocks = (int64_t)pp.E * ((pp.P + kPerfTile - 1) / kPerfTile);
+    if (blocks > INT_MAX || lds > kMaxLdsBytes) return SX_ERR_UNSUPPORTED;
+    if (int r = allow_lds(cem_perf_rollout_multi_kernel<NS, NU>, lds)) return r;
+    hipLaunchKernelGGL((cem_perf_rollout_multi_kernel<NS, NU>), dim3((unsigned)blocks), dim3(kPerfThreads), lds, stream,
+                       table, step, pp);
+    return check_launch();
+}
+
+template <int NS, int NU, bool BYOUT>
+static int launch_perf_var_multi_form(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc,
+                                      const PerfVarPtrs& vp, unsigned blocks, size_t lds, hipStream_t stream) {
+    if (int r = allow_lds(cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>, lds)) return r;
+    hipLaunchKernelGGL((cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>), dim3(blocks), dim3(kPerfVarThreads), lds, stream,
+                       table, sc, vp);
+    return check_launch();
+}
+
+template <int NS, int NU>
+int launch_perf_var_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
+                          bool byout, size_t lds, hipStream_t stream) {
+    const int64_t blocks = (int64_t)vp.p.E * ((vp.p.P + SX_TILE - 1) / SX_TILE);
+    if (blocks > INT_MAX || lds > kMaxLdsBytes) return SX_ERR_UNSUPPORTED;
+    if constexpr (NS > 1) {
+        if (byout) return launch_perf_var_multi_form<NS, NU, true>(table, sc, vp, (unsigned)blocks, lds, stream);
+    }
+    return launch_perf_var_multi_form<NS, NU, false>(table, sc, vp, (unsigned)blocks, lds, stream);
+}
+
+}  // namespace sx
+
+#define SX_PERF_MULTI_INSTANTIATE(NS, NU)                                                                              \
+    template int sx::launch_perf_rollout_multi<NS, NU>(const sx::PerfGpEntry<NS, NU>*, const sx::PerfStepConst<NS, NU>&, \
+                                                       const sx::PerfPtrs&, size_t, hipStream_t);                      \
+    template int sx::launch_perf_var_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfStepConst<NS, NU>&,  \
+                                                   const sx::PerfVarPtrs&, bool, size_t, hipStream_t);
+#define SX_PERF_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_PERF_MULTI_INSTANTIATE(NS, NU))
+SX_ROLLOUT_SHAPES(SX_PERF_MULTI_ONE, 0)

@@ -15,7 +15,7 @@ from numpy import ndarray
 from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
-from .cem_mpc import FusedCemMpc, MultiModelCemMpc, Rollouts, multi_family
+from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, multi_family
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
@@ -489,7 +489,9 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     [E x n_u], one MpcResult per solver).
 
     Over models of one family -- exact RBF GPs, feature-space GPs or MC-dropout ensembles -- that is ONE solve for all of
-    them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model); otherwise (mixed
+    them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model; solvers that all
+    have a performance trajectory with one ``cem_n_perf``, ``cem_perf_r`` and ``cem_perf_variance`` go through
+    ``MultiModelPerfCemMpc``, which adds one performance-rollout launch per iteration for all of them); otherwise (mixed
     families, JunkDimensionsSSM, ...), and where the single launch does not apply, one solve per solver.  Either way
     problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
     ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
@@ -498,9 +500,17 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     states = np.asarray(states)
     if not solvers:
         raise ValueError('get_actions_multi needs at least one solver')
-    if any(getattr(s, '_cem_n_perf', 0) > 0 for s in solvers):
-        raise NotImplementedError('get_actions_multi has no performance trajectory: solvers with cem_n_perf > 0 act one at '
-                                  'a time (get_action)')
+    # the performance trajectory (cem_n_perf > 0): all solvers or none, with one (cem_n_perf, cem_perf_r, cem_perf_variance)
+    perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False))
+            for s in solvers]
+    with_perf = any(n > 0 for n, _, _ in perf)
+    if with_perf and not all(n > 0 for n, _, _ in perf):
+        raise NotImplementedError('get_actions_multi takes solvers that all have a performance trajectory or all have none: '
+                                  f'got cem_n_perf = {[n for n, _, _ in perf]}; the ones with cem_n_perf > 0 act one at a time '
+                                  f'(get_action), or together in a call of their own')
+    if with_perf and len(set(perf)) != 1:
+        raise ValueError('the solvers of get_actions_multi must share the performance trajectory\'s settings: got '
+                         f'(cem_n_perf, cem_perf_r, cem_perf_variance) = {perf}')
     n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
     if states.ndim != 2 or states.shape != (len(solvers), n_s):
         raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')
@@ -517,7 +527,8 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
         key = tuple(id(m) for m in mpcs)
         cached = getattr(solvers[0], '_multi', None)
         if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
-            solvers[0]._multi = cached = (key, MultiModelCemMpc.from_solvers(mpcs))
+            cls = MultiModelPerfCemMpc if with_perf else MultiModelCemMpc
+            solvers[0]._multi = cached = (key, cls.from_solvers(mpcs))
         multi = cached[1]
         multi._env = mpcs[0]._env
         best, found = multi.get_actions_multi(flat)

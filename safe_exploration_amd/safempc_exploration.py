@@ -1,7 +1,7 @@
 """Exploration module over a ready-made SafeMPC: the reference's ``DynamicSafeMPCExploration``
 (``safe_exploration/safempc_exploration.py:357-393``), plus the multi-episode form of ``find_max_variance`` that
 ``exploration_runner`` can call once per iteration for all of its parallel explorations."""
-from typing import List, Tuple
+from typing import List, Sequence, Tuple
 
 import numpy as np
 from numpy import ndarray
@@ -44,3 +44,16 @@ class DynamicSafeMPCExploration:
 
     def ssm_predict(self, z: ndarray) -> Tuple[ndarray, ndarray]:
         return self.safempc.ssm_predict(z)
+
+
+def find_max_variance_multi(explorations: Sequence[DynamicSafeMPCExploration], x_0: ndarray
+                            ) -> Tuple[ndarray, ndarray, List]:
+    """``find_max_variance`` of E independent explorations -- the reference's scenarios, each with its own model -- at
+    once: exploration e starts from x_0[e] ([E x n_s]).  One ``safempc_cem.get_actions_multi`` over their solvers (with
+    ``cem_n_perf`` / ``cem_perf_variance`` the multi-model solve looks n_perf steps ahead for every scenario in the same
+    launches).  Returns (x_0 [E x n_s], u_apply [E x n_u], one MpcResult per exploration): row e is what
+    ``explorations[e].find_max_variance(x_0[e])`` returns."""
+    from .safempc_cem import get_actions_multi
+    x_0 = np.atleast_2d(x_0)
+    u_apply, results = get_actions_multi([x.safempc for x in explorations], x_0)
+    return x_0, u_apply, results
