@@ -568,6 +568,42 @@ int sx_cem_perf_rollout_var_multi(const sx_gp_model* models, const void* table, 
 int sx_cem_perf_rollout_var_form(const sx_gp_model* model, int n_perf);
 int sx_cem_perf_rollout_var_multi_form(const sx_gp_model* models, int E, int n_perf);
 
+/* ---- The performance trajectory with Taylor uncertainty propagation ("Taylor form") ----
+ * sx_cem_perf_rollout_var with the state covariance carried from step to step: a first-order propagation under the fixed
+ * feedback K = env->k_fb, the gain the safety rollout uses.  Per particle, with v_t and mu_0 as above and Sigma_0 = 0:
+ *   (mean_t, var_t, J_t) = GP posterior and mean Jacobian at [mu_t, v_t] (noise included, as sx_gp_predict), J_t = [J_x | J_u]
+ *   M = J_x + J_u K;   Hm = a + b K + M;   G_t = diag(var_t) + M Sigma_t M^T
+ *   mu_{t+1} = a mu_t + b v_t + mean_t;   Sigma_{t+1} = Hm Sigma_t Hm^T + diag(var_t)
+ *   obj += cost(mu_{t+1}, diag G_t)                                         t = 0 .. n_perf - 1
+ * cost = -tr G_t for SX_OBJ_NEG_VARIANCE, the separable objective on mu_{t+1} for SX_OBJ_AFFINE_ABS.  mu is the variance
+ * form's, bit for bit (the feedback term has zero mean); G_0 = diag(var_0) and Sigma_1 = diag(var_0) exactly.  No zero /
+ * negative fix-up.
+ * Arguments as sx_cem_perf_rollout_var, except:
+ *   env          also {k_fb, m, h_mat, h_vec}
+ *   perf_sigma   dev [E x P x n_perf x n_s] | NULL          diag G_0 .. diag G_{n_perf - 1}
+ *   perf_cov     dev [E x P x n_perf x n_s x n_s] | NULL    Sigma_1 .. Sigma_{n_perf}, row-major, symmetric to the bit
+ *   terminal_safety  != 0: the ellipsoid (mu_s, Sigma_s), s = H + 2, must lie inside the safe polytope -- some
+ *                h_j . mu_s + sqrt(h_j^T Sigma_s h_j) - h_vec_j >= 0 adds SX_STATE_VIOLATION_COST to con_cost once (a NaN
+ *                distance counts as inside, as everywhere); needs n_perf >= H + 2 and m > 0
+ *   status       OR-ed with SX_STATUS_NAN on a non-finite mu_t, var_t, G_t or Sigma_t (that particle's objective is NaN)
+ * The variance kernel's layout and forms (all outputs in LDS, else output by output up to n_pad = 1024), with the step
+ * constants (64 .. 128 doubles) in LDS behind the tile's actions; a tile's numbers do not depend on P or on the grid.
+ * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout_var, and for terminal_safety with n_perf < H + 2 or without
+ * polytope rows; SX_ERR_UNSUPPORTED as sx_cem_perf_rollout_var and for m > SX_MAX_M.
+ * Replaces: one_step_taylor / multi_step_taylor_symbolic (uncertainty_propagation_casadi.py:11-149) as the casadi solver
+ * chains them for type_perf_traj = 'taylor', and its terminal safety performance constraint (safempc_simple.py:471-479);
+ * the reference's CEM solver has neither. */
+int sx_cem_perf_rollout_taylor(const sx_gp_model* model, const sx_env* env, int E, int P, int H, int n_perf, int r,
+                               const double* x0, const double* safe_actions, const double* tail_mean,
+                               const double* tail_std, const double* tail_noise, double* rows, double* obj_cost,
+                               double* con_cost, double* perf_traj, double* perf_sigma, double* perf_cov,
+                               int terminal_safety, int32_t* status, void* stream);
+/* The form sx_cem_perf_rollout_taylor launches for this model and n_perf (no launch, no device access): SX_FORM_STREAM or
+ * SX_FORM_BYOUT, or < 0 for bad arguments and wherever the entry would answer SX_ERR_UNSUPPORTED: the contract of
+ * sx_cem_perf_rollout_var_form, decided by the same rule over the variance kernel's LDS plus the step constants
+ * (uncertainty_propagation_casadi.py:11-149 and safempc_simple.py:471-479 have no such notion). */
+int sx_cem_perf_rollout_taylor_form(const sx_gp_model* model, int n_perf);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

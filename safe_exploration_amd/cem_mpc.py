@@ -32,6 +32,9 @@ class Rollouts:
     # with FusedCemMpc(perf_variance=True): the performance trajectory's means and posterior variances [P x n_perf x n_s]
     perf_trajectories: Optional[Tensor] = None
     perf_sigma: Optional[Tensor] = None
+    # with FusedCemMpc(perf_type='taylor'): the propagated state covariances Sigma_1 .. Sigma_n_perf [P x n_perf x n_s x n_s]
+    # (perf_sigma is then diag G_t, the variance including the uncertainty of the state)
+    perf_cov: Optional[Tensor] = None
 
 
 def _rollout(suffix: str, head: tuple, x0: Tensor, horizon: int, n_s: int, n_u: int, words: int, unsupported, *,
@@ -244,11 +247,13 @@ def _require_rbf(ssms: Sequence, x0: Tensor) -> None:
 
 def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: int, n_perf: int, r: int, *, safe_actions,
                   obj_cost, con_cost, status, tail_mean, tail_std, tail_noise, rows, want_traj, want_sigma=None,
-                  unsupported=None):
-    """What `cem_perf_rollout`, `cem_perf_rollout_var` and `cem_perf_rollout_multi` share (after `_require_rbf`): the
-    buffers and the launch of `entry`(*head, E, P, H, n_perf, r, x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost,
-    con_cost, perf_traj[, perf_sigma], status, stream).  `want_sigma` is None for the mean-only entries (no perf_sigma
-    argument); `unsupported(n_s, n_u)`: what SX_ERR_UNSUPPORTED raises, where the entry has a message of its own."""
+                  unsupported=None, want_cov=None, terminal_safety=False):
+    """What `cem_perf_rollout`, `cem_perf_rollout_var`, `cem_perf_rollout_taylor` and `cem_perf_rollout_multi` share
+    (after `_require_rbf`): the buffers and the launch of `entry`(*head, E, P, H, n_perf, r, x0, safe_actions, tail_mean,
+    tail_std, tail_noise, rows, obj_cost, con_cost, perf_traj[, perf_sigma[, perf_cov, terminal_safety]], status, stream).
+    `want_sigma` is None for the mean-only entries (no perf_sigma argument), `want_cov` is None for all but the Taylor entry
+    (no perf_cov / terminal_safety arguments); `unsupported(n_s, n_u)`: what SX_ERR_UNSUPPORTED raises, where the entry has
+    a message of its own."""
     dev, n_s, n_u = x0.device, ssms[0].num_states, ssms[0].num_actions
     E, P = safe_actions.size(0), safe_actions.size(1)
     T = n_perf - r
@@ -261,6 +266,9 @@ def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: 
     traj = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_traj else None
     sigma = torch.empty((E, P, n_perf, n_s), dtype=torch.float64, device=dev) if want_sigma else None
     outs = (_lib.ptr(traj),) + (() if want_sigma is None else (_lib.ptr(sigma),))
+    cov = torch.empty((E, P, n_perf, n_s, n_s), dtype=torch.float64, device=dev) if want_cov else None
+    if want_cov is not None:
+        outs += (_lib.ptr(cov), int(bool(terminal_safety)))
     code = getattr(_lib.lib(), entry)(*head, E, P, horizon, n_perf, r, _lib.ptr(x0.contiguous()), _lib.ptr(safe_actions),
                                       _lib.ptr(tail_mean), _lib.ptr(tail_std), _lib.ptr(tail_noise), _lib.ptr(rows),
                                       _lib.ptr(obj_cost), _lib.ptr(con_cost), *outs, _lib.ptr(status), _lib.stream_ptr(dev))
@@ -270,6 +278,8 @@ def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: 
     out = dict(rows=rows, obj_cost=obj_cost, con_cost=con_cost, perf_traj=traj, status=status)
     if want_sigma is not None:
         out['perf_sigma'] = sigma
+    if want_cov is not None:
+        out['perf_cov'] = cov
     return out
 
 
@@ -310,6 +320,36 @@ def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: in
                          obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
                          unsupported=unsupported)
+
+
+PERF_TYPES = ('mean_equivalent', 'taylor')
+
+
+def cem_perf_rollout_taylor(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
+                            safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                            tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                            tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False,
+                            want_sigma: bool = False, want_cov: bool = False, terminal_safety: bool = False):
+    """Thin wrapper over sx_cem_perf_rollout_taylor: `cem_perf_rollout_var` with the state covariance propagated to first
+    order under the fixed feedback `env.k_fb` -- Sigma_{t+1} = H Sigma_t H^T + diag(var_t), and the objective sees
+    diag(G_t) = var_t + diag(M Sigma_t M^T).  Arguments as `cem_perf_rollout_var`; `want_sigma` returns diag(G_t), `want_cov`
+    Sigma_1 .. Sigma_{n_perf} [E x P x n_perf x n_s x n_s]; `terminal_safety` adds the state-violation cost where the
+    ellipsoid (mu_s, Sigma_s), s = horizon + 2, leaves the safe polytope (needs n_perf >= horizon + 2).
+    Returns dict(rows, obj_cost, con_cost, perf_traj | None, perf_sigma | None, perf_cov | None, status)."""
+    _require_rbf([ssm], x0)
+    if terminal_safety and n_perf < horizon + 2:
+        raise ValueError(f'terminal_safety checks the performance state {horizon + 2}: n_perf = {n_perf} is too short '
+                         f'(n_perf >= horizon + 2)')
+
+    def unsupported(n_s, n_u):
+        return _lib.SxError(f'sx_cem_perf_rollout_taylor: no form of the Taylor performance rollout for this model '
+                            f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
+                            f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
+    head = (ctypes.byref(ssm.device_model), ctypes.byref(env))
+    return _perf_rollout('sx_cem_perf_rollout_taylor', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
+                         obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
+                         tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
+                         unsupported=unsupported, want_cov=bool(want_cov), terminal_safety=terminal_safety)
 
 
 class PerfModelTable:
@@ -623,12 +663,19 @@ class FusedCemMpc:
     performance trajectory then carries the GP's posterior variance at every step, and with it the variance objective
     (SX_OBJ_NEG_VARIANCE: an exploration run looks n_perf steps ahead for where the model is uncertain).  Recorded rollouts
     keep the performance means and variances.
+
+    ``perf_type='taylor'`` (with ``n_perf > 0``; default ``'mean_equivalent'``) runs ``sx_cem_perf_rollout_taylor``: the
+    state covariance is propagated to first order along the performance trajectory under the fixed feedback ``env.k_fb``,
+    and the objective sees the variance including it.  It carries the variance objective by itself, as ``perf_variance``
+    does.  ``perf_terminal_safety=True`` adds the state-violation cost where the performance ellipsoid at step
+    ``time_horizon + 2`` leaves the safe polytope (``n_perf >= time_horizon + 2``).  Recorded rollouts gain ``perf_cov``.
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
                  record_rollouts: bool = False, process_group=None, force_exchange: bool = False, n_perf: int = 0,
-                 perf_r: int = 1, perf_variance: bool = False):
+                 perf_r: int = 1, perf_variance: bool = False, perf_type: str = 'mean_equivalent',
+                 perf_terminal_safety: bool = False):
         self._ssm = ssm
         self._env = env
         self._horizon = time_horizon
@@ -642,6 +689,16 @@ class FusedCemMpc:
         self._perf_variance = bool(perf_variance)
         if self._perf_variance and self._n_perf <= 0:
             raise ValueError('perf_variance=True needs a performance trajectory (n_perf > 0)')
+        if perf_type not in PERF_TYPES:
+            raise ValueError(f'perf_type must be one of {PERF_TYPES}, got {perf_type!r}')
+        self._perf_type, self._perf_terminal_safety = perf_type, bool(perf_terminal_safety)
+        if perf_type == 'taylor' and self._n_perf <= 0:
+            raise ValueError("perf_type='taylor' needs a performance trajectory (n_perf > 0)")
+        if self._perf_terminal_safety and perf_type != 'taylor':
+            raise ValueError("perf_terminal_safety needs the propagated covariance (perf_type='taylor')")
+        if self._perf_terminal_safety and self._n_perf < time_horizon + 2:
+            raise ValueError(f'perf_terminal_safety checks the performance state {time_horizon + 2}: n_perf={n_perf} is too '
+                             f'short (n_perf >= time_horizon + 2)')
         if self._n_perf > 0:
             family = getattr(ssm, 'kernel_family', 'rbf')
             if family != 'rbf':
@@ -727,10 +784,10 @@ class FusedCemMpc:
         self._prior_tensors = None
 
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
-        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and not self._perf_variance:
+        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and not (self._perf_variance or self._perf_type == 'taylor'):
             raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
                              '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function, or pass '
-                             'perf_variance=True')
+                             "perf_variance=True or perf_type='taylor'")
 
     def _prior(self):
         """(a [n_s x n_s], b [n_s x n_u], k_fb [n_u x n_s]) of the current sx_env as device tensors."""
@@ -920,7 +977,12 @@ class FusedCemMpc:
                 kw = dict(safe_actions=r['actions'], obj_cost=r['obj_cost'].contiguous(),
                           con_cost=r['con_cost'].contiguous(), status=status, tail_mean=full_mean[:, H:].contiguous(),
                           tail_std=full_std[:, H:].contiguous(), tail_noise=eps_tail)
-                if self._perf_variance:
+                if self._perf_type == 'taylor':
+                    pr = cem_perf_rollout_taylor(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
+                                                 want_traj=hook is not None or self._record, want_sigma=self._record,
+                                                 want_cov=self._record, terminal_safety=self._perf_terminal_safety)
+                    r.update(perf_traj=pr['perf_traj'], perf_sigma=pr['perf_sigma'], perf_cov=pr['perf_cov'])
+                elif self._perf_variance:
                     pr = cem_perf_rollout_var(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
                                               want_traj=hook is not None or self._record, want_sigma=self._record)
                     r.update(perf_traj=pr['perf_traj'], perf_sigma=pr['perf_sigma'])
@@ -950,6 +1012,8 @@ class FusedCemMpc:
                                             r['con_cost'][e]))
                     if r.get('perf_sigma') is not None:
                         history[-1].perf_trajectories, history[-1].perf_sigma = r['perf_traj'][e], r['perf_sigma'][e]
+                    if r.get('perf_cov') is not None:
+                        history[-1].perf_cov = r['perf_cov'][e]
             return r
 
         def rank(it, r):
@@ -1102,7 +1166,7 @@ class MultiModelCemMpc:
         def settings(m):
             init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
             names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world',
-                     '_n_perf', '_perf_r', '_perf_variance')
+                     '_n_perf', '_perf_r', '_perf_variance', '_perf_type', '_perf_terminal_safety')
             return ((type(m),) + tuple(getattr(m, a, None) for a in names)
                     + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
 
@@ -1111,7 +1175,7 @@ class MultiModelCemMpc:
             if cem != cem0:
                 raise ValueError('the solvers of a multi-model solve must share the CEM settings (horizon, rollouts, '
                                  'elites, iterations, initial distribution, device, and the performance trajectory\'s '
-                                 'n_perf, perf_r, perf_variance)')
+                                 'n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety)')
             if env != env0:
                 raise ValueError('the solvers of a multi-model solve must share the environment constants (sx_env)')
 
@@ -1199,7 +1263,8 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
     rows of H + T steps, T = n_perf - perf_r; the ranking launch refits (no prologue refit, as in ``FusedCemMpc.solve``
     with a performance trajectory).  Problem e draws solvers[e]'s noise and start distribution, which have row length.
     ``get_actions_multi`` returns the H safety actions and leaves the tail in every solver's ``last_perf_actions``.
-    Where either launch has no form for the models the problems are solved one model at a time (``per_model_solves``).
+    Where either launch has no form for the models the problems are solved one model at a time (``per_model_solves``);
+    so are solvers with ``perf_type='taylor'``, which has no multi-model launch (``fused_applies`` is False).
     """
     _perf_solvers = True
 
@@ -1239,6 +1304,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
             raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
                                       f'{[getattr(s, "kernel_family", None) for s in self._ssms]}')
         self._tail = self._n_perf - self._perf_r
+        self._taylor = any(getattr(s, '_perf_type', 'mean_equivalent') == 'taylor' for s in solvers)
         self._perf_table = PerfModelTable() if not self._perf_variance else None
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
@@ -1251,7 +1317,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         form of the performance rollout where its form query answers (sx_cem_perf_rollout_var_multi_form).  The mean-only
         form adds no condition: it stages (2 n_s + n_u) N doubles in LDS, which holds every training set the multi-model
         safety rollout takes (n_pad <= 1024).  Host only."""
-        if not super().fused_applies():
+        if not super().fused_applies() or self._taylor:
             return False
         if self._perf_variance:
             models = model_array(self._ssms, 'rbf')
@@ -1263,6 +1329,8 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
         E, H, T = len(self._ssms), self._horizon, self._tail
         n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
+        if self._taylor:
+            raise FusedMultiUnsupported("perf_type='taylor' has no multi-model launch: the solvers act one model at a time")
         if x0.shape != (E, n_s):
             raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
         if noise is None:

@@ -18,9 +18,12 @@ struct PerfVarPlan {
 
 // As plan_rollout (sx_gp_rollout.hip) decides the streaming safety kernel's: Kstar of all outputs in LDS where they fit
 // beside the n_perf actions of the tile, else output by output (n_s > 1), else unsupported -- there is no resident-W form
-// and no workspace path here.
-inline PerfVarPlan plan_perf_var(int ns, int nu, int n_train, int n_pad, int n_perf) {
-    auto lds_bytes = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, 0, n_train, n_pad, n_perf, byout); };
+// and no workspace path here.  `extra_bytes`: what the kernel keeps in LDS behind the actions (the Taylor form's step
+// constants, sx_perf_taylor.hpp).
+inline PerfVarPlan plan_perf_var(int ns, int nu, int n_train, int n_pad, int n_perf, size_t extra_bytes = 0) {
+    auto lds_bytes = [&](bool byout) {
+        return rollout_stream_lds_bytes(ns, nu, 0, n_train, n_pad, n_perf, byout) + extra_bytes;
+    };
     const bool compiled = rollout_compiled(ns, nu, 0);
     const bool fits = n_pad <= 1024;
     if (fits && lds_bytes(false) <= kMaxLdsBytes) return {SX_FORM_STREAM, compiled, lds_bytes(false)};

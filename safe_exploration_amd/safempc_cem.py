@@ -232,6 +232,22 @@ class CemSafeMPC(SafeMPC):
         self._cem_perf_variance = bool(getattr(conf, 'cem_perf_variance', False))
         if self._cem_perf_variance and not self._cem_n_perf:
             raise ValueError('cem_perf_variance needs a performance trajectory (cem_n_perf > 0)')
+        # cem_perf_type: 'mean_equivalent' (a point is propagated) or 'taylor' (sx_cem_perf_rollout_taylor: the state
+        # covariance is propagated to first order under the LQR feedback, and the variance objective includes it);
+        # cem_perf_terminal_safety: the performance ellipsoid at step mpc_time_horizon + 2 must lie in the safe polytope.
+        # Settings of their own, like cem_n_perf: the casadi solver's type_perf_traj / perf_safety_constr stay unread.
+        self._cem_perf_type = getattr(conf, 'cem_perf_type', None) or 'mean_equivalent'
+        self._cem_perf_terminal_safety = bool(getattr(conf, 'cem_perf_terminal_safety', False))
+        if self._cem_perf_type not in ('mean_equivalent', 'taylor'):
+            raise ValueError(f"cem_perf_type must be 'mean_equivalent' or 'taylor', got {self._cem_perf_type!r}")
+        taylor = self._cem_perf_type == 'taylor'
+        if taylor and not self._cem_n_perf:
+            raise ValueError("cem_perf_type='taylor' needs a performance trajectory (cem_n_perf > 0)")
+        if self._cem_perf_terminal_safety and not taylor:
+            raise ValueError("cem_perf_terminal_safety needs the propagated covariance (cem_perf_type='taylor')")
+        if self._cem_perf_terminal_safety and self._cem_n_perf < self._mpc_time_horizon + 2:
+            raise ValueError(f'cem_perf_terminal_safety checks the performance state mpc_time_horizon + 2 = '
+                             f'{self._mpc_time_horizon + 2}: cem_n_perf={self._cem_n_perf} is too short')
         if self._cem_n_perf:
             if not (1 <= self._cem_perf_r <= self._mpc_time_horizon and self._cem_n_perf > self._cem_perf_r):
                 raise ValueError(f'cem_n_perf={self._cem_n_perf} needs 1 <= cem_perf_r <= mpc_time_horizon and cem_n_perf > '
@@ -240,11 +256,11 @@ class CemSafeMPC(SafeMPC):
             if mpc is None and family != 'rbf':
                 raise NotImplementedError(f'cem_n_perf > 0 needs an exact RBF GP (GpCemSSM); kernel_family {family!r} has no '
                                           f'performance trajectory')
-            if (not self._cem_perf_variance
+            if (not self._cem_perf_variance and not taylor
                     and env.objective_cost_function(torch.zeros((1, env.n_s), dtype=torch.float64)) is None):
                 raise ValueError('cem_n_perf > 0 needs an environment objective: the performance trajectory propagates '
-                                 'means only and cannot carry the variance objective (set cem_perf_variance for one that '
-                                 'does)')
+                                 'means only and cannot carry the variance objective (set cem_perf_variance or '
+                                 "cem_perf_type='taylor' for one that does)")
 
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
@@ -346,7 +362,9 @@ class CemSafeMPC(SafeMPC):
                                     init_std=getattr(self._conf, 'cem_init_std', 1.0),
                                     warm_start=getattr(self._conf, 'cem_warm_start', None) or 'zero',
                                     record_rollouts=self._record_rollouts, n_perf=self._cem_n_perf,
-                                    perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}))
+                                    perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}),
+                                    **({'perf_type': 'taylor', 'perf_terminal_safety': self._cem_perf_terminal_safety}
+                                       if self._cem_perf_type == 'taylor' else {}))
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
         self._env_key = key
         return self._mpc
@@ -490,8 +508,10 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
 
     Over models of one family -- exact RBF GPs, feature-space GPs or MC-dropout ensembles -- that is ONE solve for all of
     them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model; solvers that all
-    have a performance trajectory with one ``cem_n_perf``, ``cem_perf_r`` and ``cem_perf_variance`` go through
-    ``MultiModelPerfCemMpc``, which adds one performance-rollout launch per iteration for all of them); otherwise (mixed
+    have a performance trajectory with one ``cem_n_perf``, ``cem_perf_r``, ``cem_perf_variance``, ``cem_perf_type`` and
+    ``cem_perf_terminal_safety`` go through ``MultiModelPerfCemMpc``, which adds one performance-rollout launch per
+    iteration for all of them -- or, with ``cem_perf_type='taylor'``, which has no multi-model launch, solves them one
+    model at a time); otherwise (mixed
     families, JunkDimensionsSSM, ...), and where the single launch does not apply, one solve per solver.  Either way
     problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
     ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
@@ -501,16 +521,17 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     if not solvers:
         raise ValueError('get_actions_multi needs at least one solver')
     # the performance trajectory (cem_n_perf > 0): all solvers or none, with one (cem_n_perf, cem_perf_r, cem_perf_variance)
-    perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False))
+    perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False),
+             getattr(s, '_cem_perf_type', 'mean_equivalent'), getattr(s, '_cem_perf_terminal_safety', False))
             for s in solvers]
-    with_perf = any(n > 0 for n, _, _ in perf)
-    if with_perf and not all(n > 0 for n, _, _ in perf):
+    with_perf = any(p[0] > 0 for p in perf)
+    if with_perf and not all(p[0] > 0 for p in perf):
         raise NotImplementedError('get_actions_multi takes solvers that all have a performance trajectory or all have none: '
-                                  f'got cem_n_perf = {[n for n, _, _ in perf]}; the ones with cem_n_perf > 0 act one at a time '
+                                  f'got cem_n_perf = {[p[0] for p in perf]}; the ones with cem_n_perf > 0 act one at a time '
                                   f'(get_action), or together in a call of their own')
     if with_perf and len(set(perf)) != 1:
         raise ValueError('the solvers of get_actions_multi must share the performance trajectory\'s settings: got '
-                         f'(cem_n_perf, cem_perf_r, cem_perf_variance) = {perf}')
+                         f'(cem_n_perf, cem_perf_r, cem_perf_variance, cem_perf_type, cem_perf_terminal_safety) = {perf}')
     n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
     if states.ndim != 2 or states.shape != (len(solvers), n_s):
         raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')

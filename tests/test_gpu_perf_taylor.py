@@ -1,0 +1,323 @@
+"""GPU: the Taylor form of the CEM solver's performance trajectory -- sx_cem_perf_rollout_taylor against the numpy oracle
+(tests/perf_taylor_oracle.py, which assembles the block matrices the kernel multiplies out) and against the project's other
+kernels, its independence of the launch's grid, the terminal-safety coupling, its forms, FusedCemMpc.solve with
+perf_type='taylor' against a numpy CEM, and CemSafeMPC.get_action over an objective-less environment.
+
+The cases are those of tests/test_gpu_perf_var.py (its case() / inputs(): E = 2, H = 5, a non-zero feedback k_fb); shapes
+(2, 1), (4, 1), (2, 2); N = 7 (one row-block), 200 (all outputs in LDS) and 590 (output by output at every shape); P = 37 (three
+tiles, the last one partial); (n_perf, r) in {(2, 1), (8, 1), (8, 3)}; both objective modes, the drawn and the given-tail form.
+Tolerances: rows, means and the affine objective rtol 1e-10, atol 1e-12; perf_sigma (diag G), perf_cov and the variance
+objective SIGMA_TOL of test_gpu_perf_var.py (rtol 1e-8, atol 1e-11, the project's tolerance for variances along a chained
+rollout); the con_cost increment exactly.  Every case prints its worst error as a fraction of the tolerance before it asserts.
+
+Measured figures: see the docstring of test_kernel_matches_the_oracle."""
+import ctypes
+import dataclasses
+from unittest import mock
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import cem as ocem
+from perf_taylor_oracle import cem_solve_perf_taylor, perf_taylor_rollout
+from safe_exploration_amd import _lib, cem_mpc, problems
+from test_gpu_perf_var import (ABS, DEV, H, MODES, SIGMA_TOL, SOLVE, VAR, N_, T, case, close, decided, inputs, pendulum,
+                               worst)
+
+pytestmark = pytest.mark.gpu
+SMALL, LARGE = 37, 4096 + 53
+SHAPES = [(2, 1), (4, 1), (2, 2)]
+SIZES = [7, 200, 590]
+HORIZONS = [(2, 1), (8, 1), (8, 3)]      # (n_perf, r)
+LARGE_CASES = [(2, 1, 200, 8, 3), (4, 1, 590, 8, 1), (2, 2, 7, 2, 1)]
+MEAN_TOL = dict(rtol=1e-10, atol=1e-12)
+OUTPUTS = ('rows', 'perf_traj', 'perf_sigma', 'perf_cov', 'obj_cost', 'con_cost')
+
+
+def launch(ssm, env, inp, n_perf, r, rows=None, terminal_safety=False):
+    """The drawn form, or with `rows` the given-tail form.  obj_cost starts as NaN (it is overwritten), con_cost as con0
+    (it is added to)."""
+    E, P = inp['safe'].shape[:2]
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    obj = torch.full((E, P), float('nan'), dtype=torch.float64, device=DEV)
+    kw = (dict(tail_mean=T(inp['mean']), tail_std=T(inp['std']), tail_noise=T(inp['noise'])) if rows is None
+          else dict(rows=rows))
+    out = cem_mpc.cem_perf_rollout_taylor(ssm, env, T(inp['x0']), H, n_perf, r, safe_actions=T(inp['safe']), obj_cost=obj,
+                                          con_cost=T(inp['con0']), status=status, want_traj=True, want_sigma=True,
+                                          want_cov=True, terminal_safety=terminal_safety, **kw)
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0
+    return out
+
+
+def launch_var(ssm, env, inp, n_perf, r):
+    E, P = inp['safe'].shape[:2]
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    obj = torch.full((E, P), float('nan'), dtype=torch.float64, device=DEV)
+    out = cem_mpc.cem_perf_rollout_var(ssm, env, T(inp['x0']), H, n_perf, r, safe_actions=T(inp['safe']), obj_cost=obj,
+                                       con_cost=T(inp['con0']), status=status, want_traj=True, want_sigma=True,
+                                       tail_mean=T(inp['mean']), tail_std=T(inp['std']), tail_noise=T(inp['noise']))
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0
+    return out
+
+
+def tails(inp):
+    return [inp['mean'][e][None] + inp['std'][e][None] * inp['noise'][e] for e in range(2)]
+
+
+def oracle_objective(prob, ref):
+    return sum(ocem.objective_cost(prob, ref.traj[:, t], ref.sigma[:, t]) for t in range(ref.traj.shape[1]))
+
+
+@pytest.mark.parametrize('n_perf,r', HORIZONS)
+@pytest.mark.parametrize('N', SIZES)
+@pytest.mark.parametrize('n_s,n_u', SHAPES)
+def test_kernel_matches_the_oracle(n_s, n_u, N, n_perf, r):
+    """Measured on an MI355X over the 27 cases (worst case, as a fraction of the tolerance): see DESIGN.md section 3.9,
+    "Taylor form"."""
+    ssm, envs, spec, gp, probs = case(n_s, n_u, N)
+    inp = inputs(n_s, n_u, SMALL, n_perf, r, seed=n_s + 7 * n_u + N + SMALL + 100 * n_perf + r)
+    refs = [perf_taylor_rollout(probs[VAR], gp, inp['x0'][e], inp['safe'][e], tail, r) for e, tail in enumerate(tails(inp))]
+    assert sum(int(ref.violations.sum()) for ref in refs) > 0, 'no tail action leaves the box'
+    if n_perf > 2:
+        # the propagated part is there to be checked: it is not lost below the tolerance of diag G
+        assert max(float((ref.sigma - ref.var).max()) for ref in refs) > 100 * SIGMA_TOL['atol']
+    outs = {}
+    for mode_name, mode in MODES.items():
+        drawn = launch(ssm, envs[mode], inp, n_perf, r)
+        given_rows = drawn['rows'].clone()
+        given_rows[:, :, :H] = float('nan')                  # the safety part of the rows is an output in both forms
+        given = launch(ssm, envs[mode], inp, n_perf, r, rows=given_rows)
+        for e, ref in enumerate(refs):
+            want_obj = oracle_objective(probs[mode], ref)
+            obj_tol = SIGMA_TOL if mode == VAR else MEAN_TOL
+            for name, out in (('drawn', drawn), ('given', given)):
+                print(f'({n_s},{n_u}) N={N} n_perf={n_perf} r={r} e={e} {mode_name} {name}: of the tolerance: traj '
+                      f'{worst(out["perf_traj"][e], ref.traj, **MEAN_TOL):.3f}, diag G '
+                      f'{worst(out["perf_sigma"][e], ref.sigma, **SIGMA_TOL):.3f}, cov '
+                      f'{worst(out["perf_cov"][e], ref.cov, **SIGMA_TOL):.3f}, obj '
+                      f'{worst(out["obj_cost"][e], want_obj, **obj_tol):.3f}; largest propagated part of diag G '
+                      f'{float((ref.sigma - ref.var).max()):.3e}, smallest variance {ref.var.min():.3e}')
+                close(out['rows'][e], ref.rows)
+                close(out['perf_traj'][e], ref.traj)
+                close(out['perf_sigma'][e], ref.sigma, **SIGMA_TOL)
+                close(out['perf_cov'][e], ref.cov, **SIGMA_TOL)
+                close(out['obj_cost'][e], want_obj, **obj_tol)
+                close(out['con_cost'][e] - T(inp['con0'][e]), ref.con_cost, rtol=0, atol=0)
+            assert torch.equal(drawn['rows'][e, :, :H], T(inp['safe'][e]))           # the shared actions: bit-identical
+        for name in OUTPUTS[1:]:
+            assert torch.equal(drawn[name], given[name]), name                      # the two forms see the same tail bits
+        assert torch.equal(drawn['perf_cov'], drawn['perf_cov'].transpose(-1, -2))   # symmetric to the bit
+        outs[mode] = drawn
+    for name in OUTPUTS[:4] + ('con_cost',):
+        assert torch.equal(outs[VAR][name], outs[ABS][name]), name                  # the mode changes the objective only
+
+
+# ---- against the project's other kernels -----------------------------------------------------------------------------------
+@pytest.mark.parametrize('N', SIZES)
+@pytest.mark.parametrize('n_s,n_u', SHAPES)
+def test_against_the_variance_kernel_and_gp_predict(n_s, n_u, N):
+    ssm, envs, spec, gp, probs = case(n_s, n_u, N)
+    n_perf, r, E, P = 8, 1, 2, SMALL
+    inp = inputs(n_s, n_u, SMALL, n_perf, r, seed=11 + n_s + N)
+    tay, var = launch(ssm, envs[VAR], inp, n_perf, r), launch_var(ssm, envs[VAR], inp, n_perf, r)
+    # the mean recursion is the variance kernel's fma chain; Sigma_0 = 0 leaves the GP's own variance at step 0
+    assert torch.equal(tay['rows'], var['rows']) and torch.equal(tay['perf_traj'], var['perf_traj'])
+    assert torch.equal(tay['con_cost'], var['con_cost'])
+    assert torch.equal(tay['perf_sigma'][:, :, 0], var['perf_sigma'][:, :, 0])
+    assert torch.equal(tay['perf_cov'][:, :, 0], torch.diag_embed(var['perf_sigma'][:, :, 0]))
+    # without feedback: M = J_x, H = a + J_x from sx_gp_predict at the recorded [mu_t, v_t]
+    env0 = _lib.SxEnv.from_buffer_copy(envs[VAR])
+    for i in range(len(env0.k_fb)):
+        env0.k_fb[i] = 0.0
+    out = launch(ssm, env0, inp, n_perf, r)
+    assert torch.equal(out['perf_traj'], tay['perf_traj'])
+    mu = torch.cat([T(inp['x0'])[:, None, None, :].expand(E, P, 1, n_s), out['perf_traj'][:, :, :-1]], dim=2)
+    v = torch.cat([out['rows'][:, :, :r], out['rows'][:, :, H:]], dim=2)
+    _, var_p, jac_p = ssm.predict_with_jacobians(mu.reshape(-1, n_s).contiguous(), v.reshape(-1, n_u).contiguous())
+    torch.cuda.synchronize()
+    var_p, jx = var_p.view(E, P, n_perf, n_s), jac_p.view(E, P, n_perf, n_s, n_s + n_u)[..., :n_s]
+    sigma = torch.zeros((E, P, n_s, n_s), dtype=torch.float64, device=DEV)
+    a = T(spec.a)
+    for t in range(n_perf):
+        m, h = jx[:, :, t], a + jx[:, :, t]
+        g = var_p[:, :, t] + torch.diagonal(m @ sigma @ m.transpose(-1, -2), dim1=-2, dim2=-1)
+        sigma = h @ sigma @ h.transpose(-1, -2) + torch.diag_embed(var_p[:, :, t])
+        print(f'({n_s},{n_u}) N={N} t={t}: of the tolerance: diag G {worst(out["perf_sigma"][:, :, t], g, **SIGMA_TOL):.3f}, '
+              f'cov {worst(out["perf_cov"][:, :, t], sigma, **SIGMA_TOL):.3f}')
+        close(out['perf_sigma'][:, :, t], g, **SIGMA_TOL)
+        close(out['perf_cov'][:, :, t], sigma, **SIGMA_TOL)
+
+
+# ---- the grid ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n_s,n_u,N,n_perf,r', LARGE_CASES)
+def test_a_tile_does_not_depend_on_the_grid(n_s, n_u, N, n_perf, r):
+    """P = 4096 + 53 per problem; the first 37 particles of each problem in a launch of their own are bit-identical."""
+    ssm, envs = case(n_s, n_u, N)[:2]
+    inp = inputs(n_s, n_u, LARGE, n_perf, r, seed=n_s + N)
+    sub = {k: (v if k in ('x0', 'mean', 'std') else np.ascontiguousarray(v[:, :SMALL])) for k, v in inp.items()}
+    for mode in MODES.values():
+        big, small = launch(ssm, envs[mode], inp, n_perf, r), launch(ssm, envs[mode], sub, n_perf, r)
+        for name in OUTPUTS:
+            assert torch.equal(small[name], big[name][:, :SMALL]), name
+
+
+# ---- the terminal-safety coupling ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n_s,n_u,N', [(2, 1, 200), (2, 1, 590), (4, 1, 7)])
+def test_terminal_safety(n_s, n_u, N):
+    """The polytope's offset comes from the oracle: every particle's largest row distance with h_vec = 0, sorted, and a
+    common h_vec in the widest gap between neighbours inside the middle half -- between 1/4 and 3/4 of the particles
+    violate and none sits within half that gap of zero."""
+    ssm, envs, spec, gp, probs = case(n_s, n_u, N)
+    n_perf, r = H + 3, 1
+    inp = inputs(n_s, n_u, SMALL, n_perf, r, seed=23 + n_s + N)
+    m = spec.h_mat.shape[0]
+    zero = dataclasses.replace(probs[VAR], h_vec=np.zeros((m, 1)))
+    d_max = np.concatenate([perf_taylor_rollout(zero, gp, inp['x0'][e], inp['safe'][e], tail, r).distances.max(axis=1)
+                            for e, tail in enumerate(tails(inp))])
+    order = np.sort(d_max)
+    lo, hi = len(order) // 4, 3 * len(order) // 4
+    i = lo + int(np.argmax(np.diff(order[lo:hi + 1])))
+    gap, offset = order[i + 1] - order[i], 0.5 * (order[i] + order[i + 1])
+    print(f'({n_s},{n_u}) N={N}: offset {offset:.6e}, gap {gap:.3e}, {int((d_max >= offset).sum())} of {len(d_max)} violate')
+    assert gap > 1e-6
+    prob = dataclasses.replace(probs[VAR], h_vec=np.full((m, 1), offset))
+    env = _lib.SxEnv.from_buffer_copy(envs[VAR])
+    for j in range(m):
+        env.h_vec[j] = offset
+    refs = [perf_taylor_rollout(prob, gp, inp['x0'][e], inp['safe'][e], tail, r, terminal_safety=True)
+            for e, tail in enumerate(tails(inp))]
+    unsafe = sum(int(ref.unsafe.sum()) for ref in refs)
+    assert len(d_max) // 4 <= unsafe <= 3 * len(d_max) // 4 + 1
+    assert min(float(np.abs(ref.distances.max(axis=1)).min()) for ref in refs) >= 0.5 * gap * (1 - 1e-9)
+    on, off = launch(ssm, env, inp, n_perf, r, terminal_safety=True), launch(ssm, env, inp, n_perf, r)
+    for e, ref in enumerate(refs):
+        close(on['con_cost'][e] - T(inp['con0'][e]), ref.con_cost, rtol=0, atol=0)
+        close(off['con_cost'][e] - T(inp['con0'][e]), ocem.ACTION_VIOLATION_COST * ref.violations, rtol=0, atol=0)
+    for name in OUTPUTS[:5]:
+        assert torch.equal(on[name], off[name]), name
+    # n_perf = H + 1 with the flag: SX_ERR_ARG from the entry, ValueError from the wrapper
+    short = inputs(n_s, n_u, SMALL, H + 1, r, seed=1)
+    with pytest.raises(ValueError, match='n_perf'):
+        launch(ssm, env, short, H + 1, r, terminal_safety=True)
+    E, P, Tl = 2, SMALL, H + 1 - r
+    bufs = [T(short['x0']), T(short['safe']), T(short['mean']), T(short['std']), T(short['noise']),
+            torch.empty((E, P, H + Tl, n_u), dtype=torch.float64, device=DEV),
+            torch.empty((E, P), dtype=torch.float64, device=DEV), T(short['con0'])]
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    code = _lib.lib().sx_cem_perf_rollout_taylor(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, H, H + 1, r,
+                                                 *[_lib.ptr(b) for b in bufs], None, None, None, 1, _lib.ptr(status),
+                                                 _lib.stream_ptr(torch.device(DEV)))
+    assert code == _lib.SX_ERR_ARG
+
+
+# ---- the forms --------------------------------------------------------------------------------------------------------------
+def test_the_forms_the_training_sets_take():
+    """N = 200 runs with all outputs in LDS and 590 output by output; beyond n_pad = 1024 there is no form, and the form
+    query says of every model what the launch does."""
+    form = lambda ssm, n_perf=8: int(_lib.lib().sx_cem_perf_rollout_taylor_form(ctypes.byref(ssm.device_model), n_perf))
+    SX_FORM_STREAM, SX_FORM_BYOUT = 0, 3
+    for n_s, n_u in SHAPES:
+        assert form(case(n_s, n_u, 590)[0]) == SX_FORM_BYOUT
+        assert form(case(n_s, n_u, 200)[0]) == SX_FORM_STREAM
+        assert form(case(n_s, n_u, 7)[0]) == SX_FORM_STREAM
+    ssm, envs = case(2, 1, 1100)[:2]
+    assert form(ssm, 2) < 0
+    inp = inputs(2, 1, SMALL, 2, 1, seed=1)
+    with pytest.raises(_lib.SxError, match='no form'):
+        launch(ssm, envs[VAR], inp, 2, 1)
+
+
+# ---- the whole solve -------------------------------------------------------------------------------------------------------
+def test_solve_with_the_taylor_form_matches_the_numpy_cem():
+    """As test_solve_with_the_variance_objective_matches_the_numpy_cem: the conditions under which the comparison means
+    something are asserted on the ORACLE's values before the GPU is touched; every iteration's costs are compared, the
+    elite sets wherever the oracle's ranking is decided by more than GAP, and the best row."""
+    from safe_exploration_amd.cem_mpc import FusedCemMpc
+    c = SOLVE
+    spec, gp = pendulum()
+    prob = problems.oracle_problem(spec, ocem)
+    assert prob.obj_mode == ocem.OBJ_NEG_VARIANCE
+    steps = c['H'] + c['n_perf'] - c['r']
+    noise = np.random.default_rng(c['seed']).normal(size=(c['iters'], c['P'], steps, 1))
+    x0 = np.array([0.02, -0.03])
+    ref_best, trace = cem_solve_perf_taylor(prob, gp, x0, noise, c['k'], c['H'], c['n_perf'], c['r'], c['init_std'])
+    assert ref_best is not None, 'the oracle\'s last iteration does not end feasible'
+    for it, (con, obj, idx, var_min) in enumerate(trace):
+        order = ocem.rank(con, obj, c['k'] + 1)
+        assert var_min > 0
+        assert decided(con, obj, order[-2], order[-1]), f'iteration {it}: the elite set hangs on the tolerance'
+    con, obj, idx, _ = trace[-1]
+    order = ocem.rank(con, obj, 2)
+    assert decided(con, obj, order[0], order[1]), 'the best row hangs on the tolerance: choose another seed'
+    ssm, env = problems.build(spec, device=DEV)
+    mpc = FusedCemMpc(ssm, env, c['H'], c['P'], c['k'], c['iters'], device=DEV, init_std=c['init_std'],
+                      n_perf=c['n_perf'], perf_r=c['r'], perf_type='taylor', record_rollouts=True)
+    best, ok, history, status = mpc.solve(T(x0[None]), noise=T(noise[:, None]))
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0 and bool(ok[0].item()) and len(history) == c['iters']
+    for it, (h, (con, obj, idx, _)) in enumerate(zip(history, trace)):
+        print(f'iteration {it}: objective {worst(h.objective_costs, obj, **SIGMA_TOL):.3f} of the tolerance')
+        close(h.constraint_costs, con, rtol=0, atol=0)
+        close(h.objective_costs, obj, **SIGMA_TOL)
+        assert tuple(h.perf_cov.shape) == (c['P'], c['n_perf'], 2, 2)
+        close(h.objective_costs, -h.perf_sigma.sum(dim=(1, 2)), **SIGMA_TOL)
+        assert set(ocem.rank(N_(h.constraint_costs), N_(h.objective_costs), c['k'])) == set(idx)
+    print(f'best row: max |device - numpy CEM| = {float(np.abs(N_(best[0]) - ref_best).max()):.3e}')
+    close(best[0], ref_best, rtol=0, atol=1e-9)
+
+
+def test_without_the_settings_no_taylor_entry_is_called(monkeypatch):
+    """A solve without perf_type, and with perf_type='mean_equivalent', never reaches the Taylor wrapper, and the two give
+    bit-identical best rows."""
+    from safe_exploration_amd.cem_mpc import FusedCemMpc
+    spy = mock.Mock(side_effect=AssertionError('sx_cem_perf_rollout_taylor reached without the setting'))
+    monkeypatch.setattr(cem_mpc, 'cem_perf_rollout_taylor', spy)
+    spec = problems.pendulum(n_train=200, seed=0, obj_mode=ABS)
+    ssm, env = problems.build(spec, device=DEV)
+    P, k, iters = 512, 50, 4
+    x0 = T(np.array([[0.02, -0.03]]))
+    for kw, steps in ((dict(), H), (dict(n_perf=15, perf_r=1), H + 14), (dict(n_perf=15, perf_r=1, perf_variance=True), H + 14)):
+        noise = T(np.random.default_rng(1).normal(size=(iters, 1, P, steps, 1)))
+        a = FusedCemMpc(ssm, env, H, P, k, iters, device=DEV, init_std=0.2, **kw).solve(x0, noise=noise)
+        b = FusedCemMpc(ssm, env, H, P, k, iters, device=DEV, init_std=0.2, perf_type='mean_equivalent',
+                        perf_terminal_safety=False, **kw).solve(x0, noise=noise)
+        torch.cuda.synchronize()
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and tuple(a[0].shape) == (1, steps, 1)
+    assert spy.call_count == 0
+
+
+class Conf:
+    mpc_time_horizon = 5
+    cem_num_rollouts = 512
+    cem_num_elites = 50
+    cem_num_iterations = 4
+    cem_init_std = 0.2
+    cem_n_perf = 10
+    cem_perf_type = 'taylor'
+    cem_perf_terminal_safety = True
+    plot_cem_optimisation = False
+    plot_cem_terminal_states = False
+    device = DEV
+    use_state_constraint = True
+    use_prior_model = True
+    exact_gp_training_iterations = 0
+    exact_gp_kernel = 'rbf'
+
+
+def test_get_action_over_an_exploration_environment():
+    from safe_exploration_amd.safempc_cem import MpcResult
+    spec = problems.pendulum(n_train=200, seed=0)
+    env = problems.StubEnv(spec, np.zeros(2))                       # no objective: the solver explores
+    assert env.objective_cost_function(torch.zeros((1, 2), dtype=torch.float64)) is None
+    solver, _ = problems.make_solver(spec, Conf(), env, device=DEV)
+    assert solver.performance_trajectory_length == 10
+    action, result = solver.get_action(np.array([0.02, -0.03]))
+    assert action.shape == (1,) and result == MpcResult.FOUND_SOLUTION
+    mpc = solver._solver()
+    assert mpc._perf_type == 'taylor' and mpc._perf_terminal_safety and not mpc._perf_variance
+    assert mpc._env.obj_mode == VAR and mpc._objective_hook is None
+    assert tuple(mpc.last_perf_actions.shape) == (1, 10 - 1, 1) and mpc.last_status == 0
+    assert bool((np.abs(solver._last_mpc_actions) <= 1.0).all())    # feasible: inside the action box

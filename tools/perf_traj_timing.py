@@ -1,8 +1,8 @@
 """Solve time with and without the performance trajectory, on this build: config 2 (pendulum, N = 200, 4096 particles,
 H = 15, 8 CEM iterations, 409 elites).
 
-    python tools/perf_traj_timing.py [--n-perf 15,30,45] [--solves 200] [--warmup 20] [--off-only] [--variance] [--label L]
-                                     [--out F]
+    python tools/perf_traj_timing.py [--n-perf 15,30,45] [--solves 200] [--warmup 20] [--off-only] [--variance] [--taylor]
+                                     [--label L] [--out F]
 
 Rows (one JSON line each: median and p95 in ms of synchronous solves -- FusedCemMpc.solve + device synchronise on the host
 clock -- `--solves` times after `--warmup` untimed ones; printed and, with `--out`, appended to that jsonl file):
@@ -16,6 +16,9 @@ clock -- `--solves` times after `--warmup` untimed ones; printed and, with `--ou
 `--variance` adds, for every K: `n_perf=K var_affine` (perf_variance=True with the same objective: the cost of the variance
 kernel alone), `n_perf=K var` (perf_variance=True over config 2's own variance objective; `extra_ms` against off_cfg2) and
 `launch_perf_var_K` (sx_cem_perf_rollout_var alone).
+`--taylor` adds, for every K: `n_perf=K taylor` (perf_type='taylor' over config 2's variance objective; `extra_ms` against
+off_cfg2), `launch_perf_taylor_K` (sx_cem_perf_rollout_taylor alone) and, on a cart-pole model of the same N (shape (4, 1),
+where the owner lanes' tail is 8 x the FMAs), `launch_perf_var_ns4_K` / `launch_perf_taylor_ns4_K`.
 `--off-only` stops after off_H30 and uses nothing the parent commit lacks: run the same file from a checkout of the parent for
 the same-session comparison (`--label` names the build in the rows).  Needs the GPU.
 """
@@ -67,6 +70,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--off-only', action='store_true')
     ap.add_argument('--variance', action='store_true')
+    ap.add_argument('--taylor', action='store_true')
     ap.add_argument('--label', default='this')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -109,6 +113,11 @@ def main():
                 med, p95 = time_solves(solver(ssm, e, H, n_perf=k, perf_r=1, perf_variance=True), x0, args.warmup, args.solves)
                 row(row=f'n_perf={k} {name}', H=H, n_perf=k, r=1, median_ms=med, p95_ms=p95, extra_ms=med - base,
                     extra_per_iteration_us=(med - base) * 1e3 / wl.iterations)
+        if args.taylor:
+            med, p95 = time_solves(solver(ssm, env_var, H, n_perf=k, perf_r=1, perf_type='taylor'), x0, args.warmup,
+                                   args.solves)
+            row(row=f'n_perf={k} taylor', H=H, n_perf=k, r=1, median_ms=med, p95_ms=p95, extra_ms=med - off_cfg2,
+                extra_per_iteration_us=(med - off_cfg2) * 1e3 / wl.iterations)
     # the launches alone
     gen = torch.Generator(device=DEV)
     gen.manual_seed(0)
@@ -132,6 +141,28 @@ def main():
                 lambda: cem_mpc.cem_perf_rollout_var(ssm, env_var, x0, H, k, 1, safe_actions=safety['actions'],
                                                      obj_cost=safety['obj_cost'], con_cost=safety['con_cost'], status=status,
                                                      tail_mean=t_mean, tail_std=t_std, tail_noise=t_noise)))
+        if args.taylor:
+            row(row=f'launch_perf_taylor_{k}', H=H, n_perf=k, r=1, us=time_launches(
+                lambda: cem_mpc.cem_perf_rollout_taylor(ssm, env_var, x0, H, k, 1, safe_actions=safety['actions'],
+                                                        obj_cost=safety['obj_cost'], con_cost=safety['con_cost'],
+                                                        status=status, tail_mean=t_mean, tail_std=t_std, tail_noise=t_noise)))
+    if args.taylor:
+        # shape (4, 1): the same N and particles over a cart-pole model, the two launches alone
+        spec4 = problems.cartpole(n_train=wl.spec.X.shape[0])
+        ssm4, env4 = problems.build(spec4, device=DEV)
+        env4 = _lib.SxEnv.from_buffer_copy(env4)
+        env4.obj_mode = _lib.SX_OBJ_NEG_VARIANCE
+        x4 = torch.zeros((1, 4), dtype=torch.float64, device=DEV)
+        safe4 = dict(actions=0.1 * rnd(1, P, H, 1), obj_cost=torch.zeros((1, P), dtype=torch.float64, device=DEV),
+                     con_cost=torch.zeros((1, P), dtype=torch.float64, device=DEV))
+        for k in ks:
+            t_mean = torch.zeros((1, k - 1, 1), dtype=torch.float64, device=DEV)
+            t_std, t_noise = torch.full_like(t_mean, 0.1), rnd(1, P, k - 1, 1)
+            for name, fn in (('var', cem_mpc.cem_perf_rollout_var), ('taylor', cem_mpc.cem_perf_rollout_taylor)):
+                row(row=f'launch_perf_{name}_ns4_{k}', H=H, n_perf=k, r=1, us=time_launches(
+                    lambda: fn(ssm4, env4, x4, H, k, 1, safe_actions=safe4['actions'], obj_cost=safe4['obj_cost'],
+                               con_cost=safe4['con_cost'], status=status, tail_mean=t_mean, tail_std=t_std,
+                               tail_noise=t_noise)))
 
 
 if __name__ == '__main__':
