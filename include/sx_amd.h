@@ -603,6 +603,28 @@ int sx_cem_perf_rollout_taylor(const sx_gp_model* model, const sx_env* env, int 
  * sx_cem_perf_rollout_var_form, decided by the same rule over the variance kernel's LDS plus the step constants
  * (uncertainty_propagation_casadi.py:11-149 and safempc_simple.py:471-479 have no such notion). */
 int sx_cem_perf_rollout_taylor_form(const sx_gp_model* model, int n_perf);
+/* sx_cem_perf_rollout_taylor over E problems with a GP each.  Arguments as sx_cem_perf_rollout_taylor except
+ *   models  host array of the E PACKED models
+ *   table   dev, the table sx_gp_model_table built from them (the one sx_cem_rollout_multi reads)
+ *   status  dev int32 [E]   one word per problem
+ * There is one env: k_fb, the polytope and the terminal-safety step H + 2 are the same for all problems.  Output by output
+ * for every problem where any model needs it, with the LDS of the largest model plus the step constants
+ * (sx_cem_perf_rollout_taylor_multi_form); where that form is model e's own (sx_cem_perf_rollout_taylor_form) problem e's
+ * numbers are those of sx_cem_perf_rollout_taylor on model e alone, bit for bit.
+ * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout_taylor, for every model, and for shapes that differ between
+ * the models or from env; SX_ERR_UNSUPPORTED (before any launch) for m > SX_MAX_M, where any model has no form or the
+ * shape no kernel.  Replaces: nothing in the reference's CEM solver; its n_scenarios casadi solvers with
+ * type_perf_traj = 'taylor' run one after another (episode_runner.py:40-123, safempc_simple.py:398-490). */
+int sx_cem_perf_rollout_taylor_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                     int n_perf, int r, const double* x0, const double* safe_actions,
+                                     const double* tail_mean, const double* tail_std, const double* tail_noise,
+                                     double* rows, double* obj_cost, double* con_cost, double* perf_traj,
+                                     double* perf_sigma, double* perf_cov, int terminal_safety, int32_t* status,
+                                     void* stream);
+/* The form sx_cem_perf_rollout_taylor_multi launches for these models and n_perf (no launch, no device access): the
+ * contract of sx_cem_perf_rollout_var_multi_form (< 0 also for unpacked models), by the rule of
+ * sx_cem_perf_rollout_taylor_form. */
+int sx_cem_perf_rollout_taylor_multi_form(const sx_gp_model* models, int E, int n_perf);
 
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]

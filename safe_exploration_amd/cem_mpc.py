@@ -248,10 +248,10 @@ def _require_rbf(ssms: Sequence, x0: Tensor) -> None:
 def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: int, n_perf: int, r: int, *, safe_actions,
                   obj_cost, con_cost, status, tail_mean, tail_std, tail_noise, rows, want_traj, want_sigma=None,
                   unsupported=None, want_cov=None, terminal_safety=False):
-    """What `cem_perf_rollout`, `cem_perf_rollout_var`, `cem_perf_rollout_taylor` and `cem_perf_rollout_multi` share
+    """What `cem_perf_rollout`, `cem_perf_rollout_var`, `cem_perf_rollout_taylor` and their multi-model forms share
     (after `_require_rbf`): the buffers and the launch of `entry`(*head, E, P, H, n_perf, r, x0, safe_actions, tail_mean,
     tail_std, tail_noise, rows, obj_cost, con_cost, perf_traj[, perf_sigma[, perf_cov, terminal_safety]], status, stream).
-    `want_sigma` is None for the mean-only entries (no perf_sigma argument), `want_cov` is None for all but the Taylor entry
+    `want_sigma` is None for the mean-only entries (no perf_sigma argument), `want_cov` is None for all but the Taylor entries
     (no perf_cov / terminal_safety arguments); `unsupported(n_s, n_u)`: what SX_ERR_UNSUPPORTED raises, where the entry has
     a message of its own."""
     dev, n_s, n_u = x0.device, ssms[0].num_states, ssms[0].num_actions
@@ -416,6 +416,43 @@ def cem_perf_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor
                          con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std, tail_noise=tail_noise,
                          rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma) if variance else None,
                          unsupported=unsupported)
+
+
+def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int,
+                                  *, safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
+                                  tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
+                                  tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                                  want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
+                                  terminal_safety: bool = False, table=None):
+    """`cem_perf_rollout_taylor` for E problems with an exact GP each (ssms[e] for problem e) in one launch
+    (sx_cem_perf_rollout_taylor_multi).  There is one `env`: the feedback gain, the safe polytope and the terminal-safety
+    step are the same for all problems.  Buffers as in the single-model wrapper, per problem; `status` is int32 [E], one
+    word per problem.  `table` keeps the device table between calls: the `GpModelTable` of `cem_rollout_multi` (a fresh
+    one is built otherwise).  Raises FusedMultiUnsupported where the library has no single launch for the models (before
+    any launch)."""
+    _require_rbf(ssms, x0)
+    E = x0.size(0)
+    if len(ssms) != E:
+        raise ValueError(f'{len(ssms)} models for {E} problems')
+    if status is not None and status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    if terminal_safety and n_perf < horizon + 2:
+        raise ValueError(f'terminal_safety checks the performance state {horizon + 2}: n_perf = {n_perf} is too short '
+                         f'(n_perf >= horizon + 2)')
+    entry = 'sx_cem_perf_rollout_taylor_multi'
+    if not isinstance(table, GpModelTable) or getattr(table, 'family', 'rbf') != 'rbf':
+        table = GpModelTable()
+    models, dev_table = table.get(ssms, x0.device)
+
+    def unsupported(n_s, n_u):
+        return FusedMultiUnsupported(f"{entry}: no single launch of the 'taylor' performance rollout for these models "
+                                     f'((n_s, n_u) = ({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, '
+                                     f'n_perf = {n_perf})')
+    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r,
+                         safe_actions=safe_actions, obj_cost=obj_cost, con_cost=con_cost, status=status,
+                         tail_mean=tail_mean, tail_std=tail_std, tail_noise=tail_noise, rows=rows, want_traj=want_traj,
+                         want_sigma=bool(want_sigma), unsupported=unsupported, want_cov=bool(want_cov),
+                         terminal_safety=terminal_safety)
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
@@ -1257,21 +1294,23 @@ class MultiModelCemMpc:
 
 class MultiModelPerfCemMpc(MultiModelCemMpc):
     """``MultiModelCemMpc`` over solvers with a performance trajectory (``FusedCemMpc(n_perf > 0)``, DESIGN.md section
-    3.9): E exact RBF GPs whose solvers share ``n_perf``, ``perf_r`` and ``perf_variance``.  An iteration is
-    ``sx_cem_rollout_multi`` over the first H steps of the rows, ONE performance-rollout launch for all problems
-    (``sx_cem_perf_rollout_multi``, or ``sx_cem_perf_rollout_var_multi`` with ``perf_variance``) and the ranking over the
-    rows of H + T steps, T = n_perf - perf_r; the ranking launch refits (no prologue refit, as in ``FusedCemMpc.solve``
-    with a performance trajectory).  Problem e draws solvers[e]'s noise and start distribution, which have row length.
+    3.9): E exact RBF GPs whose solvers share ``n_perf``, ``perf_r``, ``perf_variance``, ``perf_type`` and
+    ``perf_terminal_safety``.  An iteration is ``sx_cem_rollout_multi`` over the first H steps of the rows, ONE
+    performance-rollout launch for all problems (``sx_cem_perf_rollout_multi``, ``sx_cem_perf_rollout_var_multi`` with
+    ``perf_variance``, or ``sx_cem_perf_rollout_taylor_multi`` with ``perf_type='taylor'``) and the ranking over the rows
+    of H + T steps, T = n_perf - perf_r; the ranking launch refits (no prologue refit, as in ``FusedCemMpc.solve`` with a
+    performance trajectory).  Problem e draws solvers[e]'s noise and start distribution, which have row length.
     ``get_actions_multi`` returns the H safety actions and leaves the tail in every solver's ``last_perf_actions``.
-    Where either launch has no form for the models the problems are solved one model at a time (``per_model_solves``);
-    so are solvers with ``perf_type='taylor'``, which has no multi-model launch (``fused_applies`` is False).
+    Where either launch has no form for the models (``fused_applies`` is False) the problems are solved one model at a
+    time (``per_model_solves``).
     """
     _perf_solvers = True
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, n_perf: Optional[int] = None, perf_r: int = 1, perf_variance: bool = False,
                  device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero', process_group=None,
-                 solvers: Optional[Sequence[FusedCemMpc]] = None):
+                 solvers: Optional[Sequence[FusedCemMpc]] = None, perf_type: str = 'mean_equivalent',
+                 perf_terminal_safety: bool = False):
         if process_group is not None:
             raise NotImplementedError('the performance trajectory is not built for sharded particles (a process group)')
         if solvers is None:
@@ -1280,7 +1319,8 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                                  'without one')
             solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
                                    seed=seed + e, init_std=init_std, warm_start=warm_start, n_perf=n_perf, perf_r=perf_r,
-                                   perf_variance=perf_variance) for e, ssm in enumerate(ssms)]
+                                   perf_variance=perf_variance, perf_type=perf_type,
+                                   perf_terminal_safety=perf_terminal_safety) for e, ssm in enumerate(ssms)]
         solvers = list(solvers)
         settings = {(getattr(s, '_n_perf', 0), getattr(s, '_perf_r', 1), getattr(s, '_perf_variance', False))
                     for s in solvers}
@@ -1304,8 +1344,11 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
             raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
                                       f'{[getattr(s, "kernel_family", None) for s in self._ssms]}')
         self._tail = self._n_perf - self._perf_r
-        self._taylor = any(getattr(s, '_perf_type', 'mean_equivalent') == 'taylor' for s in solvers)
-        self._perf_table = PerfModelTable() if not self._perf_variance else None
+        # (check_solvers compares the two between the solvers)
+        self._perf_type = getattr(solvers[0], '_perf_type', 'mean_equivalent')
+        self._perf_terminal_safety = bool(getattr(solvers[0], '_perf_terminal_safety', False))
+        self._taylor = self._perf_type == 'taylor'
+        self._perf_table = PerfModelTable() if not (self._perf_variance or self._taylor) else None
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         if objective_hook is not None:
@@ -1313,24 +1356,33 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         super().set_env(env)
 
     def fused_applies(self) -> bool:
-        """Does one launch of each kind serve the models?  The safety rollout as in `MultiModelCemMpc`, and the variance
-        form of the performance rollout where its form query answers (sx_cem_perf_rollout_var_multi_form).  The mean-only
-        form adds no condition: it stages (2 n_s + n_u) N doubles in LDS, which holds every training set the multi-model
-        safety rollout takes (n_pad <= 1024).  Host only."""
-        if not super().fused_applies() or self._taylor:
+        """Does one launch of each kind serve the models?  The safety rollout as in `MultiModelCemMpc`, and the Taylor or
+        the variance form of the performance rollout where its form query answers (sx_cem_perf_rollout_taylor_multi_form,
+        sx_cem_perf_rollout_var_multi_form).  The mean-only form adds no condition: it stages (2 n_s + n_u) N doubles in
+        LDS, which holds every training set the multi-model safety rollout takes (n_pad <= 1024).  Host only."""
+        if not super().fused_applies():
             return False
+        if self._taylor:
+            return self._taylor_form() >= 0
         if self._perf_variance:
             models = model_array(self._ssms, 'rbf')
             return int(_lib.lib().sx_cem_perf_rollout_var_multi_form(models, len(self._ssms), self._n_perf)) >= 0
         return True
+
+    def _taylor_form(self) -> int:
+        """sx_cem_perf_rollout_taylor_multi_form of the models: < 0 where they have no single launch.  Host only."""
+        models = model_array(self._ssms, 'rbf')
+        return int(_lib.lib().sx_cem_perf_rollout_taylor_multi_form(models, len(self._ssms), self._n_perf))
 
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """As `MultiModelCemMpc.solve` with rows of H + T steps: noise [iters x E x P x (H + T) x n_u], and the returned
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
         E, H, T = len(self._ssms), self._horizon, self._tail
         n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
-        if self._taylor:
-            raise FusedMultiUnsupported("perf_type='taylor' has no multi-model launch: the solvers act one model at a time")
+        if self._taylor and self._taylor_form() < 0:
+            raise FusedMultiUnsupported(f"perf_type='taylor' has no multi-model launch for these models (N = "
+                                        f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {self._n_perf}): '
+                                        f'the solvers act one model at a time')
         if x0.shape != (E, n_s):
             raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
         if noise is None:
@@ -1344,12 +1396,15 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         def rollout(it, mean, std, rows):
             r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean[:, :H].contiguous(), std=std[:, :H].contiguous(),
                                   noise=noise_safe[it], status=status, table=self._table)
-            pr = cem_perf_rollout_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r,
-                                        variance=self._perf_variance, safe_actions=r['actions'],
-                                        obj_cost=r['obj_cost'], con_cost=r['con_cost'], status=status,
-                                        tail_mean=mean[:, H:].contiguous(), tail_std=std[:, H:].contiguous(),
-                                        tail_noise=noise_tail[it],
-                                        table=self._table if self._perf_variance else self._perf_table)
+            kw = dict(safe_actions=r['actions'], obj_cost=r['obj_cost'], con_cost=r['con_cost'], status=status,
+                      tail_mean=mean[:, H:].contiguous(), tail_std=std[:, H:].contiguous(), tail_noise=noise_tail[it])
+            if self._taylor:
+                pr = cem_perf_rollout_taylor_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r, **kw,
+                                                   terminal_safety=self._perf_terminal_safety, table=self._table)
+            else:
+                pr = cem_perf_rollout_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r,
+                                            variance=self._perf_variance, **kw,
+                                            table=self._table if self._perf_variance else self._perf_table)
             return dict(actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
 
         def rank(it, r):

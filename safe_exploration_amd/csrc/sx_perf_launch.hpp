@@ -1,6 +1,7 @@
 // The form of a variance performance rollout (sx_cem_perf_rollout_var[_multi]), decided here only -- the entries launch
 // it, sx_cem_perf_rollout_var[_multi]_form report it -- and the launcher of the multi-model kernels, whose instantiations
-// are compiled in sx_perf_multi.hip.  Host code only.
+// are compiled in sx_perf_multi.hip (sx_perf_taylor_multi.hip for the Taylor form, which plans with the same two
+// functions plus the bytes of its step constants).  Host code only.
 #pragma once
 #include <algorithm>
 
@@ -32,19 +33,31 @@ inline PerfVarPlan plan_perf_var(int ns, int nu, int n_train, int n_pad, int n_p
 }
 
 // One launch for E problems with a GP each, as plan_rollout_multi: output by output for every problem where any model
-// needs it, the LDS of the largest model; a model without a form makes the whole launch unsupported.
-inline PerfVarPlan plan_perf_var_multi(const sx_gp_model* models, int E, int n_perf) {
+// needs it, the LDS of the largest model; a model without a form makes the whole launch unsupported.  `extra_bytes` as
+// in plan_perf_var.
+inline PerfVarPlan plan_perf_var_multi(const sx_gp_model* models, int E, int n_perf, size_t extra_bytes = 0) {
     PerfVarPlan out{SX_FORM_STREAM, true, 0};
     const int ns = models[0].n_s, nu = models[0].n_u;
     for (int i = 0; i < E; ++i) {
-        const PerfVarPlan p = plan_perf_var(ns, nu, models[i].n_train, models[i].n_pad, n_perf);
+        const PerfVarPlan p = plan_perf_var(ns, nu, models[i].n_train, models[i].n_pad, n_perf, extra_bytes);
         if (!p.ok) return {p.form, false, 0};
         if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
     }
     for (int i = 0; i < E; ++i)
         out.lds = std::max(out.lds, rollout_stream_lds_bytes(ns, nu, 0, models[i].n_train, models[i].n_pad, n_perf,
-                                                             out.form == SX_FORM_BYOUT));
+                                                             out.form == SX_FORM_BYOUT) +
+                                        extra_bytes);
     return out;
+}
+
+// bytes of the step constants (PerfTaylorConst, sx_perf_taylor.hpp) the Taylor kernels keep in LDS behind the tile's actions
+inline size_t perf_taylor_extra_bytes(int ns, int nu) {
+    return ((size_t)2 * ns * ns + 2 * ns * nu + 2 * nu + 3 * ns + (size_t)SX_MAX_M * ns + SX_MAX_M) * sizeof(double);
+}
+
+// The Taylor form of the multi-model launch (sx_cem_perf_rollout_taylor_multi): plan_perf_var_multi with the step constants.
+inline PerfVarPlan plan_perf_taylor_multi(const sx_gp_model* models, int E, int n_perf) {
+    return plan_perf_var_multi(models, E, n_perf, perf_taylor_extra_bytes(models[0].n_s, models[0].n_u));
 }
 
 // The packed model of sx_gp_pack: W fragments, the stage table, and the padding that holds the mean / Jacobian rows
@@ -58,5 +71,14 @@ inline bool perf_var_model_ok(const sx_gp_model& m) {
 template <int NS, int NU>
 int launch_perf_var_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
                           bool byout, size_t lds, hipStream_t stream);
+
+// Launches cem_perf_taylor_rollout_multi_kernel<NS, NU, byout> (compiled in sx_perf_taylor_multi.hip) likewise;
+// tp.v.p.status holds E words.
+template <int NS, int NU>
+struct PerfTaylorConst;
+struct PerfTaylorPtrs;
+template <int NS, int NU>
+int launch_perf_taylor_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorConst<NS, NU>& tc, const PerfTaylorPtrs& tp,
+                             bool byout, size_t lds, hipStream_t stream);
 
 }  // namespace sx

@@ -510,9 +510,8 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model; solvers that all
     have a performance trajectory with one ``cem_n_perf``, ``cem_perf_r``, ``cem_perf_variance``, ``cem_perf_type`` and
     ``cem_perf_terminal_safety`` go through ``MultiModelPerfCemMpc``, which adds one performance-rollout launch per
-    iteration for all of them -- or, with ``cem_perf_type='taylor'``, which has no multi-model launch, solves them one
-    model at a time); otherwise (mixed
-    families, JunkDimensionsSSM, ...), and where the single launch does not apply, one solve per solver.  Either way
+    iteration for all of them, ``cem_perf_type='taylor'`` included); otherwise (mixed families, JunkDimensionsSSM, ...),
+    and where the single launch does not apply, one solve per solver.  Either way
     problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
     ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
     the CEM settings; ValueError otherwise."""

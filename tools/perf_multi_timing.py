@@ -2,7 +2,7 @@
 multi-model solve, on this build.
 
     python tools/perf_multi_timing.py [--shape expl|cfg2] [--scenarios 6] [--solves 100] [--warmup 10] [--sequential-only]
-                                      [--label L] [--out F]
+                                      [--taylor] [--label L] [--out F]
 
 Shapes: `expl`, the reference's dynamic-exploration shape (20 particles, H = 2, n_perf = 5, 3 elites, 8 iterations, the
 variance objective on the performance trajectory), and `cfg2`, config 2 (4096 particles, H = 15, 409 elites, 8 iterations)
@@ -14,6 +14,14 @@ to that jsonl file):
   multi            one MultiModelPerfCemMpc.solve
   launch_perf_multi, launch_perf_var_multi   sx_cem_perf_rollout_multi / sx_cem_perf_rollout_var_multi alone: 200 launches
                    back to back between two synchronisations, per launch, in us
+`--taylor` measures the Taylor form (perf_type='taylor') in place of all of the above, with rows that mean the same on
+this build and on a checkout of the commit before the multi-model Taylor launch (copy this file there):
+  taylor_sequential          E FusedCemMpc(n_perf=..., perf_type='taylor').solve calls one after another
+  taylor_get_actions_multi   MultiModelPerfCemMpc.from_solvers(...).get_actions_multi over those solvers: one multi-model
+                             solve where the build has one, else one solve per model (`per_model_solves` says which); the
+                             call ends with its own device -> host hand-off
+  launch_perf_taylor_multi, launch_perf_var_multi[_ns4]   (builds with the launch only) the two launches alone at shape
+                             (2, 1), and over cart-pole models of the same sizes at (4, 1), as above
 `--sequential-only` stops after sequential_off and uses nothing the parent commit lacks: run the same file from a checkout of
 the parent for the same-box comparison, alternating with this build (`--label` names the build in the rows).  Needs the GPU.
 """
@@ -59,6 +67,41 @@ def time_launches(fn, n=200, warmup=20):
     return (time.perf_counter() - t0) * 1e6 / n
 
 
+def taylor_rows(args, row, ssms, env, x0, c, kw):
+    """The rows of `--taylor` (see the module's docstring)."""
+    E, P, H, n_perf, k, iters = len(ssms), c['P'], c['H'], c['n_perf'], c['k'], c['iters']
+    perf = dict(n_perf=n_perf, perf_r=1, perf_type='taylor')
+    solvers = [FusedCemMpc(ssm, env, H, P, k, iters, seed=e, **kw, **perf) for e, ssm in enumerate(ssms)]
+    med, p95 = timed(lambda: [s.solve(x0[e:e + 1]) for e, s in enumerate(solvers)], args.warmup, args.solves)
+    row(row='taylor_sequential', median_ms=med, p95_ms=p95)
+    multi = cem_mpc.MultiModelPerfCemMpc.from_solvers(solvers)
+    n_s = x0.size(1)
+    states = torch.cat([x0, torch.zeros((E, n_s * n_s), dtype=torch.float64, device=DEV)], dim=1)
+    med, p95 = timed(lambda: multi.get_actions_multi(states), args.warmup, args.solves)
+    row(row='taylor_get_actions_multi', median_ms=med, p95_ms=p95, fused=bool(multi.fused_applies()),
+        per_model_solves=multi.per_model_solves)
+    if not hasattr(cem_mpc, 'cem_perf_rollout_taylor_multi'):
+        return
+    # the launches alone: Taylor beside variance, at (2, 1) and over cart-pole models of the same sizes at (4, 1)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(0)
+    rnd = lambda *shape: torch.randn(shape, dtype=torch.float64, device=DEV, generator=gen)
+    full = lambda v, *shape: torch.full(shape, float(v), dtype=torch.float64, device=DEV)
+    status = torch.zeros(E, dtype=torch.int32, device=DEV)
+    built4 = [problems.build(problems.cartpole(n_train=int(s.device_model.n_train), seed=2 + e), device=DEV)
+              for e, s in enumerate(ssms)]
+    env4 = _lib.SxEnv.from_buffer_copy(built4[0][1])
+    env4.obj_mode = _lib.SX_OBJ_NEG_VARIANCE
+    for suffix, models, e_, x in (('', ssms, env, x0), ('_ns4', [b[0] for b in built4], env4, full(0, E, 4))):
+        bufs = dict(safe_actions=0.1 * rnd(E, P, H, 1), obj_cost=full(0, E, P), con_cost=full(0, E, P), status=status,
+                    tail_mean=full(0, E, n_perf - 1, 1), tail_std=full(0.1, E, n_perf - 1, 1),
+                    tail_noise=rnd(E, P, n_perf - 1, 1), table=cem_mpc.GpModelTable())
+        row(row='launch_perf_taylor_multi' + suffix, us=time_launches(
+            lambda: cem_mpc.cem_perf_rollout_taylor_multi(models, e_, x, H, n_perf, 1, **bufs)))
+        row(row='launch_perf_var_multi' + suffix, us=time_launches(
+            lambda: cem_mpc.cem_perf_rollout_multi(models, e_, x, H, n_perf, 1, variance=True, **bufs)))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--shape', default='expl', choices=sorted(SHAPES))
@@ -66,6 +109,7 @@ def main():
     ap.add_argument('--solves', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--sequential-only', action='store_true')
+    ap.add_argument('--taylor', action='store_true')
     ap.add_argument('--label', default='this')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -88,6 +132,8 @@ def main():
     ssms, env = [b[0] for b in built], built[0][1]
     x0 = torch.tensor(problems.start_states(2, E, seed=5, std=0.03), dtype=torch.float64, device=DEV)
     kw = dict(device=DEV, init_std=0.2)
+    if args.taylor:
+        return taylor_rows(args, row, ssms, env, x0, c, kw)
     perf = dict(n_perf=n_perf, perf_r=1, perf_variance=True)
     for name, extra in (('sequential', perf), ('sequential_off', {})):
         solvers = [FusedCemMpc(ssm, env, H, P, k, iters, seed=e, **kw, **extra) for e, ssm in enumerate(ssms)]
