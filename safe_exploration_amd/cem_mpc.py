@@ -299,6 +299,14 @@ def cem_perf_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj)
 
 
+def _no_form(entry: str, what: str, ssm, n_perf: int):
+    """What SX_ERR_UNSUPPORTED raises from the single-model entry of a GP-product form, as `_perf_rollout` calls it."""
+    return lambda n_s, n_u: _lib.SxError(
+        f'{entry}: no form of the {what} performance rollout for this model ((n_s, n_u) = ({n_s}, {n_u}), N = '
+        f'{ssm.device_model.n_train}, n_perf = {n_perf}): it runs with Kstar in LDS, all outputs at once or output by output '
+        f'(n_pad <= 1024), and has no workspace path')
+
+
 def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
                          safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
                          tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
@@ -310,19 +318,20 @@ def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: in
     Returns dict(rows, obj_cost, con_cost, perf_traj [E x P x n_perf x n_s] | None, perf_sigma (same shape) | None,
     status)."""
     _require_rbf([ssm], x0)
-
-    def unsupported(n_s, n_u):
-        return _lib.SxError(f'sx_cem_perf_rollout_var: no form of the variance performance rollout for this model '
-                            f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
-                            f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
     head = (ctypes.byref(ssm.device_model), ctypes.byref(env))
     return _perf_rollout('sx_cem_perf_rollout_var', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
                          obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
-                         unsupported=unsupported)
+                         unsupported=_no_form('sx_cem_perf_rollout_var', 'variance', ssm, n_perf))
 
 
 PERF_TYPES = ('mean_equivalent', 'taylor')
+
+
+def perf_kind(perf_variance: bool, perf_type: str) -> str:
+    """The performance rollout of a solver with these two settings: 'mean' (sx_cem_perf_rollout[_multi]), 'variance'
+    (sx_cem_perf_rollout_var[_multi]) or 'taylor' (sx_cem_perf_rollout_taylor[_multi]; it carries the variance by itself)."""
+    return 'taylor' if perf_type == 'taylor' else 'variance' if perf_variance else 'mean'
 
 
 def cem_perf_rollout_taylor(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
@@ -337,19 +346,13 @@ def cem_perf_rollout_taylor(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon:
     ellipsoid (mu_s, Sigma_s), s = horizon + 2, leaves the safe polytope (needs n_perf >= horizon + 2).
     Returns dict(rows, obj_cost, con_cost, perf_traj | None, perf_sigma | None, perf_cov | None, status)."""
     _require_rbf([ssm], x0)
-    if terminal_safety and n_perf < horizon + 2:
-        raise ValueError(f'terminal_safety checks the performance state {horizon + 2}: n_perf = {n_perf} is too short '
-                         f'(n_perf >= horizon + 2)')
-
-    def unsupported(n_s, n_u):
-        return _lib.SxError(f'sx_cem_perf_rollout_taylor: no form of the Taylor performance rollout for this model '
-                            f'((n_s, n_u) = ({n_s}, {n_u}), N = {ssm.device_model.n_train}, n_perf = {n_perf}): it runs with '
-                            f'Kstar in LDS, all outputs at once or output by output (n_pad <= 1024), and has no workspace path')
+    _check_terminal_safety(terminal_safety, n_perf, horizon)
     head = (ctypes.byref(ssm.device_model), ctypes.byref(env))
     return _perf_rollout('sx_cem_perf_rollout_taylor', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
                          obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
-                         unsupported=unsupported, want_cov=bool(want_cov), terminal_safety=terminal_safety)
+                         unsupported=_no_form('sx_cem_perf_rollout_taylor', 'Taylor', ssm, n_perf), want_cov=bool(want_cov),
+                         terminal_safety=terminal_safety)
 
 
 class PerfModelTable:
@@ -386,6 +389,35 @@ class PerfModelTable:
         return array, table
 
 
+def _check_terminal_safety(terminal_safety: bool, n_perf: int, horizon: int) -> None:
+    if terminal_safety and n_perf < horizon + 2:
+        raise ValueError(f'terminal_safety checks the performance state {horizon + 2}: n_perf = {n_perf} is too short '
+                         f'(n_perf >= horizon + 2)')
+
+
+def _perf_multi_preamble(entry: str, what: str, ssms: Sequence, x0: Tensor, n_perf: int, status, table, want, *,
+                         terminal_safety: bool = False, horizon: int = 0):
+    """What the multi-model performance wrappers do before `_perf_rollout`: the checks (the Taylor form's on
+    `terminal_safety` among them), the device table (`table` if it is a `want` for exact GPs, else a fresh one) and what
+    SX_ERR_UNSUPPORTED raises.  Returns (the models, the device table, unsupported); the caller holds the table's tensor
+    until its launch is enqueued (a fresh table has no other owner)."""
+    _require_rbf(ssms, x0)
+    E = x0.size(0)
+    if len(ssms) != E:
+        raise ValueError(f'{len(ssms)} models for {E} problems')
+    if status is not None and status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    _check_terminal_safety(terminal_safety, n_perf, horizon)
+    if not isinstance(table, want) or getattr(table, 'family', 'rbf') != 'rbf':
+        table = want()
+    models, dev_table = table.get(ssms, x0.device)
+
+    def unsupported(n_s, n_u):
+        return FusedMultiUnsupported(f'{entry}: no single launch of the {what} for these models ((n_s, n_u) = '
+                                     f'({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, n_perf = {n_perf})')
+    return models, dev_table, unsupported
+
+
 def cem_perf_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
                            variance: bool = False, safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
                            tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
@@ -397,25 +429,13 @@ def cem_perf_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor
     between calls: a `PerfModelTable` for the mean-only form, the `GpModelTable` of `cem_rollout_multi` for the variance
     form (a fresh one is built otherwise).  Raises FusedMultiUnsupported where the library has no single launch for the
     models (before any launch)."""
-    _require_rbf(ssms, x0)
-    E = x0.size(0)
-    if len(ssms) != E:
-        raise ValueError(f'{len(ssms)} models for {E} problems')
-    if status is not None and status.numel() != E:
-        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
     entry = 'sx_cem_perf_rollout_var_multi' if variance else 'sx_cem_perf_rollout_multi'
-    want = GpModelTable if variance else PerfModelTable
-    if not isinstance(table, want) or getattr(table, 'family', 'rbf') != 'rbf':
-        table = want()
-    models, dev_table = table.get(ssms, x0.device)
-
-    def unsupported(n_s, n_u):
-        return FusedMultiUnsupported(f'{entry}: no single launch of the performance rollout for these models ((n_s, n_u) = '
-                                     f'({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, n_perf = {n_perf})')
-    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r, safe_actions=safe_actions, obj_cost=obj_cost,
-                         con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std, tail_noise=tail_noise,
-                         rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma) if variance else None,
-                         unsupported=unsupported)
+    models, dev_table, unsupported = _perf_multi_preamble(entry, 'performance rollout', ssms, x0, n_perf, status, table,
+                                                          GpModelTable if variance else PerfModelTable)
+    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r, safe_actions=safe_actions,
+                         obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
+                         tail_noise=tail_noise, rows=rows, want_traj=want_traj,
+                         want_sigma=bool(want_sigma) if variance else None, unsupported=unsupported)
 
 
 def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int,
@@ -430,29 +450,40 @@ def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0:
     word per problem.  `table` keeps the device table between calls: the `GpModelTable` of `cem_rollout_multi` (a fresh
     one is built otherwise).  Raises FusedMultiUnsupported where the library has no single launch for the models (before
     any launch)."""
-    _require_rbf(ssms, x0)
-    E = x0.size(0)
-    if len(ssms) != E:
-        raise ValueError(f'{len(ssms)} models for {E} problems')
-    if status is not None and status.numel() != E:
-        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
-    if terminal_safety and n_perf < horizon + 2:
-        raise ValueError(f'terminal_safety checks the performance state {horizon + 2}: n_perf = {n_perf} is too short '
-                         f'(n_perf >= horizon + 2)')
     entry = 'sx_cem_perf_rollout_taylor_multi'
-    if not isinstance(table, GpModelTable) or getattr(table, 'family', 'rbf') != 'rbf':
-        table = GpModelTable()
-    models, dev_table = table.get(ssms, x0.device)
+    models, dev_table, unsupported = _perf_multi_preamble(entry, "'taylor' performance rollout", ssms, x0, n_perf, status,
+                                                          table, GpModelTable, terminal_safety=terminal_safety,
+                                                          horizon=horizon)
+    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r, safe_actions=safe_actions,
+                         obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
+                         tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
+                         unsupported=unsupported, want_cov=bool(want_cov), terminal_safety=terminal_safety)
 
-    def unsupported(n_s, n_u):
-        return FusedMultiUnsupported(f"{entry}: no single launch of the 'taylor' performance rollout for these models "
-                                     f'((n_s, n_u) = ({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, '
-                                     f'n_perf = {n_perf})')
-    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r,
-                         safe_actions=safe_actions, obj_cost=obj_cost, con_cost=con_cost, status=status,
-                         tail_mean=tail_mean, tail_std=tail_std, tail_noise=tail_noise, rows=rows, want_traj=want_traj,
-                         want_sigma=bool(want_sigma), unsupported=unsupported, want_cov=bool(want_cov),
-                         terminal_safety=terminal_safety)
+
+def _launch_perf(kind: str, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, safety: dict,
+                 mean: Tensor, std: Tensor, tail_noise: Tensor, status: Tensor, *, multi: bool = False,
+                 want_traj: bool = False, record: bool = False, terminal_safety: bool = False, table=None):
+    """The one performance launch of a CEM iteration, for `FusedCemMpc.solve` (ssms = [the model]) and
+    `MultiModelPerfCemMpc.solve` (`multi`: a model per problem, and the solver's `table` for the kind): the rollout of
+    `kind` (`perf_kind`) behind the safety rollout's result `safety`, its tail drawn from the columns past `horizon` of the
+    full-row `mean` / `std` with `tail_noise`.  `want_traj` asks for the means; `record` for all the variance and Taylor
+    forms carry (means, variances, covariances).  A multi-model solve asks for neither.  The wrappers are looked up on the
+    module when called.  Returns the wrapper's dict."""
+    kw = dict(safe_actions=safety['actions'], obj_cost=safety['obj_cost'].contiguous(),
+              con_cost=safety['con_cost'].contiguous(), status=status, tail_mean=mean[:, horizon:].contiguous(),
+              tail_std=std[:, horizon:].contiguous(), tail_noise=tail_noise)
+    if multi:
+        kw.update(table=table, **({} if kind == 'taylor' else dict(variance=kind == 'variance')))
+    elif kind == 'mean':
+        kw.update(want_traj=want_traj)
+    else:
+        kw.update(want_traj=want_traj or record, want_sigma=record, **(dict(want_cov=record) if kind == 'taylor' else {}))
+    if kind == 'taylor':
+        kw.update(terminal_safety=terminal_safety)
+    name = 'cem_perf_rollout' + {'mean': '', 'variance': '_var', 'taylor': '_taylor'}[kind]
+    if multi:
+        name = 'cem_perf_rollout_taylor_multi' if kind == 'taylor' else 'cem_perf_rollout_multi'
+    return globals()[name](ssms if multi else ssms[0], env, x0, horizon, n_perf, r, **kw)
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
@@ -729,6 +760,7 @@ class FusedCemMpc:
         if perf_type not in PERF_TYPES:
             raise ValueError(f'perf_type must be one of {PERF_TYPES}, got {perf_type!r}')
         self._perf_type, self._perf_terminal_safety = perf_type, bool(perf_terminal_safety)
+        self._perf_kind = perf_kind(self._perf_variance, perf_type)
         if perf_type == 'taylor' and self._n_perf <= 0:
             raise ValueError("perf_type='taylor' needs a performance trajectory (n_perf > 0)")
         if self._perf_terminal_safety and perf_type != 'taylor':
@@ -821,7 +853,7 @@ class FusedCemMpc:
         self._prior_tensors = None
 
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
-        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and not (self._perf_variance or self._perf_type == 'taylor'):
+        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf_kind == 'mean':
             raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
                              '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function, or pass '
                              "perf_variance=True or perf_type='taylor'")
@@ -1011,21 +1043,10 @@ class FusedCemMpc:
                 # the performance trajectory: its objective replaces the safety trajectory's, the tail's action box adds to
                 # the constraint cost, and the rows [safety actions | tail] are what the ranking sees
                 hook, n_s = self._objective_hook, self._ssm.num_states
-                kw = dict(safe_actions=r['actions'], obj_cost=r['obj_cost'].contiguous(),
-                          con_cost=r['con_cost'].contiguous(), status=status, tail_mean=full_mean[:, H:].contiguous(),
-                          tail_std=full_std[:, H:].contiguous(), tail_noise=eps_tail)
-                if self._perf_type == 'taylor':
-                    pr = cem_perf_rollout_taylor(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
-                                                 want_traj=hook is not None or self._record, want_sigma=self._record,
-                                                 want_cov=self._record, terminal_safety=self._perf_terminal_safety)
-                    r.update(perf_traj=pr['perf_traj'], perf_sigma=pr['perf_sigma'], perf_cov=pr['perf_cov'])
-                elif self._perf_variance:
-                    pr = cem_perf_rollout_var(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
-                                              want_traj=hook is not None or self._record, want_sigma=self._record)
-                    r.update(perf_traj=pr['perf_traj'], perf_sigma=pr['perf_sigma'])
-                else:
-                    pr = cem_perf_rollout(self._ssm, self._env, x0, H, self._n_perf, self._perf_r, **kw,
-                                          want_traj=hook is not None)
+                pr = _launch_perf(self._perf_kind, [self._ssm], self._env, x0, H, self._n_perf, self._perf_r, r, full_mean,
+                                  full_std, eps_tail, status, want_traj=hook is not None, record=self._record,
+                                  terminal_safety=self._perf_terminal_safety)
+                r.update({key: pr[key] for key in ('perf_traj', 'perf_sigma', 'perf_cov') if key in pr})
                 r.update(safe_actions=r['actions'], actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
                 if hook is not None:
                     obj = torch.zeros_like(pr['obj_cost'])
@@ -1347,8 +1368,10 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         # (check_solvers compares the two between the solvers)
         self._perf_type = getattr(solvers[0], '_perf_type', 'mean_equivalent')
         self._perf_terminal_safety = bool(getattr(solvers[0], '_perf_terminal_safety', False))
-        self._taylor = self._perf_type == 'taylor'
-        self._perf_table = PerfModelTable() if not (self._perf_variance or self._taylor) else None
+        self._perf_kind = perf_kind(self._perf_variance, self._perf_type)
+        self._taylor = self._perf_kind == 'taylor'
+        # the device table the performance launch reads: alpha per model for the mean-only form, else the safety launch's
+        self._perf_table = PerfModelTable() if self._perf_kind == 'mean' else self._table
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         if objective_hook is not None:
@@ -1362,24 +1385,20 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         LDS, which holds every training set the multi-model safety rollout takes (n_pad <= 1024).  Host only."""
         if not super().fused_applies():
             return False
-        if self._taylor:
-            return self._taylor_form() >= 0
-        if self._perf_variance:
-            models = model_array(self._ssms, 'rbf')
-            return int(_lib.lib().sx_cem_perf_rollout_var_multi_form(models, len(self._ssms), self._n_perf)) >= 0
-        return True
+        return self._perf_kind == 'mean' or self._perf_form() >= 0
 
-    def _taylor_form(self) -> int:
-        """sx_cem_perf_rollout_taylor_multi_form of the models: < 0 where they have no single launch.  Host only."""
+    def _perf_form(self) -> int:
+        """sx_cem_perf_rollout_{var,taylor}_multi_form of the models: < 0 where they have no single launch.  Host only."""
+        query = {'variance': 'sx_cem_perf_rollout_var_multi_form', 'taylor': 'sx_cem_perf_rollout_taylor_multi_form'}
         models = model_array(self._ssms, 'rbf')
-        return int(_lib.lib().sx_cem_perf_rollout_taylor_multi_form(models, len(self._ssms), self._n_perf))
+        return int(getattr(_lib.lib(), query[self._perf_kind])(models, len(self._ssms), self._n_perf))
 
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """As `MultiModelCemMpc.solve` with rows of H + T steps: noise [iters x E x P x (H + T) x n_u], and the returned
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
         E, H, T = len(self._ssms), self._horizon, self._tail
         n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
-        if self._taylor and self._taylor_form() < 0:
+        if self._perf_kind == 'taylor' and self._perf_form() < 0:
             raise FusedMultiUnsupported(f"perf_type='taylor' has no multi-model launch for these models (N = "
                                         f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {self._n_perf}): '
                                         f'the solvers act one model at a time')
@@ -1396,15 +1415,9 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         def rollout(it, mean, std, rows):
             r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean[:, :H].contiguous(), std=std[:, :H].contiguous(),
                                   noise=noise_safe[it], status=status, table=self._table)
-            kw = dict(safe_actions=r['actions'], obj_cost=r['obj_cost'], con_cost=r['con_cost'], status=status,
-                      tail_mean=mean[:, H:].contiguous(), tail_std=std[:, H:].contiguous(), tail_noise=noise_tail[it])
-            if self._taylor:
-                pr = cem_perf_rollout_taylor_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r, **kw,
-                                                   terminal_safety=self._perf_terminal_safety, table=self._table)
-            else:
-                pr = cem_perf_rollout_multi(self._ssms, self._env, x0, H, self._n_perf, self._perf_r,
-                                            variance=self._perf_variance, **kw,
-                                            table=self._table if self._perf_variance else self._perf_table)
+            pr = _launch_perf(self._perf_kind, self._ssms, self._env, x0, H, self._n_perf, self._perf_r, r, mean, std,
+                              noise_tail[it], status, multi=True, terminal_safety=self._perf_terminal_safety,
+                              table=self._perf_table)
             return dict(actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
 
         def rank(it, r):

@@ -10,6 +10,7 @@
 #include "sx_launch.hpp"
 #include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES, SX_DISPATCH
 #include "sx_perf.hpp"
+#include "sx_perf_launch.hpp"   // the entries' shared checks
 
 namespace sx {
 
@@ -88,16 +89,6 @@ static int perf_multi_dispatch(const sx_gp_model* models, const void* table, con
 #undef CALL
 }
 
-// E models of one (n_s, n_u) with a training set each: checked before anything touches the device
-static bool perf_models_ok(const sx_gp_model* models, int E) {
-    if (!models || E <= 0) return false;
-    const int ns = models[0].n_s, nu = models[0].n_u;
-    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || nu > SX_MAX_NU) return false;
-    for (int i = 0; i < E; ++i)
-        if (models[i].n_s != ns || models[i].n_u != nu || models[i].n_train <= 0 || !models[i].x_train) return false;
-    return true;
-}
-
 }  // namespace sx
 
 extern "C" int64_t sx_cem_perf_table_bytes(int n_s, int n_u, int E) {
@@ -107,7 +98,8 @@ extern "C" int64_t sx_cem_perf_table_bytes(int n_s, int n_u, int E) {
 }
 
 extern "C" int sx_cem_perf_table(const sx_gp_model* models, const double* const* alphas, int E, void* table, void* stream) {
-    if (!table || !alphas || !sx::perf_models_ok(models, E)) return SX_ERR_ARG;
+    if (!table || !alphas || !models || E <= 0 || !sx::perf_shape_ok(models[0])) return SX_ERR_ARG;
+    if (!sx::perf_models_ok(models, E, sx::perf_model_has_data)) return SX_ERR_ARG;
     for (int i = 0; i < E; ++i)
         if (!alphas[i]) return SX_ERR_ARG;
 #define CALL(NS, NU) sx::build_perf_table<NS, NU>(models, alphas, E, table, (hipStream_t)stream)
@@ -120,15 +112,9 @@ extern "C" int sx_cem_perf_rollout_multi(const sx_gp_model* models, const void* 
                                          const double* tail_mean, const double* tail_std, const double* tail_noise,
                                          double* rows, double* obj_cost, double* con_cost, double* perf_traj,
                                          int32_t* status, void* stream) {
-    if (!models || !perf_table || !env || !x0 || !safe_actions || !rows || !obj_cost || !con_cost || !status)
-        return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0 || r < 1 || r > H || n_perf <= r) return SX_ERR_ARG;
-    if (tail_noise && (!tail_mean || !tail_std)) return SX_ERR_ARG;
-    if (!sx::perf_models_ok(models, E) || models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
-    if (env->obj_mode == SX_OBJ_NEG_VARIANCE) return SX_ERR_UNSUPPORTED;   // as sx_cem_perf_rollout
-    if (env->obj_mode != SX_OBJ_AFFINE_ABS) return SX_ERR_ARG;
-    const sx::PerfPtrs pp{x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost, con_cost, perf_traj, status,
-                          E, P, H, n_perf, r};
+    const sx::PerfPtrs pp = sx::make_perf_ptrs(x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost, con_cost,
+                                               perf_traj, status, E, P, H, n_perf, r);
+    if (int rc = sx::check_perf_entry(perf_table, models, E, true, sx::perf_model_has_data, env, pp, false)) return rc;
     return sx::perf_multi_dispatch(models, perf_table, env, pp, (hipStream_t)stream);
 }
 
@@ -136,13 +122,9 @@ extern "C" int sx_cem_perf_rollout(const sx_gp_model* model, const double* alpha
                                    int n_perf, int r, const double* x0, const double* safe_actions,
                                    const double* tail_mean, const double* tail_std, const double* tail_noise, double* rows,
                                    double* obj_cost, double* con_cost, double* perf_traj, int32_t* status, void* stream) {
-    if (!model || !alpha || !env || !x0 || !safe_actions || !rows || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
-    if (E <= 0 || P <= 0 || H <= 0 || r < 1 || r > H || n_perf <= r) return SX_ERR_ARG;
-    if (tail_noise && (!tail_mean || !tail_std)) return SX_ERR_ARG;
-    if (!model->x_train || model->n_train <= 0 || model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
-    if (env->obj_mode == SX_OBJ_NEG_VARIANCE) return SX_ERR_UNSUPPORTED;   // needs || W k* ||^2: the safety kernels' product
-    if (env->obj_mode != SX_OBJ_AFFINE_ABS) return SX_ERR_ARG;
-    const sx::PerfPtrs pp{x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost, con_cost, perf_traj, status,
-                          E, P, H, n_perf, r};
+    const sx::PerfPtrs pp = sx::make_perf_ptrs(x0, safe_actions, tail_mean, tail_std, tail_noise, rows, obj_cost, con_cost,
+                                               perf_traj, status, E, P, H, n_perf, r);
+    // SX_OBJ_NEG_VARIANCE needs || W k* ||^2, the safety kernels' product: SX_ERR_UNSUPPORTED here
+    if (int rc = sx::check_perf_entry(alpha, model, 1, false, sx::perf_model_has_data, env, pp, false)) return rc;
     return sx::perf_dispatch(model, alpha, env, pp, (hipStream_t)stream);
 }

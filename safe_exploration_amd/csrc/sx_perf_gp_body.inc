@@ -1,7 +1,12 @@
-// The body of cem_perf_var_rollout_kernel and cem_perf_var_rollout_multi_kernel (sx_perf_var.hpp), included into both: as
-// text, so that the single-model kernel compiles to the instructions it had before the multi-model one existed.  In scope:
-// NS, NU, BYOUT; MM (false | true: a GP per problem); `gc` (the GpConst kernel argument, or the problem's entry of the
-// device table of sx_gp_model_table), `stage_tab` (its stage table), `sc`, `vp`.
+// The body of the four GP-product performance kernels, included as text: cem_perf_var_rollout[_multi]_kernel
+// (sx_perf_var.hpp) with SX_PERF_TAYLOR 0 and cem_perf_taylor_rollout[_multi]_kernel (sx_perf_taylor.hpp) with
+// SX_PERF_TAYLOR 1.  As text and with the kind's sections picked by the preprocessor, so that every kernel sees the
+// statements it had when each kernel had a body of its own and compiles to the same instructions (a device function for
+// the shared part changed the single-model kernel's registers; tools/device_code_diff.py is the check).
+// In scope: NS, NU, BYOUT; MM (false | true: a GP per problem); `gc` (the GpConst kernel argument, or the problem's entry
+// of the device table of sx_gp_model_table), `stage_tab` (its stage table); the step constants and the pointers, which
+// are kernel arguments in both modes (there is one sx_env): `sc`, `vp` for the variance kernels, `tc_arg`, `tp` for the
+// Taylor kernels.
 // MM = true: the LDS carve-up follows the problem's n_train / n_pad inside the launch's allocation for the largest model,
 // and the status is one word per problem.  The workgroups are problem-aligned in both modes.
     constexpr int D = NS + NU;
@@ -22,6 +27,16 @@
     const MfmaHead head = gp_mfma_head(gc, stage_tab, wave, nw, lane, gc.stage_cap);
     const int4* __restrict__ const tab_one = stage_tab + (size_t)nw * (1 + gc.stage_cap);
     gp_load_xs(gc, lds);
+#if SX_PERF_TAYLOR
+    // Taylor: the step constants sit in LDS behind the actions, copied in one pass (`sc` is the variance kernels' argument)
+    constexpr int kConst = perf_taylor_const_doubles<NS, NU>();
+    static_assert(kConst <= kPerfVarThreads, "one pass copies the step constants");
+    static_assert(sizeof(PerfTaylorConst<NS, NU>) % sizeof(double) == 0, "doubles only");
+    double* const tcl = acts + SX_TILE * n_perf * NU;
+    const PerfTaylorConst<NS, NU>& tc = *reinterpret_cast<const PerfTaylorConst<NS, NU>*>(tcl);
+    const PerfStepConst<NS, NU>& sc = tc.step;
+    if (tid < kConst) tcl[tid] = reinterpret_cast<const double*>(&tc_arg)[tid];
+#endif
 
     // the tile's rows [safety actions | tail] (the tail drawn by the expression of sx_perf.hpp, or read), and its
     // performance actions v_t = u^s_t (t < r), u^p_t (t >= r) into LDS; a slot past the particles holds zeros
@@ -59,6 +74,15 @@
 #pragma unroll
         for (int i = 0; i < NS; ++i) mu[i] = pp.x0[(int64_t)e * NS + i];
     }
+#if SX_PERF_TAYLOR
+    double S[NS][NS];   // Taylor: Sigma_t beside mu_t on the owner lane, both triangles; Sigma_0 = 0
+    if (owner) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) S[i][j] = 0.0;
+    }
+#endif
     __syncthreads();
     if (owner) {
 #pragma unroll
@@ -81,14 +105,14 @@
             out[i] = s;
         }
     };
-    // the rest of step t on the owner lanes: variance, next centre, costs, stores
+    // the rest of step t on the owner lanes: posterior (Taylor: and the covariance step), next centre, costs, stores
     auto tail = [&](int t) {
         double z[D], mean[NS], var[NS], jac[NS][D], mu1[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) z[j] = mu[j];
 #pragma unroll
         for (int cidx = 0; cidx < NU; ++cidx) z[NS + cidx] = acts[(tid * n_perf + t) * NU + cidx];
-        gp_collect<NS, D, false>(gc, lds, nw, tid, z, mean, var, jac);
+        gp_collect<NS, D, SX_PERF_TAYLOR>(gc, lds, nw, tid, z, mean, var, jac);   // Taylor: with the Jacobian rows
         next_centre(tid, z, mu1);   // exactly the centre the Kstar threads of step t + 1 derive
         if (t + 1 < n_perf) {
             double* zn = zs_base + ((t + 1) & 1) * 16 * D + tid * D;
@@ -97,22 +121,75 @@
 #pragma unroll
             for (int cidx = 0; cidx < NU; ++cidx) zn[NS + cidx] = acts[(tid * n_perf + t + 1) * NU + cidx];
         }
+#if SX_PERF_TAYLOR
+        // Taylor: G = diag(var) + diag(M Sigma M^T) and Sigma_{t+1} = Hm Sigma Hm^T + diag(var) (upper triangle, then
+        // mirrored), with M = J_x + J_u K, Hm = (a + b K) + M; MS = M Sigma, HS = Hm Sigma
+        double M[NS][NS], Hm[NS][NS], G[NS], S1[NS][NS];
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                double s = jac[i][j];
+#pragma unroll
+                for (int cidx = 0; cidx < NU; ++cidx) s = fma(jac[i][NS + cidx], tc.k_fb[cidx * NS + j], s);
+                M[i][j] = s;
+                Hm[i][j] = tc.abk[i * NS + j] + s;
+            }
+        }
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            double ms[NS], hs[NS];   // rows i of M Sigma and Hm Sigma
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                double a = 0.0, b = 0.0;
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    a = fma(M[i][k], S[k][j], a);
+                    b = fma(Hm[i][k], S[k][j], b);
+                }
+                ms[j] = a;
+                hs[j] = b;
+            }
+            double g = 0.0;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) g = fma(ms[j], M[i][j], g);
+            G[i] = var[i] + g;
+#pragma unroll
+            for (int j = i; j < NS; ++j) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < NS; ++k) s = fma(hs[k], Hm[j][k], s);
+                S1[i][j] = (j == i) ? s + var[i] : s;
+                bad = bad || !(__builtin_fabs(S1[i][j]) <= 1.7976931348623157e308);
+            }
+            bad = bad || !(__builtin_fabs(mu1[i]) <= 1.7976931348623157e308) ||
+                  !(__builtin_fabs(var[i]) <= 1.7976931348623157e308) || !(__builtin_fabs(G[i]) <= 1.7976931348623157e308);
+        }
+#pragma unroll
+        for (int i = 1; i < NS; ++i)
+#pragma unroll
+            for (int j = 0; j < i; ++j) S1[i][j] = S1[j][i];
+#else
+        const double (&G)[NS] = var;   // what the objective and perf_sigma see
         bool bad = false;
 #pragma unroll
         for (int i = 0; i < NS; ++i)
             bad = bad || !(__builtin_fabs(mu1[i]) <= 1.7976931348623157e308) ||
                   !(__builtin_fabs(var[i]) <= 1.7976931348623157e308);
+#endif
         double o = 0.0;
         if (vp.obj_mode == SX_OBJ_NEG_VARIANCE) {
 #pragma unroll
-            for (int i = 0; i < NS; ++i) o -= var[i];
+            for (int i = 0; i < NS; ++i) o -= G[i];
         } else {
 #pragma unroll
             for (int i = 0; i < NS; ++i) o += sc.w_abs[i] * fabs(sc.target[i] - mu1[i]) + sc.w_lin[i] * mu1[i];
         }
         obj += o;
         if (bad) {
-            // a non-finite state or variance never ranks (the table exponential maps an infinite distance to k* = 0)
+            // a non-finite state, variance or covariance never ranks (the table exponential maps an infinite distance to
+            // k* = 0)
             st |= SX_STATUS_NAN;
             obj = __builtin_nan("");
         }
@@ -123,6 +200,13 @@
                 uviol = uviol || (z[NS + cidx] < sc.u_min[cidx]) || (z[NS + cidx] > sc.u_max[cidx]);
             if (uviol) con += SX_ACTION_VIOLATION_COST;
         }
+#if SX_PERF_TAYLOR
+        if (t == tp.safety_step) {
+            // Taylor: the terminal-safety coupling: (mu_s, Sigma_s), s = t + 1 = H + 2, inside the safe polytope
+            if (polytope_violated<SX_MAX_M, NS>(tc.h_mat, tc.h_vec, tp.m, 1.0, mu1, S1, nullptr))
+                con += SX_STATE_VIOLATION_COST;
+        }
+#endif
         const int64_t g = (int64_t)e * pp.P + c0 + tid;
         if (valid && pp.perf_traj) {
 #pragma unroll
@@ -130,8 +214,22 @@
         }
         if (valid && vp.perf_sigma) {
 #pragma unroll
-            for (int i = 0; i < NS; ++i) vp.perf_sigma[(g * n_perf + t) * NS + i] = var[i];
+            for (int i = 0; i < NS; ++i) vp.perf_sigma[(g * n_perf + t) * NS + i] = G[i];
         }
+#if SX_PERF_TAYLOR
+        // Taylor: Sigma_{t+1} goes out and becomes the next step's Sigma
+        if (valid && tp.perf_cov) {
+            double* cv = tp.perf_cov + (g * n_perf + t) * (NS * NS);
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+#pragma unroll
+                for (int j = 0; j < NS; ++j) cv[i * NS + j] = S1[i][j];
+        }
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) S[i][j] = S1[i][j];
+#endif
 #pragma unroll
         for (int i = 0; i < NS; ++i) mu[i] = mu1[i];
     };

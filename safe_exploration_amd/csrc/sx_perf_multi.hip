@@ -10,8 +10,6 @@
 
 namespace sx {
 
-static_assert(kPerfVarThreads == kRolloutThreads, "the stage table of sx_gp_pack is cut for the safety kernel's waves");
-
 template <int NS, int NU>
 int launch_perf_rollout_multi(const PerfGpEntry<NS, NU>* table, const PerfStepConst<NS, NU>& step, const PerfPtrs& pp,
                               size_t lds, hipStream_t stream) {
@@ -23,24 +21,17 @@ int launch_perf_rollout_multi(const PerfGpEntry<NS, NU>* table, const PerfStepCo
     return check_launch();
 }
 
-template <int NS, int NU, bool BYOUT>
-static int launch_perf_var_multi_form(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc,
-                                      const PerfVarPtrs& vp, unsigned blocks, size_t lds, hipStream_t stream) {
-    if (int r = allow_lds(cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>, lds)) return r;
-    hipLaunchKernelGGL((cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>), dim3(blocks), dim3(kPerfVarThreads), lds, stream,
-                       table, sc, vp);
-    return check_launch();
-}
+struct PerfVarMultiKernels {
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>;
+    }
+};
 
 template <int NS, int NU>
-int launch_perf_var_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
-                          bool byout, size_t lds, hipStream_t stream) {
-    const int64_t blocks = (int64_t)vp.p.E * ((vp.p.P + SX_TILE - 1) / SX_TILE);
-    if (blocks > INT_MAX || lds > kMaxLdsBytes) return SX_ERR_UNSUPPORTED;
-    if constexpr (NS > 1) {
-        if (byout) return launch_perf_var_multi_form<NS, NU, true>(table, sc, vp, (unsigned)blocks, lds, stream);
-    }
-    return launch_perf_var_multi_form<NS, NU, false>(table, sc, vp, (unsigned)blocks, lds, stream);
+int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
+                          bool byout, unsigned blocks, size_t lds, hipStream_t stream) {
+    return launch_perf_gp_forms<PerfVarMultiKernels, NS, NU>(byout, blocks, lds, stream, table, sc, vp);
 }
 
 }  // namespace sx
@@ -48,7 +39,8 @@ int launch_perf_var_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst
 #define SX_PERF_MULTI_INSTANTIATE(NS, NU)                                                                              \
     template int sx::launch_perf_rollout_multi<NS, NU>(const sx::PerfGpEntry<NS, NU>*, const sx::PerfStepConst<NS, NU>&, \
                                                        const sx::PerfPtrs&, size_t, hipStream_t);                      \
-    template int sx::launch_perf_var_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfStepConst<NS, NU>&,  \
-                                                   const sx::PerfVarPtrs&, bool, size_t, hipStream_t);
+    template int sx::launch_perf_gp_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfStepConst<NS, NU>&,  \
+                                                   const sx::PerfVarPtrs&, bool, unsigned, size_t,  \
+                                                   hipStream_t);
 #define SX_PERF_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_PERF_MULTI_INSTANTIATE(NS, NU))
 SX_ROLLOUT_SHAPES(SX_PERF_MULTI_ONE, 0)

@@ -15,8 +15,8 @@
 // The constants of a step (prior, a + b K, K, action box, objective, polytope: 64 .. 128 doubles) sit in LDS behind the
 // tile's actions; as kernel arguments they would stay in SGPRs for the whole kernel, which already spills its arguments.
 // A tile's numbers depend on its 16 particles alone.
-// The body is sx_perf_taylor_body.inc, included as text into the single-model kernel and into the multi-model one
-// (sx_cem_perf_rollout_taylor_multi: a GP per problem), as sx_perf_var.hpp does with its body.
+// The body is sx_perf_gp_body.inc with its Taylor sections, the text the variance kernels (sx_perf_var.hpp) include without
+// them: into the single-model kernel and into the multi-model one (sx_cem_perf_rollout_taylor_multi: a GP per problem).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,7 +54,10 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_rollout_kerne
                                                                                   const PerfTaylorConst<NS, NU> tc_arg,
                                                                                   const PerfTaylorPtrs tp) {
     constexpr bool MM = false;
-#include "sx_perf_taylor_body.inc"
+    const PerfVarPtrs& vp = tp.v;
+#define SX_PERF_TAYLOR 1
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_TAYLOR
 }
 
 // sx_cem_perf_rollout_taylor_multi: a GP per problem, one set of step constants (one sx_env).  The workgroup binds its
@@ -68,7 +71,10 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_rollout_multi
     const int problem = blockIdx.x / ((tp.v.p.P + SX_TILE - 1) / SX_TILE);
     const GpConst<NS, NS + NU>& gc = *(const GpConst<NS, NS + NU>*)((ConstG*)table + problem);
     const int4* __restrict__ const stage_tab = gc.stage_tab;
-#include "sx_perf_taylor_body.inc"
+    const PerfVarPtrs& vp = tp.v;
+#define SX_PERF_TAYLOR 1
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_TAYLOR
 }
 
 }  // namespace sx

@@ -10,32 +10,23 @@
 
 namespace sx {
 
-static_assert(kPerfVarThreads == kRolloutThreads, "the stage table of sx_gp_pack is cut for the safety kernel's waves");
-
-template <int NS, int NU, bool BYOUT>
-static int launch_perf_taylor_multi_form(const GpConst<NS, NS + NU>* table, const PerfTaylorConst<NS, NU>& tc,
-                                         const PerfTaylorPtrs& tp, unsigned blocks, size_t lds, hipStream_t stream) {
-    if (int r = allow_lds(cem_perf_taylor_rollout_multi_kernel<NS, NU, BYOUT>, lds)) return r;
-    hipLaunchKernelGGL((cem_perf_taylor_rollout_multi_kernel<NS, NU, BYOUT>), dim3(blocks), dim3(kPerfVarThreads), lds,
-                       stream, table, tc, tp);
-    return check_launch();
-}
+struct PerfTaylorMultiKernels {
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_perf_taylor_rollout_multi_kernel<NS, NU, BYOUT>;
+    }
+};
 
 template <int NS, int NU>
-int launch_perf_taylor_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorConst<NS, NU>& tc, const PerfTaylorPtrs& tp,
-                             bool byout, size_t lds, hipStream_t stream) {
-    const int64_t blocks = (int64_t)tp.v.p.E * ((tp.v.p.P + SX_TILE - 1) / SX_TILE);
-    if (blocks > INT_MAX || lds > kMaxLdsBytes) return SX_ERR_UNSUPPORTED;
-    if constexpr (NS > 1) {
-        if (byout) return launch_perf_taylor_multi_form<NS, NU, true>(table, tc, tp, (unsigned)blocks, lds, stream);
-    }
-    return launch_perf_taylor_multi_form<NS, NU, false>(table, tc, tp, (unsigned)blocks, lds, stream);
+int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorConst<NS, NU>& tc, const PerfTaylorPtrs& tp,
+                             bool byout, unsigned blocks, size_t lds, hipStream_t stream) {
+    return launch_perf_gp_forms<PerfTaylorMultiKernels, NS, NU>(byout, blocks, lds, stream, table, tc, tp);
 }
 
 }  // namespace sx
 
 #define SX_PERF_TAYLOR_MULTI_INSTANTIATE(NS, NU)                                                                        \
-    template int sx::launch_perf_taylor_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfTaylorConst<NS, NU>&, \
-                                                      const sx::PerfTaylorPtrs&, bool, size_t, hipStream_t);
+    template int sx::launch_perf_gp_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfTaylorConst<NS, NU>&, \
+                                                      const sx::PerfTaylorPtrs&, bool, unsigned, size_t, hipStream_t);
 #define SX_PERF_TAYLOR_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_PERF_TAYLOR_MULTI_INSTANTIATE(NS, NU))
 SX_ROLLOUT_SHAPES(SX_PERF_TAYLOR_MULTI_ONE, 0)

@@ -41,7 +41,9 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_perf_var_rollout_kernel(c
                                                                                const PerfStepConst<NS, NU> sc,
                                                                                const PerfVarPtrs vp) {
     constexpr bool MM = false;
-#include "sx_perf_var_body.inc"
+#define SX_PERF_TAYLOR 0
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_TAYLOR
 }
 
 // sx_cem_perf_rollout_var_multi: a GP per problem.  The workgroup binds its problem's GpConst through a restrict-qualified
@@ -54,7 +56,9 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_perf_var_rollout_multi_ke
     const int problem = blockIdx.x / ((vp.p.P + SX_TILE - 1) / SX_TILE);
     const GpConst<NS, NS + NU>& gc = *(const GpConst<NS, NS + NU>*)((ConstG*)table + problem);
     const int4* __restrict__ const stage_tab = gc.stage_tab;
-#include "sx_perf_var_body.inc"
+#define SX_PERF_TAYLOR 0
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_TAYLOR
 }
 
 }  // namespace sx
