@@ -508,7 +508,11 @@ int sx_cem_perf_rollout(const sx_gp_model* model, const double* alpha, const sx_
  * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout, and for a model without a_pack / stage_tab / a valid n_pad
  * or an obj_mode that is neither of the two; SX_ERR_UNSUPPORTED for a shape sx_cem_rollout is not instantiated for and for
  * training sets outside the two forms built: Kstar of all outputs in LDS beside the tile's n_perf actions (N up to ~ 524
- * at (n_s, n_u) = (2, 1)), else output by output (n_s > 1, n_pad <= 1024).  No resident-W form, no workspace path.
+ * at (n_s, n_u) = (2, 1)), else output by output (n_s > 1).  Both need n_pad <= 1024 AND their LDS, which grows with n_perf:
+ * one output reaches n_pad = 1024 (N = 1021 at (1, 1), up to n_perf = 68); for n_s > 1 the training inputs and one
+ * output's Kstar fill the LDS before that -- at n_perf = 2 the largest N is 988 at (2, 1), 939 at (2, 2), 923 at (3, 1),
+ * 858 at (4, 1), 809 at (4, 2) -- and a model just below goes from all outputs in LDS to output by output as n_perf grows.
+ * sx_cem_perf_rollout_var_form answers for a model and an n_perf.  No resident-W form, no workspace path.
  * Replaces: nothing in the reference's CEM solver; its casadi solver sums gp_sigma_pred of mean_equivalent_multistep
  * (safempc_simple.py:292-321, 398-490). */
 int sx_cem_perf_rollout_var(const sx_gp_model* model, const sx_env* env, int E, int P, int H, int n_perf, int r,
@@ -586,8 +590,10 @@ int sx_cem_perf_rollout_var_multi_form(const sx_gp_model* models, int E, int n_p
  *                h_j . mu_s + sqrt(h_j^T Sigma_s h_j) - h_vec_j >= 0 adds SX_STATE_VIOLATION_COST to con_cost once (a NaN
  *                distance counts as inside, as everywhere); needs n_perf >= H + 2 and m > 0
  *   status       OR-ed with SX_STATUS_NAN on a non-finite mu_t, var_t, G_t or Sigma_t (that particle's objective is NaN)
- * The variance kernel's layout and forms (all outputs in LDS, else output by output up to n_pad = 1024), with the step
- * constants (64 .. 128 doubles) in LDS behind the tile's actions; a tile's numbers do not depend on P or on the grid.
+ * The variance kernel's layout and forms (all outputs in LDS, else output by output; n_pad <= 1024 and the LDS bound both,
+ * as there), with the step constants (41 .. 144 doubles) in LDS behind the tile's actions: they count against the same LDS, so
+ * a form ends at a smaller n_perf or N than the variance kernel's (at n_perf = 2: N = 907 at (3, 1), 842 at (4, 1), else the
+ * variance form's; sx_cem_perf_rollout_taylor_form answers).  A tile's numbers do not depend on P or on the grid.
  * SX_ERR_ARG (before any device access) as sx_cem_perf_rollout_var, and for terminal_safety with n_perf < H + 2 or without
  * polytope rows; SX_ERR_UNSUPPORTED as sx_cem_perf_rollout_var and for m > SX_MAX_M.
  * Replaces: one_step_taylor / multi_step_taylor_symbolic (uncertainty_propagation_casadi.py:11-149) as the casadi solver

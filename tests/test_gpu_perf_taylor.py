@@ -215,8 +215,10 @@ def test_terminal_safety(n_s, n_u, N):
 
 # ---- the forms --------------------------------------------------------------------------------------------------------------
 def test_the_forms_the_training_sets_take():
-    """N = 200 runs with all outputs in LDS and 590 output by output; beyond n_pad = 1024 there is no form, and the form
-    query says of every model what the launch does."""
+    """N = 200 runs with all outputs in LDS and 590 output by output; N = 1100 (n_pad = 1104) has no form, and the form
+    query says of every model what the launch does.  1024 is not the limit it answers for n_s > 1: one output's Kstar, the
+    training inputs and the step constants fill the LDS before n_pad = 1024, and sooner the longer the trajectory
+    (tests/test_gpu_perf_shapes.py finds the largest N of every shape: 988 at (2, 1))."""
     form = lambda ssm, n_perf=8: int(_lib.lib().sx_cem_perf_rollout_taylor_form(ctypes.byref(ssm.device_model), n_perf))
     SX_FORM_STREAM, SX_FORM_BYOUT = 0, 3
     for n_s, n_u in SHAPES:

@@ -175,7 +175,9 @@ def test_kernel_matches_the_oracle_past_one_grid_and_does_not_depend_on_it(n_s, 
 
 def test_the_forms_the_training_sets_take():
     """N = 200 runs with all outputs in LDS and 590 output by output (sx_cem_rollout_form reports the streaming safety
-    kernel's choice, made by the same rule at the same LDS budget); beyond n_pad = 1024 there is no form."""
+    kernel's choice, made by the same rule at the same LDS budget); N = 1100 (n_pad = 1104) has no form.  1024 is not the
+    limit the form query answers for n_s > 1: one output's Kstar and the training inputs fill the LDS before n_pad = 1024,
+    and sooner the longer the trajectory (tests/test_gpu_perf_shapes.py finds the largest N of every shape: 988 here)."""
     from safe_exploration_amd.cem_mpc import cem_perf_rollout_var
     form = lambda ssm: int(_lib.lib().sx_cem_rollout_form(ssm.device_model, 40))
     SX_FORM_BYOUT = 3
