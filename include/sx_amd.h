@@ -387,6 +387,32 @@ int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, i
 #define SX_FORM_BIG 4
 int sx_cem_rollout_form(const sx_gp_model* model, int H);
 
+/* sx_cem_rollout with a start state per particle (static exploration: the start is a decision variable of the optimiser).
+ * The CEM row of a particle is [x0 (n_s) | u_0 .. u_{H-1} (H n_u)], L = n_s + H n_u entries with one Gaussian each:
+ *   mean,std dev [E x L]               sampling distribution of the rows (ignored when noise == NULL)
+ *   noise   dev [E x P x L] | NULL     standard-normal draws; NULL = `rows` is an INPUT
+ *   rows    dev [E x P x L]            out: mean + std * noise  (or in, see above)
+ *   traj, sigma, obj_cost, con_cost, status   as in sx_cem_rollout
+ * Every particle is rolled out from the point x0 of its own row with the actions of its row, and the costs are
+ * sx_cem_rollout's (env->obj_mode, env->con_mode, the action box) plus SX_STATE_VIOLATION_COST once, in either constraint
+ * mode, for a start outside the safe polytope (h_mat x0 - h_vec >= 0 in any row): a sample is taken at (x0, u_0), so the
+ * system is put there.  The reference's NLP leaves p_0 free; this rule is this library's own.
+ * The streaming kernel only (SX_FORM_STREAM or SX_FORM_BYOUT, sx_cem_rollout_starts_form): no workspace path.
+ * SX_ERR_ARG (checked before any device access) for null pointers, non-positive sizes, a model whose (n_s, n_u) differ from
+ * env's, or noise without mean / std; SX_ERR_UNSUPPORTED (before any launch) for a shape without a rollout kernel,
+ * env->m > SX_MAX_M, or a training set that needs the workspace path (sx_cem_rollout_workspace_bytes() > 0) or fits neither
+ * form.
+ * Replaces: the rollout and constraint evaluation inside StaticSafeMPCExploration's NLP over [p_0, u_0, k_ff]
+ * (safempc_exploration.py:100-163,281-330), one NLP solve per restart. */
+int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
+                          const double* std, const double* noise, double* rows, double* traj, double* sigma,
+                          double* obj_cost, double* con_cost, int32_t* status, void* stream);
+/* The form sx_cem_rollout_starts launches for this model and horizon (no launch, no device access): SX_FORM_STREAM or
+ * SX_FORM_BYOUT, or < 0 for bad arguments and wherever sx_cem_rollout_starts would answer SX_ERR_UNSUPPORTED for the model.
+ * The same contract as sx_cem_rollout_form.
+ * Replaces: nothing in safempc_exploration.py:100-163,281-330, whose NLP has one form. */
+int sx_cem_rollout_starts_form(const sx_gp_model* model, int H);
+
 /* ---- E problems with an exact GP each in one rollout launch (independent exploration runs) ----
  * Every problem e of the launch has its own training set (its own N) and hyper-parameters; all models share (n_s, n_u),
  * the sx_env and the buffer shapes of sx_cem_rollout.  The per-problem GP constants live in a device table that is built

@@ -127,6 +127,52 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
                     elite_rows=elite_rows, want_dist=want_dist, workspace=workspace)
 
 
+def _require_rbf_starts(ssm) -> None:
+    family = getattr(ssm, 'kernel_family', 'rbf')
+    if family != 'rbf':
+        raise NotImplementedError(f'per-particle start states (static exploration) are built for exact RBF GPs, not '
+                                  f'kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+
+
+def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Optional[Tensor] = None,
+                       std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                       want_traj: bool = False, want_sigma: bool = False, status: Optional[Tensor] = None):
+    """Thin wrapper over sx_cem_rollout_starts: the rollout whose particles each start from the first n_s entries of their
+    own CEM row [x0 | actions], L = n_s + H n_u (static exploration).
+
+    Either (`mean`, `std` [E x L], `noise` [E x P x L]): the rows are drawn, or `rows` [E x P x L] (given).
+    Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]); a start outside the
+    safe polytope has added SX_STATE_VIOLATION_COST to its particle's con_cost.
+    """
+    _require_rbf_starts(ssm)
+    n_s, n_u = ssm.num_states, ssm.num_actions
+    L = n_s + horizon * n_u
+    given = rows if noise is None else noise
+    if (noise is None) == (rows is None) or given.dim() != 3 or given.size(2) != L or not given.is_contiguous():
+        raise ValueError(f'either noise (the rows are drawn) or rows (given), a contiguous [E x P x {L}] tensor')
+    _lib.require_gpu(given, 'rows' if noise is None else 'noise')
+    E, P, dev = given.size(0), given.size(1), given.device
+    if noise is not None:
+        if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
+            raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
+        mean, std = mean.contiguous(), std.contiguous()
+        rows = torch.empty((E, P, L), dtype=torch.float64, device=dev)
+    S = n_s + n_s * n_s
+    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
+    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
+    con = torch.empty((E, P), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    code = _lib.lib().sx_cem_rollout_starts(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, horizon,
+                                            _lib.ptr(mean if noise is not None else None),
+                                            _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
+                                            _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                            _lib.stream_ptr(dev))
+    _lib.check(code, 'sx_cem_rollout_starts')
+    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+
+
 class FusedMultiUnsupported(_lib.SxError):
     """sx_cem_rollout_multi answered SX_ERR_UNSUPPORTED (before any launch): solve the problems one model at a time."""
 
@@ -516,7 +562,8 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
     workgroups.  `FusedCemMpc` falls back to it when a fused solve reports both SX_STATUS_NAN and SX_STATUS_ZERO_FIX --
     the only case in which the two rules can differ.  ~3 H launches per iteration instead of one; nothing synchronises.
 
-    x0 [n_s]; actions [P x H x n_u] (this rank's particles); with a process group the batch spans the ranks: the
+    x0 [n_s], or [P x n_s]: a start per particle (`StaticCemMpc`; the cost of a start outside the polytope is
+    `start_constraint_cost`, not part of this rollout); actions [P x H x n_u] (this rank's particles); with a process group the batch spans the ranks: the
     "zero present" flag is all-reduced (MAX) per step.  Returns dict(obj_cost [P], con_cost [P]); `status` is OR-ed.
     """
     n_s, n_u = ssm.num_states, ssm.num_actions
@@ -526,7 +573,7 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
     arr = lambda field, r, c: torch.tensor(list(field)[:r * c], dtype=torch.float64, device=dev).view(r, c)
     u_min, u_max = arr(env.u_min, 1, n_u), arr(env.u_max, 1, n_u)
     w_abs, target, w_lin = arr(env.obj_w_abs, 1, n_s), arr(env.obj_target, 1, n_s), arr(env.obj_w_lin, 1, n_s)
-    p = x0.reshape(1, n_s).expand(P, n_s).contiguous()
+    p = x0.reshape(-1, n_s).expand(P, n_s).contiguous()
     q = None
     obj = torch.zeros(P, dtype=torch.float64, device=dev)
     con = torch.zeros(P, dtype=torch.float64, device=dev)
@@ -566,6 +613,19 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
             con = con + _lib.SX_STATE_VIOLATION_COST * (inside == 0)
         p, q = p1, q1
     return dict(obj_cost=obj, con_cost=con)
+
+
+def start_constraint_cost(env: _lib.SxEnv, x0: Tensor) -> Tensor:
+    """[P]: SX_STATE_VIOLATION_COST for every start x0 [P x n_s] outside the safe polytope (h_mat x0 - h_vec >= 0 in any
+    row), what sx_cem_rollout_starts adds in its kernel: sx_polytope_distance on the points (an all-zero Q)."""
+    P, n_s = x0.shape
+    dev = x0.device
+    d = torch.empty((P, env.m), dtype=torch.float64, device=dev)
+    inside = torch.empty((P,), dtype=torch.uint8, device=dev)
+    q = torch.zeros((P, n_s, n_s), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().sx_polytope_distance(ctypes.byref(env), P, _lib.ptr(x0.contiguous()), _lib.ptr(q), 1.0, _lib.ptr(d),
+                                               _lib.ptr(inside), _lib.stream_ptr(dev)), 'sx_polytope_distance')
+    return _lib.SX_STATE_VIOLATION_COST * (inside == 0)
 
 
 def cem_rank_refit(con: Tensor, obj: Tensor, actions: Tensor, k: int, *, cost_stride: int = 1,
@@ -1435,3 +1495,170 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                 s.last_perf_actions = best[e:e + 1, self._horizon:]
             best = best[:, :self._horizon]
         return best, found
+
+
+class StaticCemMpc:
+    """The CEM solver of static exploration: the start state is a decision variable of every particle (the reference's
+    ``StaticSafeMPCExploration`` NLP over ``[p_0, u_0, k_ff]``, safempc_exploration.py:56-334; DESIGN.md sections 3.10, 5).
+
+    The CEM row is ``[x0 (n_s) | u_0 .. u_{H-1}]`` with one Gaussian per entry, started from ``[start_mean | 0]`` and
+    ``[start_std | init_std]``.  An iteration is ``sx_cem_rollout_starts`` and one ranking launch over the long rows, which
+    also refits them.  The objective is always the variance objective (SX_OBJ_NEG_VARIANCE); constraints are the
+    environment's own plus SX_STATE_VIOLATION_COST for a start outside the safe polytope.  ``n_restarts`` problems with the
+    same start distribution and their own draws (seed + e) run in the same launches; ``find`` answers with the feasible one
+    of lowest objective.  Exact RBF GPs on one GPU only.
+    """
+
+    def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, start_mean, start_std, n_restarts: int = 1, seed: int = 0, init_std=1.0,
+                 device=None, record_rollouts: bool = False, process_group=None):
+        family = getattr(ssm, 'kernel_family', 'rbf')
+        if family != 'rbf':
+            raise NotImplementedError(f'static exploration is built for exact RBF GPs, not kernel_family {family!r} '
+                                      f'(feature-GP, MC-dropout, JunkDimensionsSSM and step-by-step models)')
+        if process_group is not None:
+            raise NotImplementedError('static exploration is not built for sharded particles (a process group)')
+        n_s, n_u = ssm.num_states, ssm.num_actions
+        if n_restarts < 1:
+            raise ValueError(f'n_restarts={n_restarts} must be at least 1')
+        if num_elites > num_rollouts:
+            raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
+        if num_elites > RANK_MAX_ELITES:
+            raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
+        chunks = rank_chunks(num_rollouts)
+        if chunks > 1 and (num_elites > num_rollouts // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
+            raise ValueError(f'{num_rollouts} particles rank in {chunks} chunks: num_elites={num_elites} is too large for it')
+        self._ssm = ssm
+        self._horizon, self._num_rollouts, self._num_elites = time_horizon, num_rollouts, num_elites
+        self._num_iterations, self._restarts, self._record = num_iterations, int(n_restarts), record_rollouts
+        self._row_len = n_s + time_horizon * n_u
+        self._device = torch.device(device if device is not None else 'cuda:0')
+        as_row = lambda v, n: torch.as_tensor(v, dtype=torch.float64).reshape(-1).expand(n).clone()
+        act_std = torch.as_tensor(init_std, dtype=torch.float64)
+        act_std = (act_std.reshape(time_horizon, -1).expand(time_horizon, n_u) if act_std.dim() > 0
+                   else act_std.expand(time_horizon, n_u))
+        # the first iteration's distribution of the row: [start_mean | 0], [start_std | init_std]
+        self._mean0 = torch.cat([as_row(start_mean, n_s), torch.zeros(time_horizon * n_u, dtype=torch.float64)])
+        self._std0 = torch.cat([as_row(start_std, n_s), act_std.reshape(-1)])
+        self._mean0, self._std0 = self._mean0.to(self._device), self._std0.to(self._device)
+        self._seed = int(seed)
+        self._gens = None       # one generator per restart (seed + e), made with the first draw
+        self.set_env(env)
+        self.last_status = 0
+        self.stepwise_fallbacks = 0
+        self._last_noise = None
+        self.last_rows = None           # [E x L] on the host: every restart's best row of the last `find`
+        self.last_costs = None          # [E x 2] on the host: their (con, obj)
+        self.last_choice = None         # the restart `find` chose, or None
+
+    @property
+    def num_iterations(self) -> int:
+        return self._num_iterations
+
+    @property
+    def n_restarts(self) -> int:
+        return self._restarts
+
+    def set_env(self, env: _lib.SxEnv) -> None:
+        """New problem constants.  The solver keeps a copy of them with the variance objective: static exploration looks for
+        where the model is uncertain (the reference's `cost_func is None` branch, safempc_exploration.py:140-141)."""
+        self._env = _lib.SxEnv.from_buffer_copy(env)
+        self._env.obj_mode = _lib.SX_OBJ_NEG_VARIANCE
+
+    def sample_noise(self) -> Tensor:
+        """[iters x E x P x L] standard normals of one solve: restart e draws from its own generator (seed + e)."""
+        if self._gens is None:
+            self._gens = []
+            for e in range(self._restarts):
+                self._gens.append(torch.Generator(device=self._device))
+                self._gens[-1].manual_seed(self._seed + e)
+        shape = (self._num_iterations, self._num_rollouts, self._row_len)
+        return torch.stack([torch.randn(shape, dtype=torch.float64, device=self._device, generator=g) for g in self._gens],
+                           dim=1)
+
+    def _rollout_stepwise(self, mean: Tensor, std: Tensor, eps: Tensor, status: Tensor):
+        """One iteration's rollout through `cem_rollout_stepwise` with a start per particle, restart by restart."""
+        n_s, n_u = self._ssm.num_states, self._ssm.num_actions
+        rows = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x L]
+        obj, con = [], []
+        for e in range(rows.size(0)):
+            x0 = rows[e, :, :n_s].contiguous()
+            acts = rows[e, :, n_s:].reshape(-1, self._horizon, n_u).contiguous()
+            r = cem_rollout_stepwise(self._ssm, self._env, x0, acts, status=status)
+            obj.append(r['obj_cost'])
+            con.append(r['con_cost'] + start_constraint_cost(self._env, x0))
+        return dict(rows=rows, traj=None, obj_cost=torch.stack(obj), con_cost=torch.stack(con))
+
+    def solve(self, noise: Optional[Tensor] = None, stepwise: bool = False):
+        """The n_restarts solves, in the same launches.  Nothing here synchronises with the host.
+
+        noise: optional [iters x E x P x L] pre-drawn standard normals (parity tests inject them).
+        Returns (best [E x L]: every restart's first-ranked row of the last iteration, costs [E x 2]: its (con, obj),
+        best_ok int32 [E], rollouts per iteration (if recorded), status int32 [1])."""
+        E, P, L, dev = self._restarts, self._num_rollouts, self._row_len, self._device
+        if noise is None:
+            noise = self.sample_noise()
+        if tuple(noise.shape) != (self._num_iterations, E, P, L):
+            raise ValueError(f'noise must be [{self._num_iterations} x {E} x {P} x {L}], got {tuple(noise.shape)}')
+        self._last_noise = noise
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        history: List[Rollouts] = []
+        n_s, n_u = self._ssm.num_states, self._ssm.num_actions
+        mean = self._mean0.expand(E, L).contiguous()
+        std = self._std0.expand(E, L).contiguous()
+
+        def rollout(it, mean, std, rows):
+            eps = noise[it].contiguous()
+            if stepwise:
+                return self._rollout_stepwise(mean, std, eps, status)
+            r = cem_rollout_starts(self._ssm, self._env, self._horizon, mean=mean, std=std, noise=eps,
+                                   want_traj=self._record, status=status)
+            if self._record:
+                for e in range(E):
+                    history.append(Rollouts(r['traj'][e], r['rows'][e, :, n_s:].reshape(P, self._horizon, n_u),
+                                            r['obj_cost'][e], r['con_cost'][e]))
+            return r
+
+        def rank(it, r):
+            # the ranking launch refits the long rows; the last one also hands back the elite rows, whose first is the best
+            # row with its (con, obj)
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['rows'], self._num_elites,
+                                      want_rows=it == self._num_iterations - 1, want_refit=True)
+
+        out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
+        costs = out['elite_rows'][:, 0, :2]
+        return out['best'].view(E, L), costs, out['best_ok'], history, status
+
+    @staticmethod
+    def choose(found, objectives) -> Optional[int]:
+        """The restart whose answer is kept: feasible, lowest objective, lowest index on a tie; None if none is feasible."""
+        chosen = None
+        for e, (ok, obj) in enumerate(zip(found, objectives)):
+            if bool(ok) and (chosen is None or float(obj) < float(objectives[chosen])):
+                chosen = e
+        return chosen
+
+    def find(self, noise: Optional[Tensor] = None):
+        """(x0 [n_s], actions [H x n_u], objective) of the best feasible restart on the host, or None where no restart
+        found a feasible row.  One device -> host hand-off; a NaN raises as `FusedCemMpc.get_actions` does, and a solve
+        whose status has both SX_STATUS_NAN and SX_STATUS_ZERO_FIX is repeated step by step with the same draws."""
+        n_s, n_u, E, L = self._ssm.num_states, self._ssm.num_actions, self._restarts, self._row_len
+        best, costs, best_ok, history, status = self.solve(noise)
+        # the rows travel with their (con, obj): [E x (L + 2)] in the one hand-off
+        words, found, _, host = _hand_off(self, torch.cat([best, costs], dim=1), best_ok, status, None)
+        st = fold_status(words)
+        both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
+        if (st & both) == both:
+            # the reference's whole-batch zero fix-up (see _check_solve): the same draws, step by step
+            self.stepwise_fallbacks += 1
+            best, costs, best_ok, history, status = self.solve(self._last_noise, stepwise=True)
+            words, found, _, host = _hand_off(self, torch.cat([best, costs], dim=1), best_ok, status, None)
+            st = fold_status(words)
+        self.last_status = st
+        self.last_rollouts = history
+        raise_for_status(st, 'StaticCemMpc.find', dump=lambda: save_failure_state(self._ssm, self._mean0[:n_s], None))
+        self.last_rows, self.last_costs = host[:, :L], host[:, L:]
+        self.last_choice = e = self.choose(found, host[:, L + 1])
+        if e is None:
+            return None
+        return host[e, :n_s].clone(), host[e, n_s:L].reshape(self._horizon, n_u).clone(), float(host[e, L + 1])

@@ -1,7 +1,7 @@
 // The exact-GP rollout entries: which form a model's rollout takes (plan_rollout), the launch in
 // that form through the launchers of sx_rw_launch.hpp, sx_stream_launch.hpp and sx_big_launch.hpp, the GP model table, and
-// sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi, sx_cem_rollout_form, sx_cem_rollout_multi_form,
-// sx_cem_rollout_workspace_bytes.  No kernel is compiled here.
+// sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi, sx_cem_rollout_starts, sx_cem_rollout_form,
+// sx_cem_rollout_multi_form, sx_cem_rollout_starts_form, sx_cem_rollout_workspace_bytes.  No kernel is compiled here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -171,6 +171,27 @@ static int launch_rollout_multi(const sx_gp_model* models, const void* table, co
                                                plan.form == SX_FORM_BYOUT, plan.lds, stream);
 }
 
+// The rollout with a start state per particle (sx_cem_rollout_starts) has the streaming kernel only, so it takes
+// plan_rollout's streaming answer: all outputs at once or output by output; a model that needs the workspace path
+// (SX_FORM_BIG) or fits neither form has none.  sx_cem_rollout_starts launches this plan, sx_cem_rollout_starts_form
+// reports it.
+static RolloutPlan plan_rollout_starts(const sx_gp_model* m, int H) {
+    RolloutPlan p = plan_rollout(m, 0, H, false, true);
+    if (p.form == SX_FORM_BIG) p.ok = false;
+    return p;
+}
+
+template <int NS, int NU>
+static int launch_rollout_starts(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, hipStream_t stream) {
+    const RolloutPlan plan = plan_rollout_starts(m, rp.H);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    return launch_rollout_starts<NS, NU>(make_gp_const<NS, NU>(m, kRolloutThreads / 64), rc, cc, rp,
+                                         plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
 // sx_cem_rollout[_elites][_junk] after their argument checks
 static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
                        int64_t workspace_bytes, void* stream) {
@@ -243,6 +264,25 @@ int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int 
                                             E, P, H}, elite_rows, k, mean_out, std_out);
     if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
     return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
+}
+
+int sx_cem_rollout_starts_form(const sx_gp_model* model, int H) {
+    if (!model || H <= 0) return -1;
+    const sx::RolloutPlan plan = sx::plan_rollout_starts(model, H);
+    return plan.ok ? plan.form : -1;
+}
+
+int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
+                          const double* std, const double* noise, double* rows, double* traj, double* sigma,
+                          double* obj_cost, double* con_cost, int32_t* status, void* stream) {
+    if (!model || !env || !rows || !obj_cost || !con_cost || !status || E <= 0 || P <= 0 || H <= 0) return SX_ERR_ARG;
+    if (noise && !(mean && std)) return SX_ERR_ARG;
+    if (model->n_s != env->n_s || model->n_u != env->n_u || model->n_train <= 0 || model->n_pad <= 0) return SX_ERR_ARG;
+    // (x0, q0 and the elite-row fields stay empty: the kernel reads the start of a particle from its row)
+    const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
+#define CALL(NS, NU) sx::launch_rollout_starts<NS, NU>(model, env, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
 }
 
 // E models of one (n_s, n_u) with a training set each: checked before anything touches the device

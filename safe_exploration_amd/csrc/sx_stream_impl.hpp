@@ -1,5 +1,5 @@
-// Bodies of launch_rollout_stream<NS, NU, SH> and launch_rollout_stream_multi<NS, NU>; included by sx_stream_ns*.hip and
-// sx_stream_multi.hip, which instantiate them.
+// Bodies of launch_rollout_stream<NS, NU, SH>, launch_rollout_stream_multi<NS, NU> and launch_rollout_starts<NS, NU>;
+// included by sx_stream_ns*.hip, sx_stream_multi.hip and sx_stream_starts.hip, which instantiate them.
 #pragma once
 #include "sx_launch.hpp"
 #include "sx_stream_launch.hpp"
@@ -47,7 +47,29 @@ int launch_rollout_stream_multi(const GpConst<NS, NS + NU>* table, const ReachCo
     return check_launch();
 }
 
+template <int NS, int NU>
+int launch_rollout_starts(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc,
+                          const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
+                          hipStream_t stream) {
+    const int tiles = (rp.P + SX_TILE - 1) / SX_TILE;
+    if (byout) {
+        if (int r = allow_lds(cem_rollout_starts_kernel<NS, NU, true>, lds)) return r;
+        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_starts_kernel<NS, NU, true>, dim3(rp.E * tiles), dim3(kRolloutThreads),
+               lds, stream, gc, gc.stage_tab, rc, cc, rp);
+    } else {
+        if (int r = allow_lds(cem_rollout_starts_kernel<NS, NU, false>, lds)) return r;
+        launch(SX_PROF_ROLLOUT_FUSED, cem_rollout_starts_kernel<NS, NU, false>, dim3(rp.E * tiles), dim3(kRolloutThreads),
+               lds, stream, gc, gc.stage_tab, rc, cc, rp);
+    }
+    return check_launch();
+}
+
 }  // namespace sx
+
+#define SX_STREAM_STARTS_INSTANTIATE(NS, NU)                                                                         \
+    template int sx::launch_rollout_starts<NS, NU>(                                                                   \
+        const sx::GpConst<NS, NS + NU>&, const sx::ReachConst<NS, NU>&, const sx::CostConst<SX_MAX_M, NS, NU>&,      \
+        const sx::RolloutPtrs&, bool, size_t, hipStream_t);
 
 #define SX_STREAM_MULTI_INSTANTIATE(NS, NU)                                                                             \
     template int sx::launch_rollout_stream_multi<NS, NU>(                                                              \

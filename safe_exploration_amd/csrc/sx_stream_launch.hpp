@@ -1,6 +1,6 @@
 // The compiled shapes of the fused rollout, and the launchers of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
 // BYOUT, SH, MM>).  The launchers' instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
-// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip; built in parallel with the rest); sx_gp_rollout.hip
+// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip; built in parallel with the rest); sx_gp_rollout.hip
 // sees the declarations.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,5 +68,13 @@ template <int NS, int NU>
 int launch_rollout_stream_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
                                 const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
                                 hipStream_t stream);
+
+// Launches cem_rollout_starts_kernel<NS, NU, byout> (sx_cem_rollout_starts: a start state per particle, rp as the
+// SX_ROLLOUT_PS sections of sx_rollout_body.inc read it) with `lds` bytes (rollout_stream_lds_bytes, shift 0).
+// Instantiated for every shift-0 shape in sx_stream_starts.hip.
+template <int NS, int NU>
+int launch_rollout_starts(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc,
+                          const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
+                          hipStream_t stream);
 
 }  // namespace sx

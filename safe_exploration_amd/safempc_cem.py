@@ -15,12 +15,12 @@ from numpy import ndarray
 from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
-from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, multi_family
+from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc, multi_family
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
 from .ssm_cem.gp_ssm_cem import GpCemSSM
-from .ssm_cem.ssm_cem import CemSSM
+from .ssm_cem.ssm_cem import CemSSM, JunkDimensionsSSM
 from .utils import assert_shape, dlqr, get_device
 
 
@@ -368,6 +368,20 @@ class CemSafeMPC(SafeMPC):
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
         self._env_key = key
         return self._mpc
+
+    def static_solver(self, n_restarts: int, sample_mean, sample_std) -> StaticCemMpc:
+        """The solver of static exploration (StaticSafeMPCExploration): the start state is optimised with the actions, from
+        the distribution (sample_mean, sample_std) [n_s], in `n_restarts` problems side by side.  Built over this solver's
+        model, its constraint set with the variance objective, mpc_time_horizon and the cem_num_* settings.  The model is
+        read at solve time, so the solver stays valid across update_model."""
+        if isinstance(self._ssm, JunkDimensionsSSM):
+            raise NotImplementedError('static exploration is not built for JunkDimensionsSSM')
+        env, _ = self._build_env()
+        return StaticCemMpc(self._ssm, env, self._mpc_time_horizon, self._conf.cem_num_rollouts, self._conf.cem_num_elites,
+                            self._conf.cem_num_iterations, start_mean=sample_mean, start_std=sample_std,
+                            n_restarts=n_restarts, seed=int(getattr(self._conf, 'cem_seed', 0)),
+                            init_std=getattr(self._conf, 'cem_init_std', 1.0), device=self._device,
+                            record_rollouts=self._record_rollouts)
 
     def _flat_points(self, states: ndarray) -> Tensor:
         """Point states [E x n_s] as the optimiser's flat states [E x (n_s + n_s^2)] (PQFlattener.flatten(p, None): an

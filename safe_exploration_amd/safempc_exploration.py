@@ -1,7 +1,8 @@
-"""Exploration module over a ready-made SafeMPC: the reference's ``DynamicSafeMPCExploration``
-(``safe_exploration/safempc_exploration.py:357-393``), plus the multi-episode form of ``find_max_variance`` that
+"""Exploration modules over a ready-made SafeMPC: the reference's ``DynamicSafeMPCExploration``
+(``safe_exploration/safempc_exploration.py:357-393``) and ``StaticSafeMPCExploration`` (``:56-334``, over the CEM solver
+with the start state as a decision variable), plus the multi-episode form of ``find_max_variance`` that
 ``exploration_runner`` can call once per iteration for all of its parallel explorations."""
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 from numpy import ndarray
@@ -31,6 +32,65 @@ class DynamicSafeMPCExploration:
 
     def find_max_variance_verbose(self, x_0: ndarray, sol_verbose: bool = False):
         return self.safempc.get_action_verbose(x_0)      # (raises NotImplementedError for the CEM solver, as the reference)
+
+    def update_model(self, x, y, train=False, replace_old=False):
+        self.safempc.update_model(x, y, train, replace_old)
+
+    def get_information_gain(self):
+        return self.safempc.information_gain()
+
+    @property
+    def x_train(self) -> ndarray:
+        return self.safempc.x_train
+
+    def ssm_predict(self, z: ndarray) -> Tuple[ndarray, ndarray]:
+        return self.safempc.ssm_predict(z)
+
+
+class StaticSafeMPCExploration:
+    """Static exploration (reference :56-334): every sample is a distinct (x, u), so the start state is optimised with
+    the actions.  Where the reference solves ``n_restarts_optimizer`` casadi NLPs over ``[p_0, u_0, k_ff]`` from random
+    guesses and keeps the best feasible one (:281-330), this class runs ``n_restarts_optimizer`` CEM problems over the rows
+    ``[x0 | actions]`` side by side (``CemSafeMPC.static_solver``, DESIGN.md sections 3.10 and 5) and keeps the feasible one
+    with the lowest variance objective.  The start distribution is the reference's ``env._sample_start_state(sample_mean,
+    sample_std)`` (normalised); a start outside the safe polytope is infeasible (this library's rule)."""
+
+    def __init__(self, safempc: SafeMPC, env, n_restarts_optimizer: int = 1, sample_mean=None, sample_std=None,
+                 verbosity: int = 1):
+        if not hasattr(safempc, 'static_solver'):
+            raise NotImplementedError('static exploration needs a CemSafeMPC (static_solver): the casadi solver is outside '
+                                      'the accelerated path')
+        self.safempc = safempc
+        self.env = env
+        self.n_s = safempc.state_dimen
+        self.n_u = safempc.action_dimen
+        self.T = safempc.safety_trajectory_length
+        self.n_restarts_optimizer = n_restarts_optimizer
+        self.sample_mean = sample_mean
+        self.sample_std = sample_std
+        self.verbosity = verbosity
+        # env._sample_start_state(mean, std, normalize=True): std * randn + mean, scaled by inv_norm[0]
+        scale = np.asarray(env.inv_norm[0], dtype=np.float64)
+        mean = np.asarray(env.init_m if sample_mean is None else sample_mean, dtype=np.float64) * np.ones(self.n_s)
+        std = np.asarray(env.init_std if sample_std is None else sample_std, dtype=np.float64) * np.ones(self.n_s)
+        self.start_mean, self.start_std = mean * scale, std * np.abs(scale)
+        self.safempc.init_solver(None)
+        self._solver = safempc.static_solver(n_restarts_optimizer, self.start_mean, self.start_std)
+
+    def find_max_variance(self, x0=None, sol_verbose: bool = False) -> Tuple[Optional[ndarray], Optional[ndarray]]:
+        """(x_best [n_s x 1], u_best [n_u x 1]), or (None, None) where no restart found a feasible sample -- reference
+        :281-330.  `x0` is unused, as in the reference ("in static setting we optimize over x_i")."""
+        found = self._solver.find()
+        if found is None:
+            return None, None
+        x_best, actions, obj = found
+        if self.verbosity > 1:
+            print(f'New feasible solution with sigma sum {-obj} found')
+        return np.asarray(x_best, dtype=np.float64).reshape(self.n_s, 1), np.asarray(actions[0], dtype=np.float64).reshape(
+            self.n_u, 1)
+
+    def find_max_variance_verbose(self, x0=None, sol_verbose: bool = False):
+        raise NotImplementedError('static exploration has no verbose solve: the runner disables verification in static mode')
 
     def update_model(self, x, y, train=False, replace_old=False):
         self.safempc.update_model(x, y, train, replace_old)
