@@ -658,6 +658,48 @@ int sx_cem_perf_rollout_taylor_multi(const sx_gp_model* models, const void* tabl
  * sx_cem_perf_rollout_taylor_form. */
 int sx_cem_perf_rollout_taylor_multi_form(const sx_gp_model* models, int E, int n_perf);
 
+/* ---- Cautious MPC: the chance-constrained Taylor rollout ----
+ * The trajectory of sx_cem_perf_rollout_taylor on its own -- no safety rollout in front of it -- with the reference's
+ * chance constraints on every step.  A particle's row is k_ff_0 .. k_ff_{T-1} [T x n_u]; mu_0 = x0[e], Sigma_0 = 0,
+ * K = env->k_fb, beta = env->beta.  For t = 0 .. T - 1:
+ *   control  t = 0:  k_ff_0 outside [u_min, u_max] adds SX_ACTION_VIOLATION_COST
+ *            t >= 1: s_c = beta sqrt(K_c Sigma_t K_c^T); k_ff_t[c] + s_c - u_max[c] >= 0 or u_min[c] - k_ff_t[c] + s_c >= 0
+ *                    for any control c adds SX_ACTION_VIOLATION_COST, once per step
+ *   (mean_t, var_t, J_t), M, Hm, G_t, mu_{t+1}, Sigma_{t+1}: as sx_cem_perf_rollout_taylor, at [mu_t, k_ff_t]
+ *   state    some row j of env's polytope with h_j . mu_{t+1} + beta sqrt(h_j^T Sigma_{t+1} h_j) - h_vec_j >= 0 adds
+ *            SX_STATE_VIOLATION_COST, once per step (m = 0: none)
+ *   obj += cost(mu_{t+1}, diag G_t)          SX_OBJ_AFFINE_ABS | SX_OBJ_NEG_VARIANCE, as sx_cem_perf_rollout_taylor
+ * A distance d >= 0 violates and a NaN distance counts as inside, as everywhere.  Which polytope env->{m, h_mat, h_vec} is
+ * (the reference checks the obstacle polytope h_mat_obs) is the caller's choice.
+ *   mean, std    dev [E x T x n_u], noise dev [E x P x T x n_u]: the rows are drawn as mean + std * noise and written; with
+ *                noise NULL the rows are an input
+ *   rows         dev [E x P x T x n_u]
+ *   obj_cost     dev [E x P]   overwritten; NaN, with SX_STATUS_NAN in status, on a non-finite mu, var, G or Sigma
+ *   con_cost     dev [E x P]   OVERWRITTEN: there is no safety rollout before this one
+ *   traj         dev [E x P x T x n_s] | NULL          mu_1 .. mu_T
+ *   sigma        dev [E x P x T x n_s] | NULL          diag G_0 .. diag G_{T-1}
+ *   cov          dev [E x P x T x n_s x n_s] | NULL    Sigma_1 .. Sigma_T, symmetric to the bit
+ *   margins      dev [E x P x T x 2] | NULL            per step: the largest state row distance (-inf for m = 0), the
+ *                largest of the 2 n_u control distances (at t = 0 the plain box's k - u_max, u_min - k)
+ *   propagate    0: every GP step starts from Sigma_t = 0, so G_t = var_t and Sigma_{t+1} = diag(var_t) (the reference's
+ *                perf_trajectory = 'mean_equivalent', one_step_mean_equivalent); the control constraint of step t still
+ *                sees diag(var_{t-1})
+ * The Taylor kernel's layout and forms (SX_FORM_STREAM, else SX_FORM_BYOUT; n_pad <= 1024), the step constants plus beta in
+ * LDS behind the tile's T actions.  A tile's numbers do not depend on P or on the grid.
+ * SX_ERR_ARG (before any device access) for null pointers, T < 1, non-positive sizes, noise without mean / std, an
+ * unpacked model, a shape different from env's, an obj_mode that is neither of the two; SX_ERR_UNSUPPORTED (before any
+ * launch) for m > SX_MAX_M, a shape without a kernel or a model without a form.
+ * Replaces: generate_safety_constraints and _generate_control_constraint (cautious_mpc.py:337-442) over
+ * multi_step_taylor_symbolic / mean_equivalent_multistep, which CautiousMPC.init_solver hands to IPOPT as one NLP. */
+int sx_cem_cautious_rollout(const sx_gp_model* model, const sx_env* env, int E, int P, int T, const double* x0,
+                            const double* mean, const double* std, const double* noise, double* rows, double* obj_cost,
+                            double* con_cost, double* traj, double* sigma, double* cov, double* margins, int propagate,
+                            int32_t* status, void* stream);
+/* The form sx_cem_cautious_rollout launches for this model and T (no launch, no device access): SX_FORM_STREAM or
+ * SX_FORM_BYOUT, or < 0 for bad arguments (T < 1 among them) and wherever the entry would answer SX_ERR_UNSUPPORTED for
+ * the model: the contract of sx_cem_perf_rollout_taylor_form (cautious_mpc.py has no such notion). */
+int sx_cem_cautious_rollout_form(const sx_gp_model* model, int T);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -133,6 +133,9 @@ SIGNATURES = {
     'sx_cem_perf_rollout_taylor_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int, c_int,
                                                  c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
     'sx_cem_perf_rollout_taylor_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
+    'sx_cem_cautious_rollout': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 11
+                                + [c_int, c_void_p, c_void_p]),
+    'sx_cem_cautious_rollout_form': (c_int, [POINTER(SxGpModel), c_int]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -1662,3 +1662,202 @@ class StaticCemMpc:
         if e is None:
             return None
         return host[e, :n_s].clone(), host[e, n_s:L].reshape(self._horizon, n_u).clone(), float(host[e, L + 1])
+
+
+# ---- Cautious MPC ----------------------------------------------------------------------------------
+def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, mean: Optional[Tensor] = None,
+                         std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                         propagate: bool = True, want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
+                         want_margins: bool = False, status: Optional[Tensor] = None):
+    """Thin wrapper over sx_cem_cautious_rollout: the chance-constrained Taylor rollout of Cautious MPC (exact RBF GPs only).
+    x0 [E x n_s]; the rows k_ff_0 .. k_ff_{T-1} either drawn (`mean`, `std` [E x T x n_u], `noise` [E x P x T x n_u]) or
+    given as `rows` [E x P x T x n_u].  Every step adds SX_ACTION_VIOLATION_COST where the control k_ff_t +- env.beta
+    sqrt(K_c Sigma_t K_c^T) leaves the action box (the plain box at t = 0) and SX_STATE_VIOLATION_COST where the ellipsoid
+    (mu_{t+1}, env.beta, Sigma_{t+1}) leaves env's polytope; `propagate=False` starts every GP step from Sigma_t = 0 (the
+    reference's 'mean_equivalent').
+    Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj [E x P x T x n_s] | None, sigma (same shape; diag G_t) | None,
+    cov [E x P x T x n_s x n_s] | None, margins [E x P x T x 2] (largest state, largest control distance) | None, status)."""
+    _require_rbf([ssm], x0)
+    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
+    T = int(T)
+    if T < 1:
+        raise ValueError(f'the cautious rollout needs T >= 1 steps, got T={T}')
+    if x0.dim() != 2 or x0.size(1) != n_s:
+        raise ValueError(f'x0 must be [E x {n_s}], got {tuple(x0.shape)}')
+    E = x0.size(0)
+    if noise is not None:
+        if rows is not None:
+            raise ValueError('either noise (the rows are drawn) or rows (the rows are given), not both')
+        if mean is None or std is None:
+            raise ValueError('noise needs mean and std')
+        if noise.dim() != 4 or tuple(noise.shape) != (E, noise.size(1), T, n_u) or not noise.is_contiguous():
+            raise ValueError(f'noise must be a contiguous [{E} x P x {T} x {n_u}] tensor, got {tuple(noise.shape)}')
+        for name, v in (('mean', mean), ('std', std)):
+            if tuple(v.shape) != (E, T, n_u) or not v.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous [{E} x {T} x {n_u}] tensor, got {tuple(v.shape)}')
+        P = noise.size(1)
+        rows = torch.empty((E, P, T, n_u), dtype=torch.float64, device=dev)
+    elif rows is None or rows.dim() != 4 or tuple(rows.shape) != (E, rows.size(1), T, n_u) or not rows.is_contiguous():
+        raise ValueError(f'without noise, rows must be a contiguous [{E} x P x {T} x {n_u}] tensor')
+    else:
+        P = rows.size(1)
+    new = lambda *shape: torch.empty((E, P, T) + shape, dtype=torch.float64, device=dev)
+    traj = new(n_s) if want_traj else None
+    sigma = new(n_s) if want_sigma else None
+    cov = new(n_s, n_s) if want_cov else None
+    margins = new(2) if want_margins else None
+    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
+    con = torch.empty((E, P), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    entry = 'sx_cem_cautious_rollout'
+    code = getattr(_lib.lib(), entry)(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, T, _lib.ptr(x0.contiguous()),
+                                      _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(rows), _lib.ptr(obj),
+                                      _lib.ptr(con), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(cov), _lib.ptr(margins),
+                                      int(bool(propagate)), _lib.ptr(status), _lib.stream_ptr(dev))
+    if code == _lib.SX_ERR_UNSUPPORTED:
+        raise _no_form(entry, 'cautious', ssm, T)(n_s, n_u)
+    _lib.check(code, entry)
+    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, cov=cov, margins=margins, status=status)
+
+
+class CautiousCemMpc:
+    """The CEM solver of Cautious MPC (the reference's ``CautiousMPC`` NLP over ``k_ff``, cautious_mpc.py:136-200; DESIGN.md
+    section 3.11): E independent problems, the row ``k_ff_0 .. k_ff_{T-1}`` with one Gaussian per entry.  An iteration is
+    one ``sx_cem_cautious_rollout`` -- the Taylor trajectory (``propagate=False``: mean-equivalent) under the fixed gain
+    ``env.k_fb`` with the chance constraints at ``env.beta`` on every step -- and one ranking launch, which also refits.
+    ``env``'s polytope is the one the states are held in; its objective is the separable one or the variance objective, or
+    an ``objective_hook`` evaluated on the recorded means.  Exact RBF GPs on one GPU only.
+    """
+
+    def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, propagate: bool = True, device=None, seed: int = 0, init_std=1.0,
+                 record_rollouts: bool = False, process_group=None):
+        if isinstance(ssm, (list, tuple)):
+            raise ValueError('CautiousCemMpc solves its problems over ONE model (a GP per problem is not built)')
+        family = getattr(ssm, 'kernel_family', 'rbf')
+        if family != 'rbf':
+            raise NotImplementedError(f'Cautious MPC is built for exact RBF GPs, not kernel_family {family!r} '
+                                      f'(feature-GP, MC-dropout, JunkDimensionsSSM and step-by-step models)')
+        if process_group is not None:
+            raise NotImplementedError('Cautious MPC is not built for sharded particles (a process group)')
+        if time_horizon < 1:
+            raise ValueError(f'time_horizon={time_horizon} must be at least 1')
+        if num_elites > num_rollouts:
+            raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
+        if num_elites > RANK_MAX_ELITES:
+            raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
+        chunks = rank_chunks(num_rollouts)
+        if chunks > 1 and (num_elites > num_rollouts // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
+            raise ValueError(f'{num_rollouts} particles rank in {chunks} chunks: num_elites={num_elites} is too large for it')
+        self._ssm = ssm
+        self._horizon, self._num_rollouts, self._num_elites = int(time_horizon), int(num_rollouts), int(num_elites)
+        self._num_iterations, self._record, self._propagate = int(num_iterations), bool(record_rollouts), bool(propagate)
+        self._device = torch.device(device if device is not None else 'cuda:0')
+        std = torch.as_tensor(init_std, dtype=torch.float64)
+        n_u = ssm.num_actions
+        self._init_std = (std.reshape(self._horizon, -1).expand(self._horizon, n_u) if std.dim() > 0
+                          else std.expand(self._horizon, n_u)).clone().to(self._device)
+        self._gen = torch.Generator(device=self._device)
+        self._gen.manual_seed(int(seed))
+        self._objective_hook = None
+        self.set_env(env)
+        self.last_status = 0
+        self.stepwise_fallbacks = 0
+        self._last_noise = self._last_actions = None
+        self.last_rollouts: List[Rollouts] = []
+
+    @property
+    def num_iterations(self) -> int:
+        return self._num_iterations
+
+    def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
+        """New problem constants.  `objective_hook`, if given, is an ``Environment.objective_cost_function`` without a
+        kernel form: it is evaluated with torch on the recorded means mu_1 .. mu_T, T small launches per iteration."""
+        self._env = env
+        self._objective_hook = objective_hook
+
+    def sample_noise(self, episodes: int = 1) -> Tensor:
+        """[iters x E x P x T x n_u] standard normals of one solve, from this solver's generator."""
+        return torch.randn((self._num_iterations, episodes, self._num_rollouts, self._horizon, self._ssm.num_actions),
+                           dtype=torch.float64, device=self._device, generator=self._gen)
+
+    def solve(self, x0: Tensor, noise: Optional[Tensor] = None, init_mean: Optional[Tensor] = None,
+              init_std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, List[Rollouts], Tensor]:
+        """E independent solves from x0 [E x n_s].  Nothing here synchronises with the host.
+
+        noise: optional [iters x E x P x T x n_u] pre-drawn standard normals (parity tests inject them); init_mean /
+        init_std [E x T x n_u]: the first iteration's distribution (default: zero mean, the constructor's init_std).
+        Returns (best [E x T x n_u], best_ok int32 [E], rollouts per iteration (if recorded), status int32 [1])."""
+        T, n_u, E, dev = self._horizon, self._ssm.num_actions, x0.size(0), x0.device
+        if noise is None:
+            noise = self.sample_noise(E)
+        if tuple(noise.shape) != (self._num_iterations, E, self._num_rollouts, T, n_u):
+            raise ValueError(f'noise must be [{self._num_iterations} x {E} x {self._num_rollouts} x {T} x {n_u}], got '
+                             f'{tuple(noise.shape)}')
+        self._last_noise, self._last_actions = noise, None
+        mean = (init_mean.to(dev, torch.float64).reshape(E, T, n_u).contiguous() if init_mean is not None
+                else torch.zeros((E, T, n_u), dtype=torch.float64, device=dev))
+        std = (init_std.to(dev, torch.float64).reshape(E, T, n_u).contiguous() if init_std is not None
+               else self._init_std.to(dev).expand(E, T, n_u).contiguous())
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        history: List[Rollouts] = []
+        hook, n_s = self._objective_hook, self._ssm.num_states
+
+        def rollout(it, mean, std, rows):
+            r = cem_cautious_rollout(self._ssm, self._env, x0, T, mean=mean.contiguous(), std=std.contiguous(),
+                                     noise=noise[it].contiguous(), propagate=self._propagate,
+                                     want_traj=self._record or hook is not None, want_sigma=self._record,
+                                     want_cov=self._record, status=status)
+            if hook is not None:
+                obj = torch.zeros_like(r['obj_cost'])
+                for t in range(T):
+                    obj += hook(r['traj'][:, :, t].reshape(-1, n_s)).reshape(obj.shape)
+                r['obj_cost'] = obj.contiguous()
+            self._last_actions = r['rows']
+            if self._record:
+                for e in range(E):
+                    history.append(Rollouts(None, r['rows'][e], r['obj_cost'][e], r['con_cost'][e],
+                                            perf_trajectories=r['traj'][e], perf_sigma=r['sigma'][e], perf_cov=r['cov'][e]))
+            return r
+
+        def rank(it, r):
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['rows'], self._num_elites, want_refit=True)
+
+        out = _cem_iterations(self._num_iterations, rollout, rank, mean, std)
+        return out['best'].view(E, T, n_u), out['best_ok'], history, status
+
+    def _solve_checked(self, x0: Tensor, where: str, q_block: Optional[Tensor] = None, init_mean: Optional[Tensor] = None):
+        """`solve` and the ONE device -> host hand-off (`_check_solve`).  Returns (best [E x T x n_u] on the host, found
+        bool [E] on the host, rollouts)."""
+        if q_block is not None and not q_block.is_contiguous():
+            q_block = q_block.contiguous()
+        best, best_ok, history, status = self.solve(x0, init_mean=init_mean)
+        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where, [(self, slice(None))])
+        self.last_rollouts = history
+        return best_host, found, history
+
+    def get_actions_batch(self, states: Tensor, init_mean: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, List[Rollouts]]:
+        """E independent problems at once: flat start states [E x (n_s + n_s^2)], all points (as
+        ``FusedCemMpc.get_actions_batch``).  `init_mean` [E x T x n_u]: the warm start.  Returns (rows [E x T x n_u] on the
+        host, found bool [E] on the host, rollouts)."""
+        n_s = self._ssm.num_states
+        if states.dim() != 2 or states.size(1) != n_s + n_s * n_s:
+            raise ValueError(f'Wanted shape (E, {n_s + n_s * n_s}), got {tuple(states.shape)}')
+        states = states.to(self._device, torch.float64)
+        return self._solve_checked(states[:, :n_s].contiguous(), 'get_actions_batch', q_block=states[:, n_s:],
+                                   init_mean=init_mean)
+
+    def get_actions(self, state: Tensor, init_mean: Optional[Tensor] = None) -> Tuple[Optional[Tensor], List[Rollouts]]:
+        """state: the flat start state [1 x (n_s + n_s^2)] with an all-zero Q block.  Returns (row [T x n_u] on the host
+        | None where no feasible row was found, rollouts)."""
+        best, found, history = self.get_actions_batch(state.reshape(1, -1), init_mean=init_mean)
+        if not bool(found[0]):
+            return None, history
+        return best[0], history
+
+    def evaluate(self, x0: Tensor, rows: Tensor):
+        """The rollout of given rows [E x P x T x n_u] from x0 [E x n_s] with every output: what a verbose caller reads."""
+        return cem_cautious_rollout(self._ssm, self._env, x0.to(self._device, torch.float64), self._horizon,
+                                    rows=rows.to(self._device, torch.float64).contiguous(), propagate=self._propagate,
+                                    want_traj=True, want_sigma=True, want_cov=True, want_margins=True)
