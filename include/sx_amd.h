@@ -700,6 +700,54 @@ int sx_cem_cautious_rollout(const sx_gp_model* model, const sx_env* env, int E, 
  * the model: the contract of sx_cem_perf_rollout_taylor_form (cautious_mpc.py has no such notion). */
 int sx_cem_cautious_rollout_form(const sx_gp_model* model, int T);
 
+/* ---- The PILCO saturating cost of a state Gaussian, as a kernel objective of the Taylor rollouts ---------------------------
+ * What the reference's cart-pole configs hand to init_solver (defaultconfig_episode.py:113-159 over utils_casadi.py:178-363,
+ * trig_aug with a = 1, keep_radian = False).  For (mu [n_s], Sigma [n_s x n_s]) and an optional angle index i = trig_idx:
+ *   e0 = exp(-Sigma_ii / 2), s = e0 sin mu_i, c = e0 cos mu_i, e1 = exp(-2 Sigma_ii)
+ *   V_ss = (1 - e1 cos 2 mu_i) / 2 - s^2,  V_cc = (1 + e1 cos 2 mu_i) / 2 - c^2,  V_sc = e1 sin(2 mu_i) / 2 - s c
+ *   Cov(x, sin) = Sigma[:, i] c,  Cov(x, cos) = -Sigma[:, i] s
+ *   m~ = [mu without entry i, s, c] (n_a = n_s + 1), S~ the matching covariance; without an angle m~ = mu, S~ = Sigma, n_a = n_s
+ *   loss = 1 - exp(-1/2 d^T W (I + S~ W)^-1 d) / sqrt(det(I + S~ W)),  d = m~ - target,  W = V V^T
+ * evaluated in the symmetric form y = V^T d, S = I_k + V^T S~ V, L = chol(S), loss = 1 - exp(-|L^-1 y|^2 / 2) / prod diag L. */
+#define SX_SAT_MAX_DIM (SX_MAX_NS + 1)
+typedef struct sx_sat_cost {
+    int32_t trig_idx;                                /* -1: no augmentation; else 0 .. n_s-1 */
+    int32_t rank;                                    /* k, 1 .. n_a */
+    double target[SX_SAT_MAX_DIM];                   /* z [n_a] */
+    double v[SX_SAT_MAX_DIM * SX_SAT_MAX_DIM];       /* V [n_a x k] row-major, W = V V^T */
+} sx_sat_cost;
+
+/* The cost alone, one particle per lane: loss[p] of (mu[p], cov[p]), p < P (dev [P x n_s], [P x n_s x n_s], [P]).  A
+ * non-finite loss is stored as NaN and sets SX_STATUS_NAN in *status (dev int32, or-ed into).
+ * SX_ERR_ARG (before any device access) for null pointers, n_s outside 1 .. SX_MAX_NS, P <= 0, trig_idx outside
+ * -1 .. n_s-1, rank outside 1 .. n_a, a non-finite constant. */
+int sx_sat_cost_eval(const sx_sat_cost* cost, int n_s, int P, const double* mu, const double* cov, double* loss,
+                     int32_t* status, void* stream);
+
+/* sx_cem_perf_rollout_taylor, sx_cem_perf_rollout_taylor_multi and sx_cem_cautious_rollout with the saturating cost as the
+ * objective: obj_cost = sum_t loss(mu_{t+1}, Sigma_{t+1}) over the (mu, Sigma) the step holds (generic_cost: stage and
+ * terminal cost are the same function); env->obj_mode is not read.  Everything else the parent entry computes is the
+ * parent's, bit for bit.  With propagate = 0 the cautious rollout prices Sigma_{t+1} = diag(var_t).  A non-finite loss sets
+ * SX_STATUS_NAN and makes the particle's objective NaN.  The cost's constants travel as a kernel argument: the launch is
+ * the form the parent's _form query reports, with the parent's LDS plan and limits.
+ * SX_ERR_ARG (before any device access) for a NULL cost, trig_idx outside -1 .. n_s-1, rank outside 1 .. n_a, a non-finite
+ * constant, and whatever the parent entry refuses (but for obj_mode); SX_ERR_UNSUPPORTED exactly where the parent answers it. */
+int sx_cem_perf_rollout_taylor_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
+                                   int n_perf, int r, const double* x0, const double* safe_actions, const double* tail_mean,
+                                   const double* tail_std, const double* tail_noise, double* rows, double* obj_cost,
+                                   double* con_cost, double* perf_traj, double* perf_sigma, double* perf_cov,
+                                   int terminal_safety, int32_t* status, void* stream);
+int sx_cem_perf_rollout_taylor_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env,
+                                         const sx_sat_cost* cost, int E, int P, int H, int n_perf, int r, const double* x0,
+                                         const double* safe_actions, const double* tail_mean, const double* tail_std,
+                                         const double* tail_noise, double* rows, double* obj_cost, double* con_cost,
+                                         double* perf_traj, double* perf_sigma, double* perf_cov, int terminal_safety,
+                                         int32_t* status, void* stream);
+int sx_cem_cautious_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int T,
+                                const double* x0, const double* mean, const double* std, const double* noise, double* rows,
+                                double* obj_cost, double* con_cost, double* traj, double* sigma, double* cov,
+                                double* margins, int propagate, int32_t* status, void* stream);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -10,6 +10,7 @@ SX_MAX_NS = 4
 SX_MAX_NU = 2
 SX_MAX_D = SX_MAX_NS + SX_MAX_NU
 SX_MAX_M = 16
+SX_SAT_MAX_DIM = SX_MAX_NS + 1
 SX_TILE = 16
 SX_GP_FIT_ENTRY_BYTES = 360
 SX_FEAT_MAX_WIDTH = 32
@@ -61,6 +62,11 @@ class SxEnv(Structure):
                 ('h_vec', c_double * SX_MAX_M), ('u_min', c_double * SX_MAX_NU), ('u_max', c_double * SX_MAX_NU),
                 ('obj_w_abs', c_double * SX_MAX_NS), ('obj_target', c_double * SX_MAX_NS),
                 ('obj_w_lin', c_double * SX_MAX_NS)]
+
+
+class SxSatCost(Structure):
+    _fields_ = [('trig_idx', c_int32), ('rank', c_int32), ('target', c_double * SX_SAT_MAX_DIM),
+                ('v', c_double * (SX_SAT_MAX_DIM * SX_SAT_MAX_DIM))]
 
 
 # name -> (restype, argtypes): exactly the entry points include/sx_amd.h declares
@@ -136,6 +142,14 @@ SIGNATURES = {
     'sx_cem_cautious_rollout': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 11
                                 + [c_int, c_void_p, c_void_p]),
     'sx_cem_cautious_rollout_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_sat_cost_eval': (c_int, [POINTER(SxSatCost), c_int, c_int] + [c_void_p] * 5),
+    'sx_cem_perf_rollout_taylor_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int,
+                                               c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
+    'sx_cem_perf_rollout_taylor_sat_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxSatCost), c_int,
+                                                     c_int, c_int, c_int, c_int] + [c_void_p] * 11
+                                             + [c_int, c_void_p, c_void_p]),
+    'sx_cem_cautious_rollout_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int]
+                                    + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

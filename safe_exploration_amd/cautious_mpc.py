@@ -16,6 +16,7 @@ from numpy import ndarray
 
 from . import _lib
 from .cem_mpc import CautiousCemMpc, Rollouts
+from .costs import SaturatingCost
 from .gp_reachability_pytorch import make_env
 from .safempc import SafeMPC
 from .safempc_cem import LqrFeedbackController, MpcResult, objective_spec
@@ -75,6 +76,7 @@ class CautiousCemMPC(SafeMPC):
         self._record_rollouts = bool(getattr(conf, 'plot_cem_optimisation', False))
         self._injected_mpc = mpc is not None
         self._mpc = mpc
+        self._cost = None      # init_solver's SaturatingCost
         self._env_key = None
         self._objective_probe = torch.tensor([[0.3] * n_s, [-0.7] * n_s], dtype=torch.float64)
         # the reference's ladder state (cautious_mpc.py:64, 273-275): no solution yet, so the first failure is answered by k_fb
@@ -117,7 +119,13 @@ class CautiousCemMPC(SafeMPC):
         return x_train.detach().cpu().numpy()
 
     def init_solver(self, cost_func=None) -> None:
-        pass
+        """A `costs.SaturatingCost` becomes the optimiser's objective, priced in the rollout kernel on every (mean,
+        covariance) of the plan (what the reference's casadi configs hand over here); any other value is ignored: the
+        objective is then the environment's."""
+        if isinstance(cost_func, SaturatingCost):
+            self._cost = cost_func
+            if self._mpc is not None:
+                self._mpc.set_cost(cost_func)
 
     # ---- the fused optimiser --------------------------------------------------------------------------------------
     def _build_env(self) -> Tuple[_lib.SxEnv, bool]:
@@ -146,6 +154,8 @@ class CautiousCemMPC(SafeMPC):
                                        device=self._device, seed=int(getattr(self._conf, 'cem_seed', 0)),
                                        init_std=getattr(self._conf, 'cem_init_std', 1.0),
                                        record_rollouts=self._record_rollouts)
+            if self._cost is not None:
+                self._mpc.set_cost(self._cost)
         self._mpc.set_env(env, objective_hook=self._env.objective_cost_function if needs_hook else None)
         self._env_key = key
         return self._mpc

@@ -18,6 +18,7 @@ import torch
 from torch import Tensor
 
 from . import _lib, distributed
+from .costs import SaturatingCost
 from .gp_reachability_pytorch import raise_for_status, save_failure_state
 from .ssm_cem.gp_ssm_cem import GpCemSSM
 
@@ -380,21 +381,36 @@ def perf_kind(perf_variance: bool, perf_type: str) -> str:
     return 'taylor' if perf_type == 'taylor' else 'variance' if perf_variance else 'mean'
 
 
+def _cost_args(cost, ssm) -> tuple:
+    """What a `cost` adds to the arguments of a rollout entry behind `env`: nothing, or its sx_sat_cost (for `ssm`'s states)."""
+    if cost is None:
+        return ()
+    if not isinstance(cost, SaturatingCost):
+        raise TypeError(f'cost must be a costs.SaturatingCost or None, got {type(cost).__name__}')
+    n_s = ssm.num_states
+    if cost.n_s != n_s:
+        raise ValueError(f'the cost is built for n_s = {cost.n_s}, the model has n_s = {n_s}')
+    return (ctypes.byref(cost.struct),)
+
+
 def cem_perf_rollout_taylor(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, *,
                             safe_actions: Tensor, obj_cost: Tensor, con_cost: Tensor, status: Tensor,
                             tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
                             tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None, want_traj: bool = False,
-                            want_sigma: bool = False, want_cov: bool = False, terminal_safety: bool = False):
+                            want_sigma: bool = False, want_cov: bool = False, terminal_safety: bool = False, cost=None):
     """Thin wrapper over sx_cem_perf_rollout_taylor: `cem_perf_rollout_var` with the state covariance propagated to first
     order under the fixed feedback `env.k_fb` -- Sigma_{t+1} = H Sigma_t H^T + diag(var_t), and the objective sees
     diag(G_t) = var_t + diag(M Sigma_t M^T).  Arguments as `cem_perf_rollout_var`; `want_sigma` returns diag(G_t), `want_cov`
     Sigma_1 .. Sigma_{n_perf} [E x P x n_perf x n_s x n_s]; `terminal_safety` adds the state-violation cost where the
-    ellipsoid (mu_s, Sigma_s), s = horizon + 2, leaves the safe polytope (needs n_perf >= horizon + 2).
+    ellipsoid (mu_s, Sigma_s), s = horizon + 2, leaves the safe polytope (needs n_perf >= horizon + 2).  `cost` (a
+    `costs.SaturatingCost`) selects sx_cem_perf_rollout_taylor_sat: obj_cost is the sum of the cost over (mu_{t+1},
+    Sigma_{t+1}) and env.obj_mode is not read; everything else is unchanged.
     Returns dict(rows, obj_cost, con_cost, perf_traj | None, perf_sigma | None, perf_cov | None, status)."""
     _require_rbf([ssm], x0)
     _check_terminal_safety(terminal_safety, n_perf, horizon)
-    head = (ctypes.byref(ssm.device_model), ctypes.byref(env))
-    return _perf_rollout('sx_cem_perf_rollout_taylor', head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
+    head = (ctypes.byref(ssm.device_model), ctypes.byref(env)) + _cost_args(cost, ssm)
+    entry = 'sx_cem_perf_rollout_taylor' + ('_sat' if cost is not None else '')
+    return _perf_rollout(entry, head, [ssm], x0, horizon, n_perf, r, safe_actions=safe_actions,
                          obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
                          unsupported=_no_form('sx_cem_perf_rollout_taylor', 'Taylor', ssm, n_perf), want_cov=bool(want_cov),
@@ -489,18 +505,19 @@ def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0:
                                   tail_mean: Optional[Tensor] = None, tail_std: Optional[Tensor] = None,
                                   tail_noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
                                   want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
-                                  terminal_safety: bool = False, table=None):
+                                  terminal_safety: bool = False, table=None, cost=None):
     """`cem_perf_rollout_taylor` for E problems with an exact GP each (ssms[e] for problem e) in one launch
     (sx_cem_perf_rollout_taylor_multi).  There is one `env`: the feedback gain, the safe polytope and the terminal-safety
     step are the same for all problems.  Buffers as in the single-model wrapper, per problem; `status` is int32 [E], one
     word per problem.  `table` keeps the device table between calls: the `GpModelTable` of `cem_rollout_multi` (a fresh
-    one is built otherwise).  Raises FusedMultiUnsupported where the library has no single launch for the models (before
-    any launch)."""
-    entry = 'sx_cem_perf_rollout_taylor_multi'
+    one is built otherwise).  `cost` selects sx_cem_perf_rollout_taylor_sat_multi, as in the single-model wrapper.  Raises
+    FusedMultiUnsupported where the library has no single launch for the models (before any launch)."""
+    entry = 'sx_cem_perf_rollout_taylor_sat_multi' if cost is not None else 'sx_cem_perf_rollout_taylor_multi'
     models, dev_table, unsupported = _perf_multi_preamble(entry, "'taylor' performance rollout", ssms, x0, n_perf, status,
                                                           table, GpModelTable, terminal_safety=terminal_safety,
                                                           horizon=horizon)
-    return _perf_rollout(entry, (models, _lib.ptr(dev_table), ctypes.byref(env)), ssms, x0, horizon, n_perf, r, safe_actions=safe_actions,
+    head = (models, _lib.ptr(dev_table), ctypes.byref(env)) + _cost_args(cost, ssms[0])
+    return _perf_rollout(entry, head, ssms, x0, horizon, n_perf, r, safe_actions=safe_actions,
                          obj_cost=obj_cost, con_cost=con_cost, status=status, tail_mean=tail_mean, tail_std=tail_std,
                          tail_noise=tail_noise, rows=rows, want_traj=want_traj, want_sigma=bool(want_sigma),
                          unsupported=unsupported, want_cov=bool(want_cov), terminal_safety=terminal_safety)
@@ -508,13 +525,14 @@ def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0:
 
 def _launch_perf(kind: str, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, safety: dict,
                  mean: Tensor, std: Tensor, tail_noise: Tensor, status: Tensor, *, multi: bool = False,
-                 want_traj: bool = False, record: bool = False, terminal_safety: bool = False, table=None):
+                 want_traj: bool = False, record: bool = False, terminal_safety: bool = False, table=None, cost=None):
     """The one performance launch of a CEM iteration, for `FusedCemMpc.solve` (ssms = [the model]) and
     `MultiModelPerfCemMpc.solve` (`multi`: a model per problem, and the solver's `table` for the kind): the rollout of
     `kind` (`perf_kind`) behind the safety rollout's result `safety`, its tail drawn from the columns past `horizon` of the
     full-row `mean` / `std` with `tail_noise`.  `want_traj` asks for the means; `record` for all the variance and Taylor
-    forms carry (means, variances, covariances).  A multi-model solve asks for neither.  The wrappers are looked up on the
-    module when called.  Returns the wrapper's dict."""
+    forms carry (means, variances, covariances).  A multi-model solve asks for neither.  `cost` (Taylor only): the
+    saturating cost as the kernel's objective.  The wrappers are looked up on the module when called.  Returns the
+    wrapper's dict."""
     kw = dict(safe_actions=safety['actions'], obj_cost=safety['obj_cost'].contiguous(),
               con_cost=safety['con_cost'].contiguous(), status=status, tail_mean=mean[:, horizon:].contiguous(),
               tail_std=std[:, horizon:].contiguous(), tail_noise=tail_noise)
@@ -525,7 +543,7 @@ def _launch_perf(kind: str, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon
     else:
         kw.update(want_traj=want_traj or record, want_sigma=record, **(dict(want_cov=record) if kind == 'taylor' else {}))
     if kind == 'taylor':
-        kw.update(terminal_safety=terminal_safety)
+        kw.update(terminal_safety=terminal_safety, **({} if cost is None else dict(cost=cost)))
     name = 'cem_perf_rollout' + {'mean': '', 'variance': '_var', 'taylor': '_taylor'}[kind]
     if multi:
         name = 'cem_perf_rollout_taylor_multi' if kind == 'taylor' else 'cem_perf_rollout_multi'
@@ -774,6 +792,22 @@ def _check_solve(owner, x0: Tensor, q_block: Optional[Tensor], best: Tensor, bes
     return best_host, found, repeated
 
 
+def _checked_cost(cost, n_s: int, kind: Optional[str]):
+    """`cost` as `set_cost` of the solvers keeps it: None, or a SaturatingCost for this state dimension on a solver whose
+    performance rollout is the Taylor form (`kind`; the cautious solver's always is)."""
+    if cost is None:
+        return None
+    if not isinstance(cost, SaturatingCost):
+        raise TypeError(f'cost must be a costs.SaturatingCost or None, got {type(cost).__name__}')
+    if kind != 'taylor':
+        raise ValueError("a SaturatingCost prices (mean, covariance) pairs: it needs a performance trajectory with "
+                         "cem_perf_type='taylor' (perf_type='taylor', n_perf > 0), not "
+                         + ('no performance trajectory' if kind is None else f'the {kind!r} form'))
+    if cost.n_s != n_s:
+        raise ValueError(f'the cost is built for n_s = {cost.n_s}, the model has n_s = {n_s}')
+    return cost
+
+
 class FusedCemMpc:
     """Drop-in for ``ConstrainedCemMpc``: ``get_actions(flat_state [1 x S]) -> (actions [H x n_u] | None, rollouts)``.
 
@@ -888,6 +922,7 @@ class FusedCemMpc:
         self.stepwise_fallbacks = 0     # solves repeated through the step-by-step path (see _check_solve)
         self._last_noise = self._last_actions = None
         self._objective_hook = None
+        self._cost = None
         # bench.py sets this to a list: (start, end) torch.cuda.Event pairs are then recorded around every
         # sx_cem_rollout launch, on the stream the kernel runs on
         self.rollout_events = None
@@ -911,6 +946,12 @@ class FusedCemMpc:
         self._env = env
         self._objective_hook = objective_hook
         self._prior_tensors = None
+
+    def set_cost(self, cost) -> None:
+        """The saturating cost (`costs.SaturatingCost`) as the objective of the performance trajectory, priced in the kernel
+        on (mu_{t+1}, Sigma_{t+1}) of every step (sx_cem_perf_rollout_taylor_sat): env's objective is then not read and no
+        objective hook is evaluated.  None takes it off again.  Needs the propagated covariance."""
+        self._cost = _checked_cost(cost, self._ssm.num_states, self._perf_kind if self._n_perf > 0 else None)
 
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
         if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf_kind == 'mean':
@@ -1102,10 +1143,11 @@ class FusedCemMpc:
             if perf:
                 # the performance trajectory: its objective replaces the safety trajectory's, the tail's action box adds to
                 # the constraint cost, and the rows [safety actions | tail] are what the ranking sees
-                hook, n_s = self._objective_hook, self._ssm.num_states
+                # (with a kernel-form cost no hook is evaluated)
+                hook, n_s = (self._objective_hook if self._cost is None else None), self._ssm.num_states
                 pr = _launch_perf(self._perf_kind, [self._ssm], self._env, x0, H, self._n_perf, self._perf_r, r, full_mean,
                                   full_std, eps_tail, status, want_traj=hook is not None, record=self._record,
-                                  terminal_safety=self._perf_terminal_safety)
+                                  terminal_safety=self._perf_terminal_safety, cost=self._cost)
                 r.update({key: pr[key] for key in ('perf_traj', 'perf_sigma', 'perf_cov') if key in pr})
                 r.update(safe_actions=r['actions'], actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
                 if hook is not None:
@@ -1416,7 +1458,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                                                                                       self._perf_variance):
             raise ValueError(f'the solvers have (n_perf, perf_r, perf_variance) = {(self._n_perf, self._perf_r, self._perf_variance)}'
                              f', not {(n_perf, perf_r, perf_variance)}')
-        if any(getattr(s, '_objective_hook', None) is not None for s in solvers):
+        if any(getattr(s, '_objective_hook', None) is not None and getattr(s, '_cost', None) is None for s in solvers):
             raise NotImplementedError('a multi-model solve with a performance trajectory has no objective hook: solvers '
                                       'with one act one at a time (get_actions)')
         super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
@@ -1432,6 +1474,20 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         self._taylor = self._perf_kind == 'taylor'
         # the device table the performance launch reads: alpha per model for the mean-only form, else the safety launch's
         self._perf_table = PerfModelTable() if self._perf_kind == 'mean' else self._table
+        self._solver_cost()
+
+    def _solver_cost(self):
+        """The kernel-form cost of the solve: the solvers' (`FusedCemMpc.set_cost`), equal on all of them or on none."""
+        costs = [getattr(s, '_cost', None) for s in self._solvers]
+        if any(c != costs[0] for c in costs):
+            raise ValueError(f'a multi-model solve needs equal costs on all of its solvers, or none on any of them; got '
+                             f'{costs}')
+        return costs[0]
+
+    def set_cost(self, cost) -> None:
+        """`FusedCemMpc.set_cost` on every solver."""
+        for s in self._solvers:
+            s.set_cost(cost)
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         if objective_hook is not None:
@@ -1458,6 +1514,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
         E, H, T = len(self._ssms), self._horizon, self._tail
         n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
+        cost = self._solver_cost()
         if self._perf_kind == 'taylor' and self._perf_form() < 0:
             raise FusedMultiUnsupported(f"perf_type='taylor' has no multi-model launch for these models (N = "
                                         f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {self._n_perf}): '
@@ -1477,7 +1534,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                                   noise=noise_safe[it], status=status, table=self._table)
             pr = _launch_perf(self._perf_kind, self._ssms, self._env, x0, H, self._n_perf, self._perf_r, r, mean, std,
                               noise_tail[it], status, multi=True, terminal_safety=self._perf_terminal_safety,
-                              table=self._perf_table)
+                              table=self._perf_table, cost=cost)
             return dict(actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
 
         def rank(it, r):
@@ -1489,6 +1546,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
     def get_actions_multi(self, states: Tensor, where: str = 'get_actions_multi') -> Tuple[Tensor, Tensor]:
         """As `MultiModelCemMpc.get_actions_multi`: the H safety actions of every problem's best row; the row's tail
         [1 x T x n_u] becomes solvers[e].last_perf_actions."""
+        self._solver_cost()      # mixed costs raise before anything is solved, one model at a time included
         best, found = super().get_actions_multi(states, where)
         if best.size(1) != self._horizon:      # (a solve per model has cut its rows already)
             for e, s in enumerate(self._solvers):
@@ -1668,13 +1726,14 @@ class StaticCemMpc:
 def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, mean: Optional[Tensor] = None,
                          std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
                          propagate: bool = True, want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
-                         want_margins: bool = False, status: Optional[Tensor] = None):
+                         want_margins: bool = False, status: Optional[Tensor] = None, cost=None):
     """Thin wrapper over sx_cem_cautious_rollout: the chance-constrained Taylor rollout of Cautious MPC (exact RBF GPs only).
     x0 [E x n_s]; the rows k_ff_0 .. k_ff_{T-1} either drawn (`mean`, `std` [E x T x n_u], `noise` [E x P x T x n_u]) or
     given as `rows` [E x P x T x n_u].  Every step adds SX_ACTION_VIOLATION_COST where the control k_ff_t +- env.beta
     sqrt(K_c Sigma_t K_c^T) leaves the action box (the plain box at t = 0) and SX_STATE_VIOLATION_COST where the ellipsoid
     (mu_{t+1}, env.beta, Sigma_{t+1}) leaves env's polytope; `propagate=False` starts every GP step from Sigma_t = 0 (the
-    reference's 'mean_equivalent').
+    reference's 'mean_equivalent').  `cost` (a `costs.SaturatingCost`) selects sx_cem_cautious_rollout_sat: obj_cost is the
+    sum of the cost over (mu_{t+1}, Sigma_{t+1}) and env.obj_mode is not read; everything else is unchanged.
     Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj [E x P x T x n_s] | None, sigma (same shape; diag G_t) | None,
     cov [E x P x T x n_s x n_s] | None, margins [E x P x T x 2] (largest state, largest control distance) | None, status)."""
     _require_rbf([ssm], x0)
@@ -1710,11 +1769,11 @@ def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, 
     con = torch.empty((E, P), dtype=torch.float64, device=dev)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    entry = 'sx_cem_cautious_rollout'
-    code = getattr(_lib.lib(), entry)(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, T, _lib.ptr(x0.contiguous()),
-                                      _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(rows), _lib.ptr(obj),
-                                      _lib.ptr(con), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(cov), _lib.ptr(margins),
-                                      int(bool(propagate)), _lib.ptr(status), _lib.stream_ptr(dev))
+    entry = 'sx_cem_cautious_rollout' + ('_sat' if cost is not None else '')
+    code = getattr(_lib.lib(), entry)(ctypes.byref(ssm.device_model), ctypes.byref(env), *_cost_args(cost, ssm), E, P, T,
+                                      _lib.ptr(x0.contiguous()), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(rows),
+                                      _lib.ptr(obj), _lib.ptr(con), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(cov),
+                                      _lib.ptr(margins), int(bool(propagate)), _lib.ptr(status), _lib.stream_ptr(dev))
     if code == _lib.SX_ERR_UNSUPPORTED:
         raise _no_form(entry, 'cautious', ssm, T)(n_s, n_u)
     _lib.check(code, entry)
@@ -1761,6 +1820,7 @@ class CautiousCemMpc:
         self._gen = torch.Generator(device=self._device)
         self._gen.manual_seed(int(seed))
         self._objective_hook = None
+        self._cost = None
         self.set_env(env)
         self.last_status = 0
         self.stepwise_fallbacks = 0
@@ -1776,6 +1836,12 @@ class CautiousCemMpc:
         kernel form: it is evaluated with torch on the recorded means mu_1 .. mu_T, T small launches per iteration."""
         self._env = env
         self._objective_hook = objective_hook
+
+    def set_cost(self, cost) -> None:
+        """The saturating cost (`costs.SaturatingCost`) as the objective, priced in the kernel on (mu_{t+1}, Sigma_{t+1}) of
+        every step (sx_cem_cautious_rollout_sat): env's objective is then not read and no objective hook is evaluated.
+        None takes it off again."""
+        self._cost = _checked_cost(cost, self._ssm.num_states, 'taylor')
 
     def sample_noise(self, episodes: int = 1) -> Tensor:
         """[iters x E x P x T x n_u] standard normals of one solve, from this solver's generator."""
@@ -1802,13 +1868,14 @@ class CautiousCemMpc:
                else self._init_std.to(dev).expand(E, T, n_u).contiguous())
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         history: List[Rollouts] = []
-        hook, n_s = self._objective_hook, self._ssm.num_states
+        hook, n_s = (self._objective_hook if self._cost is None else None), self._ssm.num_states
 
         def rollout(it, mean, std, rows):
             r = cem_cautious_rollout(self._ssm, self._env, x0, T, mean=mean.contiguous(), std=std.contiguous(),
                                      noise=noise[it].contiguous(), propagate=self._propagate,
                                      want_traj=self._record or hook is not None, want_sigma=self._record,
-                                     want_cov=self._record, status=status)
+                                     want_cov=self._record, status=status,
+                                     **({} if self._cost is None else dict(cost=self._cost)))
             if hook is not None:
                 obj = torch.zeros_like(r['obj_cost'])
                 for t in range(T):
@@ -1860,4 +1927,5 @@ class CautiousCemMpc:
         """The rollout of given rows [E x P x T x n_u] from x0 [E x n_s] with every output: what a verbose caller reads."""
         return cem_cautious_rollout(self._ssm, self._env, x0.to(self._device, torch.float64), self._horizon,
                                     rows=rows.to(self._device, torch.float64).contiguous(), propagate=self._propagate,
-                                    want_traj=True, want_sigma=True, want_cov=True, want_margins=True)
+                                    want_traj=True, want_sigma=True, want_cov=True, want_margins=True,
+                                    **({} if self._cost is None else dict(cost=self._cost)))

@@ -2,63 +2,7 @@
 // of SX_ROLLOUT_SHAPES in both of its forms, and its entry points.  The host path from plan to launch is the performance
 // rollouts' (perf_gp_rollout, sx_perf_launch.hpp) over one more form.  A translation unit of its own: nothing the other
 // objects compile changes with it.
-#include "sx_host.hpp"
-#include "sx_launch.hpp"
-#include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES, SX_DISPATCH
-#include "sx_perf_launch.hpp"
-#include "sx_cautious.hpp"
-
-namespace sx {
-
-// bytes of the step constants (CautiousConst) behind the tile's actions: the Taylor form's plus beta
-inline size_t cautious_extra_bytes(int ns, int nu) { return perf_taylor_extra_bytes(ns, nu) + sizeof(double); }
-
-// (perf_gp_rollout names the multi-model launcher of its form; there is no multi-model cautious launch, and no caller
-// hands it a table)
-template <int NS, int NU>
-int launch_perf_gp_multi(const GpConst<NS, NS + NU>*, const CautiousConst<NS, NU>&, const CautiousPtrs&, bool, unsigned,
-                         size_t, hipStream_t) {
-    return SX_ERR_UNSUPPORTED;
-}
-
-// The cautious form for perf_gp_rollout: the Taylor form's plan (T steps of actions, the step constants behind them)
-struct CautiousForm {
-    template <int NS, int NU>
-    using Const = CautiousConst<NS, NU>;
-    using Ptrs = CautiousPtrs;
-    static const PerfPtrs& base(const Ptrs& cp) { return cp.p; }
-    static size_t extra_bytes(int ns, int nu) { return cautious_extra_bytes(ns, nu); }
-    template <int NS, int NU>
-    static void make_const(const sx_env* env, Const<NS, NU>& cc) {
-        static_assert(sizeof(CautiousConst<NS, NU>) == sizeof(PerfTaylorConst<NS, NU>) + sizeof(double),
-                      "cautious_extra_bytes counts the fields of CautiousConst");
-        PerfTaylorConst<NS, NU>& tc = cc.tc;
-        make_perf_step<NS, NU>(env, tc.step);
-        for (int i = 0; i < NS; ++i)
-            for (int j = 0; j < NS; ++j) {
-                double s = env->a[i * NS + j];
-                for (int c = 0; c < NU; ++c) s += env->b[i * NU + c] * env->k_fb[c * NS + j];
-                tc.abk[i * NS + j] = s;
-            }
-        for (int i = 0; i < NU * NS; ++i) tc.k_fb[i] = env->k_fb[i];
-        for (int i = 0; i < env->m * NS; ++i) tc.h_mat[i] = env->h_mat[i];
-        for (int i = 0; i < env->m; ++i) tc.h_vec[i] = env->h_vec[i];
-        cc.beta = env->beta;
-    }
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_cautious_rollout_kernel<NS, NU, BYOUT>;
-    }
-};
-
-// The plan of a model over T steps (plan_perf_var over the cautious constants), where the entry would take the model
-static bool cautious_plan(const sx_gp_model* model, int T, PerfVarPlan& plan) {
-    if (!model || T < 1 || !perf_shape_ok(*model) || !perf_models_ok(model, 1, perf_var_model_ok)) return false;
-    plan = plan_perf_var(model->n_s, model->n_u, model->n_train, model->n_pad, T, cautious_extra_bytes(model->n_s, model->n_u));
-    return true;
-}
-
-}  // namespace sx
+#include "sx_cautious_host.hpp"   // CautiousForm, cautious_plan
 
 extern "C" int sx_cem_cautious_rollout_form(const sx_gp_model* model, int T) {
     sx::PerfVarPlan plan;

@@ -1,96 +1,74 @@
-// The body of the four GP-product performance kernels, included as text: cem_perf_var_rollout[_multi]_kernel
-// (sx_perf_var.hpp) with SX_PERF_TAYLOR 0 and cem_perf_taylor_rollout[_multi]_kernel (sx_perf_taylor.hpp) with
-// SX_PERF_TAYLOR 1.  As text and with the kind's sections picked by the preprocessor, so that every kernel sees the
-// statements it had when each kernel had a body of its own and compiles to the same instructions (a device function for
-// the shared part changed the single-model kernel's registers; tools/device_code_diff.py is the check).
-// In scope: NS, NU, BYOUT; MM (false | true: a GP per problem); `gc` (the GpConst kernel argument, or the problem's entry
-// of the device table of sx_gp_model_table), `stage_tab` (its stage table); the step constants and the pointers, which
-// are kernel arguments in both modes (there is one sx_env): `sc`, `vp` for the variance kernels, `tc_arg`, `tp` for the
-// Taylor kernels.
-// SX_PERF_SAT (defined, with SX_PERF_TAYLOR 1; cem_perf_taylor_sat_rollout[_multi]_kernel): the objective section prices
-// (mu_{t+1}, Sigma_{t+1}) with the saturating cost of sx_sat_cost.hpp from `sat` (SatConst<NS>, a kernel argument).
-// MM = true: the LDS carve-up follows the problem's n_train / n_pad inside the launch's allocation for the largest model,
-// and the status is one word per problem.  The workgroups are problem-aligned in both modes.
+// The body of the cautious rollout kernels, included as text by sx_cautious.hpp: cem_cautious_rollout_kernel as it stands,
+// cem_cautious_sat_rollout_kernel with SX_CAUTIOUS_SAT defined (the objective section prices (mu_{t+1}, Sigma_{t+1}) with
+// the saturating cost of sx_sat_cost.hpp).  As text, as sx_perf_gp_body.inc and for its reason: the parent kernel sees the
+// statements it had and compiles to the same instructions (tools/device_code_diff.py is the check).
+// In scope: NS, NU, BYOUT; `gc`, `stage_tab`, `cc_arg`, `cp`; SX_CAUTIOUS_SAT: `sat` (SatConst<NS>, a kernel argument).
     constexpr int D = NS + NU;
     constexpr int nw = kPerfVarThreads / 64;
-    const PerfPtrs& pp = vp.p;
+    const PerfPtrs& pp = cp.p;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     GpTileLds<NS, D> lds;
-    double* acts = lds.carve(smem, gc.n_train, gc.n_pad, nw, BYOUT ? 1 : NS);   // [16][n_perf][NU]: v_t of the tile
+    double* acts = lds.carve(smem, gc.n_train, gc.n_pad, nw, BYOUT ? 1 : NS);   // [16][T][NU]: k_ff_t of the tile
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
-    const int H = pp.H, r = pp.r, n_perf = pp.n_perf, T = n_perf - r;
+    const int T = pp.n_perf;
     const int tiles_per_problem = (pp.P + SX_TILE - 1) / SX_TILE;
     const int e = blockIdx.x / tiles_per_problem;
     const int c0 = (blockIdx.x - e * tiles_per_problem) * SX_TILE;   // first particle of the tile within problem e
 
-    // the head of this wave's MFMA stream travels while X, the exp table and the actions are loaded (as in sx_rollout.hpp;
-    // output by output every phase fetches the head of its own stream)
     const MfmaHead head = gp_mfma_head(gc, stage_tab, wave, nw, lane, gc.stage_cap);
     const int4* __restrict__ const tab_one = stage_tab + (size_t)nw * (1 + gc.stage_cap);
     gp_load_xs(gc, lds);
-#if SX_PERF_TAYLOR
-    // Taylor: the step constants sit in LDS behind the actions, copied in one pass (`sc` is the variance kernels' argument)
-    constexpr int kConst = perf_taylor_const_doubles<NS, NU>();
+    // the step constants sit in LDS behind the actions, copied in one pass
+    constexpr int kConst = cautious_const_doubles<NS, NU>();
     static_assert(kConst <= kPerfVarThreads, "one pass copies the step constants");
-    static_assert(sizeof(PerfTaylorConst<NS, NU>) % sizeof(double) == 0, "doubles only");
-    double* const tcl = acts + SX_TILE * n_perf * NU;
-    const PerfTaylorConst<NS, NU>& tc = *reinterpret_cast<const PerfTaylorConst<NS, NU>*>(tcl);
+    static_assert(sizeof(CautiousConst<NS, NU>) % sizeof(double) == 0, "doubles only");
+    const int row_len = T * NU;
+    double* const ccl = acts + SX_TILE * row_len;
+    const CautiousConst<NS, NU>& cc = *reinterpret_cast<const CautiousConst<NS, NU>*>(ccl);
+    const PerfTaylorConst<NS, NU>& tc = cc.tc;
     const PerfStepConst<NS, NU>& sc = tc.step;
-    if (tid < kConst) tcl[tid] = reinterpret_cast<const double*>(&tc_arg)[tid];
-#endif
+    if (tid < kConst) ccl[tid] = reinterpret_cast<const double*>(&cc_arg)[tid];
 
-    // the tile's rows [safety actions | tail] (the tail drawn by the expression of sx_perf.hpp, or read), and its
-    // performance actions v_t = u^s_t (t < r), u^p_t (t >= r) into LDS; a slot past the particles holds zeros
-    const int row_len = (H + T) * NU, hl = H * NU;
+    // the tile's rows (drawn by the expression of sx_perf.hpp, or read) into LDS; a slot past the particles holds zeros
     for (int i = tid; i < SX_TILE * row_len; i += kPerfVarThreads) {
         const int c = i / row_len, j = i - c * row_len;
         double val = 0.0;
         if (c0 + c < pp.P) {
             const int64_t g = (int64_t)e * pp.P + c0 + c;
             double* row = pp.rows + g * row_len;
-            if (j < hl) {
-                val = pp.safe_actions[g * hl + j];
-                row[j] = val;
-            } else if (pp.tail_noise) {
-                const int k = j - hl;
-                const int64_t ek = (int64_t)e * T * NU + k;
-                val = fma(pp.tail_std[ek], pp.tail_noise[g * T * NU + k], pp.tail_mean[ek]);
+            if (pp.tail_noise) {
+                const int64_t ej = (int64_t)e * row_len + j;
+                val = fma(pp.tail_std[ej], pp.tail_noise[g * row_len + j], pp.tail_mean[ej]);
                 row[j] = val;
             } else {
                 val = row[j];
             }
         }
-        if (j < r * NU)
-            acts[c * n_perf * NU + j] = val;
-        else if (j >= hl)
-            acts[c * n_perf * NU + r * NU + (j - hl)] = val;
+        acts[i] = val;
     }
     // per-particle state lives in the registers of thread c (tid < 16) for the whole rollout
     const bool owner = tid < SX_TILE;
     const bool valid = owner && (c0 + tid < pp.P);
     double mu[NS];
+    double S[NS][NS];   // Sigma_t, both triangles; Sigma_0 = 0.  propagate == 0: diag(var_{t-1}), which only the control
+                        // constraint reads
     double obj = 0.0, con = 0.0;
     int st = 0;
     if (owner) {
 #pragma unroll
         for (int i = 0; i < NS; ++i) mu[i] = pp.x0[(int64_t)e * NS + i];
-    }
-#if SX_PERF_TAYLOR
-    double S[NS][NS];   // Taylor: Sigma_t beside mu_t on the owner lane, both triangles; Sigma_0 = 0
-    if (owner) {
 #pragma unroll
         for (int i = 0; i < NS; ++i)
 #pragma unroll
             for (int j = 0; j < NS; ++j) S[i][j] = 0.0;
     }
-#endif
     __syncthreads();
     if (owner) {
 #pragma unroll
         for (int i = 0; i < NS; ++i) lds.zs[tid * D + i] = mu[i];
 #pragma unroll
-        for (int cidx = 0; cidx < NU; ++cidx) lds.zs[tid * D + NS + cidx] = acts[(tid * n_perf + 0) * NU + cidx];
+        for (int cidx = 0; cidx < NU; ++cidx) lds.zs[tid * D + NS + cidx] = acts[(tid * T + 0) * NU + cidx];
     }
     __syncthreads();
 
@@ -107,25 +85,58 @@
             out[i] = s;
         }
     };
-    // the rest of step t on the owner lanes: posterior (Taylor: and the covariance step), next centre, costs, stores
+    // the rest of step t on the owner lanes: the control constraint on Sigma_t, posterior and covariance step, next centre,
+    // the state constraint on Sigma_{t+1}, costs, stores
     auto tail = [&](int t) {
         double z[D], mean[NS], var[NS], jac[NS][D], mu1[NS];
 #pragma unroll
         for (int j = 0; j < NS; ++j) z[j] = mu[j];
 #pragma unroll
-        for (int cidx = 0; cidx < NU; ++cidx) z[NS + cidx] = acts[(tid * n_perf + t) * NU + cidx];
-        gp_collect<NS, D, SX_PERF_TAYLOR>(gc, lds, nw, tid, z, mean, var, jac);   // Taylor: with the Jacobian rows
+        for (int cidx = 0; cidx < NU; ++cidx) z[NS + cidx] = acts[(tid * T + t) * NU + cidx];
+        // control: the plain box at t = 0, else the box shrunk by beta sqrt(K_c Sigma_t K_c^T) on either side
+        bool uviol = false;
+        double umax_d = -__builtin_inf();
+#pragma unroll
+        for (int cidx = 0; cidx < NU; ++cidx) {
+            const double k = z[NS + cidx];
+            if (t == 0) {
+                uviol = uviol || (k < sc.u_min[cidx]) || (k > sc.u_max[cidx]);
+                umax_d = fmax(umax_d, fmax(k - sc.u_max[cidx], sc.u_min[cidx] - k));
+            } else {
+                double q = 0.0;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NS; ++j) s = fma(S[i][j], tc.k_fb[cidx * NS + j], s);
+                    q = fma(tc.k_fb[cidx * NS + i], s, q);
+                }
+                const double spread = cc.beta * sqrt(q);
+                const double d_hi = (k + spread) - sc.u_max[cidx], d_lo = (sc.u_min[cidx] - k) + spread;
+                uviol = uviol || (d_hi >= 0.0) || (d_lo >= 0.0);
+                umax_d = fmax(umax_d, fmax(d_hi, d_lo));
+            }
+        }
+        if (uviol) con += SX_ACTION_VIOLATION_COST;
+
+        gp_collect<NS, D, 1>(gc, lds, nw, tid, z, mean, var, jac);   // with the Jacobian rows
         next_centre(tid, z, mu1);   // exactly the centre the Kstar threads of step t + 1 derive
-        if (t + 1 < n_perf) {
+        if (t + 1 < T) {
             double* zn = zs_base + ((t + 1) & 1) * 16 * D + tid * D;
 #pragma unroll
             for (int i = 0; i < NS; ++i) zn[i] = mu1[i];
 #pragma unroll
-            for (int cidx = 0; cidx < NU; ++cidx) zn[NS + cidx] = acts[(tid * n_perf + t + 1) * NU + cidx];
+            for (int cidx = 0; cidx < NU; ++cidx) zn[NS + cidx] = acts[(tid * T + t + 1) * NU + cidx];
         }
-#if SX_PERF_TAYLOR
-        // Taylor: G = diag(var) + diag(M Sigma M^T) and Sigma_{t+1} = Hm Sigma Hm^T + diag(var) (upper triangle, then
-        // mirrored), with M = J_x + J_u K, Hm = (a + b K) + M; MS = M Sigma, HS = Hm Sigma
+        if (!cp.propagate) {
+            // mean-equivalent: the GP step starts from Sigma_t = 0
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+#pragma unroll
+                for (int j = 0; j < NS; ++j) S[i][j] = 0.0;
+        }
+        // G = diag(var) + diag(M Sigma M^T) and Sigma_{t+1} = Hm Sigma Hm^T + diag(var) (upper triangle, then mirrored),
+        // with M = J_x + J_u K, Hm = (a + b K) + M; MS = M Sigma, HS = Hm Sigma  (sx_perf_gp_body.inc, fma for fma)
         double M[NS][NS], Hm[NS][NS], G[NS], S1[NS][NS];
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
@@ -172,21 +183,13 @@
         for (int i = 1; i < NS; ++i)
 #pragma unroll
             for (int j = 0; j < i; ++j) S1[i][j] = S1[j][i];
-#else
-        const double (&G)[NS] = var;   // what the objective and perf_sigma see
-        bool bad = false;
-#pragma unroll
-        for (int i = 0; i < NS; ++i)
-            bad = bad || !(__builtin_fabs(mu1[i]) <= 1.7976931348623157e308) ||
-                  !(__builtin_fabs(var[i]) <= 1.7976931348623157e308);
-#endif
-#ifdef SX_PERF_SAT
+#ifdef SX_CAUTIOUS_SAT
         // the saturating cost of (mu_{t+1}, Sigma_{t+1}) (sx_sat_cost.hpp); a non-finite loss never ranks
         const double o = sat_loss<NS>(sat, mu1, S1);
         bad = bad || !(__builtin_fabs(o) <= 1.7976931348623157e308);
 #else
         double o = 0.0;
-        if (vp.obj_mode == SX_OBJ_NEG_VARIANCE) {
+        if (cp.obj_mode == SX_OBJ_NEG_VARIANCE) {
 #pragma unroll
             for (int i = 0; i < NS; ++i) o -= G[i];
         } else {
@@ -196,55 +199,62 @@
 #endif
         obj += o;
         if (bad) {
-            // a non-finite state, variance or covariance never ranks (the table exponential maps an infinite distance to
-            // k* = 0)
+            // a non-finite state, variance or covariance never ranks
             st |= SX_STATUS_NAN;
             obj = __builtin_nan("");
         }
-        if (t >= r) {
-            bool uviol = false;
+        // state: the ellipsoid (mu_{t+1}, Sigma_{t+1}) scaled by beta against every row of the polytope (the sums of
+        // polytope_violated); a NaN distance is neither a violation nor a margin
+        bool sviol = false;
+        double smax_d = -__builtin_inf();
+        for (int row = 0; row < cp.m; ++row) {
+            double hc = 0.0, hq = 0.0;
 #pragma unroll
-            for (int cidx = 0; cidx < NU; ++cidx)
-                uviol = uviol || (z[NS + cidx] < sc.u_min[cidx]) || (z[NS + cidx] > sc.u_max[cidx]);
-            if (uviol) con += SX_ACTION_VIOLATION_COST;
+            for (int i = 0; i < NS; ++i) {
+                const double hi = tc.h_mat[row * NS + i];
+                hc += hi * mu1[i];
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < NS; ++j) s += S1[i][j] * tc.h_mat[row * NS + j];
+                hq += hi * s;
+            }
+            const double d = hc + cc.beta * sqrt(hq) - tc.h_vec[row];
+            sviol = sviol || (d >= 0.0);
+            smax_d = fmax(smax_d, d);
         }
-#if SX_PERF_TAYLOR
-        if (t == tp.safety_step) {
-            // Taylor: the terminal-safety coupling: (mu_s, Sigma_s), s = t + 1 = H + 2, inside the safe polytope
-            if (polytope_violated<SX_MAX_M, NS>(tc.h_mat, tc.h_vec, tp.m, 1.0, mu1, S1, nullptr))
-                con += SX_STATE_VIOLATION_COST;
-        }
-#endif
+        if (sviol) con += SX_STATE_VIOLATION_COST;
+
         const int64_t g = (int64_t)e * pp.P + c0 + tid;
         if (valid && pp.perf_traj) {
 #pragma unroll
-            for (int i = 0; i < NS; ++i) pp.perf_traj[(g * n_perf + t) * NS + i] = mu1[i];
+            for (int i = 0; i < NS; ++i) pp.perf_traj[(g * T + t) * NS + i] = mu1[i];
         }
-        if (valid && vp.perf_sigma) {
+        if (valid && cp.sigma) {
 #pragma unroll
-            for (int i = 0; i < NS; ++i) vp.perf_sigma[(g * n_perf + t) * NS + i] = G[i];
+            for (int i = 0; i < NS; ++i) cp.sigma[(g * T + t) * NS + i] = G[i];
         }
-#if SX_PERF_TAYLOR
-        // Taylor: Sigma_{t+1} goes out and becomes the next step's Sigma
-        if (valid && tp.perf_cov) {
-            double* cv = tp.perf_cov + (g * n_perf + t) * (NS * NS);
+        if (valid && cp.cov) {
+            double* cv = cp.cov + (g * T + t) * (NS * NS);
 #pragma unroll
             for (int i = 0; i < NS; ++i)
 #pragma unroll
                 for (int j = 0; j < NS; ++j) cv[i * NS + j] = S1[i][j];
         }
+        if (valid && cp.margins) {
+            cp.margins[(g * T + t) * 2 + 0] = smax_d;
+            cp.margins[(g * T + t) * 2 + 1] = umax_d;
+        }
 #pragma unroll
         for (int i = 0; i < NS; ++i)
 #pragma unroll
             for (int j = 0; j < NS; ++j) S[i][j] = S1[i][j];
-#endif
 #pragma unroll
         for (int i = 0; i < NS; ++i) mu[i] = mu1[i];
     };
 
     int q_begin, q_end;   // this wave's share of the Kstar pairs: all waves alike
     kstar_pair_range(gc.n_pad >> 3, wave, 1, nw, q_begin, q_end);
-    for (int t = 0; t < n_perf; ++t) {
+    for (int t = 0; t < T; ++t) {
         // the query point of this thread's particle
         double zq[D];
         {
@@ -258,7 +268,7 @@
 #pragma unroll
                 for (int i = 0; i < NS; ++i) zq[i] = pc[i];
 #pragma unroll
-                for (int cidx = 0; cidx < NU; ++cidx) zq[NS + cidx] = acts[(c * n_perf + t) * NU + cidx];
+                for (int cidx = 0; cidx < NU; ++cidx) zq[NS + cidx] = acts[(c * T + t) * NU + cidx];
             }
         }
         if constexpr (BYOUT) {
@@ -290,6 +300,6 @@
     if (valid) {
         const int64_t g = (int64_t)e * pp.P + c0 + tid;
         pp.obj_cost[g] = obj;
-        pp.con_cost[g] += con;
-        if (st) atomicOr(pp.status + (MM ? e : 0), st);
+        pp.con_cost[g] = con;
+        if (st) atomicOr(pp.status, st);
     }

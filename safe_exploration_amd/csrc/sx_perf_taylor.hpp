@@ -24,6 +24,7 @@
 #include "sx_gp.hpp"
 #include "sx_perf_var.hpp"   // PerfVarPtrs, kPerfVarThreads
 #include "sx_reach.hpp"      // polytope_violated
+#include "sx_sat_cost.hpp"   // SatConst, sat_loss
 
 namespace sx {
 
@@ -74,6 +75,55 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_rollout_multi
     const PerfVarPtrs& vp = tp.v;
 #define SX_PERF_TAYLOR 1
 #include "sx_perf_gp_body.inc"
+#undef SX_PERF_TAYLOR
+}
+
+// The same two kernels with the saturating cost (sx_sat_cost.hpp) as the objective (sx_cem_perf_rollout_taylor_sat[_multi]).
+// The cost's constants ride behind the step constants in one kernel argument and stay there: the owner lanes read them by
+// scalar loads, and the LDS plan is the parent's.
+template <int NS, int NU>
+struct PerfTaylorSatConst {
+    PerfTaylorConst<NS, NU> tc;
+    SatConst<NS> sat;
+};
+
+// (the launcher of the multi-model kernel over the device table, instantiated beside it in sx_perf_taylor_sat_multi.hip, as
+// sx_perf_launch.hpp declares the parents')
+template <int NS, int NU>
+int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorSatConst<NS, NU>& c, const PerfTaylorPtrs& tp,
+                         bool byout, unsigned blocks, size_t lds, hipStream_t stream);
+
+template <int NS, int NU, bool BYOUT>
+__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_sat_rollout_kernel(const GpConst<NS, NS + NU> gc,
+                                                                                      const int4* __restrict__ stage_tab,
+                                                                                      const PerfTaylorSatConst<NS, NU> arg,
+                                                                                      const PerfTaylorPtrs tp) {
+    constexpr bool MM = false;
+    const PerfTaylorConst<NS, NU>& tc_arg = arg.tc;
+    const SatConst<NS>& sat = arg.sat;
+    const PerfVarPtrs& vp = tp.v;
+#define SX_PERF_TAYLOR 1
+#define SX_PERF_SAT
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_SAT
+#undef SX_PERF_TAYLOR
+}
+
+template <int NS, int NU, bool BYOUT>
+__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_sat_rollout_multi_kernel(
+    const GpConst<NS, NS + NU>* __restrict__ table, const PerfTaylorSatConst<NS, NU> arg, const PerfTaylorPtrs tp) {
+    constexpr bool MM = true;
+    using ConstG = __attribute__((address_space(4))) const GpConst<NS, NS + NU>;
+    const int problem = blockIdx.x / ((tp.v.p.P + SX_TILE - 1) / SX_TILE);
+    const GpConst<NS, NS + NU>& gc = *(const GpConst<NS, NS + NU>*)((ConstG*)table + problem);
+    const int4* __restrict__ const stage_tab = gc.stage_tab;
+    const PerfTaylorConst<NS, NU>& tc_arg = arg.tc;
+    const SatConst<NS>& sat = arg.sat;
+    const PerfVarPtrs& vp = tp.v;
+#define SX_PERF_TAYLOR 1
+#define SX_PERF_SAT
+#include "sx_perf_gp_body.inc"
+#undef SX_PERF_SAT
 #undef SX_PERF_TAYLOR
 }
 

@@ -15,6 +15,7 @@ from numpy import ndarray
 from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
+from .costs import SaturatingCost
 from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc, multi_family
 from .gp_reachability_pytorch import make_env, onestep_reachability
 from .safempc import SafeMPC
@@ -272,6 +273,7 @@ class CemSafeMPC(SafeMPC):
         self._lqr = lqr
         self._injected_mpc = mpc is not None
         self._mpc = mpc
+        self._cost = None      # init_solver's SaturatingCost
         self._env_key = None
         self._objective_probe = torch.tensor([[0.3] * env.n_s, [-0.7] * env.n_s], dtype=torch.float64)
         self._last_mpc_actions = np.empty((0, self.action_dimen))
@@ -311,7 +313,18 @@ class CemSafeMPC(SafeMPC):
         return x_train.detach().cpu().numpy()
 
     def init_solver(self, cost_func=None) -> None:
-        pass
+        """A `costs.SaturatingCost` becomes the objective of the performance trajectory, priced in the rollout kernel on
+        every (mean, covariance) of it (what the reference's casadi configs hand over here); it needs the propagated
+        covariance.  Any other value is ignored: the objective is then the environment's."""
+        if not isinstance(cost_func, SaturatingCost):
+            return
+        if self._cem_perf_type != 'taylor' or self._cem_n_perf <= 0:
+            raise ValueError("a SaturatingCost prices (mean, covariance) pairs of the performance trajectory: it needs "
+                             f"cem_perf_type='taylor' with cem_n_perf > 0, got cem_perf_type={self._cem_perf_type!r}, "
+                             f'cem_n_perf={self._cem_n_perf}')
+        self._cost = cost_func
+        if self._mpc is not None:
+            self._mpc.set_cost(cost_func)
 
     # ---- the fused optimiser -------------------------------------------------------------------------------------
     def _prior(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -365,6 +378,8 @@ class CemSafeMPC(SafeMPC):
                                     perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}),
                                     **({'perf_type': 'taylor', 'perf_terminal_safety': self._cem_perf_terminal_safety}
                                        if self._cem_perf_type == 'taylor' else {}))
+            if self._cost is not None:
+                self._mpc.set_cost(self._cost)
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
         self._env_key = key
         return self._mpc
