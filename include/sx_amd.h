@@ -748,6 +748,40 @@ int sx_cem_cautious_rollout_sat(const sx_gp_model* model, const sx_env* env, con
                                 double* obj_cost, double* con_cost, double* traj, double* sigma, double* cov,
                                 double* margins, int propagate, int32_t* status, void* stream);
 
+/* ---- The saturating cost on the safety trajectory ----------------------------------------------------------------------------
+ * sx_cem_rollout, sx_cem_rollout_elites and their _multi forms with the saturating cost as the objective, priced on the
+ * safety ellipsoids: obj_cost = sum_{t=1..H} loss(p_t, Q_t), every centre read as a mean and every shape matrix as a
+ * covariance -- what a SafeMPC without a performance trajectory hands its solver (defaultconfig_episode.py:150-157:
+ * generic_cost over p_all, q_all).  env->obj_mode is not read, not even to reject an odd value.  actions, traj, sigma,
+ * con_cost, status and the refit are the streaming kernel's of the parent entry, bit for bit.  A non-finite loss sets
+ * SX_STATUS_NAN and makes the particle's objective NaN.  Arguments as the parent entry's with the cost behind env;
+ * sx_cem_rollout_sat takes no workspace.  The cost's constants travel as a kernel argument: the LDS plan is the parent's.
+ * The streaming kernel only: the resident forms and the workspace path (SX_FORM_RH, SX_FORM_RW, SX_FORM_BIG) are not served.
+ * SX_ERR_ARG (before any device access) for whatever the parent entry answers it for, a NULL cost, trig_idx outside
+ * -1 .. n_s-1, rank outside 1 .. n_a, a non-finite constant; SX_ERR_UNSUPPORTED (before any launch) for a shape without a
+ * kernel, m outside 1 .. SX_MAX_M, a training set on the workspace path or fitting neither streaming form, and from the
+ * elite-row entries beyond 2 H n_u <= 256 (1 + n_s). */
+int sx_cem_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
+                       const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                       double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
+                       void* stream);
+int sx_cem_rollout_elites_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
+                              const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                              double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                              int32_t* status, double* mean_out, double* std_out, void* stream);
+int sx_cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost, int E,
+                             int P, int H, const double* x0, const double* q0, const double* mean, const double* std,
+                             const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                             double* con_cost, int32_t* status, void* stream);
+int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                                    int E, int P, int H, const double* x0, const double* q0, const double* elite_rows, int k,
+                                    const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                                    double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream);
+/* The form sx_cem_rollout_sat launches for this model and H (no launch, no device access): SX_FORM_STREAM or SX_FORM_BYOUT,
+ * or < 0 for bad arguments and wherever the entry would answer SX_ERR_UNSUPPORTED for the model: the contract of
+ * sx_cem_rollout_starts_form.  The _multi entries launch what sx_cem_rollout_multi_form reports. */
+int sx_cem_rollout_sat_form(const sx_gp_model* model, int H);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -150,6 +150,15 @@ SIGNATURES = {
                                              + [c_int, c_void_p, c_void_p]),
     'sx_cem_cautious_rollout_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int]
                                     + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
+    'sx_cem_rollout_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int]
+                           + [c_void_p] * 12),
+    'sx_cem_rollout_elites_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
+    'sx_cem_rollout_sat_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int,
+                                         c_int] + [c_void_p] * 12),
+    'sx_cem_rollout_elites_sat_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxSatCost), c_int,
+                                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
+    'sx_cem_rollout_sat_form': (c_int, [POINTER(SxGpModel), c_int]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -84,19 +84,26 @@ def _rollout(suffix: str, head: tuple, x0: Tensor, horizon: int, n_s: int, n_u: 
 def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, actions: Optional[Tensor] = None,
                 mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
                 q0: Optional[Tensor] = None, want_traj: bool = False, want_sigma: bool = False,
-                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False):
+                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False, cost=None):
     """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites (and their _junk, _feat and _mlp counterparts).
 
     x0 [E x n_s]; either `actions` [E x P x H x n_u] (given), or (`mean`, `std` [E x H x n_u], `noise` [E x P x H x n_u]),
     or (`elite_rows` [E x k x (2 + H n_u)], `noise`): the distribution is then refit from the previous iteration's elite
     rows in the rollout kernel's prologue (`fused_refit_applies`), and `mean` / `std` are not read; `want_dist` returns
     that refit as `mean` / `std`.
+    `cost` (a `costs.SaturatingCost`; exact RBF GPs only) selects sx_cem_rollout_sat / sx_cem_rollout_elites_sat: obj_cost
+    is the sum of the cost over the safety ellipsoids (p_t, Q_t), t = 1 .. H, read as means and covariances, env.obj_mode
+    is not read and everything else is unchanged.  The streaming kernel only: a training set on
+    the workspace path has no such launch.
     Returns dict(actions, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]).
     """
     _lib.require_gpu(x0, 'x0')
     family = getattr(ssm, 'kernel_family', 'rbf')
     workspace, unsupported = (), None
-    if family in ('feature', 'mlp', 'feature_junk', 'mlp_junk'):
+    if cost is not None:
+        _require_rbf_cost([ssm])
+        head, suffix = (ctypes.byref(ssm.device_model), ctypes.byref(env)) + _cost_args(cost, ssm), '_sat'
+    elif family in ('feature', 'mlp', 'feature_junk', 'mlp_junk'):
         # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
         # 'mlp': MC-dropout ensembles over the frozen members, matrix cores for 1-2 hidden layers of <= 64 units
         # (csrc/sx_mlp_mfma.hpp), one particle per lane otherwise (csrc/sx_mlp.hpp).  Neither has an elite-row form.
@@ -126,6 +133,14 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     return _rollout(suffix, head, x0, horizon, ssm.num_states, ssm.num_actions, 1, unsupported, actions=actions, mean=mean,
                     std=std, noise=noise, q0=q0, want_traj=want_traj, want_sigma=want_sigma, status=status,
                     elite_rows=elite_rows, want_dist=want_dist, workspace=workspace)
+
+
+def _require_rbf_cost(ssms) -> None:
+    for ssm in ssms:
+        family = getattr(ssm, 'kernel_family', 'rbf')
+        if family != 'rbf':
+            raise NotImplementedError(f'the saturating cost on the safety trajectory is built for exact RBF GPs, not '
+                                      f'kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
 
 
 def _require_rbf_starts(ssm) -> None:
@@ -251,14 +266,17 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
                       actions: Optional[Tensor] = None, mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
                       noise: Optional[Tensor] = None, q0: Optional[Tensor] = None, want_traj: bool = False,
                       want_sigma: bool = False, status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None,
-                      want_dist: bool = False, table: Optional[GpModelTable] = None):
+                      want_dist: bool = False, table: Optional[GpModelTable] = None, cost=None):
     """`cem_rollout` for E problems with a model each (ssms[e] for problem e), one launch.  The models share one
     kernel_family: exact RBF GPs ('rbf': sx_cem_rollout_multi / sx_cem_rollout_elites_multi), feature-space GPs
     ('feature': sx_cem_rollout_feat_multi) or MC-dropout ensembles ('mlp': sx_cem_rollout_mlp_multi; neither of the last
     two has an elite-row form).  Buffers as in `cem_rollout`; `status` is int32 [E], one word per problem.  `table` keeps
     the device table of the models between calls (a fresh one is built otherwise, as where it belongs to another family).
+    `cost` as in `cem_rollout` (sx_cem_rollout_sat_multi / sx_cem_rollout_elites_sat_multi; exact RBF GPs only).
     Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch): mixed
     families, JunkDimensionsSSM and step-by-step models, differing architectures, a shape without a kernel."""
+    if cost is not None:
+        _require_rbf_cost(ssms)
     family = multi_family(ssms)
     if family is None:
         raise FusedMultiUnsupported('the multi-model rollout takes models of one kernel_family: "rbf", "feature" or "mlp"; '
@@ -274,7 +292,10 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
     if table is None or table.family != family:
         table = GpModelTable(family)
     models, tab = table.get(ssms, x0.device)
-    return _rollout(MULTI_FAMILIES[family][3], (models, _lib.ptr(tab), ctypes.byref(env)), x0, horizon,
+    head = (models, _lib.ptr(tab), ctypes.byref(env))
+    if cost is not None:
+        head += _cost_args(cost, ssms[0])
+    return _rollout(('_sat' if cost is not None else '') + MULTI_FAMILIES[family][3], head, x0, horizon,
                     ssms[0].num_states, ssms[0].num_actions, E, FusedMultiUnsupported, actions=actions, mean=mean, std=std,
                     noise=noise, q0=q0, want_traj=want_traj, want_sigma=want_sigma, status=status, elite_rows=elite_rows,
                     want_dist=want_dist)
@@ -571,7 +592,7 @@ def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candid
 
 
 def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Tensor, *, status: Tensor, group=None,
-                         objective_hook=None):
+                         objective_hook=None, cost=None):
     """The rollout of ONE problem step by step, the way the reference's optimiser drives it: H dynamics-callback calls on
     the whole particle batch (safempc_cem.py:288-302), each = sx_gp_predict + sx_onestep_reach, then the costs.
 
@@ -583,7 +604,10 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
     x0 [n_s], or [P x n_s]: a start per particle (`StaticCemMpc`; the cost of a start outside the polytope is
     `start_constraint_cost`, not part of this rollout); actions [P x H x n_u] (this rank's particles); with a process group the batch spans the ranks: the
     "zero present" flag is all-reduced (MAX) per step.  Returns dict(obj_cost [P], con_cost [P]); `status` is OR-ed.
+    `cost` (a `costs.SaturatingCost`): the objective of a step is the cost of its ellipsoid (p_{t+1}, Q_{t+1}) through
+    sx_sat_cost_eval -- one more launch per step, in place of the hook and env.obj_mode -- as sx_cem_rollout_sat prices it.
     """
+    _cost_args(cost, ssm)
     n_s, n_u = ssm.num_states, ssm.num_actions
     dev = actions.device
     P, H, _ = actions.shape
@@ -618,7 +642,9 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
                                         _lib.ptr(var.contiguous()), _lib.ptr(jac), _lib.ptr(p1), _lib.ptr(q1),
                                         _lib.ptr(sigma), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_onestep_reach')
         # costs: objective safempc_cem.py:304-312, action box test_safempc_cem.py:59-71, polytope safempc_cem.py:102-132
-        if objective_hook is not None:
+        if cost is not None:
+            obj = obj + cost.evaluate_device(p1, q1, status)
+        elif objective_hook is not None:
             obj = obj + objective_hook(p1)
         elif env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE:
             obj = obj - sigma.sum(dim=1)
@@ -792,17 +818,20 @@ def _check_solve(owner, x0: Tensor, q_block: Optional[Tensor], best: Tensor, bes
     return best_host, found, repeated
 
 
-def _checked_cost(cost, n_s: int, kind: Optional[str]):
+def _checked_cost(cost, n_s: int, kind: Optional[str], on_safety: bool = False):
     """`cost` as `set_cost` of the solvers keeps it: None, or a SaturatingCost for this state dimension on a solver whose
-    performance rollout is the Taylor form (`kind`; the cautious solver's always is)."""
+    performance rollout is the Taylor form (`kind`; the cautious solver's always is), or which prices the safety
+    ellipsoids (`on_safety`: FusedCemMpc(cost_on_safety=True), which has no performance trajectory)."""
     if cost is None:
         return None
     if not isinstance(cost, SaturatingCost):
         raise TypeError(f'cost must be a costs.SaturatingCost or None, got {type(cost).__name__}')
-    if kind != 'taylor':
+    if kind != 'taylor' and not on_safety:
         raise ValueError("a SaturatingCost prices (mean, covariance) pairs: it needs a performance trajectory with "
                          "cem_perf_type='taylor' (perf_type='taylor', n_perf > 0), not "
-                         + ('no performance trajectory' if kind is None else f'the {kind!r} form'))
+                         + ('no performance trajectory' if kind is None else f'the {kind!r} form')
+                         + ('; without one, cost_on_safety=True (cem_cost_on_safety) prices the safety ellipsoids'
+                            if kind is None else ''))
     if cost.n_s != n_s:
         raise ValueError(f'the cost is built for n_s = {cost.n_s}, the model has n_s = {n_s}')
     return cost
@@ -831,14 +860,24 @@ class FusedCemMpc:
     and the objective sees the variance including it.  It carries the variance objective by itself, as ``perf_variance``
     does.  ``perf_terminal_safety=True`` adds the state-violation cost where the performance ellipsoid at step
     ``time_horizon + 2`` leaves the safe polytope (``n_perf >= time_horizon + 2``).  Recorded rollouts gain ``perf_cov``.
+
+    ``cost_on_safety=True`` (with ``n_perf == 0``) lets ``set_cost`` take a ``SaturatingCost`` as the
+    objective of the safety trajectory itself: every ellipsoid (p_t, Q_t), t = 1 .. H, is priced as a mean and a covariance
+    in the rollout kernel (``sx_cem_rollout_sat`` / ``sx_cem_rollout_elites_sat``, the streaming form), what the reference's
+    ``n_perf = 0`` configs hand their solver.  The cost belongs to one trajectory, chosen by ``n_perf``.
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
                  record_rollouts: bool = False, process_group=None, force_exchange: bool = False, n_perf: int = 0,
                  perf_r: int = 1, perf_variance: bool = False, perf_type: str = 'mean_equivalent',
-                 perf_terminal_safety: bool = False):
+                 perf_terminal_safety: bool = False, cost_on_safety: bool = False):
         self._ssm = ssm
+        self._cost_on_safety = bool(cost_on_safety)
+        if self._cost_on_safety and int(n_perf) > 0:
+            raise ValueError(f'cost_on_safety=True prices the safety trajectory, which carries the objective only without a '
+                             f'performance trajectory: got n_perf={n_perf}.  The cost belongs to one trajectory, chosen by '
+                             f"n_perf (n_perf > 0 with perf_type='taylor' prices the performance trajectory)")
         self._env = env
         self._horizon = time_horizon
         # the performance trajectory (off with n_perf = 0): T tail steps behind the H safety steps of a row
@@ -950,8 +989,19 @@ class FusedCemMpc:
     def set_cost(self, cost) -> None:
         """The saturating cost (`costs.SaturatingCost`) as the objective of the performance trajectory, priced in the kernel
         on (mu_{t+1}, Sigma_{t+1}) of every step (sx_cem_perf_rollout_taylor_sat): env's objective is then not read and no
-        objective hook is evaluated.  None takes it off again.  Needs the propagated covariance."""
-        self._cost = _checked_cost(cost, self._ssm.num_states, self._perf_kind if self._n_perf > 0 else None)
+        objective hook is evaluated.  None takes it off again.  Needs the propagated covariance.
+        On a solver built with ``cost_on_safety=True`` (no performance trajectory) the cost prices the safety ellipsoids
+        instead (sx_cem_rollout_sat; the step-by-step path prices them with sx_sat_cost_eval): again env's objective is not
+        read, no hook is evaluated and no trajectory is recorded for one."""
+        on_safety = getattr(self, '_cost_on_safety', False)
+        if cost is not None and on_safety:
+            _require_rbf_cost([self._ssm])
+        self._cost = _checked_cost(cost, self._ssm.num_states, self._perf_kind if self._n_perf > 0 else None, on_safety)
+
+    @property
+    def _safety_cost(self):
+        """The cost where it prices the safety trajectory (cost_on_safety), else None."""
+        return self._cost if getattr(self, '_cost_on_safety', False) else None
 
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
         if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf_kind == 'mean':
@@ -1069,9 +1119,11 @@ class FusedCemMpc:
     def _rollout_stepwise(self, x0: Tensor, mean: Tensor, std: Tensor, eps: Tensor, status: Tensor):
         """One iteration's rollout through `cem_rollout_stepwise`, problem by problem."""
         acts = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x H x n_u]
+        cost = self._safety_cost
         per_e = [cem_rollout_stepwise(self._ssm, self._env, x0[e], acts[e], status=status,
                                       group=self._group if self._world > 1 else None,
-                                      objective_hook=self._objective_hook) for e in range(x0.size(0))]
+                                      objective_hook=self._objective_hook if cost is None else None,
+                                      **({} if cost is None else dict(cost=cost))) for e in range(x0.size(0))]
         return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
                     con_cost=torch.stack([q['con_cost'] for q in per_e]))
 
@@ -1108,7 +1160,10 @@ class FusedCemMpc:
         # the ranking before it (sx_cem_rollout_elites): the ranking launches then skip their refit tail.
         # (not with a performance trajectory: the prologue reads rows of 2 + H n_u, the ranking launch refits the long rows)
         in_prologue = (not stepwise) and (not perf) and self._refit_in_prologue(E)
-        want_traj = self._record or (self._objective_hook is not None and not perf)
+        # (a cost on the safety trajectory rides in the rollout call: no hook is evaluated, no trajectory recorded for one)
+        safety_cost = self._safety_cost
+        cost_kw = {} if safety_cost is None else dict(cost=safety_cost)
+        want_traj = self._record or (self._objective_hook is not None and not perf and safety_cost is None)
         if perf and noise is not None:
             # the draws of the safety steps and of the tail, each contiguous: two copies per solve
             noise_safe, noise_tail = noise[:, :, :, :H].contiguous(), noise[:, :, :, H:].contiguous()
@@ -1132,7 +1187,7 @@ class FusedCemMpc:
             else:
                 try:
                     r = cem_rollout(self._ssm, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
-                                    noise=eps.contiguous(), want_traj=want_traj, status=status)
+                                    noise=eps.contiguous(), want_traj=want_traj, status=status, **cost_kw)
                 except FusedJunkUnsupported:
                     # (answered before any launch) the junk-dimension model has no single-launch form for this training
                     # set: the whole solve goes step by step through the wrapper
@@ -1155,7 +1210,7 @@ class FusedCemMpc:
                     for t in range(self._n_perf):
                         obj += hook(pr['perf_traj'][:, :, t].reshape(-1, n_s)).reshape(obj.shape)
                     r['obj_cost'] = obj.contiguous()
-            elif self._objective_hook is not None and not stepwise:
+            elif self._objective_hook is not None and not stepwise and safety_cost is None:
                 n_s = self._ssm.num_states
                 centres = r['traj'][..., :n_s]                                   # [E x P x H x n_s]
                 obj = torch.zeros_like(r['obj_cost'])
@@ -1273,6 +1328,9 @@ class MultiModelCemMpc:
     JunkDimensionsSSM and step-by-step models, differing architectures, an exact-GP training set that needs the workspace
     path (one solve per model then), and the per-problem step-by-step repeat of ``_check_solve``.  The problems share
     `env` and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
+
+    Solvers built with ``cost_on_safety=True`` carry their ``SaturatingCost`` into the launch (``sx_cem_rollout_sat_multi`` /
+    ``sx_cem_rollout_elites_sat_multi``): equal costs on all solvers, or none on any of them.
     """
 
     _perf_solvers = False   # MultiModelPerfCemMpc: the solvers carry a performance trajectory
@@ -1310,6 +1368,20 @@ class MultiModelCemMpc:
         self._last_noise = None
         self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path
         self.per_model_solves = 0       # solves that went one model at a time (single launch not applicable)
+        self._solver_cost()
+
+    def _solver_cost(self):
+        """The kernel-form cost of the solve: the solvers' (`FusedCemMpc.set_cost`), equal on all of them or on none."""
+        costs = [getattr(s, '_cost', None) for s in self._solvers]
+        if any(c != costs[0] for c in costs):
+            raise ValueError(f'a multi-model solve needs equal costs on all of its solvers, or none on any of them; got '
+                             f'{costs}')
+        return costs[0]
+
+    def set_cost(self, cost) -> None:
+        """`FusedCemMpc.set_cost` on every solver."""
+        for s in self._solvers:
+            s.set_cost(cost)
 
     @classmethod
     def from_solvers(cls, solvers: Sequence[FusedCemMpc]) -> 'MultiModelCemMpc':
@@ -1326,7 +1398,7 @@ class MultiModelCemMpc:
         def settings(m):
             init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
             names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world',
-                     '_n_perf', '_perf_r', '_perf_variance', '_perf_type', '_perf_terminal_safety')
+                     '_n_perf', '_perf_r', '_perf_variance', '_perf_type', '_perf_terminal_safety', '_cost_on_safety')
             return ((type(m),) + tuple(getattr(m, a, None) for a in names)
                     + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
 
@@ -1334,8 +1406,8 @@ class MultiModelCemMpc:
         for cem, env in rest:
             if cem != cem0:
                 raise ValueError('the solvers of a multi-model solve must share the CEM settings (horizon, rollouts, '
-                                 'elites, iterations, initial distribution, device, and the performance trajectory\'s '
-                                 'n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety)')
+                                 'elites, iterations, initial distribution, device, the performance trajectory\'s '
+                                 'n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety, and cost_on_safety)')
             if env != env0:
                 raise ValueError('the solvers of a multi-model solve must share the environment constants (sx_env)')
 
@@ -1382,10 +1454,13 @@ class MultiModelCemMpc:
         # (solver 0 stands for all: the solvers share this solve's settings, and a model on the workspace path has no
         # multi-model launch at all)
         in_prologue = self._solvers[0]._refit_in_prologue(E)
+        # the solvers' cost where it prices the safety trajectory (cost_on_safety): it rides in the rollout call
+        cost = self._solver_cost() if getattr(self._solvers[0], '_cost_on_safety', False) else None
+        cost_kw = {} if cost is None else dict(cost=cost)
 
         def rollout(it, mean, std, rows):
             return cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
-                                     noise=noise[it].contiguous(), status=status, table=self._table)
+                                     noise=noise[it].contiguous(), status=status, table=self._table, **cost_kw)
 
         def rank(it, r):
             return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['actions'], self._num_elites, want_rows=in_prologue,
@@ -1402,6 +1477,7 @@ class MultiModelCemMpc:
         E, n_s = len(self._ssms), self._ssms[0].num_states
         if states.dim() != 2 or states.shape != (E, n_s + n_s * n_s):
             raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(states.shape)}')
+        self._solver_cost()      # mixed costs raise before anything is solved, one model at a time included
         states = states.to(self._device, torch.float64)
         x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
         if not self.fused_applies():
@@ -1474,20 +1550,6 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         self._taylor = self._perf_kind == 'taylor'
         # the device table the performance launch reads: alpha per model for the mean-only form, else the safety launch's
         self._perf_table = PerfModelTable() if self._perf_kind == 'mean' else self._table
-        self._solver_cost()
-
-    def _solver_cost(self):
-        """The kernel-form cost of the solve: the solvers' (`FusedCemMpc.set_cost`), equal on all of them or on none."""
-        costs = [getattr(s, '_cost', None) for s in self._solvers]
-        if any(c != costs[0] for c in costs):
-            raise ValueError(f'a multi-model solve needs equal costs on all of its solvers, or none on any of them; got '
-                             f'{costs}')
-        return costs[0]
-
-    def set_cost(self, cost) -> None:
-        """`FusedCemMpc.set_cost` on every solver."""
-        for s in self._solvers:
-            s.set_cost(cost)
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         if objective_hook is not None:

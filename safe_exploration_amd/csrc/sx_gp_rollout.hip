@@ -1,7 +1,8 @@
 // The exact-GP rollout entries: which form a model's rollout takes (plan_rollout), the launch in
 // that form through the launchers of sx_rw_launch.hpp, sx_stream_launch.hpp and sx_big_launch.hpp, the GP model table, and
 // sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi, sx_cem_rollout_starts, sx_cem_rollout_form,
-// sx_cem_rollout_multi_form, sx_cem_rollout_starts_form, sx_cem_rollout_workspace_bytes.  No kernel is compiled here.
+// sx_cem_rollout_multi_form, sx_cem_rollout_starts_form, sx_cem_rollout_workspace_bytes, and the entries with the saturating
+// cost on the safety ellipsoids, sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form.  No kernel is compiled here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -192,6 +193,44 @@ static int launch_rollout_starts(const sx_gp_model* m, const sx_env* env, const 
                                          plan.form == SX_FORM_BYOUT, plan.lds, stream);
 }
 
+// The rollouts with the saturating cost on the safety ellipsoids (sx_cem_rollout[_elites]_sat) have the streaming kernel
+// only, as the per-particle starts: plan_rollout's streaming answer with the elite-row bound, no workspace path.
+// sx_cem_rollout_sat_form reports it (elites = false).
+static RolloutPlan plan_rollout_sat(const sx_gp_model* m, int H, bool elites) {
+    RolloutPlan p = plan_rollout(m, 0, H, elites, true);
+    if (p.form == SX_FORM_BIG) p.ok = false;
+    return p;
+}
+
+template <int NS, int NU>
+static int launch_rollout_sat(const sx_gp_model* m, const sx_env* env, const sx_sat_cost* cost, const RolloutPtrs& rp,
+                              hipStream_t stream) {
+    const RolloutPlan plan = plan_rollout_sat(m, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    SatConst<NS> sat;
+    make_sat_const<NS>(cost, sat);
+    return launch_rollout_sat<NS, NU>(make_gp_const<NS, NU>(m, kRolloutThreads / 64), rc, cc, rp, sat,
+                                      plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
+// (the plan is sx_cem_rollout_multi's: that entry has the streaming kernel only)
+template <int NS, int NU>
+static int launch_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                                    const RolloutPtrs& rp, hipStream_t stream) {
+    const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
+    if (!plan.ok) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    SatConst<NS> sat;
+    make_sat_const<NS>(cost, sat);
+    return launch_rollout_sat_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp, sat,
+                                            plan.form == SX_FORM_BYOUT, plan.lds, stream);
+}
+
 // sx_cem_rollout[_elites][_junk] after their argument checks
 static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
                        int64_t workspace_bytes, void* stream) {
@@ -342,6 +381,70 @@ int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, co
     if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
     if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
     return cem_rollout_multi(models, table, env, rp, stream);
+}
+
+// ---- the saturating cost on the safety ellipsoids --------------------------------------------------
+int sx_cem_rollout_sat_form(const sx_gp_model* model, int H) {
+    if (!model || H <= 0) return -1;
+    const sx::RolloutPlan plan = sx::plan_rollout_sat(model, H, false);
+    return plan.ok ? plan.form : -1;
+}
+
+// sx_cem_rollout[_elites]_sat after the parents' argument checks: the cost's, then the launch (env->obj_mode is not read)
+static int cem_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, const sx::RolloutPtrs& rp,
+                           void* stream) {
+    if (!sx::sat_cost_ok(cost, env->n_s)) return SX_ERR_ARG;
+#define CALL(NS, NU) sx::launch_rollout_sat<NS, NU>(model, env, cost, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
+}
+
+static int cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                                 const sx::RolloutPtrs& rp, void* stream) {
+    if (!sx::sat_cost_ok(cost, env->n_s)) return SX_ERR_ARG;
+#define CALL(NS, NU) sx::launch_rollout_sat_multi<NS, NU>(models, table, env, cost, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
+}
+
+int sx_cem_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
+                       const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
+                       double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
+                       void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!model || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, 0)) return SX_ERR_ARG;
+    return cem_rollout_sat(model, env, cost, rp, stream);
+}
+
+int sx_cem_rollout_elites_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
+                              const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
+                              double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
+                              int32_t* status, double* mean_out, double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
+                                            E, P, H}, elite_rows, k, mean_out, std_out);
+    if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, 0)) return SX_ERR_ARG;
+    return cem_rollout_sat(model, env, cost, rp, stream);
+}
+
+int sx_cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost, int E,
+                             int P, int H, const double* x0, const double* q0, const double* mean, const double* std,
+                             const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                             double* con_cost, int32_t* status, void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    if (!table || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    return cem_rollout_sat_multi(models, table, env, cost, rp, stream);
+}
+
+int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                                    int E, int P, int H, const double* x0, const double* q0, const double* elite_rows, int k,
+                                    const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                                    double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
+                                            E, P, H}, elite_rows, k, mean_out, std_out);
+    if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    return cem_rollout_sat_multi(models, table, env, cost, rp, stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "sx_gp.hpp"
 #include "sx_reach.hpp"
 #include "sx_refit.hpp"
+#include "sx_sat_cost.hpp"   // SatConst, sat_loss
 
 namespace sx {
 
@@ -84,7 +85,9 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
     typename RolloutGpArg<NS, NS + NU + SH, MM>::type gc_arg, const int4* __restrict__ stage_tab_arg,
     ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp) {
 #define SX_ROLLOUT_PS 0
+#define SX_ROLLOUT_SAT 0
 #include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_SAT
 #undef SX_ROLLOUT_PS
 }
 
@@ -97,7 +100,36 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_starts_kernel(
     constexpr int SH = 0;
     constexpr bool MM = false;
 #define SX_ROLLOUT_PS 1
+#define SX_ROLLOUT_SAT 0
 #include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_SAT
+#undef SX_ROLLOUT_PS
+}
+
+// sx_cem_rollout[_elites]_sat[_multi]: cem_rollout_kernel (SH = 0) with the saturating cost of sx_sat_cost.hpp as the
+// objective, priced on the safety ellipsoids (p_{t+1}, Q_{t+1}) read as means and covariances (the SX_ROLLOUT_SAT section
+// of sx_rollout_body.inc) -- what the reference's n_perf = 0 configs hand their solver.  The cost's
+// constants are one more kernel argument, uniform and read by scalar loads on the owner lanes: the LDS plan is the
+// parent's byte for byte.  MM and the elite-row prologue are the body's own, so one kernel serves the four entries.
+template <int NS, int NU, bool MM>
+constexpr size_t rollout_sat_arg_bytes() {
+    constexpr size_t a = 8;   // every argument starts on 8 bytes
+    return ((sizeof(typename RolloutGpArg<NS, NS + NU, MM>::type) + a - 1) / a + (sizeof(const int4*) + a - 1) / a +
+            (sizeof(ReachConst<NS, NU>) + a - 1) / a + (sizeof(CostConst<SX_MAX_M, NS, NU>) + a - 1) / a +
+            (sizeof(RolloutPtrs) + a - 1) / a + (sizeof(SatConst<NS>) + a - 1) / a) * a;
+}
+constexpr size_t kMaxKernelArgBytes = 4096;   // what a HIP launch takes
+
+template <int NS, int NU, bool BYOUT, bool MM>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_sat_kernel(
+    typename RolloutGpArg<NS, NS + NU, MM>::type gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const SatConst<NS> sat) {
+    static_assert(rollout_sat_arg_bytes<NS, NU, MM>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
+    constexpr int SH = 0;
+#define SX_ROLLOUT_PS 0
+#define SX_ROLLOUT_SAT 1
+#include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_SAT
 #undef SX_ROLLOUT_PS
 }
 

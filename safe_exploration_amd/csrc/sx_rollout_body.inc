@@ -1,13 +1,16 @@
 // The body of cem_rollout_kernel and cem_rollout_starts_kernel (sx_rollout.hpp), included into both: as text, so that
 // cem_rollout_kernel keeps the symbol and the instructions it had before the per-particle-start mode existed (a trailing
 // template flag would have renamed every instantiation).  In scope: NS, NU, BYOUT, SH, MM; the kernel arguments gc_arg,
-// stage_tab_arg, rc, cc, rp; SX_ROLLOUT_PS (0 | 1).
+// stage_tab_arg, rc, cc, rp; SX_ROLLOUT_PS (0 | 1); SX_ROLLOUT_SAT (0 | 1).
 // SX_ROLLOUT_PS = 1 (sx_cem_rollout_starts; SH = 0, MM = false): the CEM row of a particle is [x0 (NS) | actions (H NU)],
 // L = NS + H NU entries.  rp.mean / rp.std are [E x L], rp.noise [E x P x L] | NULL, rp.actions the rows [E x P x L]
 // (written when noise is given, read otherwise); rp.x0, rp.q0 and the elite-row fields are unused.  The owner lane of a
 // particle takes its start from its own row (a point, reach_point at t = 0) and pays SX_STATE_VIOLATION_COST once where
 // that start is outside the polytope; a lane past P in the last tile reads through the problem's first particle and writes
 // nothing.  The step loop, the forms, the barriers and finish() are the text both kernels share.
+// SX_ROLLOUT_SAT = 1 (cem_rollout_sat_kernel; SH = 0, SX_ROLLOUT_PS = 0): the objective of a step is the saturating cost of
+// sx_sat_cost.hpp on the safety ellipsoid (p_{t+1}, Q_{t+1}), read as a mean and a covariance, from `sat` (SatConst<NS>, a
+// kernel argument of its own: scalar loads, no LDS); cc.obj_mode is not read.  Nothing else in the step changes.
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
@@ -238,7 +241,20 @@
         if (valid) st |= st_step;
         // costs (safempc_cem.py:102-132,304-312; action constraint: test_safempc_cem.py:59-71) and stores, as
         // constraint_costs / store_step of sx_step.hpp (which move this kernel's multi-model form by 2 %)
+#if SX_ROLLOUT_SAT
+        {
+            // the saturating cost of (p_{t+1}, Q_{t+1}); reach_point / reach_ellipsoid leave Q1 with both triangles.  A
+            // non-finite loss never ranks
+            const double o = sat_loss<NS>(sat, p1, Q1);
+            obj += o;
+            if (!(__builtin_fabs(o) <= 1.7976931348623157e308)) {
+                st |= SX_STATUS_NAN;
+                obj = __builtin_nan("");
+            }
+        }
+#else
         obj += objective_cost<SX_MAX_M, NS, NU>(cc, p1, var);
+#endif
         bool uviol = false;
 #pragma unroll
         for (int cidx = 0; cidx < NU; ++cidx) uviol = uviol || (u[cidx] < cc.u_min[cidx]) || (u[cidx] > cc.u_max[cidx]);

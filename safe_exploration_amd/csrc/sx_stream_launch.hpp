@@ -1,7 +1,8 @@
 // The compiled shapes of the fused rollout, and the launchers of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
 // BYOUT, SH, MM>).  The launchers' instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
-// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip; built in parallel with the rest); sx_gp_rollout.hip
-// sees the declarations.
+// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the
+// saturating-cost objective in sx_stream_sat.hip and sx_stream_sat_multi.hip; built in parallel with the rest);
+// sx_gp_rollout.hip sees the declarations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,5 +77,19 @@ template <int NS, int NU>
 int launch_rollout_starts(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc,
                           const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
                           hipStream_t stream);
+
+// Launches cem_rollout_sat_kernel<NS, NU, byout, false> (sx_cem_rollout[_elites]_sat: the saturating cost `sat` on the
+// safety ellipsoids as the objective) with `lds` bytes (rollout_stream_lds_bytes, shift 0: the parent's plan).
+// Instantiated for every shift-0 shape in sx_stream_sat.hip.
+template <int NS, int NU>
+int launch_rollout_sat(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
+                       const RolloutPtrs& rp, const SatConst<NS>& sat, bool byout, size_t lds, hipStream_t stream);
+
+// Launches cem_rollout_sat_kernel<NS, NU, byout, true> over E problems with a GP each (sx_cem_rollout[_elites]_sat_multi;
+// `table`, `lds` and rp.status as launch_rollout_stream_multi).  Instantiated in sx_stream_sat_multi.hip.
+template <int NS, int NU>
+int launch_rollout_sat_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
+                             const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, const SatConst<NS>& sat,
+                             bool byout, size_t lds, hipStream_t stream);
 
 }  // namespace sx

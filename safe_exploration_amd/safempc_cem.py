@@ -263,6 +263,17 @@ class CemSafeMPC(SafeMPC):
                                  'means only and cannot carry the variance objective (set cem_perf_variance or '
                                  "cem_perf_type='taylor' for one that does)")
 
+        # cem_cost_on_safety: without a performance trajectory (cem_n_perf = 0, the reference's nperf=0 configs) init_solver's
+        # SaturatingCost prices the safety ellipsoids in the rollout kernel (FusedCemMpc(cost_on_safety=True), DESIGN.md
+        # section 3.13).  The cost belongs to one trajectory, chosen by cem_n_perf as the reference's config chooses.
+        self._cem_cost_on_safety = bool(getattr(conf, 'cem_cost_on_safety', False))
+        if self._cem_cost_on_safety and self._cem_n_perf:
+            raise ValueError(f'cem_cost_on_safety prices the safety trajectory, which carries the objective only without a '
+                             f'performance trajectory: got cem_n_perf={self._cem_n_perf}')
+        if self._cem_cost_on_safety and mpc is None and getattr(ssm, 'kernel_family', None) != 'rbf':
+            raise NotImplementedError(f'cem_cost_on_safety needs an exact RBF GP (GpCemSSM), not kernel_family '
+                                      f'{getattr(ssm, "kernel_family", None)!r}')
+
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
         self._linearized_model_a = torch.tensor(linearized_model_a, device=self._device)
@@ -315,13 +326,17 @@ class CemSafeMPC(SafeMPC):
     def init_solver(self, cost_func=None) -> None:
         """A `costs.SaturatingCost` becomes the objective of the performance trajectory, priced in the rollout kernel on
         every (mean, covariance) of it (what the reference's casadi configs hand over here); it needs the propagated
-        covariance.  Any other value is ignored: the objective is then the environment's."""
+        covariance.  With conf.cem_cost_on_safety and no performance trajectory (cem_n_perf = 0) it becomes the objective of
+        the safety trajectory, priced on every ellipsoid (p_t, Q_t) as a mean and a covariance (the reference's nperf=0
+        configs).  Any other value is ignored: the objective is then the environment's."""
         if not isinstance(cost_func, SaturatingCost):
             return
-        if self._cem_perf_type != 'taylor' or self._cem_n_perf <= 0:
+        on_safety = getattr(self, '_cem_cost_on_safety', False) and self._cem_n_perf <= 0
+        if not on_safety and (self._cem_perf_type != 'taylor' or self._cem_n_perf <= 0):
             raise ValueError("a SaturatingCost prices (mean, covariance) pairs of the performance trajectory: it needs "
                              f"cem_perf_type='taylor' with cem_n_perf > 0, got cem_perf_type={self._cem_perf_type!r}, "
-                             f'cem_n_perf={self._cem_n_perf}')
+                             f'cem_n_perf={self._cem_n_perf}; without a performance trajectory, cem_cost_on_safety prices '
+                             f'the safety ellipsoids')
         self._cost = cost_func
         if self._mpc is not None:
             self._mpc.set_cost(cost_func)
@@ -377,7 +392,8 @@ class CemSafeMPC(SafeMPC):
                                     record_rollouts=self._record_rollouts, n_perf=self._cem_n_perf,
                                     perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}),
                                     **({'perf_type': 'taylor', 'perf_terminal_safety': self._cem_perf_terminal_safety}
-                                       if self._cem_perf_type == 'taylor' else {}))
+                                       if self._cem_perf_type == 'taylor' else {}),
+                                    **({'cost_on_safety': True} if getattr(self, '_cem_cost_on_safety', False) else {}))
             if self._cost is not None:
                 self._mpc.set_cost(self._cost)
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
@@ -525,8 +541,10 @@ def multi_solve_applies(mpcs: Sequence) -> bool:
     """Do these single-model optimisers go through one MultiModelCemMpc (get_actions_multi)?  Unsharded FusedCemMpc
     instances without an objective hook whose models share one kernel_family with a multi-model rollout: exact RBF GPs,
     feature-space GPs ('linear', 'nn') or MC-dropout ensembles.  (Whether one launch then serves the models -- no workspace
-    path, one architecture -- is MultiModelCemMpc.fused_applies: a solve per model otherwise.)"""
-    return (all(isinstance(m, FusedCemMpc) and m._objective_hook is None and m._world == 1 for m in mpcs)
+    path, one architecture -- is MultiModelCemMpc.fused_applies: a solve per model otherwise.  A hook is never evaluated
+    beside a cost on the safety trajectory, cost_on_safety: such solvers go through it with the cost.)"""
+    return (all(isinstance(m, FusedCemMpc) and (m._objective_hook is None or m._safety_cost is not None) and m._world == 1
+                for m in mpcs)
             and multi_family([m._ssm for m in mpcs]) is not None)
 
 

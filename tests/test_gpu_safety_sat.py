@@ -1,0 +1,400 @@
+"""GPU: the saturating cost on the safety trajectory -- sx_cem_rollout_sat, sx_cem_rollout_elites_sat and their _multi forms
+(cem_rollout_sat_kernel) against their parent entries (everything but obj_cost), against the numpy oracle
+(tests/sat_cost_oracle.py over the kernel's own traj, and tests/safety_sat_oracle.py over oracle.cem.rollout), their
+independence of obj_mode, the grid and a NaN neighbour, the fused rollout against the step-by-step one, and the solves of
+tests/safety_sat_oracle.py through FusedCemMpc(cost_on_safety=True), MultiModelCemMpc and CemSafeMPC.
+
+Shapes: P = 37 (three tiles, the last one partial), E = 2; (n_s, n_u, N) in {(2,1,7), (2,1,200), (4,1,200), (4,1,590: output
+by output), (2,2,200), (3,1,200)}; the training-set pairs of test_gpu_sat_cost.MULTI_CASES; H = 3 and 15.  Costs: cost_for of
+test_gpu_sat_cost.py (full rank at n_s = 2, the reference's cart-pole constants at n_s = 4) and a rank-2 cost at n_s = 3.
+
+Tolerances.  Against the parent entry every output but obj_cost is bit-equal where the parent runs the streaming kernel (always
+for the multi entries; single models under SX_ROLLOUT=stream, compared with a child process), and within TOL['rbf'] of
+tests/test_gpu_rollout_matrix.py where the parent takes a resident form.  obj_cost against the oracle's cost of the kernel's
+OWN traj: LOSS_TOL = 1e-12 per step, summed (the same formula on the same inputs); against the oracle's rollout TOL['rbf']'s
+objective tolerance (rtol 1e-7, atol 1e-11: a bounded smooth function of shapes held to that tolerance).  Fused against step by
+step: 1e-12 per step, constraint costs exactly.  A solve: constraint costs exactly, equal elite sets, best row within 1e-9.
+Every case prints its worst error before it asserts.  Measured figures: DESIGN.md section 3.13."""
+import ctypes
+import functools
+import os
+import subprocess
+import sys
+from unittest import mock
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:      # (this file is also the child process of the bit-equality check)
+    sys.path.insert(0, ROOT)
+
+import safety_sat_oracle as sso
+import sat_cost_oracle as so
+import test_gpu_perf_multi as multi
+from oracle import cem as ocem
+from safe_exploration_amd import _lib, cem_mpc, problems
+from safe_exploration_amd.costs import SaturatingCost
+from test_gpu_junk_fused import CountingLib
+from test_gpu_perf_var import ABS, DEV, VAR, N_, T, case, worst
+from test_gpu_rollout_matrix import TOL
+from test_gpu_sat_cost import LOSS_TOL, MULTI_CASES, cost_for
+from test_sat_cost_host import random_weight
+
+pytestmark = pytest.mark.gpu
+E, SMALL, LARGE = 2, 37, 4149
+CASES = [(2, 1, 7), (2, 1, 200), (4, 1, 200), (4, 1, 590), (2, 2, 200), (3, 1, 200)]
+STEPS = [3, 15]
+KINDS = ('given', 'drawn', 'elites')
+OUTPUTS = ('actions', 'traj', 'sigma', 'con_cost', 'status')
+RTOL_P, RTOL, ATOL = TOL['rbf']
+SX_FORM_STREAM, SX_FORM_BYOUT = 0, 3
+K_ELITES = 5
+
+
+def cost_of(n_s):
+    """(SaturatingCost, its oracle twin): cost_for of test_gpu_sat_cost.py; at n_s = 3 a rank-2 weight with the angle at 1."""
+    if n_s != 3:
+        return cost_for(n_s)
+    z, w = np.array([0.3, -0.1, 0.2, 0.8]), random_weight(np.random.default_rng(78), 4, 2) * 0.4
+    cost = SaturatingCost(z, w, 1)
+    assert cost.rank == 2
+    return cost, so.Cost(z, w, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(n_s, n_u, P, H, seed):
+    """x0 [E x n_s], the distribution, the draws and the rows they give, and elite rows [E x k x (2 + H n_u)]."""
+    rng = np.random.default_rng(seed)
+    x0 = rng.normal(0, 0.05, size=(E, n_s))
+    mean, std = rng.normal(0, 0.2, size=(E, H, n_u)), rng.uniform(0.3, 0.8, size=(E, H, n_u))
+    noise = rng.normal(size=(E, P, H, n_u))
+    elite = np.concatenate((np.zeros((E, K_ELITES, 2)), rng.normal(0, 0.5, size=(E, K_ELITES, H * n_u))), axis=2)
+    return dict(x0=x0, mean=mean, std=std, noise=noise, actions=mean[:, None] + std[:, None] * noise, elite=elite)
+
+
+def seed_of(n_s, n_u, N, H):
+    return 5 + n_s + 7 * n_u + (N if isinstance(N, int) else sum(N)) + 100 * H
+
+
+def launch(models, env, inp, H, kind, cost=None, status=None):
+    """One rollout: `models` a GpCemSSM (sx_cem_rollout[_elites][_sat]) or a list of them (the _multi entries)."""
+    many = isinstance(models, (list, tuple))
+    fn = cem_mpc.cem_rollout_multi if many else cem_mpc.cem_rollout
+    kw = dict(want_traj=True, want_sigma=True, status=status, **({} if cost is None else dict(cost=cost)))
+    if kind == 'given':
+        kw.update(actions=T(inp['actions']))
+    elif kind == 'drawn':
+        kw.update(mean=T(inp['mean']), std=T(inp['std']), noise=T(inp['noise']))
+    else:
+        kw.update(elite_rows=T(inp['elite']), noise=T(inp['noise']), want_dist=True)
+    out = fn(models, env, T(inp['x0']), H, **kw)
+    torch.cuda.synchronize()
+    return out
+
+
+def names_of(kind):
+    return OUTPUTS + (('mean', 'std') if kind == 'elites' else ())
+
+
+def assert_close_to_parent(label, parent, sat, kind, n_s, exact):
+    for name in names_of(kind):
+        a, b = sat[name], parent[name]
+        if exact or name in ('con_cost', 'status'):
+            assert torch.equal(a, b), f'{label}: {name} differs from the parent\'s bits'
+        elif name == 'traj':
+            np.testing.assert_allclose(N_(a)[..., :n_s], N_(b)[..., :n_s], rtol=RTOL_P, atol=ATOL, err_msg=f'{label}: centres')
+            np.testing.assert_allclose(N_(a)[..., n_s:], N_(b)[..., n_s:], rtol=RTOL, atol=ATOL, err_msg=f'{label}: shapes')
+        else:
+            # (actions and the refit are computed before the forms part ways; sigma is held like the shapes)
+            np.testing.assert_allclose(N_(a), N_(b), rtol=RTOL, atol=ATOL, err_msg=f'{label}: {name}')
+
+
+def split(traj, n_s):
+    traj = N_(traj)
+    return traj[..., :n_s], traj[..., n_s:].reshape(traj.shape[:-1] + (n_s, n_s))
+
+
+def check_objective(label, twin, sat, e, ref, H, n_s):
+    """obj_cost of problem e against the oracle's cost of the kernel's own traj, and against the oracle's rollout `ref`."""
+    tp, tq = split(sat['traj'][e], n_s)
+    own, oracle = so.losses(twin, tp, tq).sum(axis=1), sso.safety_cost(twin, ref)
+    obj = N_(sat['obj_cost'][e])
+    print(f'{label}: obj_cost against the oracle\'s cost of the kernel\'s own traj {np.abs(obj - own).max():.3e} (tolerance '
+          f'{LOSS_TOL * H:.1e}); against the oracle\'s rollout {worst(obj, oracle, rtol=RTOL, atol=ATOL):.3e} of the tolerance; '
+          f'objective in [{oracle.min():.3f}, {oracle.max():.3f}]; {int((ref.con_cost > 0).sum())} of {len(obj)} rows violate')
+    assert oracle.max() - oracle.min() > 1e-3, 'the objective does not tell the particles apart'
+    assert np.abs(obj - own).max() <= LOSS_TOL * H
+    np.testing.assert_allclose(obj, oracle, rtol=RTOL, atol=ATOL)
+    np.testing.assert_array_equal(N_(sat['con_cost'][e]), ref.con_cost)
+
+
+# ---- 1, 2: against the parent entry and the oracle -----------------------------------------------------------------------------
+@pytest.mark.parametrize('H', STEPS)
+@pytest.mark.parametrize('n_s,n_u,N', CASES)
+def test_sat_rollout_against_the_parent_and_the_oracle(n_s, n_u, N, H):
+    ssm, envs, spec, gp, probs = case(n_s, n_u, N)
+    cost, twin = cost_of(n_s)
+    inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H))
+    form = int(_lib.lib().sx_cem_rollout_form(ctypes.byref(ssm.device_model), H))
+    sat_form = int(_lib.lib().sx_cem_rollout_sat_form(ctypes.byref(ssm.device_model), H))
+    exact = form in (SX_FORM_STREAM, SX_FORM_BYOUT)
+    assert sat_form == (SX_FORM_BYOUT if N == 590 else SX_FORM_STREAM)
+    outs = {}
+    for kind in KINDS:
+        parent, sat = launch(ssm, envs[ABS], inp, H, kind), launch(ssm, envs[ABS], inp, H, kind, cost)
+        label = f'({n_s},{n_u}) N={N} H={H} {kind} (parent form {form}, sat form {sat_form})'
+        assert int(sat['status'].item()) == 0
+        assert_close_to_parent(label, parent, sat, kind, n_s, exact)
+        # obj_mode is not read: every output, the objective included, is the same under the variance objective
+        other = launch(ssm, envs[VAR], inp, H, kind, cost)
+        for name in names_of(kind) + ('obj_cost',):
+            assert torch.equal(sat[name], other[name]), f'{label}: {name} depends on obj_mode'
+        outs[kind] = sat
+    # the drawn form stores the actions it rolled out, and the given form on those is the same rollout
+    again = launch(ssm, envs[ABS], dict(inp, actions=N_(outs['drawn']['actions'])), H, 'given', cost)
+    for name in ('actions', 'traj', 'sigma', 'obj_cost', 'con_cost'):
+        assert torch.equal(outs['drawn'][name], again[name]), name
+    for kind in ('drawn', 'elites'):
+        acts = N_(outs[kind]['actions'])
+        for e in range(E):
+            ref = ocem.rollout(probs[ABS], gp, inp['x0'][e], acts[e])
+            check_objective(f'({n_s},{n_u}) N={N} H={H} {kind} e={e}', twin, outs[kind], e, ref, H, n_s)
+
+
+@pytest.mark.parametrize('H', STEPS)
+@pytest.mark.parametrize('n_s,n_u,sizes', MULTI_CASES)
+def test_sat_multi_rollout_against_the_parent_and_the_oracle(n_s, n_u, sizes, H):
+    ssms, envs, gps, probs = multi.case(n_s, n_u, sizes)
+    cost, twin = cost_of(n_s)
+    inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, sizes, H))
+    for kind in KINDS:
+        fresh = lambda: torch.zeros(E, dtype=torch.int32, device=DEV)
+        parent, sat = launch(ssms, envs[ABS], inp, H, kind, status=fresh()), launch(ssms, envs[ABS], inp, H, kind, cost, fresh())
+        label = f'multi ({n_s},{n_u}) N={sizes} H={H} {kind}'
+        assert sat['status'].tolist() == [0] * E
+        assert_close_to_parent(label, parent, sat, kind, n_s, True)       # the multi entries have the streaming kernel only
+        other = launch(ssms, envs[VAR], inp, H, kind, cost, fresh())
+        assert torch.equal(sat['obj_cost'], other['obj_cost'])
+        if kind != 'given':
+            acts = N_(sat['actions'])
+            for e in range(E):
+                ref = ocem.rollout(probs[ABS], gps[e], inp['x0'][e], acts[e])
+                check_objective(f'{label} e={e}', twin, sat, e, ref, H, n_s)
+
+
+# ---- 1: bit-equality to sx_cem_rollout under SX_ROLLOUT=stream, in one child process ------------------------------------------
+@pytest.fixture(scope='module')
+def streaming_parents(tmp_path_factory):
+    """sx_cem_rollout / sx_cem_rollout_elites forced to the streaming form on every case's inputs, in ONE fresh child process
+    (the override is read when the library plans its first rollout).  The child is this file's __main__."""
+    d = tmp_path_factory.mktemp('stream')
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), str(d)], env=dict(os.environ, SX_ROLLOUT='stream'),
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    return d
+
+
+@pytest.mark.parametrize('H', STEPS)
+@pytest.mark.parametrize('n_s,n_u,N', CASES)
+def test_sat_rollout_equals_the_streaming_parent_bit_for_bit(streaming_parents, n_s, n_u, N, H):
+    ssm, envs = case(n_s, n_u, N)[:2]
+    cost, _ = cost_of(n_s)
+    inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H))
+    for kind in KINDS:
+        sat = launch(ssm, envs[ABS], inp, H, kind, cost)
+        parent = dict(np.load(os.path.join(streaming_parents, f'{n_s}_{n_u}_{N}_{H}_{kind}.npz')))
+        assert int(parent['form']) == (SX_FORM_BYOUT if N == 590 else SX_FORM_STREAM)
+        for name in names_of(kind):
+            assert np.array_equal(N_(sat[name]), parent[name]), f'({n_s},{n_u}) N={N} H={H} {kind}: {name}'
+
+
+def _streaming_child(d):
+    """The parent entries (this process has SX_ROLLOUT=stream) on the inputs of every case, saved for the comparison."""
+    for n_s, n_u, N in CASES:
+        ssm, envs = case(n_s, n_u, N)[:2]
+        for H in STEPS:
+            inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H))
+            form = int(_lib.lib().sx_cem_rollout_form(ctypes.byref(ssm.device_model), H))
+            for kind in KINDS:
+                r = launch(ssm, envs[ABS], inp, H, kind)
+                np.savez(os.path.join(d, f'{n_s}_{n_u}_{N}_{H}_{kind}.npz'), form=form,
+                         **{name: N_(r[name]) for name in names_of(kind)})
+
+
+# ---- 3: independence of the surroundings ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n_s,n_u,N,H', [(2, 1, 200, 15), (4, 1, 590, 3), (3, 1, 200, 3)])
+def test_a_tile_does_not_depend_on_the_grid(n_s, n_u, N, H):
+    """37 particles alone equal the first 37 of 4149, bit for bit (single-model and multi-model)."""
+    cost, _ = cost_of(n_s)
+    ssm, envs = case(n_s, n_u, N)[:2]
+    big = dict(inputs(n_s, n_u, LARGE, H, seed_of(n_s, n_u, N, H)))
+    sub = dict(big, noise=np.ascontiguousarray(big['noise'][:, :SMALL]), actions=np.ascontiguousarray(big['actions'][:, :SMALL]))
+    runs = [(ssm, envs[ABS], None)]
+    if n_s != 3:
+        ssms, menvs = multi.case(n_s, n_u, (N, 100))[:2]
+        runs.append((ssms, menvs[ABS], E))
+    for models, env, words in runs:
+        for kind in ('drawn', 'elites'):
+            st = lambda: None if words is None else torch.zeros(words, dtype=torch.int32, device=DEV)
+            a, b = launch(models, env, big, H, kind, cost, st()), launch(models, env, sub, H, kind, cost, st())
+            for name in names_of(kind) + ('obj_cost',):
+                first = a[name] if name in ('status', 'mean', 'std') else a[name][:, :SMALL]
+                assert torch.equal(first, b[name]), f'{kind}: {name}'
+            assert bool(torch.isfinite(a['obj_cost']).all())
+
+
+@pytest.mark.parametrize('n_s,n_u,N,H', [(2, 1, 200, 3), (4, 1, 200, 3)])
+def test_a_nan_start_is_its_problems_alone(n_s, n_u, N, H):
+    cost, _ = cost_of(n_s)
+    ssms, envs = multi.case(n_s, n_u, (N, 100))[:2]
+    inp = dict(inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H)))
+    bad = dict(inp, x0=inp['x0'].copy())
+    bad['x0'][1, n_s - 1] = np.nan
+    fresh = lambda: torch.zeros(E, dtype=torch.int32, device=DEV)
+    good, nan = launch(ssms, envs[ABS], inp, H, 'drawn', cost, fresh()), launch(ssms, envs[ABS], bad, H, 'drawn', cost, fresh())
+    assert nan['status'][0].item() == 0 and nan['status'][1].item() & _lib.SX_STATUS_NAN
+    assert bool(torch.isnan(nan['obj_cost'][1]).all())
+    for name in ('actions', 'traj', 'sigma', 'obj_cost', 'con_cost'):
+        assert torch.equal(nan[name][0], good[name][0]), name
+    # the single-model entry: one status word, the other problem's particles untouched
+    one = launch(ssms[0], envs[ABS], bad, H, 'drawn', cost)
+    clean = launch(ssms[0], envs[ABS], inp, H, 'drawn', cost)
+    assert int(one['status'].item()) & _lib.SX_STATUS_NAN and int(clean['status'].item()) == 0
+    assert bool(torch.isnan(one['obj_cost'][1]).all()) and torch.equal(one['obj_cost'][0], clean['obj_cost'][0])
+
+
+# ---- 4: fused against step by step -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('H', STEPS)
+@pytest.mark.parametrize('n_s,n_u,N', CASES)
+def test_fused_equals_stepwise(n_s, n_u, N, H):
+    ssm, envs = case(n_s, n_u, N)[:2]
+    cost, _ = cost_of(n_s)
+    inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H))
+    fused = launch(ssm, envs[ABS], inp, H, 'given', cost)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for e in range(E):
+        s = cem_mpc.cem_rollout_stepwise(ssm, envs[ABS], T(inp['x0'][e]), T(inp['actions'][e]), status=status, cost=cost)
+        err = float((s['obj_cost'] - fused['obj_cost'][e]).abs().max())
+        print(f'({n_s},{n_u}) N={N} H={H} e={e}: fused against step by step, objective {err:.3e} (tolerance '
+              f'{LOSS_TOL * H:.1e}), constraint costs differ at {int((s["con_cost"] != fused["con_cost"][e]).sum())}')
+        assert err <= LOSS_TOL * H
+        assert torch.equal(s['con_cost'], fused['con_cost'][e])
+    assert int(status.item()) == int(fused['status'].item()) == 0
+
+
+# ---- 5: the solves ---------------------------------------------------------------------------------------------------------------
+def device_cost(twin):
+    return SaturatingCost(twin.target, twin.weight, twin.trig_idx)
+
+
+def check_solve(history, trace, best, ref_best):
+    assert len(history) == len(trace)
+    for it, (h, (con, obj, idx)) in enumerate(zip(history, trace)):
+        print(f'iteration {it}: objective {worst(h.objective_costs, obj, rtol=RTOL, atol=ATOL):.3e} of the tolerance, '
+              f'{int((con > 0).sum())} of {len(con)} rows violate')
+        np.testing.assert_array_equal(N_(h.constraint_costs), con)
+        np.testing.assert_allclose(N_(h.objective_costs), obj, rtol=RTOL, atol=ATOL)
+        assert set(ocem.rank(N_(h.constraint_costs), N_(h.objective_costs), sso.K)) == set(idx)
+    print(f'best row: max |device - numpy CEM| = {float(np.abs(N_(best) - ref_best).max()):.3e}')
+    np.testing.assert_allclose(N_(best), ref_best, rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize('name', ['cartpole', 'pendulum'])
+def test_solve_matches_the_numpy_cem(name):
+    """The inputs are those tests/test_safety_sat_host.py checks on the CPU: every elite set is decided by more than 1e-6."""
+    spec, twin, H, x0, init_std, noise, ref_best, trace = sso.solve(name)
+    ssm, env = problems.build(spec, device=DEV)
+    mpc = cem_mpc.FusedCemMpc(ssm, env, H, sso.P, sso.K, sso.ITERS, device=DEV, init_std=init_std, record_rollouts=True,
+                              cost_on_safety=True)
+    mpc.set_cost(device_cost(twin))
+    counting = CountingLib(_lib.lib())
+    with mock.patch.object(_lib, 'lib', lambda: counting):
+        best, ok, history, status = mpc.solve(T(x0[None]), noise=T(noise[:, None]))
+        torch.cuda.synchronize()
+    rollouts = {k: v for k, v in counting.calls.items() if k.startswith('sx_cem_rollout') and not k.endswith(('_form', '_bytes'))}
+    print(f'{name}: rollout entries {rollouts}')
+    assert set(rollouts) <= {'sx_cem_rollout_sat', 'sx_cem_rollout_elites_sat'} and sum(rollouts.values()) == sso.ITERS
+    assert int(status.item()) == 0 and bool(ok[0].item())
+    check_solve(history, trace, best[0], ref_best)
+    # the step-by-step path keeps the objective: the same solve through it ends at the same row
+    sbest, sok, _, sstatus = mpc.solve(T(x0[None]), noise=T(noise[:, None]), stepwise=True)
+    torch.cuda.synchronize()
+    print(f'{name}: step by step, best row against the numpy CEM {float(np.abs(N_(sbest[0]) - ref_best).max()):.3e}')
+    assert int(sstatus.item()) == 0 and bool(sok[0].item())
+    np.testing.assert_allclose(N_(sbest[0]), ref_best, rtol=0, atol=1e-9)
+
+
+def test_multi_model_solve_matches_two_numpy_cems():
+    names = ('pendulum', 'pendulum_100')
+    solves = [sso.solve(n) for n in names]
+    H, init_std, twin = solves[0][2], solves[0][4], solves[0][1]
+    built = [problems.build(s[0], device=DEV) for s in solves]
+    assert bytes(built[0][1]) == bytes(built[1][1])
+    solvers = [cem_mpc.FusedCemMpc(ssm, env, H, sso.P, sso.K, sso.ITERS, device=DEV, init_std=init_std, seed=e,
+                                   cost_on_safety=True) for e, (ssm, env) in enumerate(built)]
+    mpc = cem_mpc.MultiModelCemMpc.from_solvers(solvers)
+    mpc.set_cost(device_cost(twin))
+    assert mpc.fused_applies()
+    x0 = np.stack([s[3] for s in solves])
+    noise = np.stack([s[5] for s in solves], axis=1)
+    counting = CountingLib(_lib.lib())
+    with mock.patch.object(_lib, 'lib', lambda: counting):
+        best, ok, status = mpc.solve(T(x0), noise=T(noise))
+        torch.cuda.synchronize()
+    rollouts = {k: v for k, v in counting.calls.items() if k.startswith('sx_cem_rollout') and not k.endswith(('_form', '_bytes'))}
+    print(f'rollout entries {rollouts}')
+    assert set(rollouts) <= {'sx_cem_rollout_sat_multi', 'sx_cem_rollout_elites_sat_multi'}
+    assert sum(rollouts.values()) == sso.ITERS
+    assert status.tolist() == [0, 0] and ok.tolist() == [1, 1]
+    for e, s in enumerate(solves):
+        print(f'{names[e]}: best row against its numpy CEM {float(np.abs(N_(best[e]) - s[6]).max()):.3e}')
+        np.testing.assert_allclose(N_(best[e]), s[6], rtol=0, atol=1e-9)
+
+
+class Conf:
+    mpc_time_horizon = 5
+    cem_num_rollouts = sso.P
+    cem_num_elites = sso.K
+    cem_num_iterations = sso.ITERS
+    cem_init_std = 0.5
+    cem_cost_on_safety = True
+    plot_cem_optimisation = False
+    plot_cem_terminal_states = False
+    device = DEV
+    use_state_constraint = True
+    use_prior_model = True
+    exact_gp_training_iterations = 0
+    exact_gp_kernel = 'rbf'
+
+
+def test_safempc_get_action_after_init_solver():
+    from safe_exploration_amd.safempc_cem import MpcResult
+    spec, twin, H, x0, init_std, noise, ref_best, trace = sso.solve('pendulum')
+    env = problems.StubEnv(spec, np.zeros(2))                 # no objective of its own: without the cost it would explore
+    solver, _ = problems.make_solver(spec, Conf(), env, device=DEV)
+    cost = device_cost(twin)
+    solver.init_solver(lambda *a: 0.0)
+    assert solver._cost is None
+    solver.init_solver(cost)
+    mpc = solver._solver()
+    assert mpc._safety_cost is cost and mpc._n_perf == 0
+    mpc._next_noise = lambda episodes: T(noise[:, None])      # the oracle's draws
+    counting = CountingLib(_lib.lib())
+    with mock.patch.object(_lib, 'lib', lambda: counting):
+        action, result = solver.get_action(x0)
+    rollouts = {k: v for k, v in counting.calls.items() if k.startswith('sx_cem_rollout') and not k.endswith(('_form', '_bytes'))}
+    print(f'rollout entries {rollouts}; action {action}, the numpy CEM\'s {ref_best[0]}')
+    assert set(rollouts) <= {'sx_cem_rollout_sat', 'sx_cem_rollout_elites_sat'} and sum(rollouts.values()) == sso.ITERS
+    assert 'sx_sat_cost_eval' not in counting.calls and 'sx_onestep_reach' not in counting.calls
+    assert result == MpcResult.FOUND_SOLUTION and mpc.last_status == 0
+    np.testing.assert_allclose(np.asarray(action).reshape(-1), ref_best[0], rtol=0, atol=1e-9)
+    # without the setting the same solver refuses the cost, as before
+    plain, _ = problems.make_solver(spec, type('C', (Conf,), dict(cem_cost_on_safety=False))(), env, device=DEV)
+    with pytest.raises(ValueError, match="cem_perf_type='taylor'"):
+        plain.init_solver(cost)
+
+
+if __name__ == '__main__':
+    _streaming_child(sys.argv[1])
