@@ -257,6 +257,34 @@ int sx_gp_fit_multi(const sx_gp_model* models, int E, const void* table, void* s
  * Replaces: the autograd pass of the n_scenarios GpCemSSM._train_model runs (episode_runner.py:55,123). */
 int sx_gp_mll_grad_multi(const sx_gp_model* models, int E, const void* table, void* stream);
 
+/* ---- Max-variance subset of a pool of training inputs (a bounded training set for the exact GP) ----
+ * For each of E problems: m of the n_e pool rows models[e].x_train (dev [n_e x D]), chosen greedily.  Per output d the
+ * residuals r_d[i] start at s_d + noise_d; step j = 0 .. m-1 takes the pivot p_j = seed_idx[e][j] while j < n_seed, else
+ * the unchosen row with the largest sum_d r_d[i] (ties: the LOWEST index, whatever the launch geometry), records
+ * idx[e][j] = p_j and sel_var[e][j] = sum_d r_d[p_j] -- the predictive variance of x_p, noise included, given the rows
+ * chosen before it, summed over the outputs -- and updates, for every row i,
+ *     c = (k_d(x_i, x_p) + noise_d [i = p] - sum_{l<j} C_d[l][i] C_d[l][p]) / sqrt(r_d[p]),   C_d[j][i] = c,   r_d[i] -= c^2
+ * with k_d the kernel value sx_gp_fit builds K from: a jointly pivoted Cholesky factorisation of the K_d + noise_d I.
+ * If some r_d[p_j] is not > 0 (NaN included), or a seed is out of range or repeated, status[e] gets SX_STATUS_NOT_PD,
+ * idx[e][j..m) stays -1 and sel_var[e][j..m) NaN, and the problem's remaining steps do nothing (as they do where the
+ * caller passes a status word with that bit set).  The training targets play no part.
+ * Replaces: SimpleGPModel.choose_datapoints_maxvar (ssm_gpy/gaussian_process.py:279-344), without its k-means seeds.
+ *
+ * models: host array of E models with {n_s, n_u, n_train = n_e, inv_ls2, outputscale, noise, x_train} set as for
+ * sx_gp_fit_multi; one (n_s, n_u) with n_s + n_u <= SX_MAX_D, the n_e may differ.  seed_idx dev int32 [E x n_seed] or NULL
+ * (n_seed = 0); idx dev int32 [E x m]; sel_var dev [E x m]; status dev int32 [E] (or-ed into: the caller zeroes it);
+ * workspace dev, sx_gp_select_workspace_bytes(n_s, E, max n_e, m) bytes.  One init launch per 8 problems and one launch
+ * per step, all on `stream`; nothing is waited for.  Problem e's results are bit-identical to a call with that problem
+ * alone.
+ * SX_ERR_ARG (before any device access) for a null pointer, E <= 0, m <= 0, m > n_e, models of different (n_s, n_u),
+ * n_seed outside [0, m] or a workspace that is too small; SX_ERR_UNSUPPORTED for m > 4096 (sx_gp_fit's limit),
+ * n_e > 65536 or E > 65535.
+ *
+ * Bytes of the workspace; < 0 for a non-positive size, m > n_max or a size beyond those limits. */
+int64_t sx_gp_select_workspace_bytes(int n_s, int E, int n_max, int m);
+int sx_gp_select(const sx_gp_model* models, int E, int m, const int32_t* seed_idx, int n_seed, int32_t* idx,
+                 double* sel_var, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Lays W_d = L_d^-1 (dev [n_s x N x N], lower triangular) and alpha (dev [n_s x N]) out in fragment order.
  * model->{n_s,n_u,n_train,inv_ls2,x_train,a_pack,stage_tab} must be set; n_pad is filled in.
  * Replaces: GpCemSSM._update_model (ssm_cem/gp_ssm_cem.py:96-101) -- where the prediction operands are (re)built. */

@@ -79,6 +79,9 @@ SIGNATURES = {
     'sx_gp_fit_table': (c_int, [POINTER(SxGpModel), c_int] + [POINTER(c_void_p)] * 5 + [c_void_p] * 4),
     'sx_gp_fit_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),
     'sx_gp_mll_grad_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),
+    'sx_gp_select_workspace_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
+    'sx_gp_select': (c_int, [POINTER(SxGpModel), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int64, c_void_p]),
     'sx_gp_pack': (c_int, [POINTER(SxGpModel), c_void_p, c_void_p, c_void_p]),
     'sx_gp_predict': (c_int, [POINTER(SxGpModel), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                               c_void_p]),

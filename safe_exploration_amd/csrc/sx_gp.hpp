@@ -40,6 +40,21 @@ __device__ __forceinline__ int frag_index(int c, int k) {
     return (((k >> 3) * 64 + ((k & 3) << 4) + c) << 1) + ((k >> 2) & 1);
 }
 
+// k_d(x_i, x_j) = s_d exp(-1/2 sum_c (x_ic - x_jc)^2 / l_dc^2) of the training inputs a.x [N x D], statement for
+// statement what gp_fit_kernel and fit_kmat_kernel build K from (sx_fit.hpp, sx_fit_blocked.hpp): sx_gp_select judges a
+// pool with it (sx_gp_select.hpp), so that a subset is chosen on the numbers its fit will see.  `a`: any argument with
+// x, inv_ls2 and outputscale.  (The two fit kernels keep their own copy of these statements: calling this function from
+// them, inlined as it is, changed their ISA -- the by-value argument taken by reference, see gp_mll_grad_kernel.)
+template <class A>
+__device__ __forceinline__ double gp_kernel_value(const A& a, int d, int D, int i, int j) {
+    double q = 0.0;
+    for (int c = 0; c < D; ++c) {
+        const double df = a.x[(size_t)i * D + c] - a.x[(size_t)j * D + c];
+        q += df * df * a.inv_ls2[d * D + c];
+    }
+    return a.outputscale[d] * exp(-0.5 * q);
+}
+
 // 2^(j/256), j = 0..255, correctly rounded (generated with mpmath at 200 bits).
 constexpr int kExpTab = 256;
 __device__ const double kExp2Tab[kExpTab] = {

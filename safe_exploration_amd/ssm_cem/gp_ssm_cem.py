@@ -28,10 +28,14 @@ _NOISE_FLOOR = 1e-4
 
 # csrc/sx_fit.hpp kFitMaxN: the factorisation's last stage keeps one column of the system in LDS
 MAX_TRAINING_POINTS = 4096
+# csrc/sx_gp_select.hpp kSelMaxN: the pool a max-variance subset is chosen from (conf.cem_gp_subset_size)
+MAX_POOL_POINTS = 65536
 
 
 class GpCemSSM(CemSSM):
     kernel_family = 'rbf'   # 'feature' for the degenerate kernels ('linear', 'nn'): feature_gp_ssm_cem.FeatureGpCemSSM
+    _subset_size: Optional[int] = None     # conf.cem_gp_subset_size (set by __init__; the weight-space subclass has none)
+    _subset_idx: Optional[Tensor] = None
 
     def __new__(cls, conf=None, *args, **kwargs):
         # one class name for every kernel, as in the reference (gp_ssm_cem.py:45-57): the 'linear' and 'nn' kernels are
@@ -56,6 +60,13 @@ class GpCemSSM(CemSSM):
             raise ValueError(f'state/action dimension ({state_dimen}, {action_dimen}) beyond the compiled limits')
         self._device = torch.device(get_device(conf))
         self._training_iterations = int(getattr(conf, 'exact_gp_training_iterations', 0))
+        # conf.cem_gp_subset_size: fit at most that many of the stored points, the max-variance subset (sx_gp_select); None:
+        # fit them all.  A setting of its own: conf.m, which CEM configs inherit from the defaults, stays unread.
+        subset = getattr(conf, 'cem_gp_subset_size', None)
+        self._subset_size: Optional[int] = None if subset is None else int(subset)
+        if self._subset_size is not None and not 1 <= self._subset_size <= MAX_TRAINING_POINTS:
+            raise ValueError(f'cem_gp_subset_size={subset}: the fitted subset holds 1 .. {MAX_TRAINING_POINTS} points')
+        self._subset_idx: Optional[Tensor] = None   # rows of the stored pool the device model is fitted on (None: all)
         d_in = state_dimen + action_dimen
         self._raw_lengthscale = torch.zeros((state_dimen, d_in), dtype=torch.float64)
         self._raw_outputscale = torch.zeros((state_dimen,), dtype=torch.float64)
@@ -155,15 +166,44 @@ class GpCemSSM(CemSSM):
                                  _lib.ptr(logdet), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_gp_fit')
         return m, linv, alpha, logdet, status
 
-    def _update_model(self, x_train: Tensor, y_train: Tensor) -> None:
-        n = x_train.size(0)
-        if n > MAX_TRAINING_POINTS:
+    def _selects(self, n: int) -> bool:
+        """Is a pool of n points cut down to conf.cem_gp_subset_size before it is fitted?"""
+        return self._subset_size is not None and n > self._subset_size
+
+    def _check_pool_size(self, n: int) -> None:
+        if self._selects(n):
+            if n > MAX_POOL_POINTS:
+                raise ValueError(f'{n} training points: a subset is selected from up to {MAX_POOL_POINTS} (sx_gp_select)')
+        elif n > MAX_TRAINING_POINTS:
             raise ValueError(f'{n} training points: the exact-GP kernels hold up to {MAX_TRAINING_POINTS} (sx_gp_fit); keep the '
-                             f'most recent / most informative ones (update_model(..., replace_old=True))')
+                             f'most recent / most informative ones (update_model(..., replace_old=True), or '
+                             f'conf.cem_gp_subset_size)')
+
+    def select_subset(self, x: Tensor, m: int, seed_idx=None) -> Tuple[Tensor, Tensor]:
+        """The max-variance subset of the pool x [n x D] (device, float64) under the current hyper-parameters
+        (sx_gp_select): (idx LongTensor [m] in selection order, sel_var [m]), both on x's device.  seed_idx: up to m
+        distinct rows that come first, in this order.  sel_var[j] is the predictive variance of x[idx[j]], noise included,
+        given x[idx[:j]], summed over the outputs.  Raises RuntimeError where the selection meets a variance that is not
+        positive (or a seed that is out of range or repeated)."""
+        idx, sel_var = select_subsets_multi([self], [x], m, None if seed_idx is None else [seed_idx])
+        return idx[0], sel_var[0]
+
+    def _subset_of(self, x: Tensor, y: Tensor) -> Tuple[Tensor, Tensor]:
+        """The rows of the pool (x, y) the model is fitted on, in selection order; remembers which (self._subset_idx)."""
+        self._subset_idx = None
+        if self._selects(x.size(0)):
+            self._subset_idx = self.select_subset(x, self._subset_size)[0]
+            x, y = x[self._subset_idx].contiguous(), y[self._subset_idx].contiguous()
+        return x, y
+
+    def _update_model(self, x_train: Tensor, y_train: Tensor) -> None:
+        self._check_pool_size(x_train.size(0))
         _lib.require_gpu(x_train, 'train_x')
         _lib.require_gpu(y_train, 'train_y')
         x = x_train.detach().contiguous()
         y = y_train.detach().contiguous()
+        # conf.cem_gp_subset_size: the max-variance subset of a larger pool (sx_gp_select) is what gets fitted
+        x, y = self._subset_of(x, y)
         # factorise on the device (sx_gp_fit), then lay the operands out for the matrix cores (sx_gp_pack)
         m, linv, alpha, logdet, status = self._fit(x, y)
         packed = self._pack(m, linv, alpha)
@@ -235,6 +275,12 @@ class GpCemSSM(CemSSM):
         softplus chain rule stay on the host."""
         if self._training_iterations <= 0:
             return
+        pool_x, pool_y = x_train, y_train
+        if self._subset_idx is not None:
+            # a bounded model trains on the subset its last fit selected; the closing _update_model selects once more,
+            # with the trained hyper-parameters (the reference's single re-optimisation, gaussian_process.py:279-344)
+            x_train = x_train.detach()[self._subset_idx].contiguous()
+            y_train = y_train.detach()[self._subset_idx].contiguous()
         n = x_train.size(0)
         d_in = self.num_states + self.num_actions
         raw = [self._raw_lengthscale.clone().requires_grad_(True), self._raw_outputscale.clone().requires_grad_(True),
@@ -252,7 +298,7 @@ class GpCemSSM(CemSSM):
             opt.step()
         self._raw_lengthscale, self._raw_outputscale, self._raw_noise = (t.detach().clone() for t in raw)
         self._last_training_losses = losses
-        self._update_model(x_train, y_train)
+        self._update_model(pool_x, pool_y)
 
     # ---- prediction: the hot path ------------------------------------------------------------------------------
     def _predict_z(self, z: Tensor, jacobians: bool) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
@@ -300,7 +346,10 @@ class GpCemSSM(CemSSM):
             return out
         if not self._linv_current:
             # the fit workspace was reused since (hyper-parameter training): factorise once more
-            self._fit(self._x_train.detach().contiguous(), self._y_train.detach().contiguous())
+            x, y = self._x_train.detach().contiguous(), self._y_train.detach().contiguous()
+            if self._subset_idx is not None:
+                x, y = x[self._subset_idx].contiguous(), y[self._subset_idx].contiguous()
+            self._fit(x, y)
             self._linv_current = True
         _lib.check(_lib.lib().sx_gp_predict_var_jac(ctypes.byref(self._model), _lib.ptr(self._fit_ws[1]), _lib.ptr(z), n,
                                                    _lib.ptr(out), _lib.stream_ptr(z.device)), 'sx_gp_predict_var_jac')
@@ -331,6 +380,65 @@ class GpCemSSM(CemSSM):
     @property
     def parametric(self) -> bool:
         return False
+
+
+# ---- max-variance subsets of E pools in one call (sx_gp_select) ---------------------------------------------------------------
+def select_subsets_multi(ssms: Sequence['GpCemSSM'], xs: Sequence[Tensor], m: int, seed_idx=None,
+                         raws: Optional[Sequence[Optional[Tuple[Tensor, Tensor, Tensor]]]] = None) -> Tuple[Tensor, Tensor]:
+    """``ssms[e].select_subset(xs[e], m)`` for every e in ONE sx_gp_select call (an init launch per 8 problems and one launch
+    per greedy step for all of them): (idx LongTensor [E x m], sel_var [E x m]) on the pools' device, problem e's rows
+    bit-identical to the single call.  The models are exact RBF GPs of one (n_s, n_u), each with its own
+    hyper-parameters (raws[e]: raw parameters to use in place of the model's own); the pools xs[e] [n_e x D] live on one
+    device and may differ in size, m <= min n_e.  seed_idx: E sequences of one length n_seed <= m, rows that come first.
+    RuntimeError naming the problem where a selection fails (a variance that is not positive, a bad seed)."""
+    lib = _lib.lib()
+    ssms, xs = list(ssms), list(xs)
+    E = len(ssms)
+    if E == 0 or len(xs) != E:
+        raise ValueError(f'{E} models, {len(xs)} pools')
+    first = ssms[0]
+    if not all(isinstance(s, GpCemSSM) and s.kernel_family == 'rbf'
+               and (s.num_states, s.num_actions) == (first.num_states, first.num_actions) for s in ssms):
+        raise ValueError('select_subsets_multi takes exact RBF GPs (GpCemSSM) of one (n_s, n_u)')
+    dev, d_in, m = xs[0].device, first.num_states + first.num_actions, int(m)
+    pools = []
+    for x in xs:
+        _lib.require_gpu(x, 'x')
+        assert_shape(x, (x.size(0), d_in))
+        if x.device != dev:
+            raise ValueError('the pools must live on one device')
+        pools.append(x.detach().contiguous())
+    n_min, n_max = min(x.size(0) for x in pools), max(x.size(0) for x in pools)
+    if not 1 <= m <= n_min:
+        raise ValueError(f'm={m}: a subset holds 1 .. {n_min} points (the smallest pool)')
+    if m > MAX_TRAINING_POINTS or n_max > MAX_POOL_POINTS:
+        raise ValueError(f'm={m}, {n_max} pool points: sx_gp_select takes m <= {MAX_TRAINING_POINTS} of up to {MAX_POOL_POINTS}')
+    seeds, n_seed = None, 0
+    if seed_idx is not None:
+        seeds = torch.stack([torch.as_tensor(s, dtype=torch.int32).reshape(-1).cpu() for s in seed_idx]).to(dev).contiguous()
+        if seeds.size(0) != E or seeds.size(1) > m:
+            raise ValueError(f'seed_idx: {E} sequences of one length <= m, got {tuple(seeds.shape)}')
+        n_seed = seeds.size(1)
+        if n_seed == 0:
+            seeds = None
+    raws = list(raws) if raws is not None else [None] * E
+    models = (_lib.SxGpModel * E)(*[s._fit_struct(x, raw) for s, x, raw in zip(ssms, pools, raws)])
+    nbytes = int(lib.sx_gp_select_workspace_bytes(first.num_states, E, n_max, m))
+    if nbytes < 0:
+        raise _lib.SxError('sx_gp_select_workspace_bytes: bad argument')
+    workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    idx = torch.empty((E, m), dtype=torch.int32, device=dev)
+    sel_var = torch.empty((E, m), dtype=torch.float64, device=dev)
+    status = torch.zeros(E, dtype=torch.int32, device=dev)
+    _lib.check(lib.sx_gp_select(models, E, m, _lib.ptr(seeds), n_seed, _lib.ptr(idx), _lib.ptr(sel_var), _lib.ptr(status),
+                                _lib.ptr(workspace), nbytes, _lib.stream_ptr(dev)), 'sx_gp_select')
+    host = status.cpu()
+    for e in range(E):
+        if int(host[e]) & _lib.SX_STATUS_NOT_PD:
+            raise RuntimeError(f'problem {e}: the subset selection met a predictive variance that is not positive (K + noise I '
+                               f'is not positive definite for the current hyper-parameters) or a seed that is out of range '
+                               f'or repeated')
+    return idx.long(), sel_var
 
 
 # ---- E exact GPs trained in lockstep: the reference's n_scenarios models (episode_runner.py:55,123) -----------------------
@@ -427,14 +535,31 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
         assert_shape(y, (n, m.num_states))
         if not replace_old and m._x_train is not None and m._y_train is not None:
             x, y = torch.cat((m._x_train, x), dim=0), torch.cat((m._y_train, y), dim=0)
-        if x.size(0) > MAX_TRAINING_POINTS:
-            raise ValueError(f'{x.size(0)} training points: the exact-GP kernels hold up to {MAX_TRAINING_POINTS}')
+        m._check_pool_size(x.size(0))
         _lib.require_gpu(x, 'train_x')
         _lib.require_gpu(y, 'train_y')
         merged.append((x, y))
-    fit = _MultiFit(ssms, [x.detach().contiguous() for x, _ in merged], [y.detach().contiguous() for _, y in merged])
-    E, n_s, d_in = len(ssms), ssms[0].num_states, ssms[0].num_states + ssms[0].num_actions
+    # conf.cem_gp_subset_size: where every model cuts its pool down to one size, all selections go in one sx_gp_select call
+    # and the lockstep fit below runs on the subsets; a mixed list is updated one model at a time
+    selecting = [m._selects(x.size(0)) for m, (x, _) in zip(ssms, merged)]
+    if any(selecting) and not (all(selecting) and len({m._subset_size for m in ssms}) == 1):
+        for m, x, y in zip(ssms, xs, ys):
+            m.update_model(x, y, opt_hyp, replace_old)
+        return
+    selecting = all(selecting)
+    pools = [(x.detach().contiguous(), y.detach().contiguous()) for x, y in merged]
     raws = [(m._raw_lengthscale, m._raw_outputscale, m._raw_noise) for m in ssms]
+
+    def subsets(raws):
+        """the rows each model is fitted on at the raw hyper-parameters `raws` (all of them without the setting)"""
+        if not selecting:
+            return [None] * len(ssms), pools
+        idx, _ = select_subsets_multi(ssms, [x for x, _ in pools], ssms[0]._subset_size, raws=raws)
+        return list(idx), [(x[i].contiguous(), y[i].contiguous()) for (x, y), i in zip(pools, idx)]
+
+    subset_idx, data = subsets(raws)
+    fit = _MultiFit(ssms, [x for x, _ in data], [y for _, y in data])
+    E, n_s, d_in = len(ssms), ssms[0].num_states, ssms[0].num_states + ssms[0].num_actions
     losses: Optional[List[List[float]]] = None
     iterations = ssms[0]._training_iterations
     if (opt_hyp or ssms[0].parametric) and iterations > 0:
@@ -457,6 +582,10 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
                 p[2].grad = -(grad[:, d_in + 1] / n) * torch.sigmoid(p[2].detach())
             opt.step()
         raws = [tuple(t.detach().clone() for t in p) for p in params]
+        if selecting:
+            # select once more, with the trained hyper-parameters, as the single-model update does
+            subset_idx, data = subsets(raws)
+            fit = _MultiFit(ssms, [x for x, _ in data], [y for _, y in data])
     # the final fit at the trained hyper-parameters; nothing is committed before it has succeeded everywhere
     fit.new_alpha()
     models = fit.launch(raws, mll=False)
@@ -465,6 +594,7 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
     logdets = host[E:].reshape(E, n_s)
     for e, m in enumerate(ssms):
         m._x_train, m._y_train = merged[e]
+        m._subset_idx = subset_idx[e]
         m._raw_lengthscale, m._raw_outputscale, m._raw_noise = raws[e]
         if losses is not None:
             m._last_training_losses = losses[e]
