@@ -5,7 +5,9 @@ forms, CautiousCemMpc.solve against a numpy CEM, and CautiousCemMPC.get_action /
 
 The cases are those of tests/test_gpu_perf_var.py (its case() / inputs(): E = 2, a non-zero feedback k_fb, beta = 2); shapes
 (2, 1), (4, 1), (2, 2); N = 7 (one row-block), 200 (all outputs in LDS) and 590 (output by output); T in {1, 2, 8}; P = 37
-(three tiles, the last one partial); drawn and given rows, both objective modes, propagate 1 and 0.
+(three tiles, the last one partial); drawn and given rows, both objective modes, propagate 1 and 0.  The other compiled
+shapes -- (3, 1), (1, 1), (4, 2) -- and the size limits of the form at all six are in tests/test_gpu_cost_shapes.py, which
+runs the bodies of this file's kernel tests.
 Tolerances: rows, means and the affine objective rtol 1e-10, atol 1e-12; sigma (diag G), cov and the variance objective
 SIGMA_TOL of test_gpu_perf_var.py; the margins against numpy distances at the kernel's own traj / cov rtol 1e-10, atol 1e-12;
 con_cost exactly.  Every case prints its worst error as a fraction of the tolerance before it asserts.

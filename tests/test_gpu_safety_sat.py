@@ -7,6 +7,8 @@ tests/safety_sat_oracle.py through FusedCemMpc(cost_on_safety=True), MultiModelC
 Shapes: P = 37 (three tiles, the last one partial), E = 2; (n_s, n_u, N) in {(2,1,7), (2,1,200), (4,1,200), (4,1,590: output
 by output), (2,2,200), (3,1,200)}; the training-set pairs of test_gpu_sat_cost.MULTI_CASES; H = 3 and 15.  Costs: cost_for of
 test_gpu_sat_cost.py (full rank at n_s = 2, the reference's cart-pole constants at n_s = 4) and a rank-2 cost at n_s = 3.
+(1,1) and (4,2), the other shapes at N = 7 and output by output at 590 (MORE_CASES), and costs without an angle and with the
+angle first are in tests/test_gpu_cost_shapes.py; the child process below rolls out the streaming parents of both files.
 
 Tolerances.  Against the parent entry every output but obj_cost is bit-equal where the parent runs the streaming kernel (always
 for the multi entries; single models under SX_ROLLOUT=stream, compared with a child process), and within TOL['rbf'] of
@@ -45,6 +47,9 @@ from test_sat_cost_host import random_weight
 pytestmark = pytest.mark.gpu
 E, SMALL, LARGE = 2, 37, 4149
 CASES = [(2, 1, 7), (2, 1, 200), (4, 1, 200), (4, 1, 590), (2, 2, 200), (3, 1, 200)]
+# the cases of tests/test_gpu_cost_shapes.py (its part 4); listed here because the one child process below serves both files
+MORE_CASES = ([(n_s, n_u, N) for n_s, n_u in ((1, 1), (4, 2)) for N in (7, 200, 590)]
+              + [(n_s, n_u, N) for n_s, n_u in ((3, 1), (2, 2), (2, 1)) for N in (7, 590)])
 STEPS = [3, 15]
 KINDS = ('given', 'drawn', 'elites')
 OUTPUTS = ('actions', 'traj', 'sigma', 'con_cost', 'status')
@@ -185,15 +190,21 @@ def test_sat_multi_rollout_against_the_parent_and_the_oracle(n_s, n_u, sizes, H)
 
 
 # ---- 1: bit-equality to sx_cem_rollout under SX_ROLLOUT=stream, in one child process ------------------------------------------
+_STREAM_DIR = []
+
+
 @pytest.fixture(scope='module')
 def streaming_parents(tmp_path_factory):
     """sx_cem_rollout / sx_cem_rollout_elites forced to the streaming form on every case's inputs, in ONE fresh child process
-    (the override is read when the library plans its first rollout).  The child is this file's __main__."""
-    d = tmp_path_factory.mktemp('stream')
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), str(d)], env=dict(os.environ, SX_ROLLOUT='stream'),
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return d
+    (the override is read when the library plans its first rollout).  The child is this file's __main__; it is started once
+    in a session, whichever of the two files that import this fixture asks first."""
+    if not _STREAM_DIR:
+        d = tmp_path_factory.mktemp('stream')
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), str(d)], env=dict(os.environ, SX_ROLLOUT='stream'),
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        _STREAM_DIR.append(d)
+    return _STREAM_DIR[0]
 
 
 @pytest.mark.parametrize('H', STEPS)
@@ -212,7 +223,7 @@ def test_sat_rollout_equals_the_streaming_parent_bit_for_bit(streaming_parents, 
 
 def _streaming_child(d):
     """The parent entries (this process has SX_ROLLOUT=stream) on the inputs of every case, saved for the comparison."""
-    for n_s, n_u, N in CASES:
+    for n_s, n_u, N in CASES + [c for c in MORE_CASES if c not in CASES]:
         ssm, envs = case(n_s, n_u, N)[:2]
         for H in STEPS:
             inp = inputs(n_s, n_u, SMALL, H, seed_of(n_s, n_u, N, H))

@@ -6,7 +6,9 @@ cautious and a Taylor-performance solve with the reference's cart-pole constants
 CautiousCemMPC / CemSafeMPC.get_action after init_solver(SaturatingCost).
 
 Shapes: P = 37 (three tiles, the last one partial), E = 2; (n_s, n_u, N) in {(2,1,7), (2,1,200), (4,1,200), (4,1,590: output
-by output), (2,2,200)}; 3 and 15 steps.
+by output), (2,2,200)}; 3 and 15 steps.  The other compiled shapes -- (3,1), (1,1), (4,2) at N = 7, 200, 590 --, (2,1) and
+(2,2) output by output, and costs without an angle, with the angle first or last and of rank 1 are in
+tests/test_gpu_cost_shapes.py.
 Tolerances.  The loss lies in [0, 1] and is under 200 flops plus three library calls of a few ulp on inputs that keep the
 exponent q below 50: 1e-12 absolute for sx_sat_cost_eval, and 1e-12 per step summed for a rollout's obj_cost against the
 oracle's cost of the kernel's OWN traj / cov (the same formula on the same inputs).  Against the oracle's rollout obj_cost is

@@ -5,7 +5,7 @@ given-rows form, its independence of the particle count and the grid, its start 
 particle, `StaticCemMpc.solve` against the oracle's CEM over the long rows, and `StaticSafeMPCExploration` through a
 `CemSafeMPC`.
 
-Shapes: every (n_s, n_u) of {(1, 1), (2, 1), (2, 2), (4, 1), (4, 2)} with N = 33 training points, P = 37 particles (three
+Shapes: every (n_s, n_u) of {(1, 1), (2, 1), (2, 2), (3, 1), (4, 1), (4, 2)} with N = 33 training points, P = 37 particles (three
 tiles, the last one partial), H = 3 and E = 2 problems with a distribution each, plus a (4, 1) model whose training set takes
 the output-by-output form (found by scanning N, test_static_explore_host.byout_model_size).  The polytope of a case comes
 from oracle/cases.py over the oracle's trajectories with the start as step 0, so that starts lie on both sides of it.
@@ -43,7 +43,8 @@ E, P, H = 2, 37, 3
 VAR, ABS = _lib.SX_OBJ_NEG_VARIANCE, _lib.SX_OBJ_AFFINE_ABS
 TERMINAL, ALL_STATES = _lib.SX_CON_TERMINAL, _lib.SX_CON_ALL_STATES
 SX_FORM_BYOUT = 3
-SHAPES = {'1x1': (1, 1, 33), '2x1': (2, 1, 33), '2x2': (2, 2, 33), '4x1': (4, 1, 33), '4x2': (4, 2, 33), 'byout': (4, 1, None)}
+SHAPES = {'1x1': (1, 1, 33), '2x1': (2, 1, 33), '2x2': (2, 2, 33), '3x1': (3, 1, 33), '4x1': (4, 1, 33), '4x2': (4, 2, 33),
+          'byout': (4, 1, None)}
 CASES = list(SHAPES)
 
 
