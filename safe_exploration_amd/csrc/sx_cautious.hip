@@ -5,9 +5,9 @@
 #include "sx_cautious_host.hpp"   // CautiousForm, cautious_plan
 
 extern "C" int sx_cem_cautious_rollout_form(const sx_gp_model* model, int T) {
-    sx::PerfVarPlan plan;
+    sx::StreamPlan plan;
     if (!sx::cautious_plan(model, T, plan)) return -1;
-    return plan.ok ? plan.form : -1;
+    return plan.form;
 }
 
 extern "C" int sx_cem_cautious_rollout(const sx_gp_model* model, const sx_env* env, int E, int P, int T, const double* x0,
@@ -17,7 +17,7 @@ extern "C" int sx_cem_cautious_rollout(const sx_gp_model* model, const sx_env* e
     if (!model || !env || !x0 || !rows || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
     if (E <= 0 || P <= 0 || T < 1) return SX_ERR_ARG;
     if (noise && (!mean || !std)) return SX_ERR_ARG;
-    sx::PerfVarPlan plan;
+    sx::StreamPlan plan;
     if (!sx::cautious_plan(model, T, plan)) return SX_ERR_ARG;
     if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
     if (env->obj_mode != SX_OBJ_NEG_VARIANCE && env->obj_mode != SX_OBJ_AFFINE_ABS) return SX_ERR_ARG;

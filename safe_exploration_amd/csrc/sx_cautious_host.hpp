@@ -5,6 +5,7 @@
 #include "sx_launch.hpp"
 #include "sx_stream_launch.hpp"   // SX_ROLLOUT_SHAPES, SX_DISPATCH
 #include "sx_perf_launch.hpp"
+#include "sx_perf_taylor_host.hpp"   // PerfTaylorForm::make_const
 #include "sx_cautious.hpp"
 
 namespace sx {
@@ -31,17 +32,7 @@ struct CautiousForm {
     static void make_const(const sx_env* env, Const<NS, NU>& cc) {
         static_assert(sizeof(CautiousConst<NS, NU>) == sizeof(PerfTaylorConst<NS, NU>) + sizeof(double),
                       "cautious_extra_bytes counts the fields of CautiousConst");
-        PerfTaylorConst<NS, NU>& tc = cc.tc;
-        make_perf_step<NS, NU>(env, tc.step);
-        for (int i = 0; i < NS; ++i)
-            for (int j = 0; j < NS; ++j) {
-                double s = env->a[i * NS + j];
-                for (int c = 0; c < NU; ++c) s += env->b[i * NU + c] * env->k_fb[c * NS + j];
-                tc.abk[i * NS + j] = s;
-            }
-        for (int i = 0; i < NU * NS; ++i) tc.k_fb[i] = env->k_fb[i];
-        for (int i = 0; i < env->m * NS; ++i) tc.h_mat[i] = env->h_mat[i];
-        for (int i = 0; i < env->m; ++i) tc.h_vec[i] = env->h_vec[i];
+        PerfTaylorForm::make_const<NS, NU>(env, cc.tc);
         cc.beta = env->beta;
     }
     template <int NS, int NU, bool BYOUT>
@@ -50,10 +41,10 @@ struct CautiousForm {
     }
 };
 
-// The plan of a model over T steps (plan_perf_var over the cautious constants), where the entry would take the model
-inline bool cautious_plan(const sx_gp_model* model, int T, PerfVarPlan& plan) {
+// The plan of a model over T steps (the streaming plan over the cautious constants), where the entry would take the model
+inline bool cautious_plan(const sx_gp_model* model, int T, StreamPlan& plan) {
     if (!model || T < 1 || !perf_shape_ok(*model) || !perf_models_ok(model, 1, perf_var_model_ok)) return false;
-    plan = plan_perf_var(model->n_s, model->n_u, model->n_train, model->n_pad, T, cautious_extra_bytes(model->n_s, model->n_u));
+    plan = plan_stream_multi(model, 1, T, cautious_extra_bytes(model->n_s, model->n_u));
     return true;
 }
 

@@ -40,7 +40,7 @@ extern "C" int sx_cem_cautious_rollout_sat(const sx_gp_model* model, const sx_en
     if (!model || !env || !cost || !x0 || !rows || !obj_cost || !con_cost || !status) return SX_ERR_ARG;
     if (E <= 0 || P <= 0 || T < 1) return SX_ERR_ARG;
     if (noise && (!mean || !std)) return SX_ERR_ARG;
-    sx::PerfVarPlan plan;
+    sx::StreamPlan plan;
     if (!sx::cautious_plan(model, T, plan)) return SX_ERR_ARG;
     if (model->n_s != env->n_s || model->n_u != env->n_u) return SX_ERR_ARG;
     if (!sx::sat_cost_ok(cost, env->n_s)) return SX_ERR_ARG;

@@ -1,11 +1,12 @@
-// The exact-GP rollout entries: which form a model's rollout takes (plan_rollout), the launch in
-// that form through the launchers of sx_rw_launch.hpp, sx_stream_launch.hpp and sx_big_launch.hpp, the GP model table, and
-// sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi, sx_cem_rollout_starts, sx_cem_rollout_form,
-// sx_cem_rollout_multi_form, sx_cem_rollout_starts_form, sx_cem_rollout_workspace_bytes, and the entries with the saturating
-// cost on the safety ellipsoids, sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form.  No kernel is compiled here.
+// The exact-GP rollout entries: which form a model's rollout takes (plan_rollout over the streaming plan of
+// sx_stream_launch.hpp), the launch in that form through the launchers of sx_rw_launch.hpp,
+// sx_stream_launch.hpp and sx_big_launch.hpp (launch_rollout), the one host path of the entries that have the streaming
+// kernel only (stream_rollout), the GP model table, and sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi,
+// sx_cem_rollout_starts, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
+// sx_cem_rollout_workspace_bytes, and the entries with the saturating cost on the safety ellipsoids,
+// sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form.  No kernel is compiled here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -66,23 +67,24 @@ static int resident_lds_bytes(int ns, int nu, int n_train, int n_pad, int H, siz
 #undef CALL
 }
 
-// `m` is the GP over ns + nu + sh columns (m->n_u = nu + sh), sh the query shift of sx_cem_rollout_junk.
-// stream_only: the streaming kernel's answer (STREAM, BYOUT or BIG), never a resident form and no override -- the
-// multi-model rollout has only that kernel (plan_rollout_multi).
-static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites, bool stream_only = false) {
+// The refit prologue of the elite-row form keeps 2 H n_u doubles in the Kstar / mean-row buffers: at least 256 + 256 n_s
+// of them
+static bool elite_rows_fit(int ns, int nu, int H) { return 2 * H * nu <= 256 + 256 * ns; }
+
+// `m` is the GP over ns + nu + sh columns (m->n_u = nu + sh), sh the query shift of sx_cem_rollout_junk.  The streaming
+// answer is plan_stream's (sx_stream_launch.hpp); what is decided here is the workspace path, the elite-row bound, the
+// override and the resident forms.
+static RolloutPlan plan_rollout(const sx_gp_model* m, int sh, int H, bool elites) {
     const int ns = m->n_s, nu = m->n_u - sh, n_train = m->n_train, n_pad = m->n_pad;
-    auto stream_lds = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, sh, n_train, n_pad, H, byout); };
-    const bool all_at_once = n_pad <= 1024 && stream_lds(false) <= kMaxLdsBytes;
-    const bool by_output = !all_at_once && ns > 1 && n_pad <= 1024 && stream_lds(true) <= kMaxLdsBytes;
+    const StreamPlan s = plan_stream(ns, nu, sh, n_train, n_pad, H);
     bool ok = rollout_compiled(ns, nu, sh);
     // Kstar in HBM: plain rollouts only, without elite rows (the refit prologue belongs to the single-launch kernel)
-    if (!all_at_once && !by_output) return {SX_FORM_BIG, ok && sh == 0 && !elites, 0, 0};
-    // (the refit prologue keeps 2 H n_u doubles in the Kstar / mean-row buffers: at least 256 + 256 n_s of them)
-    if (elites && 2 * H * nu > 256 + 256 * ns) ok = false;
-    if (by_output) return {SX_FORM_BYOUT, ok, stream_lds(true), 0};
-    const RolloutPlan stream{SX_FORM_STREAM, ok, stream_lds(false), 0};
+    if (s.form < 0) return {SX_FORM_BIG, ok && sh == 0 && !elites, 0, 0};
+    if (elites && !elite_rows_fit(ns, nu, H)) ok = false;
+    if (s.form == SX_FORM_BYOUT) return {SX_FORM_BYOUT, ok, s.lds, 0};
+    const RolloutPlan stream{SX_FORM_STREAM, ok, s.lds, 0};
     const FormOverride& o = form_override();
-    if (!ok || sh > 0 || stream_only || o.form == SX_FORM_STREAM) return stream;
+    if (!ok || sh > 0 || o.form == SX_FORM_STREAM) return stream;
     // W partly resident on 8 waves (n_s <= 2), then all of W in the registers of 4 waves (smaller N), then W streamed from
     // L2: the 4-wave form loses to the streaming kernel only where the 8-wave form exists (n_s = 2, n_u = 1: 126.6
     // against 125.7 us at config 2), and beats it by 7 - 16 % on the shapes the 8-wave form does not cover (n_s = 3, 4;
@@ -120,25 +122,40 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
             plan = {SX_FORM_STREAM, true, rollout_stream_lds_bytes(NS, NU, SH, m->n_train, m->n_pad, rp.H, false), 0};
         }
     }
-    return launch_rollout_stream<NS, NU, SH>(make_gp_const<NS, NU + SH>(m, kRolloutThreads / 64), rc, cc, rps,
-                                             plan.form == SX_FORM_BYOUT, plan.lds, stream);
+    return launch_stream<StreamPlain<SH>, NS, NU>(make_gp_const<NS, NU + SH>(m, kRolloutThreads / 64), rc, cc, rps, nullptr,
+                                                  plan.form == SX_FORM_BYOUT, plan.lds, stream);
 }
 
-// The multi-model rollout (sx_cem_rollout_multi[_elites]): one launch of the streaming kernel for E problems with a GP
-// each, so every model takes plan_rollout's streaming answer.  The launch is output by output where any model needs it,
-// with the LDS of the largest; a model without a single-launch form (BIG, or not ok) makes the whole launch unsupported.
-static RolloutPlan plan_rollout_multi(const sx_gp_model* models, int E, int H, bool elites) {
-    RolloutPlan out{SX_FORM_STREAM, true, 0, 0};
-    for (int i = 0; i < E; ++i) {
-        const RolloutPlan p = plan_rollout(&models[i], 0, H, elites, true);
-        if (p.form == SX_FORM_BIG || !p.ok) return {p.form, false, 0, 0};
-        if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
-    }
-    const sx_gp_model& m0 = models[0];
-    for (int i = 0; i < E; ++i)
-        out.lds = std::max(out.lds, rollout_stream_lds_bytes(m0.n_s, m0.n_u, 0, models[i].n_train, models[i].n_pad, H,
-                                                             out.form == SX_FORM_BYOUT));
-    return out;
+// The entries that have the streaming kernel only -- the multi-model rollouts, the per-particle starts, the saturating
+// cost on the safety ellipsoids -- from their checked arguments to the launch of variant V, for one model or (V::MM) rp.E
+// of them behind their device `table`: the streaming plan with the elite-row bound (no workspace path, no resident form,
+// no override), the constants of `env`, those of `cost` (V::SAT), the GP argument, the launcher.
+template <class V, int NS, int NU>
+static int stream_rollout(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                          const RolloutPtrs& rp, hipStream_t stream) {
+    const StreamPlan plan = plan_stream_multi(models, V::MM ? rp.E : 1, rp.H);
+    if (plan.form < 0 || (rp.elite_rows && !elite_rows_fit(NS, NU, rp.H))) return SX_ERR_UNSUPPORTED;
+    ReachConst<NS, NU> rc;
+    CostConst<SX_MAX_M, NS, NU> cc;
+    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    SatConst<NS> sat;
+    if constexpr (V::SAT) make_sat_const<NS>(cost, sat);
+    const SatConst<NS>* satp = V::SAT ? &sat : nullptr;
+    const bool byout = plan.form == SX_FORM_BYOUT;
+    if constexpr (V::MM)
+        return launch_stream<V, NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp, satp, byout, plan.lds,
+                                        stream);
+    else
+        return launch_stream<V, NS, NU>(make_gp_const<NS, NU>(models, kRolloutThreads / 64), rc, cc, rp, satp, byout,
+                                        plan.lds, stream);
+}
+
+template <class V>
+static int stream_dispatch(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
+                           const RolloutPtrs& rp, void* stream) {
+#define CALL(NS, NU) stream_rollout<V, NS, NU>(models, table, env, cost, rp, (hipStream_t)stream)
+    SX_DISPATCH(env->n_s, env->n_u, CALL);
+#undef CALL
 }
 
 // Bytes of one sx_gp_model_table entry: the GpConst the streaming kernel takes (SX_ERR_UNSUPPORTED for a shape without
@@ -160,83 +177,67 @@ static int build_gp_table(const sx_gp_model* models, int E, void* table, hipStre
     return copy_model_table(host, table, stream);
 }
 
-template <int NS, int NU>
-static int launch_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const RolloutPtrs& rp,
-                                hipStream_t stream) {
-    const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
-    if (!plan.ok) return SX_ERR_UNSUPPORTED;
-    ReachConst<NS, NU> rc;
-    CostConst<SX_MAX_M, NS, NU> cc;
-    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
-    return launch_rollout_stream_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp,
-                                               plan.form == SX_FORM_BYOUT, plan.lds, stream);
+// The elite-row form of a rollout's actions: the refit prologue derives the sampling distribution from k sorted elite
+// rows and, where mean_out and std_out are given, writes it out
+static RolloutPtrs with_elites(RolloutPtrs rp, const double* elite_rows, int k, double* mean_out, double* std_out) {
+    rp.elite_rows = elite_rows;
+    rp.elite_k = k;
+    rp.mean_out = mean_out;
+    rp.std_out = std_out;
+    return rp;
 }
 
-// The rollout with a start state per particle (sx_cem_rollout_starts) has the streaming kernel only, so it takes
-// plan_rollout's streaming answer: all outputs at once or output by output; a model that needs the workspace path
-// (SX_FORM_BIG) or fits neither form has none.  sx_cem_rollout_starts launches this plan, sx_cem_rollout_starts_form
-// reports it.
-static RolloutPlan plan_rollout_starts(const sx_gp_model* m, int H) {
-    RolloutPlan p = plan_rollout(m, 0, H, false, true);
-    if (p.form == SX_FORM_BIG) p.ok = false;
-    return p;
+// The objective of a safety rollout: env's own, or (`sat`) the saturating cost `cost` on the safety ellipsoids (DESIGN.md
+// section 3.13; env->obj_mode is then not read), which has the streaming kernel only
+struct Objective {
+    bool sat;
+    const sx_sat_cost* cost;
+};
+constexpr Objective kEnvObjective{false, nullptr};
+
+// (model, env, query_shift) of the rollout entries: checked before anything touches the device
+static bool rollout_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
+    return model->n_s == env->n_s && query_shift >= 0 && query_shift <= env->n_u && model->n_u == env->n_u + query_shift;
 }
 
-template <int NS, int NU>
-static int launch_rollout_starts(const sx_gp_model* m, const sx_env* env, const RolloutPtrs& rp, hipStream_t stream) {
-    const RolloutPlan plan = plan_rollout_starts(m, rp.H);
-    if (!plan.ok) return SX_ERR_UNSUPPORTED;
-    ReachConst<NS, NU> rc;
-    CostConst<SX_MAX_M, NS, NU> cc;
-    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
-    return launch_rollout_starts<NS, NU>(make_gp_const<NS, NU>(m, kRolloutThreads / 64), rc, cc, rp,
-                                         plan.form == SX_FORM_BYOUT, plan.lds, stream);
+// E models of one (n_s, n_u) with a training set each: checked before anything touches the device
+static bool multi_models_ok(const sx_gp_model* models, int E) {
+    if (!models || E <= 0) return false;
+    const int ns = models[0].n_s, nu = models[0].n_u;
+    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || nu > SX_MAX_NU) return false;
+    for (int i = 0; i < E; ++i)
+        if (models[i].n_s != ns || models[i].n_u != nu || models[i].n_train <= 0 || models[i].n_pad <= 0) return false;
+    return true;
 }
 
-// The rollouts with the saturating cost on the safety ellipsoids (sx_cem_rollout[_elites]_sat) have the streaming kernel
-// only, as the per-particle starts: plan_rollout's streaming answer with the elite-row bound, no workspace path.
-// sx_cem_rollout_sat_form reports it (elites = false).
-static RolloutPlan plan_rollout_sat(const sx_gp_model* m, int H, bool elites) {
-    RolloutPlan p = plan_rollout(m, 0, H, elites, true);
-    if (p.form == SX_FORM_BIG) p.ok = false;
-    return p;
-}
-
-template <int NS, int NU>
-static int launch_rollout_sat(const sx_gp_model* m, const sx_env* env, const sx_sat_cost* cost, const RolloutPtrs& rp,
-                              hipStream_t stream) {
-    const RolloutPlan plan = plan_rollout_sat(m, rp.H, rp.elite_rows != nullptr);
-    if (!plan.ok) return SX_ERR_UNSUPPORTED;
-    ReachConst<NS, NU> rc;
-    CostConst<SX_MAX_M, NS, NU> cc;
-    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
-    SatConst<NS> sat;
-    make_sat_const<NS>(cost, sat);
-    return launch_rollout_sat<NS, NU>(make_gp_const<NS, NU>(m, kRolloutThreads / 64), rc, cc, rp, sat,
-                                      plan.form == SX_FORM_BYOUT, plan.lds, stream);
-}
-
-// (the plan is sx_cem_rollout_multi's: that entry has the streaming kernel only)
-template <int NS, int NU>
-static int launch_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                                    const RolloutPtrs& rp, hipStream_t stream) {
-    const RolloutPlan plan = plan_rollout_multi(models, rp.E, rp.H, rp.elite_rows != nullptr);
-    if (!plan.ok) return SX_ERR_UNSUPPORTED;
-    ReachConst<NS, NU> rc;
-    CostConst<SX_MAX_M, NS, NU> cc;
-    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
-    SatConst<NS> sat;
-    make_sat_const<NS>(cost, sat);
-    return launch_rollout_sat_multi<NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp, sat,
-                                            plan.form == SX_FORM_BYOUT, plan.lds, stream);
-}
-
-// sx_cem_rollout[_elites][_junk] after their argument checks
-static int cem_rollout(const sx_gp_model* model, const sx_env* env, int query_shift, const RolloutPtrs& rp, void* workspace,
-                       int64_t workspace_bytes, void* stream) {
+// The entries over one model, behind their RolloutPtrs (`elites`: with_elites'): the argument checks, the cost's after
+// them, then the launch -- launch_rollout's full plan, or the streaming kernel priced by the cost.
+static int cem_rollout_single(const sx_gp_model* model, const sx_env* env, int query_shift, Objective obj, bool elites,
+                              const RolloutPtrs& rp, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!model || (elites && !rp.elite_rows) || !rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift))
+        return SX_ERR_ARG;
+    if (obj.sat) {
+        if (!sat_cost_ok(obj.cost, env->n_s)) return SX_ERR_ARG;
+        return stream_dispatch<StreamSat<false>>(model, nullptr, env, obj.cost, rp, stream);
+    }
 #define CALL(NS, NU, SH) launch_rollout<NS, NU, SH>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
     SX_ROLLOUT_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
 #undef CALL
+}
+
+// The entries over rp.E models behind their device `table`, as cem_rollout_single: every one has the streaming kernel only
+static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, Objective obj, bool elites,
+                             const RolloutPtrs& rp, void* stream) {
+    if (!table || (elites && !rp.elite_rows) || !rollout_args_ok(env, rp) || !multi_models_ok(models, rp.E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    if (!obj.sat) return stream_dispatch<StreamPlain<0, true>>(models, table, env, nullptr, rp, stream);
+    if (!sat_cost_ok(obj.cost, env->n_s)) return SX_ERR_ARG;
+    return stream_dispatch<StreamSat<true>>(models, table, env, obj.cost, rp, stream);
+}
+
+// What the form queries of the stream-only entries answer: the form of the launch, -1 where there is none
+static int stream_form(const sx_gp_model* models, int E, int H) {
+    return models && H > 0 ? plan_stream_multi(models, E, H).form : -1;
 }
 
 }  // namespace sx
@@ -271,45 +272,24 @@ int sx_cem_rollout_elites(const sx_gp_model* model, const sx_env* env, int E, in
                                       con_cost, status, mean_out, std_out, stream);
 }
 
-// The elite-row form of a rollout's actions: the refit prologue derives the sampling distribution from k sorted elite
-// rows and, where mean_out and std_out are given, writes it out
-static sx::RolloutPtrs with_elites(sx::RolloutPtrs rp, const double* elite_rows, int k, double* mean_out, double* std_out) {
-    rp.elite_rows = elite_rows;
-    rp.elite_k = k;
-    rp.mean_out = mean_out;
-    rp.std_out = std_out;
-    return rp;
-}
-
-// (model, env, query_shift) of the rollout entries: checked before anything touches the device
-static bool rollout_shapes_ok(const sx_gp_model* model, const sx_env* env, int query_shift) {
-    return model->n_s == env->n_s && query_shift >= 0 && query_shift <= env->n_u && model->n_u == env->n_u + query_shift;
-}
-
 int sx_cem_rollout_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H, const double* x0,
                         const double* q0, const double* mean, const double* std, const double* noise, double* actions,
                         double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* workspace,
                         int64_t workspace_bytes, void* stream) {
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-    if (!model || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
-    return sx::cem_rollout(model, env, query_shift, rp, workspace, workspace_bytes, stream);
+    return sx::cem_rollout_single(model, env, query_shift, sx::kEnvObjective, false, rp, workspace, workspace_bytes, stream);
 }
 
 int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int query_shift, int E, int P, int H,
                                const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
                                double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                                int32_t* status, double* mean_out, double* std_out, void* stream) {
-    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
-                                            E, P, H}, elite_rows, k, mean_out, std_out);
-    if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, query_shift)) return SX_ERR_ARG;
-    return sx::cem_rollout(model, env, query_shift, rp, nullptr, 0, stream);
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_single(model, env, query_shift, sx::kEnvObjective, true, rp, nullptr, 0, stream);
 }
 
-int sx_cem_rollout_starts_form(const sx_gp_model* model, int H) {
-    if (!model || H <= 0) return -1;
-    const sx::RolloutPlan plan = sx::plan_rollout_starts(model, H);
-    return plan.ok ? plan.form : -1;
-}
+int sx_cem_rollout_starts_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
 
 int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
                           const double* std, const double* noise, double* rows, double* traj, double* sigma,
@@ -319,19 +299,7 @@ int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, in
     if (model->n_s != env->n_s || model->n_u != env->n_u || model->n_train <= 0 || model->n_pad <= 0) return SX_ERR_ARG;
     // (x0, q0 and the elite-row fields stay empty: the kernel reads the start of a particle from its row)
     const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
-#define CALL(NS, NU) sx::launch_rollout_starts<NS, NU>(model, env, rp, (hipStream_t)stream)
-    SX_DISPATCH(env->n_s, env->n_u, CALL);
-#undef CALL
-}
-
-// E models of one (n_s, n_u) with a training set each: checked before anything touches the device
-static bool multi_models_ok(const sx_gp_model* models, int E) {
-    if (!models || E <= 0) return false;
-    const int ns = models[0].n_s, nu = models[0].n_u;
-    if (ns <= 0 || ns > SX_MAX_NS || nu <= 0 || nu > SX_MAX_NU) return false;
-    for (int i = 0; i < E; ++i)
-        if (models[i].n_s != ns || models[i].n_u != nu || models[i].n_train <= 0 || models[i].n_pad <= 0) return false;
-    return true;
+    return sx::stream_dispatch<sx::StreamStarts>(model, nullptr, env, nullptr, rp, stream);
 }
 
 int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E) {
@@ -341,7 +309,7 @@ int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E) {
 }
 
 int sx_gp_model_table(const sx_gp_model* models, int E, void* table, void* stream) {
-    if (!table || !multi_models_ok(models, E)) return SX_ERR_ARG;
+    if (!table || !sx::multi_models_ok(models, E)) return SX_ERR_ARG;
     for (int i = 0; i < E; ++i)
         if (!models[i].x_train || !models[i].a_pack || !models[i].stage_tab) return SX_ERR_ARG;
 #define CALL(NS, NU) sx::build_gp_table<NS, NU>(models, E, table, (hipStream_t)stream)
@@ -350,16 +318,7 @@ int sx_gp_model_table(const sx_gp_model* models, int E, void* table, void* strea
 }
 
 int sx_cem_rollout_multi_form(const sx_gp_model* models, int E, int H) {
-    if (!multi_models_ok(models, E) || H <= 0) return -1;
-    const sx::RolloutPlan plan = sx::plan_rollout_multi(models, E, H, false);
-    return plan.ok ? plan.form : -1;
-}
-
-static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx::RolloutPtrs& rp,
-                             void* stream) {
-#define CALL(NS, NU) sx::launch_rollout_multi<NS, NU>(models, table, env, rp, (hipStream_t)stream)
-    SX_DISPATCH(env->n_s, env->n_u, CALL);
-#undef CALL
+    return sx::multi_models_ok(models, E) ? sx::stream_form(models, E, H) : -1;
 }
 
 int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
@@ -367,63 +326,36 @@ int sx_cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_
                          double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
                          void* stream) {
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-    if (!table || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
-    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
-    return cem_rollout_multi(models, table, env, rp, stream);
+    return sx::cem_rollout_multi(models, table, env, sx::kEnvObjective, false, rp, stream);
 }
 
 int sx_cem_rollout_elites_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
                                 const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
                                 double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                                 int32_t* status, double* mean_out, double* std_out, void* stream) {
-    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
-                                            E, P, H}, elite_rows, k, mean_out, std_out);
-    if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
-    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
-    return cem_rollout_multi(models, table, env, rp, stream);
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_multi(models, table, env, sx::kEnvObjective, true, rp, stream);
 }
 
-// ---- the saturating cost on the safety ellipsoids --------------------------------------------------
-int sx_cem_rollout_sat_form(const sx_gp_model* model, int H) {
-    if (!model || H <= 0) return -1;
-    const sx::RolloutPlan plan = sx::plan_rollout_sat(model, H, false);
-    return plan.ok ? plan.form : -1;
-}
-
-// sx_cem_rollout[_elites]_sat after the parents' argument checks: the cost's, then the launch (env->obj_mode is not read)
-static int cem_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, const sx::RolloutPtrs& rp,
-                           void* stream) {
-    if (!sx::sat_cost_ok(cost, env->n_s)) return SX_ERR_ARG;
-#define CALL(NS, NU) sx::launch_rollout_sat<NS, NU>(model, env, cost, rp, (hipStream_t)stream)
-    SX_DISPATCH(env->n_s, env->n_u, CALL);
-#undef CALL
-}
-
-static int cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                                 const sx::RolloutPtrs& rp, void* stream) {
-    if (!sx::sat_cost_ok(cost, env->n_s)) return SX_ERR_ARG;
-#define CALL(NS, NU) sx::launch_rollout_sat_multi<NS, NU>(models, table, env, cost, rp, (hipStream_t)stream)
-    SX_DISPATCH(env->n_s, env->n_u, CALL);
-#undef CALL
-}
+// ---- the saturating cost on the safety ellipsoids: the entries above with a cost handed in ----------
+int sx_cem_rollout_sat_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
 
 int sx_cem_rollout_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
                        const double* x0, const double* q0, const double* mean, const double* std, const double* noise,
                        double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost, int32_t* status,
                        void* stream) {
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-    if (!model || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, 0)) return SX_ERR_ARG;
-    return cem_rollout_sat(model, env, cost, rp, stream);
+    return sx::cem_rollout_single(model, env, 0, {true, cost}, false, rp, nullptr, 0, stream);
 }
 
 int sx_cem_rollout_elites_sat(const sx_gp_model* model, const sx_env* env, const sx_sat_cost* cost, int E, int P, int H,
                               const double* x0, const double* q0, const double* elite_rows, int k, const double* noise,
                               double* actions, double* traj, double* sigma, double* obj_cost, double* con_cost,
                               int32_t* status, double* mean_out, double* std_out, void* stream) {
-    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
-                                            E, P, H}, elite_rows, k, mean_out, std_out);
-    if (!model || !elite_rows || !sx::rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, 0)) return SX_ERR_ARG;
-    return cem_rollout_sat(model, env, cost, rp, stream);
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_single(model, env, 0, {true, cost}, true, rp, nullptr, 0, stream);
 }
 
 int sx_cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost, int E,
@@ -431,20 +363,16 @@ int sx_cem_rollout_sat_multi(const sx_gp_model* models, const void* table, const
                              const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
                              double* con_cost, int32_t* status, void* stream) {
     const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
-    if (!table || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
-    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
-    return cem_rollout_sat_multi(models, table, env, cost, rp, stream);
+    return sx::cem_rollout_multi(models, table, env, {true, cost}, false, rp, stream);
 }
 
 int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
                                     int E, int P, int H, const double* x0, const double* q0, const double* elite_rows, int k,
                                     const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
                                     double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream) {
-    const sx::RolloutPtrs rp = with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost, status,
-                                            E, P, H}, elite_rows, k, mean_out, std_out);
-    if (!table || !elite_rows || !sx::rollout_args_ok(env, rp) || !multi_models_ok(models, E)) return SX_ERR_ARG;
-    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
-    return cem_rollout_sat_multi(models, table, env, cost, rp, stream);
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_multi(models, table, env, {true, cost}, true, rp, stream);
 }
 
 }  // extern "C"

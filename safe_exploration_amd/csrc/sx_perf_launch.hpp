@@ -1,15 +1,14 @@
 // Host side of the performance rollouts, shared by their five translation units: the argument checks of the six rollout
-// entries, the form of a GP-product rollout (variance | Taylor; decided here only -- the entries launch it, the four _form
-// queries report it), the one path from plan to launch of those two forms, and the launchers of their multi-model kernels,
+// entries, the form of a GP-product rollout (variance | Taylor; the streaming plan of sx_stream_launch.hpp over their LDS
+// -- the entries launch it, the four _form queries report it), the one path from plan to launch of those two forms, and the launchers of their multi-model kernels,
 // whose instantiations are compiled in sx_perf_multi.hip and sx_perf_taylor_multi.hip.  Host code only.
 #pragma once
-#include <algorithm>
 #include <climits>
 #include <cstring>
 
 #include "sx_host.hpp"
 #include "sx_launch.hpp"
-#include "sx_stream_launch.hpp"   // rollout_compiled, rollout_stream_lds_bytes
+#include "sx_stream_launch.hpp"   // plan_stream_multi, SX_DISPATCH
 #include "sx_perf_var.hpp"
 
 namespace sx {
@@ -60,57 +59,18 @@ inline int check_perf_entry(bool head, const sx_gp_model* models, int n, bool bo
     return env->obj_mode == SX_OBJ_AFFINE_ABS ? SX_OK : SX_ERR_ARG;
 }
 
-struct PerfVarPlan {
-    int form;     // SX_FORM_STREAM (Kstar of all outputs in LDS) | SX_FORM_BYOUT
-    bool ok;      // false: the entry answers SX_ERR_UNSUPPORTED
-    size_t lds;   // dynamic LDS bytes
-};
-
-// As plan_rollout (sx_gp_rollout.hip) decides the streaming safety kernel's: Kstar of all outputs in LDS where they fit
-// beside the n_perf actions of the tile, else output by output (n_s > 1), else unsupported -- there is no resident-W form
-// and no workspace path here.  `extra_bytes`: what the kernel keeps in LDS behind the actions (the Taylor form's step
-// constants, sx_perf_taylor.hpp).
-inline PerfVarPlan plan_perf_var(int ns, int nu, int n_train, int n_pad, int n_perf, size_t extra_bytes = 0) {
-    auto lds_bytes = [&](bool byout) {
-        return rollout_stream_lds_bytes(ns, nu, 0, n_train, n_pad, n_perf, byout) + extra_bytes;
-    };
-    const bool compiled = rollout_compiled(ns, nu, 0);
-    const bool fits = n_pad <= 1024;
-    if (fits && lds_bytes(false) <= kMaxLdsBytes) return {SX_FORM_STREAM, compiled, lds_bytes(false)};
-    if (ns > 1 && fits && lds_bytes(true) <= kMaxLdsBytes) return {SX_FORM_BYOUT, compiled, lds_bytes(true)};
-    return {SX_FORM_STREAM, false, 0};
-}
-
-// One launch for E problems with a GP each, as plan_rollout_multi: output by output for every problem where any model
-// needs it, the LDS of the largest model; a model without a form makes the whole launch unsupported.  `extra_bytes` as
-// in plan_perf_var.
-inline PerfVarPlan plan_perf_var_multi(const sx_gp_model* models, int E, int n_perf, size_t extra_bytes = 0) {
-    PerfVarPlan out{SX_FORM_STREAM, true, 0};
-    const int ns = models[0].n_s, nu = models[0].n_u;
-    for (int i = 0; i < E; ++i) {
-        const PerfVarPlan p = plan_perf_var(ns, nu, models[i].n_train, models[i].n_pad, n_perf, extra_bytes);
-        if (!p.ok) return {p.form, false, 0};
-        if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
-    }
-    for (int i = 0; i < E; ++i)
-        out.lds = std::max(out.lds, rollout_stream_lds_bytes(ns, nu, 0, models[i].n_train, models[i].n_pad, n_perf,
-                                                             out.form == SX_FORM_BYOUT) +
-                                        extra_bytes);
-    return out;
-}
-
 // bytes of the step constants (PerfTaylorConst, sx_perf_taylor.hpp) the Taylor kernels keep in LDS behind the tile's actions
 inline size_t perf_taylor_extra_bytes(int ns, int nu) {
     return ((size_t)2 * ns * ns + 2 * ns * nu + 2 * nu + 3 * ns + (size_t)SX_MAX_M * ns + SX_MAX_M) * sizeof(double);
 }
 
-// What the four _form queries answer for `n` models (one: plan_perf_var_multi over a single model is plan_perf_var): the
-// form of the launch, -1 where an entry would refuse the models or has no form for them.
+// What the four _form queries answer for `n` models: the form of the launch by the streaming plan the safety kernel takes
+// (plan_stream_multi, sx_stream_launch.hpp: n_perf actions in the tile, the Taylor form's step constants behind them;
+// there is no resident-W form and no workspace path here), -1 where an entry would refuse the models or has no form for them.
 inline int perf_gp_form(const sx_gp_model* models, int n, int n_perf, bool taylor) {
     if (n_perf <= 1 || !perf_models_ok(models, n, perf_var_model_ok) || !perf_shape_ok(models[0])) return -1;
     const size_t extra = taylor ? perf_taylor_extra_bytes(models[0].n_s, models[0].n_u) : 0;
-    const PerfVarPlan plan = plan_perf_var_multi(models, n, n_perf, extra);
-    return plan.ok ? plan.form : -1;
+    return plan_stream_multi(models, n, n_perf, extra).form;
 }
 
 // One launch of a GP-product kernel with `lds` bytes: `args` are the kernel's own
@@ -153,9 +113,9 @@ template <class F, int NS, int NU>
 int perf_gp_rollout(const sx_gp_model* models, const void* table, const sx_env* env, const typename F::Ptrs& ptrs,
                     hipStream_t stream) {
     const PerfPtrs& pp = F::base(ptrs);
-    const PerfVarPlan plan = plan_perf_var_multi(models, table ? pp.E : 1, pp.n_perf, F::extra_bytes(NS, NU));
+    const StreamPlan plan = plan_stream_multi(models, table ? pp.E : 1, pp.n_perf, F::extra_bytes(NS, NU));
     const int64_t blocks = (int64_t)pp.E * ((pp.P + SX_TILE - 1) / SX_TILE);
-    if (!plan.ok || blocks > INT_MAX) return SX_ERR_UNSUPPORTED;
+    if (plan.form < 0 || blocks > INT_MAX) return SX_ERR_UNSUPPORTED;
     typename F::template Const<NS, NU> c;
     std::memset(&c, 0, sizeof(c));
     F::template make_const<NS, NU>(env, c);

@@ -1,6 +1,7 @@
 // Host side of the Taylor performance rollouts, shared by sx_perf_taylor.hip (the parent entries) and
 // sx_perf_taylor_sat.hip (the entries with the saturating cost): the form for perf_gp_rollout and what the entries do
-// behind check_perf_entry.  Host code only.
+// behind check_perf_entry.  The cautious form (sx_cautious_host.hpp) fills its Taylor constants through
+// PerfTaylorForm::make_const too.  Host code only.
 #pragma once
 #include "sx_host.hpp"
 #include "sx_launch.hpp"

@@ -1,19 +1,23 @@
-// The compiled shapes of the fused rollout, and the launchers of the streaming rollout kernel (cem_rollout_kernel<NS, NU,
-// BYOUT, SH, MM>).  The launchers' instantiations are compiled in translation units of their own (sx_stream_ns12.hip,
-// sx_stream_ns34.hip; the multi-model mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the
-// saturating-cost objective in sx_stream_sat.hip and sx_stream_sat_multi.hip; built in parallel with the rest);
-// sx_gp_rollout.hip sees the declarations.
+// The compiled shapes of the fused rollout, the streaming plan every exact-GP rollout shares (plan_stream,
+// plan_stream_multi: the LDS rule and its fold over several models, written here only), and the launcher of the streaming
+// rollout kernels (launch_stream<V, NS, NU> over a variant V that names the kernel).  The launcher's instantiations are
+// compiled in translation units of their own, beside the kernels (sx_stream_ns12.hip, sx_stream_ns34.hip; the multi-model
+// mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
+// sx_stream_sat.hip and sx_stream_sat_multi.hip; built in parallel with the rest); sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "../../include/sx_amd.h"
 #include "sx_gp.hpp"
+#include "sx_launch.hpp"   // kMaxLdsBytes
 #include "sx_reach.hpp"
 #include "sx_rollout.hpp"
 
 // (n_s, n_u, query shift) of every compiled fused rollout: X(NS, NU, SH, ...).  Shift 0 is sx_cem_rollout (and the shape
 // set of every other exact-GP entry point), shift > 0 sx_cem_rollout_junk (n_s + n_u + shift <= SX_MAX_D).  Each entry
-// has an instantiation of launch_rollout_stream in sx_stream_ns*.hip; ssm_cem.JUNK_FUSED_SHAPES is checked against it.
+// has an instantiation of launch_stream<StreamPlain<SH>> in sx_stream_ns*.hip; ssm_cem.JUNK_FUSED_SHAPES is checked against it.
 #define SX_ROLLOUT_SHAPES(X, ...)                                                                                       \
     X(2, 1, 0, __VA_ARGS__) X(4, 1, 0, __VA_ARGS__) X(2, 2, 0, __VA_ARGS__) X(4, 2, 0, __VA_ARGS__)                     \
     X(3, 1, 0, __VA_ARGS__) X(1, 1, 0, __VA_ARGS__) X(2, 1, 1, __VA_ARGS__) X(4, 1, 1, __VA_ARGS__)                     \
@@ -57,39 +61,80 @@ inline size_t rollout_stream_lds_bytes(int ns, int nu, int sh, int n_train, int 
             (size_t)SX_TILE * H * nu) * sizeof(double);
 }
 
-// Launches cem_rollout_kernel<NS, NU, byout, SH> with `lds` bytes (rollout_stream_lds_bytes) of dynamic LDS on `stream`.
-template <int NS, int NU, int SH>
-int launch_rollout_stream(const GpConst<NS, NS + NU + SH>& gc, const ReachConst<NS, NU>& rc,
-                          const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
-                          hipStream_t stream);
+// The streaming plan of one launch: the form, and the dynamic LDS bytes of its kernel
+struct StreamPlan {
+    int form;     // SX_FORM_STREAM (Kstar of all outputs in LDS) | SX_FORM_BYOUT | -1: no streaming form fits
+    size_t lds;
+};
 
-// Launches cem_rollout_kernel<NS, NU, byout, 0, true> over E problems with a GP each: `table` is the device array of their
-// GpConst (sx_gp_model_table), `lds` the largest rollout_stream_lds_bytes over them.  rp.status holds E words.
-template <int NS, int NU>
-int launch_rollout_stream_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
-                                const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
-                                hipStream_t stream);
+// The LDS rule of the streaming kernels, decided here only, for a GP over ns + nu + sh columns, `steps` steps of nu
+// actions in the tile and `extra_bytes` behind them (the step constants of the Taylor and cautious kernels; 0 for the
+// safety rollouts): Kstar of all outputs in LDS where they fit, else output by output (n_s > 1), else none; n_pad <= 1024
+// (the stage tables are cut for that).  Does not ask whether the shape is compiled.
+inline StreamPlan plan_stream(int ns, int nu, int sh, int n_train, int n_pad, int steps, size_t extra_bytes = 0) {
+    auto lds = [&](bool byout) { return rollout_stream_lds_bytes(ns, nu, sh, n_train, n_pad, steps, byout) + extra_bytes; };
+    if (n_pad <= 1024 && lds(false) <= kMaxLdsBytes) return {SX_FORM_STREAM, lds(false)};
+    if (n_pad <= 1024 && ns > 1 && lds(true) <= kMaxLdsBytes) return {SX_FORM_BYOUT, lds(true)};
+    return {-1, 0};
+}
 
-// Launches cem_rollout_starts_kernel<NS, NU, byout> (sx_cem_rollout_starts: a start state per particle, rp as the
-// SX_ROLLOUT_PS sections of sx_rollout_body.inc read it) with `lds` bytes (rollout_stream_lds_bytes, shift 0).
-// Instantiated for every shift-0 shape in sx_stream_starts.hip.
-template <int NS, int NU>
-int launch_rollout_starts(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc,
-                          const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, bool byout, size_t lds,
-                          hipStream_t stream);
+// One launch for E problems with a GP each (E = 1: the entries that have the streaming kernel only), shift 0: output by
+// output for every problem where any model needs it, the LDS of the largest model in that form; a model without a
+// streaming form, or a shape that is not compiled, leaves the whole launch without one.
+inline StreamPlan plan_stream_multi(const sx_gp_model* models, int E, int steps, size_t extra_bytes = 0) {
+    const int ns = models[0].n_s, nu = models[0].n_u;
+    if (!rollout_compiled(ns, nu, 0)) return {-1, 0};
+    StreamPlan out{SX_FORM_STREAM, 0};
+    for (int i = 0; i < E; ++i) {
+        const StreamPlan p = plan_stream(ns, nu, 0, models[i].n_train, models[i].n_pad, steps, extra_bytes);
+        if (p.form < 0) return p;
+        if (p.form == SX_FORM_BYOUT) out.form = SX_FORM_BYOUT;
+    }
+    for (int i = 0; i < E; ++i)
+        out.lds = std::max(out.lds, rollout_stream_lds_bytes(ns, nu, 0, models[i].n_train, models[i].n_pad, steps,
+                                                             out.form == SX_FORM_BYOUT) + extra_bytes);
+    return out;
+}
 
-// Launches cem_rollout_sat_kernel<NS, NU, byout, false> (sx_cem_rollout[_elites]_sat: the saturating cost `sat` on the
-// safety ellipsoids as the objective) with `lds` bytes (rollout_stream_lds_bytes, shift 0: the parent's plan).
-// Instantiated for every shift-0 shape in sx_stream_sat.hip.
-template <int NS, int NU>
-int launch_rollout_sat(const GpConst<NS, NS + NU>& gc, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
-                       const RolloutPtrs& rp, const SatConst<NS>& sat, bool byout, size_t lds, hipStream_t stream);
+// The variants of the streaming kernel: which kernel a launch names (kernel<NS, NU, BYOUT>()), its query shift SH, whether
+// its first argument is the device table of the problems' GpConst (MM; sx_gp_model_table), and whether it takes the
+// saturating cost's constants as a trailing argument (SAT).
+template <int SH_, bool MM_ = false>
+struct StreamPlain {   // cem_rollout_kernel: sx_cem_rollout[_elites][_junk] (MM: sx_cem_rollout[_elites]_multi)
+    static constexpr int SH = SH_;
+    static constexpr bool MM = MM_, SAT = false;
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_rollout_kernel<NS, NU, BYOUT, SH_, MM_>;
+    }
+};
+struct StreamStarts {   // cem_rollout_starts_kernel: sx_cem_rollout_starts, rp as the SX_ROLLOUT_PS sections read it
+    static constexpr int SH = 0;
+    static constexpr bool MM = false, SAT = false;
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_rollout_starts_kernel<NS, NU, BYOUT>;
+    }
+};
+template <bool MM_>
+struct StreamSat {   // cem_rollout_sat_kernel: sx_cem_rollout[_elites]_sat (MM: ..._sat_multi)
+    static constexpr int SH = 0;
+    static constexpr bool MM = MM_, SAT = true;
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_rollout_sat_kernel<NS, NU, BYOUT, MM_>;
+    }
+};
 
-// Launches cem_rollout_sat_kernel<NS, NU, byout, true> over E problems with a GP each (sx_cem_rollout[_elites]_sat_multi;
-// `table`, `lds` and rp.status as launch_rollout_stream_multi).  Instantiated in sx_stream_sat_multi.hip.
-template <int NS, int NU>
-int launch_rollout_sat_multi(const GpConst<NS, NS + NU>* table, const ReachConst<NS, NU>& rc,
-                             const CostConst<SX_MAX_M, NS, NU>& cc, const RolloutPtrs& rp, const SatConst<NS>& sat,
-                             bool byout, size_t lds, hipStream_t stream);
+// The first kernel argument of variant V: the GpConst, or with V::MM the device table of E of them
+template <class V, int NS, int NU>
+using StreamGpArg = typename RolloutGpArg<NS, NS + NU + V::SH, V::MM>::type;
+
+// Launches V::kernel<NS, NU, byout>() on `stream` over rp.E * ceil(rp.P / SX_TILE) workgroups with `lds` bytes of dynamic
+// LDS (plan_stream's; with V::MM plan_stream_multi's, and rp.status holds a word per problem).  `sat` is read with V::SAT
+// only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
+template <class V, int NS, int NU>
+int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
+                  const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream);
 
 }  // namespace sx

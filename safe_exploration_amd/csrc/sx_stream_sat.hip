@@ -3,5 +3,5 @@
 // forms.  A translation unit of its own: nothing the other objects compile changes with it.
 #include "sx_stream_impl.hpp"
 
-#define SX_SAT_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_SAT_INSTANTIATE(NS, NU))
+#define SX_SAT_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_INSTANTIATE(NS, NU, StreamSat<false>))
 SX_ROLLOUT_SHAPES(SX_SAT_ONE, 0)

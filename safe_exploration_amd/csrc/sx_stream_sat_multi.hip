@@ -3,5 +3,5 @@
 // shape of SX_ROLLOUT_SHAPES in both forms.
 #include "sx_stream_impl.hpp"
 
-#define SX_SAT_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_SAT_MULTI_INSTANTIATE(NS, NU))
+#define SX_SAT_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_INSTANTIATE(NS, NU, StreamSat<true>))
 SX_ROLLOUT_SHAPES(SX_SAT_MULTI_ONE, 0)

@@ -2,5 +2,5 @@
 // SX_ROLLOUT_SHAPES.
 #include "sx_stream_impl.hpp"
 
-#define SX_STARTS_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_STARTS_INSTANTIATE(NS, NU))
+#define SX_STARTS_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_STREAM_INSTANTIATE(NS, NU, StreamStarts))
 SX_ROLLOUT_SHAPES(SX_STARTS_ONE, 0)
