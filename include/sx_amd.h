@@ -810,6 +810,59 @@ int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table
  * sx_cem_rollout_starts_form.  The _multi entries launch what sx_cem_rollout_multi_form reports. */
 int sx_cem_rollout_sat_form(const sx_gp_model* model, int H);
 
+/* ---- The SafeMPC constraint set on the safety trajectory ---------------------------------------------------------------------
+ * What the reference's SafeMPC constrains beside the terminal safe set (safempc_simple.py:325-396, _generate_control_constraint
+ * :492-536), as penalties of the CEM rollout.  Steps t = 0 .. H-1; (p_t, Q_t) is the ellipsoid step t starts from (Q_0 = q0,
+ * or a point), u_t the row's action (k_ff), (p_{t+1}, Q_{t+1}) what the step reaches, K = env->k_fb.
+ *   feedback bounds (ctrl_ellipsoid = 1): a step that starts from an ellipsoid is ellipsoid-violated where the control
+ *       ellipsoid (u_t, Q_u = K Q_t K^T) is not certified inside the action box: some
+ *       +-u_c + sqrt(Q_u[c][c]) -+ bound_c >= 0, the polytope test over h = [I; -I], h_vec = [u_max; -u_min], c_safety = 1
+ *       (a NaN distance is not a violation).  The step costs SX_ACTION_VIOLATION_COST ONCE if it is box-violated (the
+ *       parent's strict test) or ellipsoid-violated.  A step that starts from a point keeps the box test alone.
+ *   obstacle polytope (m_obs > 0): every step with t + 1 < H whose (p_{t+1}, Q_{t+1}) is not certified inside
+ *       h_mat_obs x <= h_obs (some h_j . p + sqrt(h_j^T Q h_j) - h_obs_j >= 0) costs SX_STATE_VIOLATION_COST, on top of
+ *       whatever env->con_mode charges for the safe polytope.  The terminal ellipsoid is not checked against these rows.
+ *   m_obs = 0 and ctrl_ellipsoid = 0: the empty set; every output is the streaming parent's bit for bit. */
+typedef struct sx_con_set {
+    int32_t m_obs;                            /* obstacle rows, 0 .. SX_MAX_M */
+    int32_t ctrl_ellipsoid;                   /* 0 | 1: the feedback bounds */
+    double h_mat_obs[SX_MAX_M * SX_MAX_NS];   /* [m_obs x n_s] row-major, rows n_s apart (as sx_env.h_mat) */
+    double h_obs[SX_MAX_M];
+} sx_con_set;
+
+/* The set's cost of one step alone, one particle per lane (the step-by-step path's and the tests'):
+ *   con_step[p] = SX_ACTION_VIOLATION_COST if u[p] is box-violated, or q_start is given, ctrl_ellipsoid is set and
+ *                 (u[p], K q_start[p] K^T) is ellipsoid-violated
+ *               + SX_STATE_VIOLATION_COST if check_obstacle != 0 and (p_next[p], q_next[p]) violates the obstacle rows
+ * u dev [P x n_u], q_start dev [P x n_s x n_s] or NULL (the step starts from a point), p_next dev [P x n_s], q_next dev
+ * [P x n_s x n_s] (both may be NULL with check_obstacle = 0 or m_obs = 0), con_step dev [P] (overwritten).  Reads n_s,
+ * n_u, k_fb, u_min, u_max of env.  No status word: nothing here fails.
+ * SX_ERR_ARG (before any device access) for null pointers, P <= 0, n_s outside 1 .. SX_MAX_NS, n_u outside
+ * 1 .. SX_MAX_NU, m_obs outside 0 .. SX_MAX_M, ctrl_ellipsoid outside {0, 1}, a non-finite constant in the rows in use. */
+int sx_conset_eval(const sx_env* env, const sx_con_set* cons, int P, const double* u, const double* q_start,
+                   const double* p_next, const double* q_next, int check_obstacle, double* con_step, void* stream);
+
+/* sx_cem_rollout and sx_cem_rollout_elites with the constraint set in the step: con_cost carries the set's costs beside the
+ * parent's; actions, traj, sigma, obj_cost, status and the refit are those of the same launch with the empty set, bit for
+ * bit.  cost == NULL: the objective of env->obj_mode, and the launch with the empty set is the streaming kernel of the parent
+ * entry bit for bit.  Otherwise the saturating cost on the safety ellipsoids, exactly as sx_cem_rollout_sat (env->obj_mode is
+ * not read) -- what the reference's n_perf = 0 cart-pole configs solve.  Arguments as the parent entry's with (cons, cost)
+ * behind env; no workspace.  The set's constants travel as a kernel argument: the LDS plan is the parent's.
+ * The streaming kernel only: the resident forms and the workspace path are not served.
+ * SX_ERR_ARG (before any device access) for whatever the parent entry answers it for, a NULL cons, m_obs outside
+ * 0 .. SX_MAX_M, ctrl_ellipsoid outside {0, 1}, a non-finite constant in the rows in use, and a cost sx_cem_rollout_sat
+ * refuses; SX_ERR_UNSUPPORTED exactly where sx_cem_rollout_sat answers it. */
+int sx_cem_rollout_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost, int E,
+                        int P, int H, const double* x0, const double* q0, const double* mean, const double* std,
+                        const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                        double* con_cost, int32_t* status, void* stream);
+int sx_cem_rollout_elites_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost,
+                               int E, int P, int H, const double* x0, const double* q0, const double* elite_rows, int k,
+                               const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                               double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream);
+/* The form sx_cem_rollout_cons launches for this model and H: the contract of sx_cem_rollout_sat_form. */
+int sx_cem_rollout_cons_form(const sx_gp_model* model, int H);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -69,6 +69,11 @@ class SxSatCost(Structure):
                 ('v', c_double * (SX_SAT_MAX_DIM * SX_SAT_MAX_DIM))]
 
 
+class SxConSet(Structure):
+    _fields_ = [('m_obs', c_int32), ('ctrl_ellipsoid', c_int32), ('h_mat_obs', c_double * (SX_MAX_M * SX_MAX_NS)),
+                ('h_obs', c_double * SX_MAX_M)]
+
+
 # name -> (restype, argtypes): exactly the entry points include/sx_amd.h declares
 SIGNATURES = {
     'sx_version': (c_char_p, []),
@@ -162,6 +167,12 @@ SIGNATURES = {
     'sx_cem_rollout_elites_sat_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxSatCost), c_int,
                                                 c_int, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
     'sx_cem_rollout_sat_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_conset_eval': (c_int, [POINTER(SxEnv), POINTER(SxConSet), c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
+    'sx_cem_rollout_cons': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxConSet), POINTER(SxSatCost), c_int, c_int,
+                                    c_int] + [c_void_p] * 12),
+    'sx_cem_rollout_elites_cons': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxConSet), POINTER(SxSatCost), c_int,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
+    'sx_cem_rollout_cons_form': (c_int, [POINTER(SxGpModel), c_int]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -84,7 +84,8 @@ def _rollout(suffix: str, head: tuple, x0: Tensor, horizon: int, n_s: int, n_u: 
 def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, actions: Optional[Tensor] = None,
                 mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
                 q0: Optional[Tensor] = None, want_traj: bool = False, want_sigma: bool = False,
-                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False, cost=None):
+                status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None, want_dist: bool = False, cost=None,
+                con_set=None):
     """Thin wrapper over sx_cem_rollout / sx_cem_rollout_elites (and their _junk, _feat and _mlp counterparts).
 
     x0 [E x n_s]; either `actions` [E x P x H x n_u] (given), or (`mean`, `std` [E x H x n_u], `noise` [E x P x H x n_u]),
@@ -95,12 +96,20 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     is the sum of the cost over the safety ellipsoids (p_t, Q_t), t = 1 .. H, read as means and covariances, env.obj_mode
     is not read and everything else is unchanged.  The streaming kernel only: a training set on
     the workspace path has no such launch.
+    `con_set` (an `_lib.SxConSet`, `make_con_set`; exact RBF GPs only) selects sx_cem_rollout_cons /
+    sx_cem_rollout_elites_cons, together with `cost` where given: con_cost then carries the feedback bounds on the control
+    ellipsoids and the obstacle polytope on the intermediate safety ellipsoids, everything else is
+    the launch's with the empty set.  The streaming kernel only, as with `cost`.
     Returns dict(actions, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]).
     """
     _lib.require_gpu(x0, 'x0')
     family = getattr(ssm, 'kernel_family', 'rbf')
     workspace, unsupported = (), None
-    if cost is not None:
+    if con_set is not None:
+        _require_rbf_con_set(ssm)
+        head = (ctypes.byref(ssm.device_model), ctypes.byref(env), _con_set_arg(con_set)) + (_cost_args(cost, ssm) or (None,))
+        suffix = '_cons'
+    elif cost is not None:
         _require_rbf_cost([ssm])
         head, suffix = (ctypes.byref(ssm.device_model), ctypes.byref(env)) + _cost_args(cost, ssm), '_sat'
     elif family in ('feature', 'mlp', 'feature_junk', 'mlp_junk'):
@@ -141,6 +150,37 @@ def _require_rbf_cost(ssms) -> None:
         if family != 'rbf':
             raise NotImplementedError(f'the saturating cost on the safety trajectory is built for exact RBF GPs, not '
                                       f'kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+
+
+def _require_rbf_con_set(ssm) -> None:
+    family = getattr(ssm, 'kernel_family', 'rbf')
+    if family != 'rbf':
+        raise NotImplementedError(f'the constraint set (con_set: feedback bounds, obstacle polytope) is built for exact RBF '
+                                  f'GPs, not kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and '
+                                  f'step-by-step models)')
+
+
+def _con_set_arg(con_set):
+    """The sx_con_set pointer of a rollout entry's arguments."""
+    if not isinstance(con_set, _lib.SxConSet):
+        raise TypeError(f'con_set must be an _lib.SxConSet (make_con_set) or None, got {type(con_set).__name__}')
+    return ctypes.byref(con_set)
+
+
+def conset_eval(env: _lib.SxEnv, con_set, u: Tensor, q_start: Optional[Tensor], p_next: Optional[Tensor],
+                q_next: Optional[Tensor], check_obstacle: bool = True) -> Tensor:
+    """Thin wrapper over sx_conset_eval: [P], the constraint set's cost of one step of P particles -- the action cost (3)
+    where u [P x n_u] leaves the box or, from an ellipsoid (., q_start [P x n_s x n_s]; None: a point) with the feedback
+    bounds on, the control ellipsoid (u, K q_start K^T) is not certified inside it, plus (`check_obstacle`) the state cost
+    (10) where (p_next [P x n_s], q_next [P x n_s x n_s]) is not certified inside the obstacle rows."""
+    _lib.require_gpu(u, 'u')
+    P, dev = u.size(0), u.device
+    out = torch.empty(P, dtype=torch.float64, device=dev)
+    c = lambda t: None if t is None else t.contiguous()
+    _lib.check(_lib.lib().sx_conset_eval(ctypes.byref(env), _con_set_arg(con_set), P, _lib.ptr(c(u)), _lib.ptr(c(q_start)),
+                                         _lib.ptr(c(p_next)), _lib.ptr(c(q_next)), int(bool(check_obstacle)), _lib.ptr(out),
+                                         _lib.stream_ptr(dev)), 'sx_conset_eval')
+    return out
 
 
 def _require_rbf_starts(ssm) -> None:
@@ -592,7 +632,7 @@ def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candid
 
 
 def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Tensor, *, status: Tensor, group=None,
-                         objective_hook=None, cost=None):
+                         objective_hook=None, cost=None, con_set=None):
     """The rollout of ONE problem step by step, the way the reference's optimiser drives it: H dynamics-callback calls on
     the whole particle batch (safempc_cem.py:288-302), each = sx_gp_predict + sx_onestep_reach, then the costs.
 
@@ -606,8 +646,12 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
     "zero present" flag is all-reduced (MAX) per step.  Returns dict(obj_cost [P], con_cost [P]); `status` is OR-ed.
     `cost` (a `costs.SaturatingCost`): the objective of a step is the cost of its ellipsoid (p_{t+1}, Q_{t+1}) through
     sx_sat_cost_eval -- one more launch per step, in place of the hook and env.obj_mode -- as sx_cem_rollout_sat prices it.
+    `con_set` (an `_lib.SxConSet`): the action cost of a step and the obstacle cost of the ellipsoid it reaches come from
+    sx_conset_eval -- one launch per step in place of the box test -- as sx_cem_rollout_cons charges them.
     """
     _cost_args(cost, ssm)
+    if con_set is not None:
+        _con_set_arg(con_set)
     n_s, n_u = ssm.num_states, ssm.num_actions
     dev = actions.device
     P, H, _ = actions.shape
@@ -650,7 +694,11 @@ def cem_rollout_stepwise(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, actions: Te
             obj = obj - sigma.sum(dim=1)
         else:
             obj = obj + (w_abs * (target - p1).abs() + w_lin * p1).sum(dim=1)
-        con = con + _lib.SX_ACTION_VIOLATION_COST * ((u < u_min) | (u > u_max)).any(dim=1)
+        if con_set is None:
+            con = con + _lib.SX_ACTION_VIOLATION_COST * ((u < u_min) | (u > u_max)).any(dim=1)
+        else:
+            # (q: the ellipsoid the step starts from, None at a point; the terminal ellipsoid meets no obstacle row)
+            con = con + conset_eval(env, con_set, u, q, p1, q1, check_obstacle=t + 1 < H)
         if env.con_mode == _lib.SX_CON_ALL_STATES or t == H - 1:
             _lib.check(lib.sx_polytope_distance(ctypes.byref(env), P, _lib.ptr(p1), _lib.ptr(q1), 1.0, _lib.ptr(d),
                                                 _lib.ptr(inside), _lib.stream_ptr(dev)), 'sx_polytope_distance')
@@ -865,14 +913,29 @@ class FusedCemMpc:
     objective of the safety trajectory itself: every ellipsoid (p_t, Q_t), t = 1 .. H, is priced as a mean and a covariance
     in the rollout kernel (``sx_cem_rollout_sat`` / ``sx_cem_rollout_elites_sat``, the streaming form), what the reference's
     ``n_perf = 0`` configs hand their solver.  The cost belongs to one trajectory, chosen by ``n_perf``.
+
+    ``con_set`` (an ``_lib.SxConSet``, ``make_con_set``) adds the reference's SafeMPC constraints to
+    the safety trajectory: the control ellipsoid (k_ff_t, K Q_t K^T) inside the action box wherever a step starts from an
+    ellipsoid, and the obstacle polytope on every intermediate safety ellipsoid, as penalties of 3 and 10 in the rollout
+    kernel (``sx_cem_rollout_cons`` / ``sx_cem_rollout_elites_cons``, the streaming form; the step-by-step path charges
+    them with ``sx_conset_eval``).  Exact RBF GPs on one GPU without a performance trajectory; ``set_env`` keeps the set.
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
                  record_rollouts: bool = False, process_group=None, force_exchange: bool = False, n_perf: int = 0,
                  perf_r: int = 1, perf_variance: bool = False, perf_type: str = 'mean_equivalent',
-                 perf_terminal_safety: bool = False, cost_on_safety: bool = False):
+                 perf_terminal_safety: bool = False, cost_on_safety: bool = False, con_set=None):
         self._ssm = ssm
+        self._con_set = con_set
+        if con_set is not None:
+            _con_set_arg(con_set)
+            _require_rbf_con_set(ssm)
+            if int(n_perf) > 0:
+                raise NotImplementedError(f'con_set constrains the safety trajectory of a solve without a performance '
+                                          f'trajectory: got n_perf={n_perf} (cem_n_perf > 0 is not built)')
+            if process_group is not None:
+                raise NotImplementedError('con_set is not built for sharded particles (a process group)')
         self._cost_on_safety = bool(cost_on_safety)
         if self._cost_on_safety and int(n_perf) > 0:
             raise ValueError(f'cost_on_safety=True prices the safety trajectory, which carries the objective only without a '
@@ -1003,6 +1066,12 @@ class FusedCemMpc:
         """The cost where it prices the safety trajectory (cost_on_safety), else None."""
         return self._cost if getattr(self, '_cost_on_safety', False) else None
 
+    @property
+    def _con_set_kw(self) -> dict:
+        """What the constraint set adds to a rollout call (nothing without one)."""
+        con_set = getattr(self, '_con_set', None)
+        return {} if con_set is None else dict(con_set=con_set)
+
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
         if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf_kind == 'mean':
             raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
@@ -1123,7 +1192,8 @@ class FusedCemMpc:
         per_e = [cem_rollout_stepwise(self._ssm, self._env, x0[e], acts[e], status=status,
                                       group=self._group if self._world > 1 else None,
                                       objective_hook=self._objective_hook if cost is None else None,
-                                      **({} if cost is None else dict(cost=cost))) for e in range(x0.size(0))]
+                                      **({} if cost is None else dict(cost=cost)),
+                                      **self._con_set_kw) for e in range(x0.size(0))]
         return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
                     con_cost=torch.stack([q['con_cost'] for q in per_e]))
 
@@ -1162,7 +1232,7 @@ class FusedCemMpc:
         in_prologue = (not stepwise) and (not perf) and self._refit_in_prologue(E)
         # (a cost on the safety trajectory rides in the rollout call: no hook is evaluated, no trajectory recorded for one)
         safety_cost = self._safety_cost
-        cost_kw = {} if safety_cost is None else dict(cost=safety_cost)
+        cost_kw = dict({} if safety_cost is None else dict(cost=safety_cost), **self._con_set_kw)
         want_traj = self._record or (self._objective_hook is not None and not perf and safety_cost is None)
         if perf and noise is not None:
             # the draws of the safety steps and of the tail, each contiguous: two copies per solve
@@ -1402,6 +1472,9 @@ class MultiModelCemMpc:
             return ((type(m),) + tuple(getattr(m, a, None) for a in names)
                     + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
 
+        if any(getattr(m, '_con_set', None) is not None for m in solvers):
+            raise NotImplementedError('a multi-model solve (MultiModelCemMpc) is not built for con_set: the _cons rollouts '
+                                      'take one model')
         (cem0, env0), *rest = [settings(m) for m in solvers]
         for cem, env in rest:
             if cem != cem0:

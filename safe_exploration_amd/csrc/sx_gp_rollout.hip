@@ -4,7 +4,8 @@
 // kernel only (stream_rollout), the GP model table, and sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi,
 // sx_cem_rollout_starts, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
 // sx_cem_rollout_workspace_bytes, and the entries with the saturating cost on the safety ellipsoids,
-// sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form.  No kernel is compiled here.
+// sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form, and those with the SafeMPC constraint set in the step,
+// sx_cem_rollout[_elites]_cons, sx_cem_rollout_cons_form.  No kernel is compiled here.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -129,10 +130,10 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
 // The entries that have the streaming kernel only -- the multi-model rollouts, the per-particle starts, the saturating
 // cost on the safety ellipsoids -- from their checked arguments to the launch of variant V, for one model or (V::MM) rp.E
 // of them behind their device `table`: the streaming plan with the elite-row bound (no workspace path, no resident form,
-// no override), the constants of `env`, those of `cost` (V::SAT), the GP argument, the launcher.
+// no override), the constants of `env`, those of `cost` (V::SAT) and of `cons` (V::CONS), the GP argument, the launcher.
 template <class V, int NS, int NU>
 static int stream_rollout(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                          const RolloutPtrs& rp, hipStream_t stream) {
+                          const sx_con_set* cons, const RolloutPtrs& rp, hipStream_t stream) {
     const StreamPlan plan = plan_stream_multi(models, V::MM ? rp.E : 1, rp.H);
     if (plan.form < 0 || (rp.elite_rows && !elite_rows_fit(NS, NU, rp.H))) return SX_ERR_UNSUPPORTED;
     ReachConst<NS, NU> rc;
@@ -141,19 +142,22 @@ static int stream_rollout(const sx_gp_model* models, const void* table, const sx
     SatConst<NS> sat;
     if constexpr (V::SAT) make_sat_const<NS>(cost, sat);
     const SatConst<NS>* satp = V::SAT ? &sat : nullptr;
+    ConConst<NS> con;
+    if constexpr (V::CONS) make_con_const<NS>(cons, con);
+    const ConConst<NS>* conp = V::CONS ? &con : nullptr;
     const bool byout = plan.form == SX_FORM_BYOUT;
     if constexpr (V::MM)
         return launch_stream<V, NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp, satp, byout, plan.lds,
-                                        stream);
+                                        stream, conp);
     else
         return launch_stream<V, NS, NU>(make_gp_const<NS, NU>(models, kRolloutThreads / 64), rc, cc, rp, satp, byout,
-                                        plan.lds, stream);
+                                        plan.lds, stream, conp);
 }
 
 template <class V>
 static int stream_dispatch(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                           const RolloutPtrs& rp, void* stream) {
-#define CALL(NS, NU) stream_rollout<V, NS, NU>(models, table, env, cost, rp, (hipStream_t)stream)
+                           const RolloutPtrs& rp, void* stream, const sx_con_set* cons = nullptr) {
+#define CALL(NS, NU) stream_rollout<V, NS, NU>(models, table, env, cost, cons, rp, (hipStream_t)stream)
     SX_DISPATCH(env->n_s, env->n_u, CALL);
 #undef CALL
 }
@@ -223,6 +227,17 @@ static int cem_rollout_single(const sx_gp_model* model, const sx_env* env, int q
 #define CALL(NS, NU, SH) launch_rollout<NS, NU, SH>(model, env, rp, (double*)workspace, workspace_bytes, (hipStream_t)stream)
     SX_ROLLOUT_DISPATCH(env->n_s, env->n_u, query_shift, CALL);
 #undef CALL
+}
+
+// sx_cem_rollout[_elites]_cons: cem_rollout_single's checks, the set's and the cost's after them, then the streaming kernel
+// with the set in its step, priced by env's objective (cost == NULL) or by the cost
+static int cem_rollout_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost,
+                            bool elites, const RolloutPtrs& rp, void* stream) {
+    if (!model || (elites && !rp.elite_rows) || !rollout_args_ok(env, rp) || !rollout_shapes_ok(model, env, 0))
+        return SX_ERR_ARG;
+    if (!con_set_ok(cons, env->n_s) || (cost && !sat_cost_ok(cost, env->n_s))) return SX_ERR_ARG;
+    if (cost) return stream_dispatch<StreamCons<true>>(model, nullptr, env, cost, rp, stream, cons);
+    return stream_dispatch<StreamCons<false>>(model, nullptr, env, nullptr, rp, stream, cons);
 }
 
 // The entries over rp.E models behind their device `table`, as cem_rollout_single: every one has the streaming kernel only
@@ -373,6 +388,26 @@ int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table
     const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
                                                 status, E, P, H}, elite_rows, k, mean_out, std_out);
     return sx::cem_rollout_multi(models, table, env, {true, cost}, true, rp, stream);
+}
+
+// ---- the SafeMPC constraint set in the step: the single-model entries with a set handed in ---------
+int sx_cem_rollout_cons_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
+
+int sx_cem_rollout_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost, int E,
+                        int P, int H, const double* x0, const double* q0, const double* mean, const double* std,
+                        const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                        double* con_cost, int32_t* status, void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::cem_rollout_cons(model, env, cons, cost, false, rp, stream);
+}
+
+int sx_cem_rollout_elites_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost,
+                               int E, int P, int H, const double* x0, const double* q0, const double* elite_rows, int k,
+                               const double* noise, double* actions, double* traj, double* sigma, double* obj_cost,
+                               double* con_cost, int32_t* status, double* mean_out, double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_cons(model, env, cons, cost, true, rp, stream);
 }
 
 }  // extern "C"

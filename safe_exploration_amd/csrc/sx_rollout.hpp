@@ -2,10 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/sx_amd.h"
 #include "sx_gp.hpp"
 #include "sx_reach.hpp"
 #include "sx_refit.hpp"
+#include "sx_conset.hpp"     // ConConst, ctrl_ellipsoid_violated
 #include "sx_sat_cost.hpp"   // SatConst, sat_loss
 
 namespace sx {
@@ -86,7 +89,9 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
     ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp) {
 #define SX_ROLLOUT_PS 0
 #define SX_ROLLOUT_SAT 0
+#define SX_ROLLOUT_CONS 0
 #include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
 #undef SX_ROLLOUT_SAT
 #undef SX_ROLLOUT_PS
 }
@@ -101,7 +106,9 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_starts_kernel(
     constexpr bool MM = false;
 #define SX_ROLLOUT_PS 1
 #define SX_ROLLOUT_SAT 0
+#define SX_ROLLOUT_CONS 0
 #include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
 #undef SX_ROLLOUT_SAT
 #undef SX_ROLLOUT_PS
 }
@@ -128,7 +135,50 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_sat_kernel(
     constexpr int SH = 0;
 #define SX_ROLLOUT_PS 0
 #define SX_ROLLOUT_SAT 1
+#define SX_ROLLOUT_CONS 0
 #include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
+#undef SX_ROLLOUT_SAT
+#undef SX_ROLLOUT_PS
+}
+
+// sx_cem_rollout[_elites]_cons: cem_rollout_kernel (SH = 0, one GP) with the constraint set of sx_conset.hpp in finish()
+// (the SX_ROLLOUT_CONS sections of sx_rollout_body.inc) and, with SAT, the saturating cost on the
+// safety ellipsoids as the objective, as cem_rollout_sat_kernel has it.  The set's constants are one more kernel argument,
+// uniform and read by scalar loads on the owner lanes: the LDS plan is the parent's byte for byte.  The two objectives are
+// two templates of one name (the body is text, and its objective a preprocessor choice); SAT picks between them.
+template <int NS, int NU>
+constexpr size_t rollout_cons_arg_bytes() {
+    return rollout_sat_arg_bytes<NS, NU, false>() + (sizeof(ConConst<NS>) + 7) / 8 * 8;
+}
+
+template <int NS, int NU, bool BYOUT, bool SAT, std::enable_if_t<!SAT, int> = 0>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
+    GpConst<NS, NS + NU> gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const ConConst<NS> cons) {
+    constexpr int SH = 0;
+    constexpr bool MM = false;
+#define SX_ROLLOUT_PS 0
+#define SX_ROLLOUT_SAT 0
+#define SX_ROLLOUT_CONS 1
+#include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
+#undef SX_ROLLOUT_SAT
+#undef SX_ROLLOUT_PS
+}
+
+template <int NS, int NU, bool BYOUT, bool SAT, std::enable_if_t<SAT, int> = 0>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
+    GpConst<NS, NS + NU> gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const ConConst<NS> cons, const SatConst<NS> sat) {
+    static_assert(rollout_cons_arg_bytes<NS, NU>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
+    constexpr int SH = 0;
+    constexpr bool MM = false;
+#define SX_ROLLOUT_PS 0
+#define SX_ROLLOUT_SAT 1
+#define SX_ROLLOUT_CONS 1
+#include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
 #undef SX_ROLLOUT_SAT
 #undef SX_ROLLOUT_PS
 }

@@ -1,7 +1,7 @@
 // The body of cem_rollout_kernel and cem_rollout_starts_kernel (sx_rollout.hpp), included into both: as text, so that
 // cem_rollout_kernel keeps the symbol and the instructions it had before the per-particle-start mode existed (a trailing
 // template flag would have renamed every instantiation).  In scope: NS, NU, BYOUT, SH, MM; the kernel arguments gc_arg,
-// stage_tab_arg, rc, cc, rp; SX_ROLLOUT_PS (0 | 1); SX_ROLLOUT_SAT (0 | 1).
+// stage_tab_arg, rc, cc, rp; SX_ROLLOUT_PS (0 | 1); SX_ROLLOUT_SAT (0 | 1); SX_ROLLOUT_CONS (0 | 1).
 // SX_ROLLOUT_PS = 1 (sx_cem_rollout_starts; SH = 0, MM = false): the CEM row of a particle is [x0 (NS) | actions (H NU)],
 // L = NS + H NU entries.  rp.mean / rp.std are [E x L], rp.noise [E x P x L] | NULL, rp.actions the rows [E x P x L]
 // (written when noise is given, read otherwise); rp.x0, rp.q0 and the elite-row fields are unused.  The owner lane of a
@@ -11,6 +11,11 @@
 // SX_ROLLOUT_SAT = 1 (cem_rollout_sat_kernel; SH = 0, SX_ROLLOUT_PS = 0): the objective of a step is the saturating cost of
 // sx_sat_cost.hpp on the safety ellipsoid (p_{t+1}, Q_{t+1}), read as a mean and a covariance, from `sat` (SatConst<NS>, a
 // kernel argument of its own: scalar loads, no LDS); cc.obj_mode is not read.  Nothing else in the step changes.
+// SX_ROLLOUT_CONS = 1 (cem_rollout_cons_kernel; SH = 0, SX_ROLLOUT_PS = 0): the constraint set of sx_conset.hpp, from `cons`
+// (ConConst<NS>, a kernel argument of its own as `sat` is).  A step that starts from an ellipsoid pays its action cost
+// where the control ellipsoid (u_t, K Q_t K^T) is not certified inside the action box either (once per step, with the box
+// test), and every step but the last pays SX_STATE_VIOLATION_COST where (p_{t+1}, Q_{t+1}) is not certified inside the
+// obstacle rows.  The objective is SX_ROLLOUT_SAT's, either one; with an empty set the step is the parent's.
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
@@ -202,6 +207,11 @@
             z[UC + cidx] = u[cidx];
         }
         int st_step = 0;
+#if SX_ROLLOUT_CONS
+        // the feedback bounds, from the ellipsoid the step starts from (before p, Q are overwritten below)
+        bool eviol = false;
+        if (cons.ctrl_ellipsoid && have_q) eviol = ctrl_ellipsoid_violated<NS, NU>(rc.kfb, cc.u_min, cc.u_max, u, Q);
+#endif
         if (have_q) {
             gp_collect<NS, D, true>(gc, lds, nw, tid, z, mean, var, jac);
             if constexpr (SH == 0) {
@@ -258,11 +268,20 @@
         bool uviol = false;
 #pragma unroll
         for (int cidx = 0; cidx < NU; ++cidx) uviol = uviol || (u[cidx] < cc.u_min[cidx]) || (u[cidx] > cc.u_max[cidx]);
+#if SX_ROLLOUT_CONS
+        if (uviol || eviol) con += SX_ACTION_VIOLATION_COST;
+#else
         if (uviol) con += SX_ACTION_VIOLATION_COST;
+#endif
         if (cc.con_mode == SX_CON_ALL_STATES || t == H - 1) {
             if (polytope_violated<SX_MAX_M, NS>(cc.h_mat, cc.h_vec, cc.m, 1.0, p1, Q1, nullptr))
                 con += SX_STATE_VIOLATION_COST;
         }
+#if SX_ROLLOUT_CONS
+        // the obstacle rows, on every safety ellipsoid but the terminal one
+        if (t + 1 < H && polytope_violated<SX_MAX_M, NS>(cons.h_mat_obs, cons.h_obs, cons.m_obs, 1.0, p1, Q1, nullptr))
+            con += SX_STATE_VIOLATION_COST;
+#endif
         const int64_t g = (int64_t)e * rp.P + c0 + tid;
         if (valid && rp.traj) {
             double* tr = rp.traj + (g * H + t) * S;

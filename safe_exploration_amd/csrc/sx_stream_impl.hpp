@@ -1,6 +1,6 @@
 // Body of launch_stream<V, NS, NU> (sx_stream_launch.hpp), the one launcher of the streaming rollout kernels; included by
-// sx_stream_ns*.hip, sx_stream_multi.hip, sx_stream_starts.hip, sx_stream_sat.hip and sx_stream_sat_multi.hip, which
-// instantiate it for their variant V and so compile that variant's kernels.
+// sx_stream_ns*.hip, sx_stream_multi.hip, sx_stream_starts.hip, sx_stream_sat.hip, sx_stream_sat_multi.hip,
+// sx_stream_cons.hip and sx_stream_cons_sat.hip, which instantiate it for their variant V and so compile that variant's kernels.
 #pragma once
 #include <climits>
 #include <type_traits>
@@ -12,7 +12,8 @@ namespace sx {
 
 template <class V, int NS, int NU>
 int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
-                  const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream) {
+                  const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream,
+                  const ConConst<NS>* cons) {
     static_assert(V::SH >= 0 && V::SH <= NU && NS + NU + V::SH <= SX_MAX_D, "query shift outside the junk-dimension shapes");
 #ifdef SX_STAMPS
     if constexpr (std::is_same<V, StreamPlain<V::SH>>::value) {
@@ -29,7 +30,13 @@ int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc
     // (the table's entries carry a stage table each)
     const int4* stage_tab = nullptr;
     if constexpr (!V::MM) stage_tab = gp.stage_tab;
-    if constexpr (V::SAT)
+    if constexpr (V::CONS && V::SAT)
+        launch(SX_PROF_ROLLOUT_FUSED, kernel, dim3((unsigned)grid), dim3(kRolloutThreads), lds, stream, gp, stage_tab, rc, cc,
+               rp, *cons, *sat);
+    else if constexpr (V::CONS)
+        launch(SX_PROF_ROLLOUT_FUSED, kernel, dim3((unsigned)grid), dim3(kRolloutThreads), lds, stream, gp, stage_tab, rc, cc,
+               rp, *cons);
+    else if constexpr (V::SAT)
         launch(SX_PROF_ROLLOUT_FUSED, kernel, dim3((unsigned)grid), dim3(kRolloutThreads), lds, stream, gp, stage_tab, rc, cc,
                rp, *sat);
     else
@@ -40,8 +47,10 @@ int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc
 
 }  // namespace sx
 
-// launch_stream of variant V (the trailing argument: StreamPlain<SH>, StreamPlain<0, true>, StreamStarts, StreamSat<MM>)
+// launch_stream of variant V (the trailing argument: StreamPlain<SH>, StreamPlain<0, true>, StreamStarts, StreamSat<MM>,
+// StreamCons<SAT>)
 #define SX_STREAM_INSTANTIATE(NS, NU, ...)                                                                            \
     template int sx::launch_stream<sx::__VA_ARGS__, NS, NU>(                                                          \
         const sx::StreamGpArg<sx::__VA_ARGS__, NS, NU>&, const sx::ReachConst<NS, NU>&,                               \
-        const sx::CostConst<SX_MAX_M, NS, NU>&, const sx::RolloutPtrs&, const sx::SatConst<NS>*, bool, size_t, hipStream_t);
+        const sx::CostConst<SX_MAX_M, NS, NU>&, const sx::RolloutPtrs&, const sx::SatConst<NS>*, bool, size_t, hipStream_t, \
+        const sx::ConConst<NS>*);

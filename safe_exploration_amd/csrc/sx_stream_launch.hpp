@@ -3,7 +3,8 @@
 // rollout kernels (launch_stream<V, NS, NU> over a variant V that names the kernel).  The launcher's instantiations are
 // compiled in translation units of their own, beside the kernels (sx_stream_ns12.hip, sx_stream_ns34.hip; the multi-model
 // mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
-// sx_stream_sat.hip and sx_stream_sat_multi.hip; built in parallel with the rest); sx_gp_rollout.hip sees the declaration.
+// sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip; built
+// in parallel with the rest); sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -98,11 +99,11 @@ inline StreamPlan plan_stream_multi(const sx_gp_model* models, int E, int steps,
 
 // The variants of the streaming kernel: which kernel a launch names (kernel<NS, NU, BYOUT>()), its query shift SH, whether
 // its first argument is the device table of the problems' GpConst (MM; sx_gp_model_table), and whether it takes the
-// saturating cost's constants as a trailing argument (SAT).
+// saturating cost's constants as a trailing argument (SAT), behind the constraint set's where it takes those (CONS).
 template <int SH_, bool MM_ = false>
 struct StreamPlain {   // cem_rollout_kernel: sx_cem_rollout[_elites][_junk] (MM: sx_cem_rollout[_elites]_multi)
     static constexpr int SH = SH_;
-    static constexpr bool MM = MM_, SAT = false;
+    static constexpr bool MM = MM_, SAT = false, CONS = false;
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
         return cem_rollout_kernel<NS, NU, BYOUT, SH_, MM_>;
@@ -110,7 +111,7 @@ struct StreamPlain {   // cem_rollout_kernel: sx_cem_rollout[_elites][_junk] (MM
 };
 struct StreamStarts {   // cem_rollout_starts_kernel: sx_cem_rollout_starts, rp as the SX_ROLLOUT_PS sections read it
     static constexpr int SH = 0;
-    static constexpr bool MM = false, SAT = false;
+    static constexpr bool MM = false, SAT = false, CONS = false;
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
         return cem_rollout_starts_kernel<NS, NU, BYOUT>;
@@ -119,10 +120,19 @@ struct StreamStarts {   // cem_rollout_starts_kernel: sx_cem_rollout_starts, rp 
 template <bool MM_>
 struct StreamSat {   // cem_rollout_sat_kernel: sx_cem_rollout[_elites]_sat (MM: ..._sat_multi)
     static constexpr int SH = 0;
-    static constexpr bool MM = MM_, SAT = true;
+    static constexpr bool MM = MM_, SAT = true, CONS = false;
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
         return cem_rollout_sat_kernel<NS, NU, BYOUT, MM_>;
+    }
+};
+template <bool SAT_>
+struct StreamCons {   // cem_rollout_cons_kernel: sx_cem_rollout[_elites]_cons, without (SAT_ = false) and with a cost
+    static constexpr int SH = 0;
+    static constexpr bool MM = false, SAT = SAT_, CONS = true;
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_rollout_cons_kernel<NS, NU, BYOUT, SAT_>;
     }
 };
 
@@ -132,9 +142,10 @@ using StreamGpArg = typename RolloutGpArg<NS, NS + NU + V::SH, V::MM>::type;
 
 // Launches V::kernel<NS, NU, byout>() on `stream` over rp.E * ceil(rp.P / SX_TILE) workgroups with `lds` bytes of dynamic
 // LDS (plan_stream's; with V::MM plan_stream_multi's, and rp.status holds a word per problem).  `sat` is read with V::SAT
-// only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
+// only and `cons` with V::CONS only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
 template <class V, int NS, int NU>
 int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
-                  const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream);
+                  const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream,
+                  const ConConst<NS>* cons = nullptr);
 
 }  // namespace sx

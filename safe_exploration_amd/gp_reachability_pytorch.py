@@ -55,6 +55,30 @@ def make_env(n_s: int, n_u: int, *, a=None, b=None, k_fb=None, l_mu=None, l_sigm
     return env
 
 
+def make_con_set(n_s: int, *, h_mat_obs=None, h_obs=None, ctrl_ellipsoid: bool = False) -> _lib.SxConSet:
+    """Host-side sx_con_set (the SafeMPC constraint set of the _cons rollouts) from
+    numpy-convertible constants: the obstacle polytope h_mat_obs x <= h_obs ([m_obs x n_s], [m_obs]; None: no rows) and
+    whether the feedback bounds on the control ellipsoid apply."""
+    if not 1 <= n_s <= _lib.SX_MAX_NS:
+        raise ValueError(f'state dimension {n_s} beyond the compiled limits')
+    if (h_mat_obs is None) != (h_obs is None):
+        raise ValueError('the obstacle polytope needs both h_mat_obs and h_obs')
+    cons = _lib.SxConSet()
+    cons.ctrl_ellipsoid = 1 if ctrl_ellipsoid else 0
+    if h_mat_obs is not None:
+        h_mat_obs = np.asarray(h_mat_obs, dtype=np.float64).reshape(-1, n_s)
+        m = h_mat_obs.shape[0]
+        if m > _lib.SX_MAX_M:
+            raise ValueError(f'{m} obstacle rows exceed SX_MAX_M={_lib.SX_MAX_M}')
+        h_obs = np.asarray(h_obs, dtype=np.float64).reshape(m)
+        if not (np.isfinite(h_mat_obs).all() and np.isfinite(h_obs).all()):
+            raise ValueError('the obstacle polytope must be finite')
+        cons.m_obs = m
+        _lib.fill(cons.h_mat_obs, h_mat_obs)
+        _lib.fill(cons.h_obs, h_obs)
+    return cons
+
+
 def _host(x) -> Optional[np.ndarray]:
     return None if x is None else x.detach().cpu().numpy()
 

@@ -304,9 +304,10 @@ class StubEnv:
         return {'stub_env_steps': self.steps}
 
 
-def make_solver(spec: ProblemSpec, conf, env=None, device='cuda:0'):
+def make_solver(spec: ProblemSpec, conf, env=None, device='cuda:0', opt_env=None):
     """A ``CemSafeMPC`` over the spec's GP and constants, the way ``utils_config.create_solver``'s ``safempc_cem`` branch
-    builds it (reference utils_config.py:116-121): (solver, env)."""
+    builds it (reference utils_config.py:116-121): (solver, env).  `opt_env`: further entries of the solver's opt_env
+    (``h_mat_obs`` / ``h_obs``, the obstacle polytope) beside the linear model."""
     from .safempc_cem import CemSafeMPC, construct_constraints
     from .ssm_cem.gp_ssm_cem import GpCemSSM
     env = env if env is not None else StubEnv(spec, np.zeros(spec.n_s))
@@ -314,7 +315,7 @@ def make_solver(spec: ProblemSpec, conf, env=None, device='cuda:0'):
     ssm.set_hyperparameters(spec.lengthscale, spec.outputscale, spec.noise)
     q_lqr = np.diag([1.0, 2.0]) if spec.n_s == 2 else np.diag([2.0, 6.0, 12.0, 4.0])[:spec.n_s, :spec.n_s]
     r_lqr = (25.0 if spec.n_s == 2 else 40.0) * np.eye(spec.n_u)
-    solver = CemSafeMPC(ssm, construct_constraints(conf, env), env, conf, {'lin_model': (spec.a, spec.b)},
+    solver = CemSafeMPC(ssm, construct_constraints(conf, env), env, conf, dict(opt_env or {}, lin_model=(spec.a, spec.b)),
                         wx_feedback_cost=q_lqr, wu_feedback_cost=r_lqr, beta_safety=spec.beta,
                         safe_policy=lambda x: spec.k_fb @ x)
     # update_model subtracts the prior, so hand it y + prior to end up with the spec's targets

@@ -17,7 +17,7 @@ from torch import Tensor
 from . import _lib, gp_reachability_pytorch
 from .costs import SaturatingCost
 from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc, multi_family
-from .gp_reachability_pytorch import make_env, onestep_reachability
+from .gp_reachability_pytorch import make_con_set, make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
 from .ssm_cem.gp_ssm_cem import GpCemSSM
@@ -274,6 +274,27 @@ class CemSafeMPC(SafeMPC):
             raise NotImplementedError(f'cem_cost_on_safety needs an exact RBF GP (GpCemSSM), not kernel_family '
                                       f'{getattr(ssm, "kernel_family", None)!r}')
 
+        # cem_ctrl_ellipsoid_constraint / cem_obstacle_constraint: the reference SafeMPC's feedback bounds on the control
+        # ellipsoids (k_ff_t, K Q_t K^T) and its obstacle polytope (opt_env['h_mat_obs'] / ['h_obs']; None: no rows) on the
+        # intermediate safety ellipsoids, as penalties of the rollout kernel (FusedCemMpc(con_set=...), DESIGN.md section
+        # 3.15).  Both off by default: the solver then calls exactly what it called without them.
+        ctrl_ellipsoid = bool(getattr(conf, 'cem_ctrl_ellipsoid_constraint', False))
+        obstacle = bool(getattr(conf, 'cem_obstacle_constraint', False))
+        self._con_set = None
+        if ctrl_ellipsoid or obstacle:
+            setting = ' / '.join(name for name, on in (('cem_ctrl_ellipsoid_constraint', ctrl_ellipsoid),
+                                                       ('cem_obstacle_constraint', obstacle)) if on)
+            if self._cem_n_perf:
+                raise NotImplementedError(f'{setting} constrains the safety trajectory of a solve without a performance '
+                                          f'trajectory: got cem_n_perf={self._cem_n_perf}')
+            if mpc is None and getattr(ssm, 'kernel_family', None) != 'rbf':
+                raise NotImplementedError(f'{setting} needs an exact RBF GP (GpCemSSM), not kernel_family '
+                                          f'{getattr(ssm, "kernel_family", None)!r}')
+            h_mat_obs = opt_env.get('h_mat_obs') if obstacle else None
+            self._con_set = make_con_set(env.n_s, h_mat_obs=h_mat_obs, h_obs=None if h_mat_obs is None else opt_env['h_obs'],
+                                         ctrl_ellipsoid=ctrl_ellipsoid)
+            self._con_set_setting = setting
+
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
         self._linearized_model_a = torch.tensor(linearized_model_a, device=self._device)
@@ -393,7 +414,8 @@ class CemSafeMPC(SafeMPC):
                                     perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}),
                                     **({'perf_type': 'taylor', 'perf_terminal_safety': self._cem_perf_terminal_safety}
                                        if self._cem_perf_type == 'taylor' else {}),
-                                    **({'cost_on_safety': True} if getattr(self, '_cem_cost_on_safety', False) else {}))
+                                    **({'cost_on_safety': True} if getattr(self, '_cem_cost_on_safety', False) else {}),
+                                    **({} if getattr(self, '_con_set', None) is None else {'con_set': self._con_set}))
             if self._cost is not None:
                 self._mpc.set_cost(self._cost)
         self._mpc.set_env(env, objective_hook=self._env_objective_cost_func if needs_hook else None)
@@ -407,6 +429,8 @@ class CemSafeMPC(SafeMPC):
         read at solve time, so the solver stays valid across update_model."""
         if isinstance(self._ssm, JunkDimensionsSSM):
             raise NotImplementedError('static exploration is not built for JunkDimensionsSSM')
+        if getattr(self, '_con_set', None) is not None:
+            raise NotImplementedError(f'static exploration is not built for {self._con_set_setting}')
         env, _ = self._build_env()
         return StaticCemMpc(self._ssm, env, self._mpc_time_horizon, self._conf.cem_num_rollouts, self._conf.cem_num_elites,
                             self._conf.cem_num_iterations, start_mean=sample_mean, start_std=sample_std,
@@ -566,6 +590,10 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     states = np.asarray(states)
     if not solvers:
         raise ValueError('get_actions_multi needs at least one solver')
+    for s in solvers:
+        if getattr(s, '_con_set', None) is not None:
+            raise NotImplementedError(f'get_actions_multi is not built for {s._con_set_setting}: such solvers act one at a '
+                                      f'time (get_action)')
     # the performance trajectory (cem_n_perf > 0): all solvers or none, with one (cem_n_perf, cem_perf_r, cem_perf_variance)
     perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False),
              getattr(s, '_cem_perf_type', 'mean_equivalent'), getattr(s, '_cem_perf_terminal_safety', False))
