@@ -863,6 +863,28 @@ int sx_cem_rollout_elites_cons(const sx_gp_model* model, const sx_env* env, cons
 /* The form sx_cem_rollout_cons launches for this model and H: the contract of sx_cem_rollout_sat_form. */
 int sx_cem_rollout_cons_form(const sx_gp_model* model, int H);
 
+/* sx_cem_rollout_multi and sx_cem_rollout_elites_multi with the constraint set in the step: E problems with a GP each behind
+ * their device table (sx_gp_model_table) and ONE set shared by all of them, as they share env.  Arguments as the parent
+ * entry's with (cons, cost) behind env; status dev int32 [E].  cost == NULL: the objective of env->obj_mode, and the launch
+ * with the empty set is sx_cem_rollout[_elites]_multi bit for bit; otherwise the saturating cost, and the launch with the
+ * empty set is sx_cem_rollout[_elites]_sat_multi bit for bit.  Problem e of a launch is sx_cem_rollout[_elites]_cons of
+ * model e alone, bit for bit where that launch has the same form.
+ * SX_ERR_ARG (before any device access), checked in this order: whatever sx_cem_rollout[_elites]_multi answers it for (a NULL
+ * table, a missing elite_rows, models of differing shape or not of env's), then a NULL cons, m_obs outside 0 .. SX_MAX_M,
+ * ctrl_ellipsoid outside {0, 1}, a non-finite constant in the rows in use, then a cost sx_cem_rollout_sat refuses;
+ * SX_ERR_UNSUPPORTED exactly where sx_cem_rollout_sat_multi answers it. */
+int sx_cem_rollout_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_con_set* cons,
+                              const sx_sat_cost* cost, int E, int P, int H, const double* x0, const double* q0,
+                              const double* mean, const double* std, const double* noise, double* actions, double* traj,
+                              double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
+int sx_cem_rollout_elites_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_con_set* cons,
+                                     const sx_sat_cost* cost, int E, int P, int H, const double* x0, const double* q0,
+                                     const double* elite_rows, int k, const double* noise, double* actions, double* traj,
+                                     double* sigma, double* obj_cost, double* con_cost, int32_t* status, double* mean_out,
+                                     double* std_out, void* stream);
+/* The form sx_cem_rollout_cons_multi launches for these models and H: the contract of sx_cem_rollout_multi_form. */
+int sx_cem_rollout_cons_multi_form(const sx_gp_model* models, int E, int H);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

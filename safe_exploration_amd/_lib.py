@@ -173,6 +173,12 @@ SIGNATURES = {
     'sx_cem_rollout_elites_cons': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxConSet), POINTER(SxSatCost), c_int,
                                            c_int, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
     'sx_cem_rollout_cons_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_cem_rollout_cons_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxConSet),
+                                          POINTER(SxSatCost), c_int, c_int, c_int] + [c_void_p] * 12),
+    'sx_cem_rollout_elites_cons_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxConSet),
+                                                 POINTER(SxSatCost), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_int] + [c_void_p] * 10),
+    'sx_cem_rollout_cons_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

@@ -306,15 +306,20 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
                       actions: Optional[Tensor] = None, mean: Optional[Tensor] = None, std: Optional[Tensor] = None,
                       noise: Optional[Tensor] = None, q0: Optional[Tensor] = None, want_traj: bool = False,
                       want_sigma: bool = False, status: Optional[Tensor] = None, elite_rows: Optional[Tensor] = None,
-                      want_dist: bool = False, table: Optional[GpModelTable] = None, cost=None):
+                      want_dist: bool = False, table: Optional[GpModelTable] = None, cost=None, con_set=None):
     """`cem_rollout` for E problems with a model each (ssms[e] for problem e), one launch.  The models share one
     kernel_family: exact RBF GPs ('rbf': sx_cem_rollout_multi / sx_cem_rollout_elites_multi), feature-space GPs
     ('feature': sx_cem_rollout_feat_multi) or MC-dropout ensembles ('mlp': sx_cem_rollout_mlp_multi; neither of the last
     two has an elite-row form).  Buffers as in `cem_rollout`; `status` is int32 [E], one word per problem.  `table` keeps
     the device table of the models between calls (a fresh one is built otherwise, as where it belongs to another family).
     `cost` as in `cem_rollout` (sx_cem_rollout_sat_multi / sx_cem_rollout_elites_sat_multi; exact RBF GPs only).
+    `con_set` as in `cem_rollout`: ONE set for all problems, as they share `env` (sx_cem_rollout_cons_multi /
+    sx_cem_rollout_elites_cons_multi, together with `cost` where given; exact RBF GPs only).
     Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch): mixed
     families, JunkDimensionsSSM and step-by-step models, differing architectures, a shape without a kernel."""
+    if con_set is not None:
+        for ssm in ssms:
+            _require_rbf_con_set(ssm)
     if cost is not None:
         _require_rbf_cost(ssms)
     family = multi_family(ssms)
@@ -333,9 +338,14 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
         table = GpModelTable(family)
     models, tab = table.get(ssms, x0.device)
     head = (models, _lib.ptr(tab), ctypes.byref(env))
-    if cost is not None:
-        head += _cost_args(cost, ssms[0])
-    return _rollout(('_sat' if cost is not None else '') + MULTI_FAMILIES[family][3], head, x0, horizon,
+    if con_set is not None:
+        head += (_con_set_arg(con_set),) + (_cost_args(cost, ssms[0]) or (None,))
+        suffix = '_cons'
+    else:
+        if cost is not None:
+            head += _cost_args(cost, ssms[0])
+        suffix = '_sat' if cost is not None else ''
+    return _rollout(suffix + MULTI_FAMILIES[family][3], head, x0, horizon,
                     ssms[0].num_states, ssms[0].num_actions, E, FusedMultiUnsupported, actions=actions, mean=mean, std=std,
                     noise=noise, q0=q0, want_traj=want_traj, want_sigma=want_sigma, status=status, elite_rows=elite_rows,
                     want_dist=want_dist)
@@ -1400,10 +1410,12 @@ class MultiModelCemMpc:
     `env` and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
 
     Solvers built with ``cost_on_safety=True`` carry their ``SaturatingCost`` into the launch (``sx_cem_rollout_sat_multi`` /
-    ``sx_cem_rollout_elites_sat_multi``): equal costs on all solvers, or none on any of them.
+    ``sx_cem_rollout_elites_sat_multi``): equal costs on all solvers, or none on any of them.  Solvers with a constraint set
+    (``con_set``) are refused here: ``MultiModelConsCemMpc`` solves those.
     """
 
     _perf_solvers = False   # MultiModelPerfCemMpc: the solvers carry a performance trajectory
+    _cons_solvers = False   # MultiModelConsCemMpc: the solvers carry a constraint set
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
@@ -1427,6 +1439,9 @@ class MultiModelCemMpc:
         if not self._perf_solvers and any(getattr(s, '_n_perf', 0) > 0 for s in solvers):
             raise NotImplementedError('MultiModelCemMpc solves have no performance trajectory (solvers with n_perf > 0): '
                                       'MultiModelPerfCemMpc solves those')
+        if not self._cons_solvers and any(getattr(s, '_con_set', None) is not None for s in solvers):
+            raise NotImplementedError(f'{type(self).__name__} solves without a constraint set (solvers with con_set): '
+                                      f'MultiModelConsCemMpc solves those')
         self._solvers = list(solvers)
         self._env = env
         self._horizon = time_horizon
@@ -1453,6 +1468,10 @@ class MultiModelCemMpc:
         for s in self._solvers:
             s.set_cost(cost)
 
+    def _con_set_kw(self) -> dict:
+        """What the rollout call takes for the solvers' constraint set: nothing here (MultiModelConsCemMpc: the set)."""
+        return {}
+
     @classmethod
     def from_solvers(cls, solvers: Sequence[FusedCemMpc]) -> 'MultiModelCemMpc':
         """The multi-model solve over existing single-model solvers, solvers[e] for problem e, with their settings (which
@@ -1462,9 +1481,10 @@ class MultiModelCemMpc:
                    first._num_iterations, device=first._device, solvers=solvers)
 
     @staticmethod
-    def check_solvers(solvers: Sequence) -> None:
+    def check_solvers(solvers: Sequence, check_con_set: bool = True) -> None:
         """ValueError unless the solvers share the CEM settings and the environment constants (sx_env).  (Read with
-        defaults: an injected optimiser need not be a FusedCemMpc.)"""
+        defaults: an injected optimiser need not be a FusedCemMpc.)  NotImplementedError for solvers with a constraint
+        set (`check_con_set`; MultiModelConsCemMpc.check_solvers compares the sets itself)."""
         def settings(m):
             init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
             names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world',
@@ -1472,9 +1492,9 @@ class MultiModelCemMpc:
             return ((type(m),) + tuple(getattr(m, a, None) for a in names)
                     + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
 
-        if any(getattr(m, '_con_set', None) is not None for m in solvers):
-            raise NotImplementedError('a multi-model solve (MultiModelCemMpc) is not built for con_set: the _cons rollouts '
-                                      'take one model')
+        if check_con_set and any(getattr(m, '_con_set', None) is not None for m in solvers):
+            raise NotImplementedError('a multi-model solve (MultiModelCemMpc) is not built for con_set: '
+                                      'MultiModelConsCemMpc solves over solvers that all carry one set')
         (cem0, env0), *rest = [settings(m) for m in solvers]
         for cem, env in rest:
             if cem != cem0:
@@ -1529,7 +1549,7 @@ class MultiModelCemMpc:
         in_prologue = self._solvers[0]._refit_in_prologue(E)
         # the solvers' cost where it prices the safety trajectory (cost_on_safety): it rides in the rollout call
         cost = self._solver_cost() if getattr(self._solvers[0], '_cost_on_safety', False) else None
-        cost_kw = {} if cost is None else dict(cost=cost)
+        cost_kw = dict({} if cost is None else dict(cost=cost), **self._con_set_kw())
 
         def rollout(it, mean, std, rows):
             return cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
@@ -1562,6 +1582,71 @@ class MultiModelCemMpc:
         best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
                                            [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
         return best_host, found
+
+
+class MultiModelConsCemMpc(MultiModelCemMpc):
+    """``MultiModelCemMpc`` over solvers with a constraint set (``FusedCemMpc(con_set=...)``): E
+    exact RBF GPs whose solvers carry ONE set -- the scenarios share the environment, and so its obstacle rows and feedback
+    bounds.  An iteration is ``sx_cem_rollout_cons_multi`` / ``sx_cem_rollout_elites_cons_multi`` (with the solvers'
+    ``cost_on_safety`` cost where they have one) and the ranking launch, as in the parent.  The per-problem step-by-step
+    repeat of ``_check_solve`` and the one-solve-per-model fallback (a training set on the workspace path) are the
+    solvers' own, which carry the set already.
+    """
+    _cons_solvers = True
+
+    def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, con_set=None, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
+                 process_group=None, solvers: Optional[Sequence[FusedCemMpc]] = None):
+        if process_group is not None:
+            raise NotImplementedError('con_set is not built for sharded particles (a process group)')
+        if solvers is None:
+            if con_set is None:
+                raise ValueError('MultiModelConsCemMpc needs a constraint set (con_set); MultiModelCemMpc solves without one')
+            solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
+                                   seed=seed + e, init_std=init_std, warm_start=warm_start, con_set=con_set)
+                       for e, ssm in enumerate(ssms)]
+        solvers = list(solvers)
+        self._con_set = self._solver_con_set(solvers)
+        if con_set is not None and bytes(con_set) != bytes(self._con_set):
+            raise ValueError('the solvers carry another constraint set than the con_set given')
+        super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
+                         init_std=init_std, warm_start=warm_start, solvers=solvers)
+        for ssm in self._ssms:
+            _require_rbf_con_set(ssm)
+
+    @staticmethod
+    def _solver_con_set(solvers: Sequence):
+        """The one set of the solvers: byte-equal on all of them (as the environments are compared)."""
+        sets = [getattr(m, '_con_set', None) for m in solvers]
+        if any(c is None for c in sets):
+            raise NotImplementedError('MultiModelConsCemMpc takes solvers that all carry a constraint set (con_set): '
+                                      'the ones without act in a MultiModelCemMpc of their own'
+                                      if any(c is not None for c in sets) else
+                                      'MultiModelConsCemMpc needs solvers with a constraint set (con_set); '
+                                      'MultiModelCemMpc solves the others')
+        for c in sets:
+            _con_set_arg(c)
+        if any(bytes(c) != bytes(sets[0]) for c in sets[1:]):
+            raise ValueError('the solvers of a multi-model solve must share one constraint set (con_set: the obstacle '
+                             'rows and the feedback bounds of the environment they share)')
+        return sets[0]
+
+    @staticmethod
+    def check_solvers(solvers: Sequence) -> None:
+        """`MultiModelCemMpc.check_solvers` for solvers that all carry one constraint set: ValueError for differing sets,
+        NotImplementedError (naming con_set) where only some solvers carry one."""
+        MultiModelConsCemMpc._solver_con_set(solvers)
+        MultiModelCemMpc.check_solvers(solvers, check_con_set=False)
+
+    def _con_set_kw(self) -> dict:
+        return dict(con_set=self._solver_con_set(self._solvers))
+
+    def fused_applies(self) -> bool:
+        """Does one sx_cem_rollout_cons_multi launch serve the models (sx_cem_rollout_cons_multi_form)?  Host only."""
+        if multi_family(self._ssms) != 'rbf':
+            return False
+        models = model_array(self._ssms, 'rbf')
+        return int(_lib.lib().sx_cem_rollout_cons_multi_form(models, len(self._ssms), self._horizon)) >= 0
 
 
 class MultiModelPerfCemMpc(MultiModelCemMpc):

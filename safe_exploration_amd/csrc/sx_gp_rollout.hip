@@ -5,7 +5,7 @@
 // sx_cem_rollout_starts, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
 // sx_cem_rollout_workspace_bytes, and the entries with the saturating cost on the safety ellipsoids,
 // sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form, and those with the SafeMPC constraint set in the step,
-// sx_cem_rollout[_elites]_cons, sx_cem_rollout_cons_form.  No kernel is compiled here.
+// sx_cem_rollout[_elites]_cons[_multi], sx_cem_rollout_cons_form, sx_cem_rollout_cons_multi_form.  No kernel is compiled here.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -240,6 +240,17 @@ static int cem_rollout_cons(const sx_gp_model* model, const sx_env* env, const s
     return stream_dispatch<StreamCons<false>>(model, nullptr, env, nullptr, rp, stream, cons);
 }
 
+// sx_cem_rollout[_elites]_cons_multi: cem_rollout_multi's checks, the set's and the cost's after them, then the multi-model
+// streaming kernel with the ONE set of all problems in its step
+static int cem_rollout_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_con_set* cons,
+                                  const sx_sat_cost* cost, bool elites, const RolloutPtrs& rp, void* stream) {
+    if (!table || (elites && !rp.elite_rows) || !rollout_args_ok(env, rp) || !multi_models_ok(models, rp.E)) return SX_ERR_ARG;
+    if (models[0].n_s != env->n_s || models[0].n_u != env->n_u) return SX_ERR_ARG;
+    if (!con_set_ok(cons, env->n_s) || (cost && !sat_cost_ok(cost, env->n_s))) return SX_ERR_ARG;
+    if (cost) return stream_dispatch<StreamCons<true, true>>(models, table, env, cost, rp, stream, cons);
+    return stream_dispatch<StreamCons<false, true>>(models, table, env, nullptr, rp, stream, cons);
+}
+
 // The entries over rp.E models behind their device `table`, as cem_rollout_single: every one has the streaming kernel only
 static int cem_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, Objective obj, bool elites,
                              const RolloutPtrs& rp, void* stream) {
@@ -390,7 +401,7 @@ int sx_cem_rollout_elites_sat_multi(const sx_gp_model* models, const void* table
     return sx::cem_rollout_multi(models, table, env, {true, cost}, true, rp, stream);
 }
 
-// ---- the SafeMPC constraint set in the step: the single-model entries with a set handed in ---------
+// ---- the SafeMPC constraint set in the step: the entries with a set handed in ---------------------------
 int sx_cem_rollout_cons_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
 
 int sx_cem_rollout_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, const sx_sat_cost* cost, int E,
@@ -408,6 +419,29 @@ int sx_cem_rollout_elites_cons(const sx_gp_model* model, const sx_env* env, cons
     const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
                                                 status, E, P, H}, elite_rows, k, mean_out, std_out);
     return sx::cem_rollout_cons(model, env, cons, cost, true, rp, stream);
+}
+
+// the multi-model entries with the set handed in: one set for all problems, a GP each
+int sx_cem_rollout_cons_multi_form(const sx_gp_model* models, int E, int H) {
+    return sx::multi_models_ok(models, E) ? sx::stream_form(models, E, H) : -1;
+}
+
+int sx_cem_rollout_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_con_set* cons,
+                              const sx_sat_cost* cost, int E, int P, int H, const double* x0, const double* q0,
+                              const double* mean, const double* std, const double* noise, double* actions, double* traj,
+                              double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
+    const sx::RolloutPtrs rp{x0, q0, mean, std, noise, actions, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::cem_rollout_cons_multi(models, table, env, cons, cost, false, rp, stream);
+}
+
+int sx_cem_rollout_elites_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env, const sx_con_set* cons,
+                                     const sx_sat_cost* cost, int E, int P, int H, const double* x0, const double* q0,
+                                     const double* elite_rows, int k, const double* noise, double* actions, double* traj,
+                                     double* sigma, double* obj_cost, double* con_cost, int32_t* status, double* mean_out,
+                                     double* std_out, void* stream) {
+    const sx::RolloutPtrs rp = sx::with_elites({x0, q0, nullptr, nullptr, noise, actions, traj, sigma, obj_cost, con_cost,
+                                                status, E, P, H}, elite_rows, k, mean_out, std_out);
+    return sx::cem_rollout_cons_multi(models, table, env, cons, cost, true, rp, stream);
 }
 
 }  // extern "C"

@@ -142,22 +142,23 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_sat_kernel(
 #undef SX_ROLLOUT_PS
 }
 
-// sx_cem_rollout[_elites]_cons: cem_rollout_kernel (SH = 0, one GP) with the constraint set of sx_conset.hpp in finish()
-// (the SX_ROLLOUT_CONS sections of sx_rollout_body.inc) and, with SAT, the saturating cost on the
-// safety ellipsoids as the objective, as cem_rollout_sat_kernel has it.  The set's constants are one more kernel argument,
-// uniform and read by scalar loads on the owner lanes: the LDS plan is the parent's byte for byte.  The two objectives are
-// two templates of one name (the body is text, and its objective a preprocessor choice); SAT picks between them.
-template <int NS, int NU>
+// sx_cem_rollout[_elites]_cons[_multi]: cem_rollout_kernel (SH = 0; MM: a GP per problem) with the constraint set of
+// sx_conset.hpp in finish() (the SX_ROLLOUT_CONS sections of sx_rollout_body.inc) and, with SAT, the
+// saturating cost on the safety ellipsoids as the objective, as cem_rollout_sat_kernel has it.  The set's constants are one
+// more kernel argument, uniform and read by scalar loads on the owner lanes: the LDS plan is the parent's byte for byte.
+// The two objectives are two templates of one name (the body is text, and its objective a preprocessor choice); SAT picks
+// between them.  With MM the set stays ONE argument shared by all problems (the scenarios share sx_env, and so the set);
+// only the GP is per problem.
+template <int NS, int NU, bool MM>
 constexpr size_t rollout_cons_arg_bytes() {
-    return rollout_sat_arg_bytes<NS, NU, false>() + (sizeof(ConConst<NS>) + 7) / 8 * 8;
+    return rollout_sat_arg_bytes<NS, NU, MM>() + (sizeof(ConConst<NS>) + 7) / 8 * 8;
 }
 
-template <int NS, int NU, bool BYOUT, bool SAT, std::enable_if_t<!SAT, int> = 0>
+template <int NS, int NU, bool BYOUT, bool SAT, bool MM, std::enable_if_t<!SAT, int> = 0>
 __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
-    GpConst<NS, NS + NU> gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    typename RolloutGpArg<NS, NS + NU, MM>::type gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
     CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const ConConst<NS> cons) {
     constexpr int SH = 0;
-    constexpr bool MM = false;
 #define SX_ROLLOUT_PS 0
 #define SX_ROLLOUT_SAT 0
 #define SX_ROLLOUT_CONS 1
@@ -167,13 +168,12 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
 #undef SX_ROLLOUT_PS
 }
 
-template <int NS, int NU, bool BYOUT, bool SAT, std::enable_if_t<SAT, int> = 0>
+template <int NS, int NU, bool BYOUT, bool SAT, bool MM, std::enable_if_t<SAT, int> = 0>
 __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
-    GpConst<NS, NS + NU> gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    typename RolloutGpArg<NS, NS + NU, MM>::type gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
     CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const ConConst<NS> cons, const SatConst<NS> sat) {
-    static_assert(rollout_cons_arg_bytes<NS, NU>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
+    static_assert(rollout_cons_arg_bytes<NS, NU, MM>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
     constexpr int SH = 0;
-    constexpr bool MM = false;
 #define SX_ROLLOUT_PS 0
 #define SX_ROLLOUT_SAT 1
 #define SX_ROLLOUT_CONS 1

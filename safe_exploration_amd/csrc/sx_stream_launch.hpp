@@ -3,8 +3,9 @@
 // rollout kernels (launch_stream<V, NS, NU> over a variant V that names the kernel).  The launcher's instantiations are
 // compiled in translation units of their own, beside the kernels (sx_stream_ns12.hip, sx_stream_ns34.hip; the multi-model
 // mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
-// sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip; built
-// in parallel with the rest); sx_gp_rollout.hip sees the declaration.
+// sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip, in the
+// multi-model mode in sx_stream_cons_multi.hip and sx_stream_cons_sat_multi.hip; built in parallel with the rest);
+// sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -126,13 +127,13 @@ struct StreamSat {   // cem_rollout_sat_kernel: sx_cem_rollout[_elites]_sat (MM:
         return cem_rollout_sat_kernel<NS, NU, BYOUT, MM_>;
     }
 };
-template <bool SAT_>
-struct StreamCons {   // cem_rollout_cons_kernel: sx_cem_rollout[_elites]_cons, without (SAT_ = false) and with a cost
+template <bool SAT_, bool MM_ = false>
+struct StreamCons {   // cem_rollout_cons_kernel: sx_cem_rollout[_elites]_cons (MM: ..._cons_multi), SAT_: with a cost
     static constexpr int SH = 0;
-    static constexpr bool MM = false, SAT = SAT_, CONS = true;
+    static constexpr bool MM = MM_, SAT = SAT_, CONS = true;
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_rollout_cons_kernel<NS, NU, BYOUT, SAT_>;
+        return cem_rollout_cons_kernel<NS, NU, BYOUT, SAT_, MM_>;
     }
 };
 

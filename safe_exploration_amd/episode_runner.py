@@ -50,7 +50,9 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
     `solver`: a ``CemSafeMPC`` (``get_action_batch``) or None (random actions, exit code 5), or a list of ``CemSafeMPC``,
     one per episode: independent scenarios, each with its own model (the reference's n_scenarios solvers,
     episode_runner.py:40-123), served by ``get_actions_multi`` -- one solve per step for the episodes still running, each
-    solver with its own ladder, episode e exactly as ``do_rollout`` with solver e.  An episode whose environment reports
+    solver with its own ladder, episode e exactly as ``do_rollout`` with solver e.  Solvers that all carry one constraint set
+    (``cem_ctrl_ellipsoid_constraint`` / ``cem_obstacle_constraint``) are served the same way, unchanged here: the
+    multi-model launch carries the set (``MultiModelConsCemMpc``).  An episode whose environment reports
     `done` stops (safety failure, reference :311-313); the others carry on.
     """
     E = len(envs)

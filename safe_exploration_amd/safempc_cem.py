@@ -16,7 +16,8 @@ from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
 from .costs import SaturatingCost
-from .cem_mpc import FusedCemMpc, MultiModelCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc, multi_family
+from .cem_mpc import (FusedCemMpc, MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc,
+                      multi_family)
 from .gp_reachability_pytorch import make_con_set, make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
@@ -581,7 +582,9 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     them (``MultiModelCemMpc``: one rollout launch per CEM iteration, each problem with its own model; solvers that all
     have a performance trajectory with one ``cem_n_perf``, ``cem_perf_r``, ``cem_perf_variance``, ``cem_perf_type`` and
     ``cem_perf_terminal_safety`` go through ``MultiModelPerfCemMpc``, which adds one performance-rollout launch per
-    iteration for all of them, ``cem_perf_type='taylor'`` included); otherwise (mixed families, JunkDimensionsSSM, ...),
+    iteration for all of them, ``cem_perf_type='taylor'`` included; solvers that all have
+    ``cem_ctrl_ellipsoid_constraint`` / ``cem_obstacle_constraint`` on, with one constraint set, go through
+    ``MultiModelConsCemMpc``, whose launch carries the set); otherwise (mixed families, JunkDimensionsSSM, ...),
     and where the single launch does not apply, one solve per solver.  Either way
     problem e draws solver e's noise, and each solver keeps its own PREVIOUS_SOLUTION / SAFE_CONTROLLER ladder, the one
     ``get_action_batch`` keeps for a single episode.  The solvers must agree on the environment constants (sx_env) and
@@ -590,10 +593,12 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     states = np.asarray(states)
     if not solvers:
         raise ValueError('get_actions_multi needs at least one solver')
-    for s in solvers:
-        if getattr(s, '_con_set', None) is not None:
-            raise NotImplementedError(f'get_actions_multi is not built for {s._con_set_setting}: such solvers act one at a '
-                                      f'time (get_action)')
+    # the constraint set (cem_ctrl_ellipsoid_constraint / cem_obstacle_constraint): all solvers or none, with one set
+    with_set = [s for s in solvers if getattr(s, '_con_set', None) is not None]
+    if with_set and len(with_set) != len(solvers):
+        raise NotImplementedError(f'get_actions_multi takes solvers that all have a constraint set or all have none: '
+                                  f'{len(with_set)} of {len(solvers)} have {with_set[0]._con_set_setting}; those act one at '
+                                  f'a time (get_action), or together in a call of their own')
     # the performance trajectory (cem_n_perf > 0): all solvers or none, with one (cem_n_perf, cem_perf_r, cem_perf_variance)
     perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False),
              getattr(s, '_cem_perf_type', 'mean_equivalent'), getattr(s, '_cem_perf_terminal_safety', False))
@@ -616,13 +621,14 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
             s._batch_last_actions = [np.empty((0, n_u))]
             s._batch_executed = [0]
     mpcs = [s._solver() for s in solvers]
-    MultiModelCemMpc.check_solvers(mpcs)
+    (MultiModelConsCemMpc if with_set else MultiModelCemMpc).check_solvers(mpcs)
     flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
     if multi_solve_applies(mpcs):
         key = tuple(id(m) for m in mpcs)
         cached = getattr(solvers[0], '_multi', None)
-        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
-            cls = MultiModelPerfCemMpc if with_perf else MultiModelCemMpc
+        cls = MultiModelPerfCemMpc if with_perf else MultiModelConsCemMpc if with_set else MultiModelCemMpc
+        if (cached is None or cached[0] != key or type(cached[1]) is not cls
+                or any(a is not b for a, b in zip(cached[1].solvers, mpcs))):
             solvers[0]._multi = cached = (key, cls.from_solvers(mpcs))
         multi = cached[1]
         multi._env = mpcs[0]._env

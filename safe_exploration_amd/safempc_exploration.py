@@ -111,7 +111,8 @@ def find_max_variance_multi(explorations: Sequence[DynamicSafeMPCExploration], x
     """``find_max_variance`` of E independent explorations -- the reference's scenarios, each with its own model -- at
     once: exploration e starts from x_0[e] ([E x n_s]).  One ``safempc_cem.get_actions_multi`` over their solvers (with
     ``cem_n_perf`` / ``cem_perf_variance`` the multi-model solve looks n_perf steps ahead for every scenario in the same
-    launches).  Returns (x_0 [E x n_s], u_apply [E x n_u], one MpcResult per exploration): row e is what
+    launches; explorations whose solvers all carry one constraint set -- ``cem_ctrl_ellipsoid_constraint`` /
+    ``cem_obstacle_constraint`` -- go through the multi-model launch with the set, unchanged here).  Returns (x_0 [E x n_s], u_apply [E x n_u], one MpcResult per exploration): row e is what
     ``explorations[e].find_max_variance(x_0[e])`` returns."""
     from .safempc_cem import get_actions_multi
     x_0 = np.atleast_2d(x_0)

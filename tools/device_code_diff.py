@@ -9,8 +9,11 @@ the instruction text, the .amdhsa_kernel descriptor block and the kernel's entry
 numbers, comments and section directives are ignored (they count functions per translation unit), so a kernel may move
 from one translation unit to another and still compare equal.  Prints the kernels only one side has, the kernels a side
 compiles more than once (two translation units would each register a copy: the LDS grants and device symbols are keyed on
-one), and the kernels that differ, with the first differing line; exits 1 if there is any of them.  DESIGN.md section 3.5
-describes the method.  SX_EXTRA_FLAGS is passed on as csrc/build.sh does.
+one), and the kernels that differ, with the first differing line; exits 1 if there is any of them.  A kernel whose
+symbol only one side has is then looked for on the other side by content (its own symbol replaced by a placeholder in
+all three parts): a template that gained a parameter renames every instantiation, and such a kernel is reported as
+`renamed` and counts as identical, not as a finding.  DESIGN.md section 3.5 describes the method.  SX_EXTRA_FLAGS is
+passed on as csrc/build.sh does.
 """
 import argparse
 import concurrent.futures
@@ -95,6 +98,24 @@ def first_difference(a, b):
     return f'{len(a)} lines | {len(b)} lines'
 
 
+def _anonymous(name, parts):
+    """The three parts of a kernel with its own symbol replaced by a placeholder, hashable."""
+    return tuple(tuple(line.replace(name, '<kernel>') for line in part) for part in parts)
+
+
+def renamed(old, new):
+    """{old symbol: new symbol} of the kernels whose symbol only one side has and whose parts are equal but for the symbol."""
+    by_content = {}
+    for name in sorted(set(new) - set(old)):
+        by_content.setdefault(_anonymous(name, new[name][0][1]), []).append(name)
+    pairs = {}
+    for name in sorted(set(old) - set(new)):
+        twins = by_content.get(_anonymous(name, old[name][0][1]))
+        if twins:
+            pairs[name] = twins.pop(0)
+    return pairs
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('old_csrc')
@@ -103,8 +124,12 @@ def main():
     args = ap.parse_args()
     old, new = compile_dir(args.old_csrc, args.jobs), compile_dir(args.new_csrc, args.jobs)
     bad = 0
+    pairs = renamed(old, new)
+    for a, b in sorted(pairs.items()):
+        print(f'renamed: {a} ({old[a][0][0]}) -> {b} ({new[b][0][0]})')
+    moved = set(pairs) | set(pairs.values())
     for side, here, there in (('old', old, new), ('new', new, old)):
-        for name in sorted(set(here) - set(there)):
+        for name in sorted(set(here) - set(there) - moved):
             print(f'only in {side}: {name} ({here[name][0][0]})')
             bad += 1
         for name in sorted(here):
@@ -123,7 +148,8 @@ def main():
             bad += 1
         else:
             same += 1
-    print(f'{len(old)} kernels in old, {len(new)} in new, {same} identical, {bad} findings')
+    print(f'{len(old)} kernels in old, {len(new)} in new, {same} identical, {len(pairs)} renamed and identical, '
+          f'{bad} findings')
     return 1 if bad else 0
 
 
