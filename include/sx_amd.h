@@ -885,6 +885,25 @@ int sx_cem_rollout_elites_cons_multi(const sx_gp_model* models, const void* tabl
 /* The form sx_cem_rollout_cons_multi launches for these models and H: the contract of sx_cem_rollout_multi_form. */
 int sx_cem_rollout_cons_multi_form(const sx_gp_model* models, int E, int H);
 
+/* sx_cem_rollout_starts with the constraint set in the step (static exploration with the reference's constraints:
+ * StaticSafeMPCExploration optimises [p_0, u_0, k_ff] with the gain a fixed parameter, so the set is its NLP's constraints
+ * term for term).  Arguments as sx_cem_rollout_starts' with cons behind env.  A particle starts from a point, so step 0 pays
+ * the box test alone, steps t >= 1 the feedback bounds, every (p_{t+1}, Q_{t+1}) with t + 1 < H the obstacle rows; and the
+ * start x0 itself (a point, Q = 0) costs SX_STATE_VIOLATION_COST once where it violates the obstacle rows (some
+ * h_j . x0 - h_obs_j >= 0; a NaN distance is not a violation), independent of the safe-polytope cost of the start: a start
+ * outside both pays twice.  The reference bounds p_1 .. p_{H-1} only; the start test is this library's own (DESIGN.md section
+ * 7).  rows, traj, sigma, obj_cost and status are those of the same launch with the empty set, bit for bit; with the empty
+ * set (m_obs = 0, ctrl_ellipsoid = 0) every output is sx_cem_rollout_starts'.  The objective is env->obj_mode's.
+ * The plan is sx_cem_rollout_starts': sx_cem_rollout_starts_form answers for both entries (the set's constants travel as a
+ * kernel argument, the LDS plan is the parent's).
+ * SX_ERR_ARG (before any device access) for whatever sx_cem_rollout_starts answers it for, then a NULL cons, m_obs outside
+ * 0 .. SX_MAX_M, ctrl_ellipsoid outside {0, 1}, a non-finite constant in the rows in use; SX_ERR_UNSUPPORTED (before any
+ * launch) exactly where sx_cem_rollout_starts answers it.
+ * Replaces: the constraint groups of StaticSafeMPCExploration's NLP (safempc_exploration.py:100-233). */
+int sx_cem_rollout_starts_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, int E, int P, int H,
+                               const double* mean, const double* std, const double* noise, double* rows, double* traj,
+                               double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

@@ -192,15 +192,22 @@ def _require_rbf_starts(ssm) -> None:
 
 def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Optional[Tensor] = None,
                        std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
-                       want_traj: bool = False, want_sigma: bool = False, status: Optional[Tensor] = None):
+                       want_traj: bool = False, want_sigma: bool = False, status: Optional[Tensor] = None, con_set=None):
     """Thin wrapper over sx_cem_rollout_starts: the rollout whose particles each start from the first n_s entries of their
     own CEM row [x0 | actions], L = n_s + H n_u (static exploration).
 
     Either (`mean`, `std` [E x L], `noise` [E x P x L]): the rows are drawn, or `rows` [E x P x L] (given).
     Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj | None, sigma | None, status int32[1]); a start outside the
     safe polytope has added SX_STATE_VIOLATION_COST to its particle's con_cost.
+    `con_set` (an `_lib.SxConSet`, `make_con_set`) selects sx_cem_rollout_starts_cons: the feedback bounds from step 1 on,
+    the obstacle rows on every intermediate ellipsoid, and SX_STATE_VIOLATION_COST once more for a start that violates the
+    obstacle rows; everything but con_cost is the launch's without the set.
     """
     _require_rbf_starts(ssm)
+    entry, head = 'sx_cem_rollout_starts', (ctypes.byref(ssm.device_model), ctypes.byref(env))
+    if con_set is not None:
+        _require_rbf_con_set(ssm)
+        entry, head = 'sx_cem_rollout_starts_cons', head + (_con_set_arg(con_set),)
     n_s, n_u = ssm.num_states, ssm.num_actions
     L = n_s + horizon * n_u
     given = rows if noise is None else noise
@@ -220,12 +227,11 @@ def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Op
     con = torch.empty((E, P), dtype=torch.float64, device=dev)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    code = _lib.lib().sx_cem_rollout_starts(ctypes.byref(ssm.device_model), ctypes.byref(env), E, P, horizon,
-                                            _lib.ptr(mean if noise is not None else None),
-                                            _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
-                                            _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                            _lib.stream_ptr(dev))
-    _lib.check(code, 'sx_cem_rollout_starts')
+    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, _lib.ptr(mean if noise is not None else None),
+                                      _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
+                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                      _lib.stream_ptr(dev))
+    _lib.check(code, entry)
     return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
 
 
@@ -728,6 +734,18 @@ def start_constraint_cost(env: _lib.SxEnv, x0: Tensor) -> Tensor:
     _lib.check(_lib.lib().sx_polytope_distance(ctypes.byref(env), P, _lib.ptr(x0.contiguous()), _lib.ptr(q), 1.0, _lib.ptr(d),
                                                _lib.ptr(inside), _lib.stream_ptr(dev)), 'sx_polytope_distance')
     return _lib.SX_STATE_VIOLATION_COST * (inside == 0)
+
+
+def start_obstacle_cost(env: _lib.SxEnv, con_set, x0: Tensor) -> Tensor:
+    """[P]: SX_STATE_VIOLATION_COST for every start x0 [P x n_s] that violates the obstacle rows of `con_set` (some
+    h_obs-row distance of the point >= 0), what sx_cem_rollout_starts_cons adds in its kernel beside `start_constraint_cost`:
+    sx_conset_eval's obstacle part on the points (an all-zero Q) with no feedback bounds and an action inside the box."""
+    P, n_s = x0.shape
+    n_u, dev = env.n_u, x0.device
+    # (the box's lower bound is inside the strict box test, so the action part of the cost is zero)
+    u = torch.tensor(list(env.u_min)[:n_u], dtype=torch.float64, device=dev).expand(P, n_u).contiguous()
+    q = torch.zeros((P, n_s, n_s), dtype=torch.float64, device=dev)
+    return conset_eval(env, con_set, u, None, x0, q, check_obstacle=True)
 
 
 def cem_rank_refit(con: Tensor, obj: Tensor, actions: Tensor, k: int, *, cost_stride: int = 1,
@@ -1785,11 +1803,23 @@ class StaticCemMpc:
     environment's own plus SX_STATE_VIOLATION_COST for a start outside the safe polytope.  ``n_restarts`` problems with the
     same start distribution and their own draws (seed + e) run in the same launches; ``find`` answers with the feasible one
     of lowest objective.  Exact RBF GPs on one GPU only.
+
+    ``con_set`` (an ``_lib.SxConSet``, ``make_con_set``; DESIGN.md section 3.10, "the constraint set") adds the constraints of
+    the reference's static NLP, whose gain is a fixed parameter: an iteration is then ``sx_cem_rollout_starts_cons``.  The
+    rule, the same in the fused and the step-by-step rollout: a particle starts from a point, so step 0 pays the action box
+    alone; a step t >= 1 pays SX_ACTION_VIOLATION_COST once where its action leaves the box or its control ellipsoid
+    (u_t, K Q_t K^T) is not certified inside it; every (p_{t+1}, Q_{t+1}) with t + 1 < H pays SX_STATE_VIOLATION_COST where it
+    is not certified inside the obstacle rows; and a start that violates the obstacle rows pays SX_STATE_VIOLATION_COST once,
+    beside and independent of the safe-polytope cost of the start (a start outside both pays 20).
     """
 
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, start_mean, start_std, n_restarts: int = 1, seed: int = 0, init_std=1.0,
-                 device=None, record_rollouts: bool = False, process_group=None):
+                 device=None, record_rollouts: bool = False, process_group=None, con_set=None):
+        self._con_set = con_set
+        if con_set is not None:
+            _con_set_arg(con_set)
+            _require_rbf_con_set(ssm)
         family = getattr(ssm, 'kernel_family', 'rbf')
         if family != 'rbf':
             raise NotImplementedError(f'static exploration is built for exact RBF GPs, not kernel_family {family!r} '
@@ -1854,17 +1884,27 @@ class StaticCemMpc:
         return torch.stack([torch.randn(shape, dtype=torch.float64, device=self._device, generator=g) for g in self._gens],
                            dim=1)
 
+    @property
+    def _con_set_kw(self) -> dict:
+        """The constraint set as the rollouts' keyword; empty without one, so that they are called as before."""
+        con_set = getattr(self, '_con_set', None)
+        return {} if con_set is None else dict(con_set=con_set)
+
     def _rollout_stepwise(self, mean: Tensor, std: Tensor, eps: Tensor, status: Tensor):
-        """One iteration's rollout through `cem_rollout_stepwise` with a start per particle, restart by restart."""
+        """One iteration's rollout through `cem_rollout_stepwise` with a start per particle, restart by restart; with a
+        constraint set the steps are charged by sx_conset_eval and the start by `start_obstacle_cost`."""
         n_s, n_u = self._ssm.num_states, self._ssm.num_actions
         rows = (mean.unsqueeze(1) + std.unsqueeze(1) * eps).contiguous()       # [E x P x L]
         obj, con = [], []
         for e in range(rows.size(0)):
             x0 = rows[e, :, :n_s].contiguous()
             acts = rows[e, :, n_s:].reshape(-1, self._horizon, n_u).contiguous()
-            r = cem_rollout_stepwise(self._ssm, self._env, x0, acts, status=status)
+            r = cem_rollout_stepwise(self._ssm, self._env, x0, acts, status=status, **self._con_set_kw)
             obj.append(r['obj_cost'])
-            con.append(r['con_cost'] + start_constraint_cost(self._env, x0))
+            start = start_constraint_cost(self._env, x0)
+            if self._con_set is not None:
+                start = start + start_obstacle_cost(self._env, self._con_set, x0)
+            con.append(r['con_cost'] + start)
         return dict(rows=rows, traj=None, obj_cost=torch.stack(obj), con_cost=torch.stack(con))
 
     def solve(self, noise: Optional[Tensor] = None, stepwise: bool = False):
@@ -1890,7 +1930,7 @@ class StaticCemMpc:
             if stepwise:
                 return self._rollout_stepwise(mean, std, eps, status)
             r = cem_rollout_starts(self._ssm, self._env, self._horizon, mean=mean, std=std, noise=eps,
-                                   want_traj=self._record, status=status)
+                                   want_traj=self._record, status=status, **self._con_set_kw)
             if self._record:
                 for e in range(E):
                     history.append(Rollouts(r['traj'][e], r['rows'][e, :, n_s:].reshape(P, self._horizon, n_u),

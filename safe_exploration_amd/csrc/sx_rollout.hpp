@@ -183,4 +183,29 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_cons_kernel(
 #undef SX_ROLLOUT_PS
 }
 
+// sx_cem_rollout_starts_cons: cem_rollout_starts_kernel with the constraint set of sx_conset.hpp (the SX_ROLLOUT_PS and the
+// SX_ROLLOUT_CONS sections of sx_rollout_body.inc together; DESIGN.md section 3.10, "the constraint set"): the reference's
+// static-exploration NLP has the gain fixed, so the set is its constraints term for term.  The set is one more kernel
+// argument, as cem_rollout_cons_kernel takes it: the LDS plan is cem_rollout_starts_kernel's byte for byte.
+template <int NS, int NU>
+constexpr size_t rollout_starts_cons_arg_bytes() {
+    return rollout_cons_arg_bytes<NS, NU, false>() - (sizeof(SatConst<NS>) + 7) / 8 * 8;
+}
+
+template <int NS, int NU, bool BYOUT>
+__global__ __launch_bounds__(kRolloutThreads) void cem_rollout_starts_cons_kernel(
+    GpConst<NS, NS + NU> gc_arg, const int4* __restrict__ stage_tab_arg, ReachConst<NS, NU> rc,
+    CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const ConConst<NS> cons) {
+    static_assert(rollout_starts_cons_arg_bytes<NS, NU>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
+    constexpr int SH = 0;
+    constexpr bool MM = false;
+#define SX_ROLLOUT_PS 1
+#define SX_ROLLOUT_SAT 0
+#define SX_ROLLOUT_CONS 1
+#include "sx_rollout_body.inc"
+#undef SX_ROLLOUT_CONS
+#undef SX_ROLLOUT_SAT
+#undef SX_ROLLOUT_PS
+}
+
 }  // namespace sx

@@ -11,11 +11,15 @@
 // SX_ROLLOUT_SAT = 1 (cem_rollout_sat_kernel; SH = 0, SX_ROLLOUT_PS = 0): the objective of a step is the saturating cost of
 // sx_sat_cost.hpp on the safety ellipsoid (p_{t+1}, Q_{t+1}), read as a mean and a covariance, from `sat` (SatConst<NS>, a
 // kernel argument of its own: scalar loads, no LDS); cc.obj_mode is not read.  Nothing else in the step changes.
-// SX_ROLLOUT_CONS = 1 (cem_rollout_cons_kernel; SH = 0, SX_ROLLOUT_PS = 0): the constraint set of sx_conset.hpp, from `cons`
+// SX_ROLLOUT_CONS = 1 (cem_rollout_cons_kernel; SH = 0): the constraint set of sx_conset.hpp, from `cons`
 // (ConConst<NS>, a kernel argument of its own as `sat` is).  A step that starts from an ellipsoid pays its action cost
 // where the control ellipsoid (u_t, K Q_t K^T) is not certified inside the action box either (once per step, with the box
 // test), and every step but the last pays SX_STATE_VIOLATION_COST where (p_{t+1}, Q_{t+1}) is not certified inside the
 // obstacle rows.  The objective is SX_ROLLOUT_SAT's, either one; with an empty set the step is the parent's.
+// SX_ROLLOUT_CONS = 1 with SX_ROLLOUT_PS = 1 (cem_rollout_starts_cons_kernel; SX_ROLLOUT_SAT = 0, MM = false): the set on the
+// static rollout.  finish() is the text above: a particle starts from a point, so step 0 pays the box test only.  The
+// prologue adds one test: the start x0 itself (a point) against the obstacle rows, SX_STATE_VIOLATION_COST once, beside and
+// independent of the safe-polytope cost of the start (DESIGN.md section 3.10, "the constraint set").
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
@@ -152,6 +156,12 @@
             for (int j = 0; j < NS; ++j) Q[i][j] = 0.0;
         }
         if (polytope_violated<SX_MAX_M, NS>(cc.h_mat, cc.h_vec, cc.m, 1.0, p, Q, nullptr)) con += SX_STATE_VIOLATION_COST;
+#if SX_ROLLOUT_CONS
+        // the obstacle rows on the start itself (a point: some h_obs-row distance >= 0), once and beside the cost above: the
+        // system is put at x0, and with H = 1 no ellipsoid of the rollout meets these rows
+        if (polytope_violated<SX_MAX_M, NS>(cons.h_mat_obs, cons.h_obs, cons.m_obs, 1.0, p, Q, nullptr))
+            con += SX_STATE_VIOLATION_COST;
+#endif
     }
 #else
     if (owner) {

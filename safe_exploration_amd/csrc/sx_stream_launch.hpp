@@ -4,7 +4,8 @@
 // compiled in translation units of their own, beside the kernels (sx_stream_ns12.hip, sx_stream_ns34.hip; the multi-model
 // mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
 // sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip, in the
-// multi-model mode in sx_stream_cons_multi.hip and sx_stream_cons_sat_multi.hip; built in parallel with the rest);
+// multi-model mode in sx_stream_cons_multi.hip and sx_stream_cons_sat_multi.hip, on the per-particle starts in
+// sx_stream_starts_cons.hip; built in parallel with the rest);
 // sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -134,6 +135,14 @@ struct StreamCons {   // cem_rollout_cons_kernel: sx_cem_rollout[_elites]_cons (
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
         return cem_rollout_cons_kernel<NS, NU, BYOUT, SAT_, MM_>;
+    }
+};
+struct StreamStartsCons {   // cem_rollout_starts_cons_kernel: sx_cem_rollout_starts_cons, StreamStarts' rp with the set
+    static constexpr int SH = 0;
+    static constexpr bool MM = false, SAT = false, CONS = true;
+    template <int NS, int NU, bool BYOUT>
+    static auto kernel() {
+        return cem_rollout_starts_cons_kernel<NS, NU, BYOUT>;
     }
 };
 

@@ -296,6 +296,15 @@ class CemSafeMPC(SafeMPC):
                                          ctrl_ellipsoid=ctrl_ellipsoid)
             self._con_set_setting = setting
 
+        # cem_static_ctrl_ellipsoid_constraint / cem_static_obstacle_constraint: the same two constraint groups in static
+        # exploration (static_solver: StaticCemMpc(con_set=...)), where they are the reference NLP's own
+        # (its gain is a fixed parameter).  Settings of their own, both off by default and independent of the two above,
+        # which remain the dynamic solver's; the set is built, and a model it is not built for refused, at static_solver.
+        self._static_ctrl_ellipsoid = bool(getattr(conf, 'cem_static_ctrl_ellipsoid_constraint', False))
+        self._static_obstacle = bool(getattr(conf, 'cem_static_obstacle_constraint', False))
+        self._static_obs_rows = ((opt_env.get('h_mat_obs'), opt_env.get('h_obs')) if self._static_obstacle
+                                 else (None, None))
+
         linearized_model_a, linearized_model_b = opt_env['lin_model']
         self.lin_model = opt_env['lin_model']
         self._linearized_model_a = torch.tensor(linearized_model_a, device=self._device)
@@ -427,17 +436,32 @@ class CemSafeMPC(SafeMPC):
         """The solver of static exploration (StaticSafeMPCExploration): the start state is optimised with the actions, from
         the distribution (sample_mean, sample_std) [n_s], in `n_restarts` problems side by side.  Built over this solver's
         model, its constraint set with the variance objective, mpc_time_horizon and the cem_num_* settings.  The model is
-        read at solve time, so the solver stays valid across update_model."""
+        read at solve time, so the solver stays valid across update_model.  conf.cem_static_ctrl_ellipsoid_constraint /
+        conf.cem_static_obstacle_constraint add the feedback bounds and the obstacle rows (opt_env['h_mat_obs'] / ['h_obs'];
+        None: no rows) to it: StaticCemMpc(con_set=...)."""
+        ctrl_ellipsoid = getattr(self, '_static_ctrl_ellipsoid', False)
+        obstacle = getattr(self, '_static_obstacle', False)
+        con_kw = {}
+        if ctrl_ellipsoid or obstacle:
+            setting = ' / '.join(name for name, on in (('cem_static_ctrl_ellipsoid_constraint', ctrl_ellipsoid),
+                                                       ('cem_static_obstacle_constraint', obstacle)) if on)
+            if getattr(self._ssm, 'kernel_family', None) != 'rbf':
+                raise NotImplementedError(f'{setting} needs an exact RBF GP (GpCemSSM), not kernel_family '
+                                          f'{getattr(self._ssm, "kernel_family", None)!r}')
+            h_mat_obs, h_obs = self._static_obs_rows
+            con_kw['con_set'] = make_con_set(self._state_dimen, h_mat_obs=h_mat_obs,
+                                             h_obs=None if h_mat_obs is None else h_obs, ctrl_ellipsoid=ctrl_ellipsoid)
+        elif getattr(self, '_con_set', None) is not None:
+            # (the dynamic solver's set says nothing about the static solve: its settings are the two above)
+            raise NotImplementedError(f'static exploration is not built for {self._con_set_setting}')
         if isinstance(self._ssm, JunkDimensionsSSM):
             raise NotImplementedError('static exploration is not built for JunkDimensionsSSM')
-        if getattr(self, '_con_set', None) is not None:
-            raise NotImplementedError(f'static exploration is not built for {self._con_set_setting}')
         env, _ = self._build_env()
         return StaticCemMpc(self._ssm, env, self._mpc_time_horizon, self._conf.cem_num_rollouts, self._conf.cem_num_elites,
                             self._conf.cem_num_iterations, start_mean=sample_mean, start_std=sample_std,
                             n_restarts=n_restarts, seed=int(getattr(self._conf, 'cem_seed', 0)),
                             init_std=getattr(self._conf, 'cem_init_std', 1.0), device=self._device,
-                            record_rollouts=self._record_rollouts)
+                            record_rollouts=self._record_rollouts, **con_kw)
 
     def _flat_points(self, states: ndarray) -> Tensor:
         """Point states [E x n_s] as the optimiser's flat states [E x (n_s + n_s^2)] (PQFlattener.flatten(p, None): an

@@ -2,6 +2,7 @@
 the streaming kernel, on this build: config 2 (pendulum, N = 200, 4096 particles, H = 15, 8 CEM iterations, 409 elites).
 
     python tools/static_explore_timing.py [--restarts 1,6] [--solves 200] [--warmup 20] [--plain-only] [--label L] [--out F]
+                                          [--repeats 5]
 
 Rows (one JSON line each: median and p95 in ms of synchronous solves -- solve + device synchronise on the host clock --
 `--solves` times after `--warmup` untimed ones; printed and, with `--out`, appended to that jsonl file):
@@ -14,6 +15,13 @@ Rows (one JSON line each: median and p95 in ms of synchronous solves -- solve + 
                    start's draw and polytope test in the rollout
   launch_plain, launch_starts   one launch alone (sx_cem_rollout on the streaming kernel; sx_cem_rollout_starts): 200
                    launches back to back between two synchronisations, per launch, in us
+  static_cons_E    StaticCemMpc(con_set=...).solve with a full set (the feedback bounds and two obstacle rows, as
+                   tools/conset_timing.py builds them), measured in alternation with the same solver without the set,
+                   `--repeats` rounds of `--solves` / `--repeats` solves each: the median of the rounds' medians, `parent_ms`
+                   likewise for the solver without the set, `ratio` = median / parent's, `parent_spread` = (largest - smallest)
+                   / median of the parent's rounds: what a ratio is read against
+  launch_starts_cons   sx_cem_rollout_starts_cons with that set on launch_starts' buffers, in the same alternation with
+                   sx_cem_rollout_starts (`parent_us`): median, smallest and largest of `--repeats` measurements
 A static solve is the streaming kernel plus the longer rows, so it is compared with plain_stream, not with the resident form
 a plain config-2 solve takes by default.  `--plain-only` stops after the plain rows and uses nothing the parent commit
 lacks: run the same file from a checkout of the parent for the same-session comparison (`--label` names the build in the
@@ -70,6 +78,7 @@ def main():
     ap.add_argument('--plain-only', action='store_true')
     ap.add_argument('--label', default='this')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--repeats', type=int, default=5)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('static_explore_timing.py needs the GPU')
@@ -101,6 +110,27 @@ def main():
         med, p95 = time_solves(mpc.solve, args.warmup, args.solves)
         row(row=f'static_{E}', E=E, median_ms=med, p95_ms=p95, extra_ms=med - plain[E],
             extra_per_iteration_us=(med - plain[E]) * 1e3 / wl.iterations)
+    # the constraint set: the feedback bounds, and the first two rows of the safe polytope pulled in as the obstacle
+    from safe_exploration_amd.gp_reachability_pytorch import make_con_set
+    con_set = make_con_set(n_s, h_mat_obs=wl.spec.h_mat[:2], h_obs=0.9 * wl.spec.h_vec[:2, 0], ctrl_ellipsoid=True)
+
+    def alternate(parent, ours, measure):
+        a, b = [], []
+        for _ in range(args.repeats):
+            a.append(measure(parent))
+            b.append(measure(ours))
+        med = float(np.median(a))
+        return dict(parent=med, ours=float(np.median(b)), lo=float(min(b)), hi=float(max(b)), ratio=float(np.median(b)) / med,
+                    parent_spread=(max(a) - min(a)) / med)
+
+    per_round = max(1, args.solves // args.repeats)
+    for E in restarts:
+        kw = dict(start_mean=wl.x0[0, :n_s], start_std=np.full(n_s, 0.05), n_restarts=E, init_std=wl.init_std, device=DEV)
+        without = cem_mpc.StaticCemMpc(ssm, env, H, P, wl.elites, wl.iterations, **kw)
+        with_set = cem_mpc.StaticCemMpc(ssm, env, H, P, wl.elites, wl.iterations, con_set=con_set, **kw)
+        m = alternate(without.solve, with_set.solve, lambda solve: time_solves(solve, args.warmup, per_round)[0])
+        row(row=f'static_cons_{E}', E=E, median_ms=m['ours'], min_ms=m['lo'], max_ms=m['hi'], parent_ms=m['parent'],
+            ratio=m['ratio'], parent_spread=m['parent_spread'], repeats=args.repeats)
     # the launches alone
     gen = torch.Generator(device=DEV)
     gen.manual_seed(0)
@@ -118,6 +148,11 @@ def main():
     r_noise = rnd(1, P, L)
     row(row='launch_starts', E=1, us=time_launches(
         lambda: cem_mpc.cem_rollout_starts(ssm, env, H, mean=r_mean, std=r_std, noise=r_noise, status=status)))
+    m = alternate(lambda: cem_mpc.cem_rollout_starts(ssm, env, H, mean=r_mean, std=r_std, noise=r_noise, status=status),
+                  lambda: cem_mpc.cem_rollout_starts(ssm, env, H, mean=r_mean, std=r_std, noise=r_noise, status=status,
+                                                     con_set=con_set), time_launches)
+    row(row='launch_starts_cons', E=1, us=m['ours'], min_us=m['lo'], max_us=m['hi'], parent_us=m['parent'], ratio=m['ratio'],
+        parent_spread=m['parent_spread'], repeats=args.repeats)
 
 
 if __name__ == '__main__':
