@@ -37,7 +37,7 @@ struct CautiousForm {
     }
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_cautious_rollout_kernel<NS, NU, BYOUT>;
+        return cem_cautious_rollout_kernel<NS, NU, BYOUT, false>;
     }
 };
 

@@ -1,6 +1,6 @@
 // sx_cem_cautious_rollout_sat: the cautious rollout with the saturating cost as its objective
-// (cem_cautious_sat_rollout_kernel, sx_cautious.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES in both forms, and its
-// entry.  The plan is the parent's (sx_cem_cautious_rollout_form answers for it): the cost's constants are no LDS.  A
+// (cem_cautious_rollout_kernel<..., SAT = true>, sx_cautious.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES in both
+// forms, and its entry.  The plan is the parent's (sx_cem_cautious_rollout_form answers for it): the cost's constants are no LDS.  A
 // translation unit of its own: nothing the other objects compile changes with it.
 #include "sx_cautious_host.hpp"   // CautiousForm, cautious_plan
 
@@ -26,7 +26,7 @@ struct CautiousSatForm {
     }
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_cautious_sat_rollout_kernel<NS, NU, BYOUT>;
+        return cem_cautious_rollout_kernel<NS, NU, BYOUT, true>;
     }
 };
 

@@ -81,18 +81,18 @@ int launch_perf_gp(Kernel kernel, unsigned blocks, size_t lds, hipStream_t strea
     return check_launch();
 }
 
-// The multi-model kernel K::kernel<NS, NU, byout>(); one output has no output-by-output kernel.
+// The multi-model kernel of kind K (PerfVarKind | PerfTaylorKind<SAT>); one output has no output-by-output kernel.
 template <class K, int NS, int NU, class... Args>
 int launch_perf_gp_forms(bool byout, unsigned blocks, size_t lds, hipStream_t stream, const Args&... args) {
     if constexpr (NS > 1) {
-        if (byout) return launch_perf_gp(K::template kernel<NS, NU, true>(), blocks, lds, stream, args...);
+        if (byout) return launch_perf_gp(cem_perf_gp_rollout_kernel<K, NS, NU, true, true>, blocks, lds, stream, args...);
     }
-    return launch_perf_gp(K::template kernel<NS, NU, false>(), blocks, lds, stream, args...);
+    return launch_perf_gp(cem_perf_gp_rollout_kernel<K, NS, NU, false, true>, blocks, lds, stream, args...);
 }
 
 // The launchers of the multi-model kernels over `table` (sx_gp_model_table's; the status holds a word per problem),
-// instantiated for every shape beside the kernels: launch_perf_gp_forms over cem_perf_var_rollout_multi_kernel
-// (sx_perf_multi.hip) and over cem_perf_taylor_rollout_multi_kernel (sx_perf_taylor_multi.hip)
+// instantiated for every shape beside the kernels: launch_perf_gp_forms over cem_perf_gp_rollout_kernel<..., MM = true> of
+// kind PerfVarKind (sx_perf_multi.hip) and of kind PerfTaylorKind<false> (sx_perf_taylor_multi.hip)
 template <int NS, int NU>
 int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
                          bool byout, unsigned blocks, size_t lds, hipStream_t stream);

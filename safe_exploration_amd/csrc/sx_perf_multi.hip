@@ -15,23 +15,16 @@ int launch_perf_rollout_multi(const PerfGpEntry<NS, NU>* table, const PerfStepCo
                               size_t lds, hipStream_t stream) {
     const int64_t blocks = (int64_t)pp.E * ((pp.P + kPerfTile - 1) / kPerfTile);
     if (blocks > INT_MAX || lds > kMaxLdsBytes) return SX_ERR_UNSUPPORTED;
-    if (int r = allow_lds(cem_perf_rollout_multi_kernel<NS, NU>, lds)) return r;
-    hipLaunchKernelGGL((cem_perf_rollout_multi_kernel<NS, NU>), dim3((unsigned)blocks), dim3(kPerfThreads), lds, stream,
-                       table, step, pp);
+    const auto kernel = cem_perf_rollout_kernel<NS, NU, true, PerfStepConst<NS, NU>>;
+    if (int r = allow_lds(kernel, lds)) return r;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kPerfThreads), lds, stream, table, step, pp);
     return check_launch();
 }
-
-struct PerfVarMultiKernels {
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_perf_var_rollout_multi_kernel<NS, NU, BYOUT>;
-    }
-};
 
 template <int NS, int NU>
 int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfStepConst<NS, NU>& sc, const PerfVarPtrs& vp,
                           bool byout, unsigned blocks, size_t lds, hipStream_t stream) {
-    return launch_perf_gp_forms<PerfVarMultiKernels, NS, NU>(byout, blocks, lds, stream, table, sc, vp);
+    return launch_perf_gp_forms<PerfVarKind, NS, NU>(byout, blocks, lds, stream, table, sc, vp);
 }
 
 }  // namespace sx

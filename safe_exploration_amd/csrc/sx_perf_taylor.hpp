@@ -15,10 +15,12 @@
 // The constants of a step (prior, a + b K, K, action box, objective, polytope: 64 .. 128 doubles) sit in LDS behind the
 // tile's actions; as kernel arguments they would stay in SGPRs for the whole kernel, which already spills its arguments.
 // A tile's numbers depend on its 16 particles alone.
-// The body is sx_perf_gp_body.inc with its Taylor sections, the text the variance kernels (sx_perf_var.hpp) include without
-// them: into the single-model kernel and into the multi-model one (sx_cem_perf_rollout_taylor_multi: a GP per problem).
+// The kernel is cem_perf_gp_rollout_kernel (sx_perf_var.hpp) of kind PerfTaylorKind: the variance kernels' body with its
+// Taylor sections, single-model and multi-model (sx_cem_perf_rollout_taylor_multi: a GP per problem) alike.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/sx_amd.h"
 #include "sx_gp.hpp"
@@ -37,50 +39,15 @@ struct PerfTaylorConst {
     double h_vec[SX_MAX_M];
 };
 
-struct PerfTaylorPtrs {
-    PerfVarPtrs v;       // v.perf_sigma: diag G_t
+struct PerfTaylorPtrs : PerfVarPtrs {   // perf_sigma: diag G_t
     double* perf_cov;    // [E x P x n_perf x NS x NS] | NULL: Sigma_1 .. Sigma_{n_perf}
     int m;               // polytope rows
     int safety_step;     // t whose (mu_{t+1}, Sigma_{t+1}) is checked against the polytope (H + 1), or -1
 };
 
-template <int NS, int NU>
-constexpr int perf_taylor_const_doubles() {
-    return (int)(sizeof(PerfTaylorConst<NS, NU>) / sizeof(double));
-}
-
-template <int NS, int NU, bool BYOUT>
-__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_rollout_kernel(const GpConst<NS, NS + NU> gc,
-                                                                                  const int4* __restrict__ stage_tab,
-                                                                                  const PerfTaylorConst<NS, NU> tc_arg,
-                                                                                  const PerfTaylorPtrs tp) {
-    constexpr bool MM = false;
-    const PerfVarPtrs& vp = tp.v;
-#define SX_PERF_TAYLOR 1
-#include "sx_perf_gp_body.inc"
-#undef SX_PERF_TAYLOR
-}
-
-// sx_cem_perf_rollout_taylor_multi: a GP per problem, one set of step constants (one sx_env).  The workgroup binds its
-// problem's GpConst through a restrict-qualified pointer into the constant address space (scalar loads; the kernel never
-// writes the table), as cem_perf_var_rollout_multi_kernel does.
-template <int NS, int NU, bool BYOUT>
-__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_rollout_multi_kernel(
-    const GpConst<NS, NS + NU>* __restrict__ table, const PerfTaylorConst<NS, NU> tc_arg, const PerfTaylorPtrs tp) {
-    constexpr bool MM = true;
-    using ConstG = __attribute__((address_space(4))) const GpConst<NS, NS + NU>;
-    const int problem = blockIdx.x / ((tp.v.p.P + SX_TILE - 1) / SX_TILE);
-    const GpConst<NS, NS + NU>& gc = *(const GpConst<NS, NS + NU>*)((ConstG*)table + problem);
-    const int4* __restrict__ const stage_tab = gc.stage_tab;
-    const PerfVarPtrs& vp = tp.v;
-#define SX_PERF_TAYLOR 1
-#include "sx_perf_gp_body.inc"
-#undef SX_PERF_TAYLOR
-}
-
-// The same two kernels with the saturating cost (sx_sat_cost.hpp) as the objective (sx_cem_perf_rollout_taylor_sat[_multi]).
+// The same kernels with the saturating cost (sx_sat_cost.hpp) as the objective (sx_cem_perf_rollout_taylor_sat[_multi]).
 // The cost's constants ride behind the step constants in one kernel argument and stay there: the owner lanes read them by
-// scalar loads, and the LDS plan is the parent's.
+// scalar loads, and the LDS plan is the same.
 template <int NS, int NU>
 struct PerfTaylorSatConst {
     PerfTaylorConst<NS, NU> tc;
@@ -93,38 +60,13 @@ template <int NS, int NU>
 int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorSatConst<NS, NU>& c, const PerfTaylorPtrs& tp,
                          bool byout, unsigned blocks, size_t lds, hipStream_t stream);
 
-template <int NS, int NU, bool BYOUT>
-__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_sat_rollout_kernel(const GpConst<NS, NS + NU> gc,
-                                                                                      const int4* __restrict__ stage_tab,
-                                                                                      const PerfTaylorSatConst<NS, NU> arg,
-                                                                                      const PerfTaylorPtrs tp) {
-    constexpr bool MM = false;
-    const PerfTaylorConst<NS, NU>& tc_arg = arg.tc;
-    const SatConst<NS>& sat = arg.sat;
-    const PerfVarPtrs& vp = tp.v;
-#define SX_PERF_TAYLOR 1
-#define SX_PERF_SAT
-#include "sx_perf_gp_body.inc"
-#undef SX_PERF_SAT
-#undef SX_PERF_TAYLOR
-}
-
-template <int NS, int NU, bool BYOUT>
-__global__ __launch_bounds__(kPerfVarThreads) void cem_perf_taylor_sat_rollout_multi_kernel(
-    const GpConst<NS, NS + NU>* __restrict__ table, const PerfTaylorSatConst<NS, NU> arg, const PerfTaylorPtrs tp) {
-    constexpr bool MM = true;
-    using ConstG = __attribute__((address_space(4))) const GpConst<NS, NS + NU>;
-    const int problem = blockIdx.x / ((tp.v.p.P + SX_TILE - 1) / SX_TILE);
-    const GpConst<NS, NS + NU>& gc = *(const GpConst<NS, NS + NU>*)((ConstG*)table + problem);
-    const int4* __restrict__ const stage_tab = gc.stage_tab;
-    const PerfTaylorConst<NS, NU>& tc_arg = arg.tc;
-    const SatConst<NS>& sat = arg.sat;
-    const PerfVarPtrs& vp = tp.v;
-#define SX_PERF_TAYLOR 1
-#define SX_PERF_SAT
-#include "sx_perf_gp_body.inc"
-#undef SX_PERF_SAT
-#undef SX_PERF_TAYLOR
-}
+// The Taylor kinds of cem_perf_gp_rollout_kernel (sx_perf_var.hpp): its Taylor sections, and with SAT the saturating cost
+template <bool SAT_>
+struct PerfTaylorKind {
+    static constexpr bool TAYLOR = true, SAT = SAT_;
+    template <int NS, int NU>
+    using Const = std::conditional_t<SAT_, PerfTaylorSatConst<NS, NU>, PerfTaylorConst<NS, NU>>;
+    using Ptrs = PerfTaylorPtrs;
+};
 
 }  // namespace sx

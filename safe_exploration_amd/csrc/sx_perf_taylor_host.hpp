@@ -17,7 +17,7 @@ struct PerfTaylorForm {
     template <int NS, int NU>
     using Const = PerfTaylorConst<NS, NU>;
     using Ptrs = PerfTaylorPtrs;
-    static const PerfPtrs& base(const Ptrs& tp) { return tp.v.p; }
+    static const PerfPtrs& base(const Ptrs& tp) { return tp.p; }
     static size_t extra_bytes(int ns, int nu) { return perf_taylor_extra_bytes(ns, nu); }
     template <int NS, int NU>
     static void make_const(const sx_env* env, Const<NS, NU>& tc) {
@@ -37,7 +37,7 @@ struct PerfTaylorForm {
     }
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_perf_taylor_rollout_kernel<NS, NU, BYOUT>;
+        return cem_perf_gp_rollout_kernel<PerfTaylorKind<false>, NS, NU, BYOUT, false, const int4* __restrict__>;
     }
 };
 

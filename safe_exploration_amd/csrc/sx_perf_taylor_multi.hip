@@ -10,23 +10,16 @@
 
 namespace sx {
 
-struct PerfTaylorMultiKernels {
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_perf_taylor_rollout_multi_kernel<NS, NU, BYOUT>;
-    }
-};
-
 template <int NS, int NU>
 int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorConst<NS, NU>& tc, const PerfTaylorPtrs& tp,
                              bool byout, unsigned blocks, size_t lds, hipStream_t stream) {
-    return launch_perf_gp_forms<PerfTaylorMultiKernels, NS, NU>(byout, blocks, lds, stream, table, tc, tp);
+    return launch_perf_gp_forms<PerfTaylorKind<false>, NS, NU>(byout, blocks, lds, stream, table, tc, tp);
 }
 
 }  // namespace sx
 
-#define SX_PERF_TAYLOR_MULTI_INSTANTIATE(NS, NU)                                                                        \
+#define SX_TAYLOR_MULTI_INSTANTIATE(NS, NU)                                                                        \
     template int sx::launch_perf_gp_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfTaylorConst<NS, NU>&, \
                                                       const sx::PerfTaylorPtrs&, bool, unsigned, size_t, hipStream_t);
-#define SX_PERF_TAYLOR_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_PERF_TAYLOR_MULTI_INSTANTIATE(NS, NU))
-SX_ROLLOUT_SHAPES(SX_PERF_TAYLOR_MULTI_ONE, 0)
+#define SX_TAYLOR_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_TAYLOR_MULTI_INSTANTIATE(NS, NU))
+SX_ROLLOUT_SHAPES(SX_TAYLOR_MULTI_ONE, 0)

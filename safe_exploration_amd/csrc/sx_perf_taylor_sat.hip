@@ -1,5 +1,5 @@
 // sx_cem_perf_rollout_taylor_sat[_multi]: the Taylor performance rollout with the saturating cost as its objective
-// (cem_perf_taylor_sat_rollout_kernel, sx_perf_taylor.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES in both forms, and
+// (cem_perf_gp_rollout_kernel of kind PerfTaylorKind<true>) for every shift-0 shape of SX_ROLLOUT_SHAPES in both forms, and
 // the two entries (the multi-model kernels are compiled in sx_perf_taylor_sat_multi.hip).  The plan is the parent's: the
 // cost's constants are no LDS.  A translation unit of its own: nothing the other objects compile changes with it.
 #include "sx_perf_taylor_host.hpp"   // PerfTaylorForm, perf_taylor_launch
@@ -10,7 +10,7 @@ struct PerfTaylorSatForm {
     template <int NS, int NU>
     using Const = PerfTaylorSatConst<NS, NU>;
     using Ptrs = PerfTaylorPtrs;
-    static const PerfPtrs& base(const Ptrs& tp) { return tp.v.p; }
+    static const PerfPtrs& base(const Ptrs& tp) { return tp.p; }
     static size_t extra_bytes(int ns, int nu) { return perf_taylor_extra_bytes(ns, nu); }
     template <int NS, int NU>
     static void make_const(const sx_env* env, Const<NS, NU>& c) {
@@ -19,7 +19,7 @@ struct PerfTaylorSatForm {
     }
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_perf_taylor_sat_rollout_kernel<NS, NU, BYOUT>;
+        return cem_perf_gp_rollout_kernel<PerfTaylorKind<true>, NS, NU, BYOUT, false, const int4* __restrict__>;
     }
 };
 

@@ -10,23 +10,16 @@
 
 namespace sx {
 
-struct PerfTaylorSatMultiKernels {
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_perf_taylor_sat_rollout_multi_kernel<NS, NU, BYOUT>;
-    }
-};
-
 template <int NS, int NU>
 int launch_perf_gp_multi(const GpConst<NS, NS + NU>* table, const PerfTaylorSatConst<NS, NU>& c, const PerfTaylorPtrs& tp,
                          bool byout, unsigned blocks, size_t lds, hipStream_t stream) {
-    return launch_perf_gp_forms<PerfTaylorSatMultiKernels, NS, NU>(byout, blocks, lds, stream, table, c, tp);
+    return launch_perf_gp_forms<PerfTaylorKind<true>, NS, NU>(byout, blocks, lds, stream, table, c, tp);
 }
 
 }  // namespace sx
 
-#define SX_PERF_TAYLOR_SAT_MULTI_INSTANTIATE(NS, NU)                                                                       \
+#define SX_TAYLOR_SAT_MULTI_INSTANTIATE(NS, NU)                                                                       \
     template int sx::launch_perf_gp_multi<NS, NU>(const sx::GpConst<NS, NS + NU>*, const sx::PerfTaylorSatConst<NS, NU>&, \
                                                   const sx::PerfTaylorPtrs&, bool, unsigned, size_t, hipStream_t);
-#define SX_PERF_TAYLOR_SAT_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_PERF_TAYLOR_SAT_MULTI_INSTANTIATE(NS, NU))
-SX_ROLLOUT_SHAPES(SX_PERF_TAYLOR_SAT_MULTI_ONE, 0)
+#define SX_TAYLOR_SAT_MULTI_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_TAYLOR_SAT_MULTI_INSTANTIATE(NS, NU))
+SX_ROLLOUT_SHAPES(SX_TAYLOR_SAT_MULTI_ONE, 0)

@@ -22,7 +22,7 @@ struct PerfVarForm {
     }
     template <int NS, int NU, bool BYOUT>
     static auto kernel() {
-        return cem_perf_var_rollout_kernel<NS, NU, BYOUT>;
+        return cem_perf_gp_rollout_kernel<PerfVarKind, NS, NU, BYOUT, false, const int4* __restrict__>;
     }
 };
 

@@ -1,6 +1,6 @@
 // The compiled shapes of the fused rollout, the streaming plan every exact-GP rollout shares (plan_stream,
 // plan_stream_multi: the LDS rule and its fold over several models, written here only), and the launcher of the streaming
-// rollout kernels (launch_stream<V, NS, NU> over a variant V that names the kernel).  The launcher's instantiations are
+// rollout kernel (launch_stream<V, NS, NU> over a variant V of it).  The launcher's instantiations are
 // compiled in translation units of their own, beside the kernels (sx_stream_ns12.hip, sx_stream_ns34.hip; the multi-model
 // mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
 // sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip, in the
@@ -99,59 +99,49 @@ inline StreamPlan plan_stream_multi(const sx_gp_model* models, int E, int steps,
     return out;
 }
 
-// The variants of the streaming kernel: which kernel a launch names (kernel<NS, NU, BYOUT>()), its query shift SH, whether
-// its first argument is the device table of the problems' GpConst (MM; sx_gp_model_table), and whether it takes the
-// saturating cost's constants as a trailing argument (SAT), behind the constraint set's where it takes those (CONS).
-template <int SH_, bool MM_ = false>
-struct StreamPlain {   // cem_rollout_kernel: sx_cem_rollout[_elites][_junk] (MM: sx_cem_rollout[_elites]_multi)
+// The variant of the streaming kernel a launch names: cem_rollout_kernel<V, NS, NU, BYOUT, X...> (sx_rollout.hpp) reads
+// these flags, and launch_stream forms X... from them.  The step loop, the forms, the barriers and the LDS plan are the same
+// in every variant.
+//   SH    the query shift (sx_cem_rollout_junk; described at RolloutGpArg).
+//   MM    the first argument is the device table of the problems' GpConst (sx_gp_model_table; at RolloutGpArg too).
+//   PS    (sx_cem_rollout_starts; SH = 0, MM = false) a start state per particle: the CEM row of a particle is
+//         [x0 (NS) | actions (H NU)], L = NS + H NU entries.  rp.mean / rp.std are [E x L], rp.noise [E x P x L] | NULL,
+//         rp.actions the rows [E x P x L] (written when noise is given, read otherwise); rp.x0, rp.q0 and the elite-row
+//         fields are unused.  The owner lane of a particle takes its start from its own row (a point, reach_point at t = 0)
+//         and pays SX_STATE_VIOLATION_COST once where that start is outside the polytope; a lane past P in the last tile
+//         reads through the problem's first particle and writes nothing.
+//   SAT   (SH = 0, PS = false) the objective of a step is the saturating cost of sx_sat_cost.hpp on the safety ellipsoid
+//         (p_{t+1}, Q_{t+1}), read as a mean and a covariance, from a trailing SatConst<NS> argument; cc.obj_mode is not
+//         read.  Nothing else in the step changes.
+//   CONS  (SH = 0) the constraint set of sx_conset.hpp, from a trailing ConConst<NS> argument ahead of SAT's: ONE set, shared
+//         by all problems with MM.  A step that starts from an ellipsoid pays its action cost where the control ellipsoid
+//         (u_t, K Q_t K^T) is not certified inside the action box either (once per step, with the box test), and every step
+//         but the last pays SX_STATE_VIOLATION_COST where (p_{t+1}, Q_{t+1}) is not certified inside the obstacle rows.  The
+//         objective is SAT's, either one; with an empty set the step is the variant's without CONS (section 3.15).
+//         With PS (the static rollout; the reference's static-exploration NLP has the gain fixed, so the set is its
+//         constraints term for term): a particle starts from a point, so step 0 pays the box test only, and the prologue
+//         tests the start x0 itself against the obstacle rows, SX_STATE_VIOLATION_COST once, beside and independent of the
+//         safe-polytope cost of the start (section 3.10, "the constraint set").
+template <int SH_, bool MM_, bool PS_, bool SAT_, bool CONS_>
+struct StreamVariant {
     static constexpr int SH = SH_;
-    static constexpr bool MM = MM_, SAT = false, CONS = false;
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_rollout_kernel<NS, NU, BYOUT, SH_, MM_>;
-    }
+    static constexpr bool MM = MM_, PS = PS_, SAT = SAT_, CONS = CONS_;
 };
-struct StreamStarts {   // cem_rollout_starts_kernel: sx_cem_rollout_starts, rp as the SX_ROLLOUT_PS sections read it
-    static constexpr int SH = 0;
-    static constexpr bool MM = false, SAT = false, CONS = false;
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_rollout_starts_kernel<NS, NU, BYOUT>;
-    }
-};
-template <bool MM_>
-struct StreamSat {   // cem_rollout_sat_kernel: sx_cem_rollout[_elites]_sat (MM: ..._sat_multi)
-    static constexpr int SH = 0;
-    static constexpr bool MM = MM_, SAT = true, CONS = false;
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_rollout_sat_kernel<NS, NU, BYOUT, MM_>;
-    }
-};
-template <bool SAT_, bool MM_ = false>
-struct StreamCons {   // cem_rollout_cons_kernel: sx_cem_rollout[_elites]_cons (MM: ..._cons_multi), SAT_: with a cost
-    static constexpr int SH = 0;
-    static constexpr bool MM = MM_, SAT = SAT_, CONS = true;
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_rollout_cons_kernel<NS, NU, BYOUT, SAT_, MM_>;
-    }
-};
-struct StreamStartsCons {   // cem_rollout_starts_cons_kernel: sx_cem_rollout_starts_cons, StreamStarts' rp with the set
-    static constexpr int SH = 0;
-    static constexpr bool MM = false, SAT = false, CONS = true;
-    template <int NS, int NU, bool BYOUT>
-    static auto kernel() {
-        return cem_rollout_starts_cons_kernel<NS, NU, BYOUT>;
-    }
-};
+template <int SH, bool MM = false>
+using StreamPlain = StreamVariant<SH, MM, false, false, false>;   // sx_cem_rollout[_elites][_junk] (MM: ..._multi)
+using StreamStarts = StreamVariant<0, false, true, false, false>;   // sx_cem_rollout_starts
+template <bool MM>
+using StreamSat = StreamVariant<0, MM, false, true, false>;   // sx_cem_rollout[_elites]_sat (MM: ..._sat_multi)
+template <bool SAT, bool MM = false>
+using StreamCons = StreamVariant<0, MM, false, SAT, true>;   // sx_cem_rollout[_elites]_cons[_multi], SAT: with a cost
+using StreamStartsCons = StreamVariant<0, false, true, false, true>;   // sx_cem_rollout_starts_cons
 
 // The first kernel argument of variant V: the GpConst, or with V::MM the device table of E of them
 template <class V, int NS, int NU>
 using StreamGpArg = typename RolloutGpArg<NS, NS + NU + V::SH, V::MM>::type;
 
-// Launches V::kernel<NS, NU, byout>() on `stream` over rp.E * ceil(rp.P / SX_TILE) workgroups with `lds` bytes of dynamic
-// LDS (plan_stream's; with V::MM plan_stream_multi's, and rp.status holds a word per problem).  `sat` is read with V::SAT
+// Launches cem_rollout_kernel<V, NS, NU, byout, ...> on `stream` over rp.E * ceil(rp.P / SX_TILE) workgroups with `lds`
+// bytes of dynamic LDS (plan_stream's; with V::MM plan_stream_multi's, and rp.status holds a word per problem).  `sat` is read with V::SAT
 // only and `cons` with V::CONS only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
 template <class V, int NS, int NU>
 int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,

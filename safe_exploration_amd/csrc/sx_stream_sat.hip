@@ -1,5 +1,5 @@
 // Streaming rollout kernels with the saturating cost on the safety ellipsoids as the objective (sx_cem_rollout_sat,
-// sx_cem_rollout_elites_sat; cem_rollout_sat_kernel<NS, NU, BYOUT, false>): every shift-0 shape of SX_ROLLOUT_SHAPES in both
+// sx_cem_rollout_elites_sat; cem_rollout_kernel<StreamSat<false>, ...>): every shift-0 shape of SX_ROLLOUT_SHAPES in both
 // forms.  A translation unit of its own: nothing the other objects compile changes with it.
 #include "sx_stream_impl.hpp"
 

@@ -1,5 +1,5 @@
 // Streaming rollout kernels with a start state per particle and the SafeMPC constraint set (sx_cem_rollout_starts_cons;
-// cem_rollout_starts_cons_kernel<NS, NU, BYOUT>): every shift-0 shape of SX_ROLLOUT_SHAPES in both forms.  A translation unit
+// cem_rollout_kernel<StreamStartsCons, ...>): every shift-0 shape of SX_ROLLOUT_SHAPES in both forms.  A translation unit
 // of its own: nothing the other objects compile changes with it.
 #include "sx_stream_impl.hpp"
 

@@ -1,6 +1,6 @@
 """GPU: the SafeMPC constraint set of the CEM rollout -- sx_conset_eval against the numpy oracle
-(tests/conset_oracle.py); sx_cem_rollout_cons / sx_cem_rollout_elites_cons (cem_rollout_cons_kernel) with the empty set
-against the streaming parent, bit for bit, and with a full set against the empty-set launch plus the oracle's extra cost of the
+(tests/conset_oracle.py); sx_cem_rollout_cons / sx_cem_rollout_elites_cons (cem_rollout_kernel<StreamCons<SAT>>) with the empty
+set against the streaming parent, bit for bit, and with a full set against the empty-set launch plus the oracle's extra cost of the
 kernel's own trajectory; the fused rollout against the step-by-step one; the solve of tests/conset_oracle.py through
 FusedCemMpc(con_set=...); and CemSafeMPC through its two conf settings.
 

@@ -1,5 +1,5 @@
 """GPU: the SafeMPC constraint set in multi-model CEM solves ("the multi-model form") --
-sx_cem_rollout_cons_multi / sx_cem_rollout_elites_cons_multi (cem_rollout_cons_kernel<..., MM = true>) against the
+sx_cem_rollout_cons_multi / sx_cem_rollout_elites_cons_multi (cem_rollout_kernel<StreamCons<SAT, true>>) against the
 single-model entries problem by problem, with the empty set against the multi-model parents, with a full set against the
 empty-set launch plus the numpy oracle's extra cost of the kernel's own trajectory (tests/conset_oracle.py), with a NaN start
 in one problem; the solve of tests/conset_multi_oracle.py through MultiModelConsCemMpc; and get_actions_multi over CemSafeMPCs

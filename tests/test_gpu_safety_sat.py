@@ -1,5 +1,5 @@
 """GPU: the saturating cost on the safety trajectory -- sx_cem_rollout_sat, sx_cem_rollout_elites_sat and their _multi forms
-(cem_rollout_sat_kernel) against their parent entries (everything but obj_cost), against the numpy oracle
+(cem_rollout_kernel<StreamSat<MM>>) against their parent entries (everything but obj_cost), against the numpy oracle
 (tests/sat_cost_oracle.py over the kernel's own traj, and tests/safety_sat_oracle.py over oracle.cem.rollout), their
 independence of obj_mode, the grid and a NaN neighbour, the fused rollout against the step-by-step one, and the solves of
 tests/safety_sat_oracle.py through FusedCemMpc(cost_on_safety=True), MultiModelCemMpc and CemSafeMPC.

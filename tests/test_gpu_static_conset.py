@@ -1,6 +1,6 @@
 """GPU: the SafeMPC constraint set in static exploration ("the constraint set") --
-sx_cem_rollout_starts_cons (cem_rollout_starts_cons_kernel) with the empty set against sx_cem_rollout_starts, bit for bit; with
-a full set against the empty-set launch plus the oracle's extra cost of the kernel's own trajectory and starts
+sx_cem_rollout_starts_cons (cem_rollout_kernel<StreamStartsCons>) with the empty set against sx_cem_rollout_starts, bit for bit;
+with a full set against the empty-set launch plus the oracle's extra cost of the kernel's own trajectory and starts
 (tests/static_conset_oracle.py); against the oracle's rollout from every row's own start; its independence of the particle
 count; the fused rollout against StaticCemMpc._rollout_stepwise; the solve of the oracle file through
 StaticCemMpc(con_set=...); and StaticSafeMPCExploration over a CemSafeMPC with the two static settings.
