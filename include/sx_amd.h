@@ -727,6 +727,27 @@ int sx_cem_cautious_rollout(const sx_gp_model* model, const sx_env* env, int E, 
  * SX_FORM_BYOUT, or < 0 for bad arguments (T < 1 among them) and wherever the entry would answer SX_ERR_UNSUPPORTED for
  * the model: the contract of sx_cem_perf_rollout_taylor_form (cautious_mpc.py has no such notion). */
 int sx_cem_cautious_rollout_form(const sx_gp_model* model, int T);
+/* sx_cem_cautious_rollout over E problems with a GP each.  Arguments as sx_cem_cautious_rollout except
+ *   models  host array of the E PACKED models, all of one (n_s, n_u)
+ *   table   dev, the table sx_gp_model_table built from them (the one sx_cem_rollout_multi reads)
+ *   status  dev int32 [E]   one word per problem
+ * There is one env: k_fb, the box, the polytope and beta are the same for all problems.  Output by output for every
+ * problem where any model needs it, with the LDS of the largest model plus the step constants
+ * (sx_cem_cautious_rollout_multi_form); where that form is model e's own (sx_cem_cautious_rollout_form) problem e's numbers
+ * are those of sx_cem_cautious_rollout on model e alone, bit for bit.
+ * SX_ERR_ARG (before any device access) as sx_cem_cautious_rollout, for every model, a NULL table, and for shapes that
+ * differ between the models or from env; SX_ERR_UNSUPPORTED (before any launch) for m > SX_MAX_M, where any model has no
+ * form or the shape no kernel.  Replaces: nothing in the reference's solver; the n_scenarios CautiousMPC solvers of an
+ * experiment run one after another (episode_runner.py:40-123 over cautious_mpc.py:337-442). */
+int sx_cem_cautious_rollout_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int T,
+                                  const double* x0, const double* mean, const double* std, const double* noise,
+                                  double* rows, double* obj_cost, double* con_cost, double* traj, double* sigma,
+                                  double* cov, double* margins, int propagate, int32_t* status, void* stream);
+/* The form sx_cem_cautious_rollout_multi launches for these n models and T (no launch, no device access): SX_FORM_STREAM
+ * where every model's Kstar fits in LDS, SX_FORM_BYOUT as soon as one model needs it, < 0 for bad arguments (T < 1, mixed
+ * shapes or an unpacked model among them) and wherever the entry would answer SX_ERR_UNSUPPORTED: the contract of
+ * sx_cem_perf_rollout_taylor_multi_form over the cautious step constants (cautious_mpc.py has no such notion). */
+int sx_cem_cautious_rollout_multi_form(const sx_gp_model* models, int n, int T);
 
 /* ---- The PILCO saturating cost of a state Gaussian, as a kernel objective of the Taylor rollouts ---------------------------
  * What the reference's cart-pole configs hand to init_solver (defaultconfig_episode.py:113-159 over utils_casadi.py:178-363,
@@ -775,6 +796,15 @@ int sx_cem_cautious_rollout_sat(const sx_gp_model* model, const sx_env* env, con
                                 const double* x0, const double* mean, const double* std, const double* noise, double* rows,
                                 double* obj_cost, double* con_cost, double* traj, double* sigma, double* cov,
                                 double* margins, int propagate, int32_t* status, void* stream);
+/* sx_cem_cautious_rollout_multi with the saturating cost: one cost for all problems, everything else the multi-model
+ * parent's, bit for bit; the form is the one sx_cem_cautious_rollout_multi_form reports.  Replaces: the n_scenarios
+ * CautiousMPC solvers of the reference's cart-pole configs, run one after another (episode_runner.py:40-123 with the cost of
+ * defaultconfig_episode.py:113-159). */
+int sx_cem_cautious_rollout_sat_multi(const sx_gp_model* models, const void* table, const sx_env* env,
+                                      const sx_sat_cost* cost, int E, int P, int T, const double* x0, const double* mean,
+                                      const double* std, const double* noise, double* rows, double* obj_cost,
+                                      double* con_cost, double* traj, double* sigma, double* cov, double* margins,
+                                      int propagate, int32_t* status, void* stream);
 
 /* ---- The saturating cost on the safety trajectory ----------------------------------------------------------------------------
  * sx_cem_rollout, sx_cem_rollout_elites and their _multi forms with the saturating cost as the objective, priced on the

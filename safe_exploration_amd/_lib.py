@@ -150,6 +150,9 @@ SIGNATURES = {
     'sx_cem_cautious_rollout': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 11
                                 + [c_int, c_void_p, c_void_p]),
     'sx_cem_cautious_rollout_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_cem_cautious_rollout_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int]
+                                      + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
+    'sx_cem_cautious_rollout_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
     'sx_sat_cost_eval': (c_int, [POINTER(SxSatCost), c_int, c_int] + [c_void_p] * 5),
     'sx_cem_perf_rollout_taylor_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int,
                                                c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
@@ -158,6 +161,8 @@ SIGNATURES = {
                                              + [c_int, c_void_p, c_void_p]),
     'sx_cem_cautious_rollout_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int]
                                     + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
+    'sx_cem_cautious_rollout_sat_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxSatCost), c_int,
+                                                  c_int, c_int] + [c_void_p] * 11 + [c_int, c_void_p, c_void_p]),
     'sx_cem_rollout_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int]
                            + [c_void_p] * 12),
     'sx_cem_rollout_elites_sat': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxSatCost), c_int, c_int, c_int,

@@ -8,17 +8,18 @@ state (``generate_safety_constraints``, cautious_mpc.py:337-442).  The surface -
 reference's; the NLP is not: ``CautiousCemMpc`` ranks sampled rows by (constraint cost, objective) where the reference hands
 IPOPT one NLP, and the objective is the environment's separable objective or ``-tr G_t`` (DESIGN.md sections 3.11, 7).
 """
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from numpy import ndarray
 
 from . import _lib
-from .cem_mpc import CautiousCemMpc, Rollouts
+from .cem_mpc import CautiousCemMpc, MultiModelCautiousCemMpc, Rollouts
 from .costs import SaturatingCost
 from .gp_reachability_pytorch import make_env
 from .safempc import SafeMPC
+from .ssm_cem import gp_ssm_cem
 from .safempc_cem import LqrFeedbackController, MpcResult, objective_spec
 from .utils import assert_shape, get_device
 
@@ -268,3 +269,68 @@ class CautiousCemMPC(SafeMPC):
 
     def collect_metrics(self) -> Dict[str, float]:
         return self._ssm.collect_metrics()
+
+
+def get_actions_multi(solvers: Sequence[CautiousCemMPC], states: ndarray) -> Tuple[ndarray, List[MpcResult]]:
+    """``get_action`` of several independent Cautious MPC solvers at once -- the cautious arm of the reference's
+    experiments, each scenario with its own model and data (episode_runner.py:40-123) -- where solver e acts in states[e]
+    ([E x n_s]).  Returns (actions [E x n_u], one MpcResult per solver).
+
+    Over ``CautiousCemMpc`` optimisers that is ONE solve for all of them (``MultiModelCautiousCemMpc``: one rollout launch
+    per CEM iteration, each problem with its own GP; where the single launch does not apply, one solve per solver); injected
+    optimisers of another kind solve one at a time.  Either way problem e draws solver e's noise, and every solver keeps its
+    own ladder (``n_fail``, ``k_ff_old``) and warm start (``_init_controls``), exactly as its own ``get_action`` would.  The
+    solvers must agree on the CEM settings, the environment constants (sx_env) and the cost; ValueError otherwise."""
+    solvers = list(solvers)
+    states = np.asarray(states, dtype=np.float64)
+    if not solvers:
+        raise ValueError('get_actions_multi needs at least one solver')
+    n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
+    if states.ndim != 2 or states.shape != (len(solvers), n_s):
+        raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')
+    for s in solvers:
+        if not isinstance(s, CautiousCemMPC):
+            raise ValueError(f'cautious_mpc.get_actions_multi takes CautiousCemMPC solvers, got {type(s).__name__}')
+        if (s.state_dimen, s.action_dimen, s.T) != (n_s, n_u, solvers[0].T):
+            raise ValueError('the solvers of get_actions_multi must share (n_s, n_u) and T')
+    mpcs = [s._solver() for s in solvers]
+    MultiModelCautiousCemMpc.check_solvers(mpcs)
+    starts = [s._init_controls(s.n_fail, s.k_ff_old) for s in solvers]
+    flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
+    if all(isinstance(m, CautiousCemMpc) for m in mpcs):
+        key = tuple(id(m) for m in mpcs)
+        cached = getattr(solvers[0], '_multi', None)
+        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
+            solvers[0]._multi = cached = (key, MultiModelCautiousCemMpc.from_solvers(mpcs))
+        best, found = cached[1].get_actions_multi(flat, init_mean=solvers[0]._warm(starts))
+        rows = [best[e].detach().cpu().numpy().copy() if bool(found[e]) else None for e in range(len(solvers))]
+    else:
+        rows = []
+        for e, (s, m) in enumerate(zip(solvers, mpcs)):
+            row, _ = m.get_actions(flat[e:e + 1], init_mean=s._warm(starts[e:e + 1]))
+            rows.append(row.detach().cpu().numpy() if row is not None else None)
+    actions: List[ndarray] = []
+    results: List[MpcResult] = []
+    for e, s in enumerate(solvers):
+        s.last_rollouts = []
+        action, result, s.n_fail, s.k_ff_old = s._rung(s.n_fail, s.k_ff_old, states[e], rows[e])
+        actions.append(action)
+        results.append(result)
+    return np.stack(actions), results
+
+
+def update_models_multi(solvers: Sequence[CautiousCemMPC], xs: Sequence[ndarray], ys: Sequence[ndarray], opt_hyp=False,
+                        replace_old=True) -> None:
+    """``update_model`` of several independent Cautious MPC solvers at once, the counterpart of ``get_actions_multi`` for
+    the reference's retraining of every scenario's model after an episode (episode_runner.py:55,123): solver e's model
+    learns the error of (xs[e], ys[e]) to its linear prior, as ``CautiousCemMPC.update_model``, and the exact GPs train in
+    lockstep (``gp_ssm_cem.update_models_multi``)."""
+    solvers, xs, ys = list(solvers), list(xs), list(ys)
+    if not len(solvers) == len(xs) == len(ys):
+        raise ValueError(f'{len(solvers)} solvers, {len(xs)} input sets, {len(ys)} target sets')
+    xs_t, ys_t = [], []
+    for s, x, y in zip(solvers, xs, ys):
+        x_s, x_u = x[:, :s.state_dimen], x[:, s.state_dimen:]
+        xs_t.append(torch.tensor(x, device=s._device))
+        ys_t.append(torch.tensor(y - s.eval_prior(x_s, x_u), device=s._device))
+    gp_ssm_cem.update_models_multi([s._ssm for s in solvers], xs_t, ys_t, opt_hyp, replace_old)

@@ -1983,21 +1983,13 @@ class StaticCemMpc:
 
 
 # ---- Cautious MPC ----------------------------------------------------------------------------------
-def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, mean: Optional[Tensor] = None,
-                         std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
-                         propagate: bool = True, want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
-                         want_margins: bool = False, status: Optional[Tensor] = None, cost=None):
-    """Thin wrapper over sx_cem_cautious_rollout: the chance-constrained Taylor rollout of Cautious MPC (exact RBF GPs only).
-    x0 [E x n_s]; the rows k_ff_0 .. k_ff_{T-1} either drawn (`mean`, `std` [E x T x n_u], `noise` [E x P x T x n_u]) or
-    given as `rows` [E x P x T x n_u].  Every step adds SX_ACTION_VIOLATION_COST where the control k_ff_t +- env.beta
-    sqrt(K_c Sigma_t K_c^T) leaves the action box (the plain box at t = 0) and SX_STATE_VIOLATION_COST where the ellipsoid
-    (mu_{t+1}, env.beta, Sigma_{t+1}) leaves env's polytope; `propagate=False` starts every GP step from Sigma_t = 0 (the
-    reference's 'mean_equivalent').  `cost` (a `costs.SaturatingCost`) selects sx_cem_cautious_rollout_sat: obj_cost is the
-    sum of the cost over (mu_{t+1}, Sigma_{t+1}) and env.obj_mode is not read; everything else is unchanged.
-    Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj [E x P x T x n_s] | None, sigma (same shape; diag G_t) | None,
-    cov [E x P x T x n_s x n_s] | None, margins [E x P x T x 2] (largest state, largest control distance) | None, status)."""
-    _require_rbf([ssm], x0)
-    dev, n_s, n_u = x0.device, ssm.num_states, ssm.num_actions
+def _cautious_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, T: int, words: int, unsupported, *, mean, std,
+                      noise, rows, propagate, want_traj, want_sigma, want_cov, want_margins, status):
+    """The buffers and the call of the cautious rollout entries: `head` are the entry's arguments in front of E (the model or
+    models and table, env, the cost), `words` the status words of a fresh status, `unsupported(n_s, n_u)` what
+    SX_ERR_UNSUPPORTED raises."""
+    _require_rbf(ssms, x0)
+    dev, n_s, n_u = x0.device, ssms[0].num_states, ssms[0].num_actions
     T = int(T)
     if T < 1:
         raise ValueError(f'the cautious rollout needs T >= 1 steps, got T={T}')
@@ -2028,16 +2020,67 @@ def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, 
     obj = torch.empty((E, P), dtype=torch.float64, device=dev)
     con = torch.empty((E, P), dtype=torch.float64, device=dev)
     if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    entry = 'sx_cem_cautious_rollout' + ('_sat' if cost is not None else '')
-    code = getattr(_lib.lib(), entry)(ctypes.byref(ssm.device_model), ctypes.byref(env), *_cost_args(cost, ssm), E, P, T,
+        status = torch.zeros(words, dtype=torch.int32, device=dev)
+    code = getattr(_lib.lib(), entry)(*head, E, P, T,
                                       _lib.ptr(x0.contiguous()), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(noise), _lib.ptr(rows),
                                       _lib.ptr(obj), _lib.ptr(con), _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(cov),
                                       _lib.ptr(margins), int(bool(propagate)), _lib.ptr(status), _lib.stream_ptr(dev))
     if code == _lib.SX_ERR_UNSUPPORTED:
-        raise _no_form(entry, 'cautious', ssm, T)(n_s, n_u)
+        raise unsupported(n_s, n_u)
     _lib.check(code, entry)
     return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, cov=cov, margins=margins, status=status)
+
+
+def cem_cautious_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, T: int, *, mean: Optional[Tensor] = None,
+                         std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                         propagate: bool = True, want_traj: bool = False, want_sigma: bool = False, want_cov: bool = False,
+                         want_margins: bool = False, status: Optional[Tensor] = None, cost=None):
+    """Thin wrapper over sx_cem_cautious_rollout: the chance-constrained Taylor rollout of Cautious MPC (exact RBF GPs only).
+    x0 [E x n_s]; the rows k_ff_0 .. k_ff_{T-1} either drawn (`mean`, `std` [E x T x n_u], `noise` [E x P x T x n_u]) or
+    given as `rows` [E x P x T x n_u].  Every step adds SX_ACTION_VIOLATION_COST where the control k_ff_t +- env.beta
+    sqrt(K_c Sigma_t K_c^T) leaves the action box (the plain box at t = 0) and SX_STATE_VIOLATION_COST where the ellipsoid
+    (mu_{t+1}, env.beta, Sigma_{t+1}) leaves env's polytope; `propagate=False` starts every GP step from Sigma_t = 0 (the
+    reference's 'mean_equivalent').  `cost` (a `costs.SaturatingCost`) selects sx_cem_cautious_rollout_sat: obj_cost is the
+    sum of the cost over (mu_{t+1}, Sigma_{t+1}) and env.obj_mode is not read; everything else is unchanged.
+    Returns dict(rows, obj_cost [E x P], con_cost [E x P], traj [E x P x T x n_s] | None, sigma (same shape; diag G_t) | None,
+    cov [E x P x T x n_s x n_s] | None, margins [E x P x T x 2] (largest state, largest control distance) | None, status)."""
+    _require_rbf([ssm], x0)
+    entry = 'sx_cem_cautious_rollout' + ('_sat' if cost is not None else '')
+    head = (ctypes.byref(ssm.device_model), ctypes.byref(env)) + _cost_args(cost, ssm)
+    return _cautious_rollout(entry, head, [ssm], x0, T, 1, _no_form(entry, 'cautious', ssm, int(T)), mean=mean, std=std,
+                             noise=noise, rows=rows, propagate=propagate, want_traj=want_traj, want_sigma=want_sigma,
+                             want_cov=want_cov, want_margins=want_margins, status=status)
+
+
+def cem_cautious_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, T: int, *,
+                               mean: Optional[Tensor] = None, std: Optional[Tensor] = None, noise: Optional[Tensor] = None,
+                               rows: Optional[Tensor] = None, propagate: bool = True, want_traj: bool = False,
+                               want_sigma: bool = False, want_cov: bool = False, want_margins: bool = False,
+                               status: Optional[Tensor] = None, table: Optional[GpModelTable] = None, cost=None):
+    """`cem_cautious_rollout` for E problems with an exact GP each (ssms[e] for problem e) in one launch
+    (sx_cem_cautious_rollout_multi; with `cost` sx_cem_cautious_rollout_sat_multi).  There is one `env` -- the feedback gain,
+    the action box, the polytope and beta are the same for all problems -- and one `cost`.  Buffers as in the single-model
+    wrapper, per problem; `status` is int32 [E], one word per problem.  `table` keeps the device table between calls: the
+    `GpModelTable` of `cem_rollout_multi` (a fresh one is built otherwise).  Raises FusedMultiUnsupported where the library
+    has no single launch for the models (before any launch)."""
+    entry = 'sx_cem_cautious_rollout' + ('_sat' if cost is not None else '') + '_multi'
+    _require_rbf(ssms, x0)
+    if x0.dim() != 2 or len(ssms) != x0.size(0):
+        raise ValueError(f'{len(ssms)} models for x0 of shape {tuple(x0.shape)}: one model per problem')
+    E = x0.size(0)
+    if status is not None and status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    if not isinstance(table, GpModelTable) or table.family != 'rbf':
+        table = GpModelTable()
+    models, dev_table = table.get(ssms, x0.device)
+
+    def unsupported(n_s, n_u):
+        return FusedMultiUnsupported(f'{entry}: no single launch of the cautious rollout for these models ((n_s, n_u) = '
+                                     f'({n_s}, {n_u}), N = {[ssm.device_model.n_train for ssm in ssms]}, T = {int(T)})')
+    head = (models, _lib.ptr(dev_table), ctypes.byref(env)) + _cost_args(cost, ssms[0])
+    return _cautious_rollout(entry, head, ssms, x0, T, E, unsupported, mean=mean, std=std, noise=noise, rows=rows,
+                             propagate=propagate, want_traj=want_traj, want_sigma=want_sigma, want_cov=want_cov,
+                             want_margins=want_margins, status=status)
 
 
 class CautiousCemMpc:
@@ -2053,7 +2096,8 @@ class CautiousCemMpc:
                  num_iterations: int, *, propagate: bool = True, device=None, seed: int = 0, init_std=1.0,
                  record_rollouts: bool = False, process_group=None):
         if isinstance(ssm, (list, tuple)):
-            raise ValueError('CautiousCemMpc solves its problems over ONE model (a GP per problem is not built)')
+            raise ValueError('CautiousCemMpc solves its problems over ONE model: MultiModelCautiousCemMpc solves over a GP per '
+                             'problem')
         family = getattr(ssm, 'kernel_family', 'rbf')
         if family != 'rbf':
             raise NotImplementedError(f'Cautious MPC is built for exact RBF GPs, not kernel_family {family!r} '
@@ -2189,3 +2233,186 @@ class CautiousCemMpc:
                                     rows=rows.to(self._device, torch.float64).contiguous(), propagate=self._propagate,
                                     want_traj=True, want_sigma=True, want_cov=True, want_margins=True,
                                     **({} if self._cost is None else dict(cost=self._cost)))
+
+
+class MultiModelCautiousCemMpc:
+    """E independent Cautious MPC problems with an exact GP each -- the cautious arm of the reference's experiments, one
+    scenario per model (episode_runner.py:40-123) -- solved together: one ``sx_cem_cautious_rollout_multi`` launch
+    (``sx_cem_cautious_rollout_sat_multi`` where the solvers carry a ``SaturatingCost``) and one ranking launch per CEM
+    iteration for all of them, where ``CautiousCemMpc`` needs one solve per model.
+
+    Problem e keeps a ``CautiousCemMpc`` of its own (``solvers[e]``, built here from the same settings with seed
+    ``seed + e`` unless given): it supplies the problem's noise draws (``sample_noise(1)`` of solver e), so a multi-model
+    solve samples exactly what E sequential ``get_actions`` calls would, and it takes over where the single launch does not
+    apply: a model without a form (``FusedMultiUnsupported``; one solve per solver then, ``per_model_solves``) or a solver
+    with an objective hook and no kernel cost.  The solvers share T, particles, elites, iterations, ``propagate``, the
+    initial spread, the environment constants (there is ONE sx_env: k_fb, the box, the polytope, beta) and the cost.
+    """
+
+    # what the solvers of one solve share, by the name a disagreement is reported under
+    _SHARED = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
+               ('num_iterations', '_num_iterations'), ('propagate', '_propagate'), ('device', '_device'))
+
+    def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
+                 num_iterations: int, *, propagate: bool = True, device=None, seed: int = 0, init_std=1.0,
+                 process_group=None, solvers: Optional[Sequence[CautiousCemMpc]] = None):
+        if process_group is not None:
+            raise NotImplementedError('Cautious MPC is not built for sharded particles (a process group)')
+        self._ssms = list(ssms)
+        if not self._ssms:
+            raise ValueError('MultiModelCautiousCemMpc needs at least one model')
+        if len({(s.num_states, s.num_actions) for s in self._ssms}) != 1:
+            raise ValueError('the models of a multi-model solve must share (n_s, n_u)')
+        if solvers is None:
+            solvers = [CautiousCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, propagate=propagate,
+                                      device=device, seed=seed + e, init_std=init_std) for e, ssm in enumerate(self._ssms)]
+        solvers = list(solvers)
+        if len(solvers) != len(self._ssms) or any(s._ssm is not m for s, m in zip(solvers, self._ssms)):
+            raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: solvers[e] solves over ssms[e]')
+        self.check_solvers(solvers)
+        self._solvers = solvers
+        self._table = GpModelTable()
+        self._last_noise = self._last_actions = None
+        self.stepwise_fallbacks = 0     # (what _check_solve counts; the cautious kernel has no step-by-step repeat)
+        self.per_model_solves = 0       # solves that went one solver at a time (single launch not applicable)
+
+    @classmethod
+    def from_solvers(cls, solvers: Sequence[CautiousCemMpc]) -> 'MultiModelCautiousCemMpc':
+        """The multi-model solve over existing single-model solvers, solvers[e] for problem e, with their settings (which
+        `check_solvers` compares)."""
+        first = solvers[0]
+        return cls([s._ssm for s in solvers], first._env, first._horizon, first._num_rollouts, first._num_elites,
+                   first._num_iterations, propagate=first._propagate, device=first._device, solvers=solvers)
+
+    @staticmethod
+    def check_solvers(solvers: Sequence) -> None:
+        """ValueError, naming the setting, unless the solvers share time_horizon, num_rollouts, num_elites, num_iterations,
+        propagate, device, init_std, the environment constants (env) and the cost.  (Read with defaults: an injected
+        optimiser need not be a CautiousCemMpc.)"""
+        def flat(t):
+            return None if t is None else tuple(torch.as_tensor(t).reshape(-1).tolist())
+
+        first = solvers[0]
+        for e, s in enumerate(solvers[1:], start=1):
+            for name, attr in MultiModelCautiousCemMpc._SHARED:
+                a, b = getattr(first, attr, None), getattr(s, attr, None)
+                if a != b:
+                    raise ValueError(f'the solvers of a multi-model cautious solve must share {name}: solver 0 has {a!r}, '
+                                     f'solver {e} has {b!r}')
+            if flat(getattr(first, '_init_std', None)) != flat(getattr(s, '_init_std', None)):
+                raise ValueError(f'the solvers of a multi-model cautious solve must share init_std: solver {e} differs from '
+                                 f'solver 0')
+            env0, env = getattr(first, '_env', None), getattr(s, '_env', None)
+            if (None if env0 is None else bytes(env0)) != (None if env is None else bytes(env)):
+                raise ValueError(f'the solvers of a multi-model cautious solve must share the environment constants (env: '
+                                 f'one sx_env with k_fb, the box, the polytope and beta): solver {e} differs from solver 0')
+            if getattr(first, '_cost', None) != getattr(s, '_cost', None):
+                raise ValueError(f'the solvers of a multi-model cautious solve must share the cost (equal SaturatingCosts '
+                                 f'on all of them, or none on any): solver {e} differs from solver 0')
+
+    @property
+    def solvers(self) -> List[CautiousCemMpc]:
+        return self._solvers
+
+    @property
+    def last_status(self) -> List[int]:
+        """The status word of every problem's last solve."""
+        return [s.last_status for s in self._solvers]
+
+    @property
+    def _env(self) -> _lib.SxEnv:
+        return self._solvers[0]._env      # (check_solvers compares the solvers' before every solve)
+
+    def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
+        """`CautiousCemMpc.set_env` on every solver."""
+        for s in self._solvers:
+            s.set_env(env, objective_hook=objective_hook)
+
+    def set_cost(self, cost) -> None:
+        """`CautiousCemMpc.set_cost` on every solver."""
+        for s in self._solvers:
+            s.set_cost(cost)
+
+    def form(self) -> int:
+        """sx_cem_cautious_rollout_multi_form of the models: < 0 where they have no single launch.  Host only."""
+        first = self._solvers[0]
+        return int(_lib.lib().sx_cem_cautious_rollout_multi_form(model_array(self._ssms, 'rbf'), len(self._ssms),
+                                                                 first._horizon))
+
+    def fused_applies(self) -> bool:
+        """Does one launch serve the solve?  Every model has a form (`form`), and no solver evaluates an objective hook
+        (a hook without a kernel cost: torch on the recorded means, one solver at a time).  Host only."""
+        if any(s._objective_hook is not None and s._cost is None for s in self._solvers):
+            return False
+        return self.form() >= 0
+
+    def solve(self, x0: Tensor, noise: Optional[Tensor] = None, init_mean: Optional[Tensor] = None
+              ) -> Tuple[Tensor, Tensor, Tensor]:
+        """E = len(models) solves from x0 [E x n_s] in one rollout and one ranking launch per iteration.  Nothing
+        synchronises.  noise: optional [iters x E x P x T x n_u] standard normals; by default problem e draws
+        ``solvers[e].sample_noise(1)``.  init_mean [E x T x n_u]: the warm start (default zero).
+        Returns (best [E x T x n_u], best_ok int32 [E], status int32 [E]: one word per problem).
+        Raises FusedMultiUnsupported (before any draw or launch) where the single launch does not apply."""
+        self.check_solvers(self._solvers)
+        first = self._solvers[0]
+        E, T, n_s, n_u = len(self._ssms), first._horizon, self._ssms[0].num_states, self._ssms[0].num_actions
+        if x0.shape != (E, n_s):
+            raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
+        if not self.fused_applies():
+            raise FusedMultiUnsupported(f'no single launch of the cautious solve for these solvers (N = '
+                                        f'{[ssm.device_model.n_train for ssm in self._ssms]}, T = {T}, or an objective '
+                                        f'hook without a kernel cost): the solvers act one at a time')
+        dev = x0.device
+        if noise is None:
+            noise = torch.stack([s.sample_noise(1)[:, 0] for s in self._solvers], dim=1)
+        if tuple(noise.shape) != (first._num_iterations, E, first._num_rollouts, T, n_u):
+            raise ValueError(f'noise must be [{first._num_iterations} x {E} x {first._num_rollouts} x {T} x {n_u}], got '
+                             f'{tuple(noise.shape)}')
+        self._last_noise, self._last_actions = noise, None
+        mean = (init_mean.to(dev, torch.float64).reshape(E, T, n_u).contiguous() if init_mean is not None
+                else torch.zeros((E, T, n_u), dtype=torch.float64, device=dev))
+        std = first._init_std.to(dev).expand(E, T, n_u).contiguous()
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
+        env, cost, propagate, k = first._env, first._cost, first._propagate, first._num_elites
+
+        def rollout(it, mean, std, rows):
+            r = cem_cautious_rollout_multi(self._ssms, env, x0, T, mean=mean.contiguous(), std=std.contiguous(),
+                                           noise=noise[it].contiguous(), propagate=propagate, status=status,
+                                           table=self._table, **({} if cost is None else dict(cost=cost)))
+            self._last_actions = r['rows']
+            return r
+
+        def rank(it, r):
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['rows'], k, want_refit=True)
+
+        out = _cem_iterations(first._num_iterations, rollout, rank, mean, std)
+        return out['best'].view(E, T, n_u), out['best_ok'], status
+
+    def get_actions_multi(self, flat_states: Tensor, init_mean: Optional[Tensor] = None,
+                          where: str = 'get_actions_multi') -> Tuple[Tensor, Tensor]:
+        """Flat start states [E x (n_s + n_s^2)], all points, problem e for model e; `init_mean` [E x T x n_u]: every
+        problem's warm start.  Returns (rows [E x T x n_u] on the host, found bool [E] on the host); ``found[e] == False``
+        is the ``get_actions`` ``None`` of problem e.  Raises like ``CautiousCemMpc.get_actions`` where a problem hit a
+        numerical failure, for that problem only (one status word per problem)."""
+        self.check_solvers(self._solvers)
+        E, n_s = len(self._ssms), self._ssms[0].num_states
+        if flat_states.dim() != 2 or flat_states.shape != (E, n_s + n_s * n_s):
+            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(flat_states.shape)}')
+        dev = self._solvers[0]._device
+        states = flat_states.to(dev, torch.float64)
+        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
+        if init_mean is not None:
+            init_mean = init_mean.to(dev, torch.float64).reshape(E, self._solvers[0]._horizon, -1)
+        if not self.fused_applies():
+            # one solve per solver, each with its own checks
+            self.per_model_solves += 1
+            per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1],
+                                    init_mean=None if init_mean is None else init_mean[e:e + 1])
+                   for e, s in enumerate(self._solvers)]
+            return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
+        best, best_ok, status = self.solve(x0, init_mean=init_mean)
+        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
+                                           [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
+        for s in self._solvers:
+            s.last_rollouts = []
+        return best_host, found

@@ -15,7 +15,8 @@
 // 2 m n_s^2 + 2 n_u n_s^2 FMAs and m + n_u square roots per step on the owner lane.  The covariance step is written as in
 // cem_perf_gp_rollout_kernel (sx_perf_var.hpp), fma for fma: with m = 0 and a wide box mu, diag G and Sigma are the Taylor
 // kernel's bits.
-// A tile's numbers depend on its 16 particles alone.
+// A tile's numbers depend on its 16 particles alone -- in the multi-model mode (MM, sx_cem_cautious_rollout_multi: a GP per
+// problem behind a device table) on them and on its problem's model.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,10 +61,34 @@ struct CautiousSatConst {
 // SAT: the objective section prices (mu_{t+1}, Sigma_{t+1}) with the saturating cost, and the constants argument is a
 // CautiousSatConst; nothing else differs (tools/device_code_diff.py: either instantiation holds the instructions its kernel
 // had as a definition of its own).
-template <int NS, int NU, bool BYOUT, bool SAT = false>
+// MM, TAB...: the conventions of cem_perf_gp_rollout_kernel (sx_perf_var.hpp).  MM = false: the arguments are (GpConst, its
+// stage table, constants, pointers) -- TAB... is that one `const int4* __restrict__`, named by whoever names the kernel.
+// MM = true (a GP per problem): (the device table of sx_gp_model_table, constants, pointers); the workgroup binds its
+// problem's GpConst through a pointer into the constant address space, takes the stage table from it, carves the LDS by the
+// problem's n_train / n_pad inside the launch's allocation for the largest model, and the status is one word per problem.
+// There is one sx_env (and one sx_sat_cost) for all problems.
+template <int NS, int NU, bool BYOUT, bool SAT, bool MM, class... TAB>
 __global__ __launch_bounds__(kPerfVarThreads) void cem_cautious_rollout_kernel(
-    const GpConst<NS, NS + NU> gc, const int4* __restrict__ stage_tab,
+    const std::conditional_t<MM, const GpConst<NS, NS + NU>* __restrict__, GpConst<NS, NS + NU>> gc_arg,
+    const TAB... stage_tab_arg,
     const std::conditional_t<SAT, CautiousSatConst<NS, NU>, CautiousConst<NS, NU>> arg, const CautiousPtrs cp) {
+    static_assert(sizeof...(TAB) == (MM ? 0 : 1), "TAB... is the single-model kernel's stage table");
+    // (the single-model `gc` is the argument itself, bound as in cem_perf_gp_rollout_kernel: a call that takes it by
+    // reference in between changes the single-model kernels' registers)
+    const GpConst<NS, NS + NU>* gc_ptr;
+    if constexpr (MM) {
+        using ConstG = __attribute__((address_space(4))) const GpConst<NS, NS + NU>;
+        const int problem = blockIdx.x / ((cp.p.P + SX_TILE - 1) / SX_TILE);
+        gc_ptr = (const GpConst<NS, NS + NU>*)((ConstG*)gc_arg + problem);
+    } else {
+        gc_ptr = &gc_arg;
+    }
+    const GpConst<NS, NS + NU>& gc = *gc_ptr;
+    const int4* __restrict__ const stage_tab = [&gc](const auto&... tab) {
+        (void)gc;   // (single-model: not read)
+        if constexpr (MM) return gc.stage_tab;
+        else return (tab, ...);
+    }(stage_tab_arg...);
     const CautiousConst<NS, NU>& cc_arg = [&]() -> const CautiousConst<NS, NU>& {
         if constexpr (SAT) return arg.cc;
         else return arg;
@@ -364,7 +389,7 @@ __global__ __launch_bounds__(kPerfVarThreads) void cem_cautious_rollout_kernel(
         const int64_t g = (int64_t)e * pp.P + c0 + tid;
         pp.obj_cost[g] = obj;
         pp.con_cost[g] = con;
-        if (st) atomicOr(pp.status, st);
+        if (st) atomicOr(pp.status + (MM ? e : 0), st);
     }
 }
 

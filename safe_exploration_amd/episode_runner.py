@@ -16,6 +16,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import cautious_mpc
 from .safempc_cem import MpcResult, get_actions_multi
 
 
@@ -52,13 +53,23 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
     episode_runner.py:40-123), served by ``get_actions_multi`` -- one solve per step for the episodes still running, each
     solver with its own ladder, episode e exactly as ``do_rollout`` with solver e.  Solvers that all carry one constraint set
     (``cem_ctrl_ellipsoid_constraint`` / ``cem_obstacle_constraint``) are served the same way, unchanged here: the
-    multi-model launch carries the set (``MultiModelConsCemMpc``).  An episode whose environment reports
+    multi-model launch carries the set (``MultiModelConsCemMpc``).  A list whose members are all ``CautiousCemMPC`` (the
+    cautious arm of the comparison) goes to ``cautious_mpc.get_actions_multi`` in the same way; a list mixing the two solver
+    classes raises ValueError.  An episode whose environment reports
     `done` stops (safety failure, reference :311-313); the others carry on.
     """
     E = len(envs)
     per_episode = isinstance(solver, (list, tuple))
     if per_episode and len(solver) != E:
         raise ValueError(f'{len(solver)} solvers for {E} episodes')
+    multi_actions = get_actions_multi
+    if per_episode:
+        cautious = [isinstance(s, cautious_mpc.CautiousCemMPC) for s in solver]
+        if any(cautious) and not all(cautious):
+            raise ValueError(f'do_rollout_batch takes a list of CemSafeMPC or a list of CautiousCemMPC, not a mix of the two '
+                             f'({sum(cautious)} of {E} are CautiousCemMPC): run each arm in a call of its own')
+        if E and all(cautious):
+            multi_actions = cautious_mpc.get_actions_multi
     ids = list(episode_ids) if episode_ids is not None else list(range(E))
     states = [np.asarray(env.reset(mean, std), dtype=np.float64) for env in envs]
     xx = [[np.zeros(envs[e].n_s + envs[e].n_u)] for e in range(E)]
@@ -84,7 +95,7 @@ def do_rollout_batch(envs: Sequence, n_steps: int, solver=None, metrics=None, ep
             t0 = time.time()
             batch = np.stack([states[e] for e in active])
             if per_episode:
-                acts, step_results = get_actions_multi([solver[e] for e in active], batch)
+                acts, step_results = multi_actions([solver[e] for e in active], batch)
             else:
                 acts, step_results = solver.get_action_batch(batch, episode_ids=active, num_episodes=E)
             dt = time.time() - t0

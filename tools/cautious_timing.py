@@ -15,6 +15,21 @@ Rows (one JSON line each; printed and, with `--out`, appended to that jsonl file
   launch_cautious_me_T  the same with propagate 0
   solve_cautious_T    a CautiousCemMpc solve (config 2's particles, elites and iterations) at T = --solve-steps: median and
                       p95 in ms of `--solves` synchronous solves after `--warmup` untimed ones
+
+    python tools/cautious_timing.py --multi [--models 6] [--multi-steps 10] [--particles 20,4096] [--repeats 7]
+                                    [--launches 200] [--solves 100] [--warmup 20] [--out profiles/cautious_multi_timing.jsonl]
+
+The multi-model mode: `--models` GPs with data and hyper-parameters of their own, over config 2's pendulum (N = 200 - 10 e)
+and over a cart-pole model of the same sizes, T = --multi-steps, at every particle count of `--particles` (the reference's CEM
+shape, 20 rollouts, and 4096 rows per problem).  Rows per (model, P):
+  launch_multi        ONE sx_cem_cautious_rollout_multi launch for all models: us per launch, measured as above
+  launch_sequential   the sum of one sx_cem_cautious_rollout launch per model, measured in alternation with it; `speedup` =
+                      sequential / multi
+  launch_single_e1 / launch_multi_e1   the `MM = false` kernel and the multi-model kernel on model 0 alone (E = 1), in
+                      alternation: `ratio` = multi / single, the per-launch cost of the multi-model mode
+  solve_sequential / solve_multi   `--models` CautiousCemMpc.get_actions in turn against one
+                      MultiModelCautiousCemMpc.get_actions_multi (config 2's elites and iterations; at 20 rollouts 5 elites):
+                      median and p95 in ms of `--solves` synchronous solves after `--warmup` untimed ones; `speedup`
 Needs the GPU.
 """
 import argparse
@@ -29,7 +44,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from safe_exploration_amd import cem_mpc, problems  # noqa: E402
-from safe_exploration_amd.cem_mpc import CautiousCemMpc  # noqa: E402
+from safe_exploration_amd.cem_mpc import CautiousCemMpc, GpModelTable, MultiModelCautiousCemMpc  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -45,6 +60,88 @@ def time_launches(fn, n, warmup):
     return (time.perf_counter() - t0) * 1e6 / n
 
 
+def time_solves(fn, n, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ms)), float(np.percentile(ms, 95))
+
+
+def multi_mode(args, row):
+    """One multi-model launch / solve against one per model, for the pendulum and a cart-pole model."""
+    wl = problems.baseline_workload(2)
+    E, T = args.models, args.multi_steps
+    sizes = [200 - 10 * e for e in range(E)]
+    families = (('pendulum', [problems.pendulum(n_train=n, seed=e) for e, n in enumerate(sizes)]),
+                ('cartpole', [problems.cartpole(n_train=n, seed=2 + e) for e, n in enumerate(sizes)]))
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(0)
+    for family, specs in families:
+        for e, spec in enumerate(specs):       # hyper-parameters of their own
+            spec.lengthscale, spec.outputscale = spec.lengthscale * (0.8 + 0.1 * e), spec.outputscale * (1.0 + 0.1 * e)
+        built = [problems.build(spec, device=DEV) for spec in specs]
+        ssms, env = [b[0] for b in built], built[0][1]
+        n_s, n_u = specs[0].n_s, specs[0].n_u
+        x0 = torch.tensor(problems.start_states(n_s, E, seed=5, std=0.03), dtype=torch.float64, device=DEV)
+        flat = torch.zeros((E, n_s + n_s * n_s), dtype=torch.float64, device=DEV)
+        flat[:, :n_s] = x0
+        for P in [int(p) for p in args.particles.split(',')]:
+            info = dict(model=family, E=E, N=sizes, P=P, T=T)
+            mean = torch.zeros((E, T, n_u), dtype=torch.float64, device=DEV)
+            std = torch.full((E, T, n_u), wl.init_std, dtype=torch.float64, device=DEV)
+            noise = torch.randn((E, P, T, n_u), dtype=torch.float64, device=DEV, generator=gen)
+            table, table1 = GpModelTable(), GpModelTable()
+            st_e, st_1 = (torch.zeros(n, dtype=torch.int32, device=DEV) for n in (E, 1))
+            per = [(x0[e:e + 1].contiguous(), mean[e:e + 1].contiguous(), std[e:e + 1].contiguous(),
+                    noise[e:e + 1].contiguous()) for e in range(E)]
+
+            def multi():
+                cem_mpc.cem_cautious_rollout_multi(ssms, env, x0, T, mean=mean, std=std, noise=noise, status=st_e, table=table)
+
+            def single(e):
+                a, m, s, z = per[e]
+                cem_mpc.cem_cautious_rollout(ssms[e], env, a, T, mean=m, std=s, noise=z, status=st_1)
+
+            def sequential():
+                for e in range(E):
+                    single(e)
+
+            def multi_e1():
+                a, m, s, z = per[0]
+                cem_mpc.cem_cautious_rollout_multi(ssms[:1], env, a, T, mean=m, std=s, noise=z, status=st_1, table=table1)
+
+            kinds = (('multi', multi), ('sequential', sequential), ('single_e1', lambda: single(0)), ('multi_e1', multi_e1))
+            us = {name: [] for name, _ in kinds}
+            for _ in range(args.repeats):
+                for name, fn in kinds:                  # in alternation: a drift of the clocks meets all alike
+                    us[name].append(time_launches(fn, args.launches, args.warmup))
+            med = {name: float(np.median(v)) for name, v in us.items()}
+            stats = lambda name: dict(us=med[name], us_min=min(us[name]), us_max=max(us[name]), repeats=args.repeats,
+                                      launches=args.launches)
+            row(row='launch_multi', **info, **stats('multi'))
+            row(row='launch_sequential', **info, **stats('sequential'), speedup=med['sequential'] / med['multi'])
+            row(row='launch_single_e1', **info, **stats('single_e1'))
+            row(row='launch_multi_e1', **info, **stats('multi_e1'), ratio=med['multi_e1'] / med['single_e1'])
+            elites = min(wl.elites, max(P // 4, 1))
+            solvers = [CautiousCemMpc(ssm, env, T, P, elites, wl.iterations, device=DEV, init_std=wl.init_std, seed=e)
+                       for e, ssm in enumerate(ssms)]
+            mpc = MultiModelCautiousCemMpc.from_solvers(solvers)
+            assert mpc.fused_applies()
+            seq_ms = time_solves(lambda: [s.get_actions(flat[e:e + 1]) for e, s in enumerate(solvers)], args.solves,
+                                 args.warmup)
+            multi_ms = time_solves(lambda: mpc.get_actions_multi(flat), args.solves, args.warmup)
+            solve = dict(info, iters=wl.iterations, elites=elites, solves=args.solves)
+            row(row='solve_sequential', **solve, median_ms=seq_ms[0], p95_ms=seq_ms[1])
+            row(row='solve_multi', **solve, median_ms=multi_ms[0], p95_ms=multi_ms[1], speedup=seq_ms[0] / multi_ms[0],
+                per_model_solves=mpc.per_model_solves)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--steps', default='10,20')
@@ -54,10 +151,22 @@ def main():
     ap.add_argument('--solves', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--multi', action='store_true', help='the multi-model mode')
+    ap.add_argument('--models', type=int, default=6)
+    ap.add_argument('--multi-steps', type=int, default=10)
+    ap.add_argument('--particles', default='20,4096')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('cautious_timing.py needs the GPU')
     out = open(args.out, 'a') if args.out else None
+    if args.multi:
+        def multi_row(**kw):
+            line = json.dumps(dict(workload='cautious multi', **kw))
+            print(line, flush=True)
+            if out:
+                out.write(line + '\n')
+                out.flush()
+        return multi_mode(args, multi_row)
     wl = problems.baseline_workload(2)
     ssm, env = problems.build(wl.spec, device=DEV)
     P = wl.particles

@@ -12,7 +12,8 @@ compiles more than once (two translation units would each register a copy: the L
 one), and the kernels that differ, with the first differing line; exits 1 if there is any of them.  A kernel whose
 symbol only one side has is then looked for on the other side by content (its own symbol replaced by a placeholder in
 all three parts): a template that gained a parameter renames every instantiation, and such a kernel is reported as
-`renamed` and counts as identical, not as a finding.  DESIGN.md section 3.5 describes the method.  SX_EXTRA_FLAGS is
+`renamed` and counts as identical, not as a finding.  --added REGEX names the kernels a change adds on purpose: a symbol
+only the new side has that matches is printed as `added` and is no finding either.  DESIGN.md section 3.5 describes the method.  SX_EXTRA_FLAGS is
 passed on as csrc/build.sh does.
 """
 import argparse
@@ -121,6 +122,8 @@ def main():
     ap.add_argument('old_csrc')
     ap.add_argument('new_csrc')
     ap.add_argument('-j', '--jobs', type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument('--added', metavar='REGEX', help='kernels only the new side has whose symbol matches are the change\'s '
+                    'own: printed as `added`, not counted as findings')
     args = ap.parse_args()
     old, new = compile_dir(args.old_csrc, args.jobs), compile_dir(args.new_csrc, args.jobs)
     bad = 0
@@ -128,8 +131,13 @@ def main():
     for a, b in sorted(pairs.items()):
         print(f'renamed: {a} ({old[a][0][0]}) -> {b} ({new[b][0][0]})')
     moved = set(pairs) | set(pairs.values())
+    added = 0
     for side, here, there in (('old', old, new), ('new', new, old)):
         for name in sorted(set(here) - set(there) - moved):
+            if side == 'new' and args.added and re.search(args.added, name):
+                print(f'added: {name} ({here[name][0][0]})')
+                added += 1
+                continue
             print(f'only in {side}: {name} ({here[name][0][0]})')
             bad += 1
         for name in sorted(here):
@@ -149,7 +157,7 @@ def main():
         else:
             same += 1
     print(f'{len(old)} kernels in old, {len(new)} in new, {same} identical, {len(pairs)} renamed and identical, '
-          f'{bad} findings')
+          f'{added} added, {bad} findings')
     return 1 if bad else 0
 
 
