@@ -934,6 +934,36 @@ int sx_cem_rollout_starts_cons(const sx_gp_model* model, const sx_env* env, cons
                                const double* mean, const double* std, const double* noise, double* rows, double* traj,
                                double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
 
+/* sx_cem_rollout_starts over E problems with an exact GP each in ONE launch (static exploration of several scenarios at
+ * once, every scenario with its restarts): problem e is rolled out under models[e] and entry e of `table`
+ * (sx_gp_model_table over the same E models, unchanged); a scenario with R restarts stands R times in `models` and in the
+ * table.  All models share (n_s, n_u) and the env.  Buffers are sx_cem_rollout_starts' ([E x L] mean and std, so that every
+ * problem has a start distribution of its own); status holds one word PER PROBLEM.  Problem e's outputs are those of
+ * sx_cem_rollout_starts(models + e, E = 1) on its slice of the buffers, bit for bit where that model's own form
+ * (sx_cem_rollout_starts_form) is the launch's; where another model moves the launch to SX_FORM_BYOUT, con_cost and
+ * status are the same and the rest agrees to the rollout's rounding ("the multi-model form").
+ * SX_ERR_ARG (before any device access) for null models / table / env / rows / cost / status pointers, non-positive sizes,
+ * noise without mean / std, any model whose (n_s, n_u) differ from env's or whose training set is empty; SX_ERR_UNSUPPORTED
+ * (before any launch) exactly where sx_cem_rollout_starts_multi_form answers < 0, or env->m > SX_MAX_M.
+ * Replaces: the per-scenario loop over StaticSafeMPCExploration's NLP solves (sacred_helper.py's n_scenarios runs of
+ * safempc_exploration.py:281-330). */
+int sx_cem_rollout_starts_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                const double* mean, const double* std, const double* noise, double* rows, double* traj,
+                                double* sigma, double* obj_cost, double* con_cost, int32_t* status /* [E] */, void* stream);
+/* sx_cem_rollout_starts_multi with the constraint set of sx_cem_rollout_starts_cons in the step: ONE set, shared by all
+ * problems.  With the empty set every output is sx_cem_rollout_starts_multi's.  SX_ERR_ARG as sx_cem_rollout_starts_multi,
+ * then as sx_cem_rollout_starts_cons for the set; SX_ERR_UNSUPPORTED where sx_cem_rollout_starts_multi answers it.
+ * Replaces: as sx_cem_rollout_starts_multi, with the constraint groups of safempc_exploration.py:100-233. */
+int sx_cem_rollout_starts_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env,
+                                     const sx_con_set* cons, int E, int P, int H, const double* mean, const double* std,
+                                     const double* noise, double* rows, double* traj, double* sigma, double* obj_cost,
+                                     double* con_cost, int32_t* status /* [E] */, void* stream);
+/* The form sx_cem_rollout_starts[_cons]_multi launch for these models and H (no launch, no device access): the fold of
+ * sx_cem_rollout_starts_form over the models -- SX_FORM_BYOUT where any model needs it, < 0 where any model has no form or
+ * for bad arguments.  The contract of sx_cem_rollout_multi_form.
+ * Replaces: nothing in the reference. */
+int sx_cem_rollout_starts_multi_form(const sx_gp_model* models, int E, int H);
+
 /* The ONE device -> host hand-off of a solve, packed by one launch: out dev double [G + E + 1 + E*row_len] =
  *   [status words of the G ranks | best_ok[E] | 1.0 if any of the `q_count` doubles at `q_block` is non-zero | best [E x row_len]]
  * (q_block may be NULL: the flag is 0).  The caller copies `out` to the host once and reads everything from it.

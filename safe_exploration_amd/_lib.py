@@ -186,6 +186,11 @@ SIGNATURES = {
     'sx_cem_rollout_cons_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
     'sx_cem_rollout_starts_cons': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), POINTER(SxConSet), c_int, c_int, c_int]
                                    + [c_void_p] * 10),
+    'sx_cem_rollout_starts_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int]
+                                    + [c_void_p] * 10),
+    'sx_cem_rollout_starts_cons_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), POINTER(SxConSet), c_int,
+                                                 c_int, c_int] + [c_void_p] * 10),
+    'sx_cem_rollout_starts_multi_form': (c_int, [POINTER(SxGpModel), c_int, c_int]),
     'sx_profile_enable': (c_int, [c_int]),
     'sx_profile_stride': (c_int, [c_int]),
     'sx_profile_stride_kind': (c_int, [c_int, c_int]),

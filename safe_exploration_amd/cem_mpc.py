@@ -357,6 +357,58 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
                     want_dist=want_dist)
 
 
+def cem_rollout_starts_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, horizon: int, *, mean: Optional[Tensor] = None,
+                             std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                             want_traj: bool = False, want_sigma: bool = False, status: Optional[Tensor] = None,
+                             table: Optional[GpModelTable] = None, con_set=None):
+    """`cem_rollout_starts` for E problems with an exact RBF GP each (ssms[e] for problem e; a scenario with R restarts
+    stands R times in the list), one launch: sx_cem_rollout_starts_multi, with `con_set` (ONE set for all problems)
+    sx_cem_rollout_starts_cons_multi.  Buffers as in `cem_rollout_starts` (`mean`, `std` [E x L]: a start distribution per
+    problem); `status` is int32 [E], one word per problem.  `table` keeps the device table of the models between calls.
+    Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch)."""
+    for ssm in ssms:
+        _require_rbf_starts(ssm)
+        if con_set is not None:
+            _require_rbf_con_set(ssm)
+    n_s, n_u = ssms[0].num_states, ssms[0].num_actions
+    L = n_s + horizon * n_u
+    given = rows if noise is None else noise
+    if (noise is None) == (rows is None) or given.dim() != 3 or given.size(2) != L or not given.is_contiguous():
+        raise ValueError(f'either noise (the rows are drawn) or rows (given), a contiguous [E x P x {L}] tensor')
+    _lib.require_gpu(given, 'rows' if noise is None else 'noise')
+    E, P, dev = given.size(0), given.size(1), given.device
+    if len(ssms) != E:
+        raise ValueError(f'{len(ssms)} models for {E} problems')
+    if status is not None and status.numel() != E:
+        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+    if noise is not None:
+        if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
+            raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
+        mean, std = mean.contiguous(), std.contiguous()
+        rows = torch.empty((E, P, L), dtype=torch.float64, device=dev)
+    if table is None or table.family != 'rbf':
+        table = GpModelTable()
+    models, tab = table.get(ssms, dev)
+    entry, head = 'sx_cem_rollout_starts_multi', (models, _lib.ptr(tab), ctypes.byref(env))
+    if con_set is not None:
+        entry, head = 'sx_cem_rollout_starts_cons_multi', head + (_con_set_arg(con_set),)
+    S = n_s + n_s * n_s
+    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
+    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
+    con = torch.empty((E, P), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
+    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, _lib.ptr(mean if noise is not None else None),
+                                      _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
+                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                      _lib.stream_ptr(dev))
+    if code == _lib.SX_ERR_UNSUPPORTED:
+        raise FusedMultiUnsupported(f'{entry}: no single-launch form for the models')
+    _lib.check(code, entry)
+    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+
+
 class FusedJunkUnsupported(_lib.SxError):
     """sx_cem_rollout_junk answered SX_ERR_UNSUPPORTED (before any launch): the solve goes step by step."""
 
@@ -1980,6 +2032,186 @@ class StaticCemMpc:
         if e is None:
             return None
         return host[e, :n_s].clone(), host[e, n_s:L].reshape(self._horizon, n_u).clone(), float(host[e, L + 1])
+
+
+class MultiModelStaticCemMpc:
+    """S independent static-exploration problems with an exact GP each -- the reference's scenarios, one model per scenario
+    (sacred_helper.py's n_scenarios runs of StaticSafeMPCExploration) -- solved together: scenario s with its R restarts is
+    the problems e = s R .. s R + R - 1 of ONE ``sx_cem_rollout_starts_multi`` launch (``sx_cem_rollout_starts_cons_multi``
+    where the solvers carry a constraint set) and one ranking launch per CEM iteration, where ``StaticCemMpc`` needs a
+    solve per scenario ("the multi-model form").
+
+    Scenario s keeps its ``StaticCemMpc`` (``solvers[s]``): it supplies the scenario's start distribution (rows of the
+    [E x L] mean and std, so the scenarios' may differ) and noise draws (``sample_noise()``: its generators advance exactly
+    as in a solve of its own), decides among its restarts (``StaticCemMpc.choose``), takes the step-by-step repeat of a
+    scenario whose status has SX_STATUS_NAN | SX_STATUS_ZERO_FIX, and solves alone where the models have no single launch
+    (``fused_applies``).  The solvers share (n_s, n_u), the horizon, particles, elites, iterations, restarts, the device, ONE
+    sx_env and ONE constraint set (or none)."""
+
+    # what the solvers of one solve share, by the name a disagreement is reported under
+    _SHARED = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
+               ('num_iterations', '_num_iterations'), ('n_restarts', '_restarts'), ('device', '_device'),
+               ('record_rollouts', '_record'))
+
+    def __init__(self, solvers: Sequence[StaticCemMpc]):
+        solvers = list(solvers)
+        if not solvers:
+            raise ValueError('MultiModelStaticCemMpc needs at least one solver')
+        self.check_solvers(solvers)
+        self._solvers = solvers
+        self._table = GpModelTable()
+        self.stepwise_fallbacks = 0     # scenarios repeated step by step
+        self.per_model_solves = 0       # finds that went one scenario at a time (single launch not applicable)
+
+    @classmethod
+    def from_solvers(cls, solvers: Sequence[StaticCemMpc]) -> 'MultiModelStaticCemMpc':
+        """The multi-model solve over existing single-model solvers, solvers[s] for scenario s, with their settings (which
+        `check_solvers` compares)."""
+        return cls(solvers)
+
+    @staticmethod
+    def check_solvers(solvers: Sequence) -> None:
+        """ValueError, naming the mismatch, unless the solvers share (n_s, n_u), time_horizon, num_rollouts, num_elites,
+        num_iterations, n_restarts, device, the environment constants (sx_env, byte for byte) and the constraint set (byte
+        for byte); NotImplementedError where only some solvers carry a set (naming con_set), or for a model that is not an
+        exact RBF GP."""
+        for s, m in enumerate(solvers):
+            family = getattr(m._ssm, 'kernel_family', 'rbf')
+            if family != 'rbf':
+                raise NotImplementedError(f'a multi-model static solve is built for exact RBF GPs: solver {s} has '
+                                          f'kernel_family {family!r}')
+        first = solvers[0]
+        shape0 = (first._ssm.num_states, first._ssm.num_actions)
+        sets = [getattr(m, '_con_set', None) for m in solvers]
+        if any(c is None for c in sets) and any(c is not None for c in sets):
+            raise NotImplementedError(f'the solvers of a multi-model static solve all carry a constraint set (con_set) or '
+                                      f'none does: {sum(c is not None for c in sets)} of {len(sets)} have one')
+        for s, m in enumerate(solvers[1:], start=1):
+            shape = (m._ssm.num_states, m._ssm.num_actions)
+            if shape != shape0:
+                raise ValueError(f'the solvers of a multi-model static solve must share (n_s, n_u): solver 0 has {shape0}, '
+                                 f'solver {s} has {shape}')
+            for name, attr in MultiModelStaticCemMpc._SHARED:
+                a, b = getattr(first, attr, None), getattr(m, attr, None)
+                if a != b:
+                    raise ValueError(f'the solvers of a multi-model static solve must share {name}: solver 0 has {a!r}, '
+                                     f'solver {s} has {b!r}')
+            if bytes(first._env) != bytes(m._env):
+                raise ValueError(f'the solvers of a multi-model static solve must share the environment constants (env: '
+                                 f'one sx_env): solver {s} differs from solver 0')
+            if sets[0] is not None and bytes(sets[0]) != bytes(sets[s]):
+                raise ValueError(f'the solvers of a multi-model static solve must share one constraint set (con_set): '
+                                 f'solver {s} differs from solver 0')
+
+    @property
+    def solvers(self) -> List[StaticCemMpc]:
+        return self._solvers
+
+    @property
+    def last_status(self) -> List[int]:
+        """The status word of every scenario's last find."""
+        return [s.last_status for s in self._solvers]
+
+    def _models(self) -> List[GpCemSSM]:
+        """The model of every problem: scenario s's, once per restart."""
+        return [s._ssm for s in self._solvers for _ in range(s._restarts)]
+
+    def form(self) -> int:
+        """sx_cem_rollout_starts_multi_form of the problems' models: < 0 where they have no single launch.  Host only."""
+        ssms = self._models()
+        return int(_lib.lib().sx_cem_rollout_starts_multi_form(model_array(ssms, 'rbf'), len(ssms),
+                                                               self._solvers[0]._horizon))
+
+    def fused_applies(self) -> bool:
+        """Does one launch serve all scenarios (`form`)?  Host only."""
+        return self.form() >= 0
+
+    def sample_noise(self) -> Tensor:
+        """[iters x S R x P x L]: every solver's own `sample_noise()`, along the problem axis."""
+        return torch.cat([s.sample_noise() for s in self._solvers], dim=1)
+
+    def solve(self, noise: Optional[Tensor] = None):
+        """The S R solves in the same launches.  Nothing here synchronises with the host.
+        noise: optional [iters x S R x P x L] standard normals; by default scenario s draws ``solvers[s].sample_noise()``.
+        Returns (best [E x L], costs [E x 2]: (con, obj) of the best rows, best_ok int32 [E], per scenario the rollouts per
+        iteration (if recorded), status int32 [E]: one word per problem).
+        Raises FusedMultiUnsupported (before any launch) where the single launch does not apply."""
+        self.check_solvers(self._solvers)
+        first = self._solvers[0]
+        S, R, P, L, dev = len(self._solvers), first._restarts, first._num_rollouts, first._row_len, first._device
+        E, H, k, iters = S * R, first._horizon, first._num_elites, first._num_iterations
+        if noise is None:
+            noise = self.sample_noise()
+        if tuple(noise.shape) != (iters, E, P, L):
+            raise ValueError(f'noise must be [{iters} x {E} x {P} x {L}], got {tuple(noise.shape)}')
+        for s, m in enumerate(self._solvers):
+            m._last_noise = noise[:, s * R:(s + 1) * R]
+        ssms = self._models()
+        n_s, n_u = ssms[0].num_states, ssms[0].num_actions
+        mean = torch.cat([m._mean0.expand(R, L) for m in self._solvers]).contiguous()
+        std = torch.cat([m._std0.expand(R, L) for m in self._solvers]).contiguous()
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
+        histories: List[List[Rollouts]] = [[] for _ in range(S)]
+        con_kw = first._con_set_kw
+
+        def rollout(it, mean, std, rows):
+            r = cem_rollout_starts_multi(ssms, first._env, H, mean=mean, std=std, noise=noise[it].contiguous(),
+                                         want_traj=first._record, status=status, table=self._table, **con_kw)
+            if first._record:
+                for e in range(E):
+                    histories[e // R].append(Rollouts(r['traj'][e], r['rows'][e, :, n_s:].reshape(P, H, n_u),
+                                                      r['obj_cost'][e], r['con_cost'][e]))
+            return r
+
+        def rank(it, r):
+            return cem_rank_refit_any(r['con_cost'], r['obj_cost'], r['rows'], k, want_rows=it == iters - 1,
+                                      want_refit=True)
+
+        out = _cem_iterations(iters, rollout, rank, mean, std)
+        return out['best'].view(E, L), out['elite_rows'][:, 0, :2], out['best_ok'], histories, status
+
+    def find(self, noise: Optional[Tensor] = None) -> list:
+        """Entry s is what ``solvers[s].find(noise_s)`` returns -- (x0 [n_s], actions [H x n_u], objective) of the scenario's
+        best feasible restart on the host, or None -- and solver s holds the scenario's `last_rows`, `last_costs`,
+        `last_choice` and `last_status`.  ONE device -> host hand-off for all scenarios.  A scenario whose status words carry
+        SX_STATUS_NAN | SX_STATUS_ZERO_FIX is repeated alone, step by step, with its own draws; a NaN raises as
+        `StaticCemMpc.find` does, naming the scenario.  Where the models have no single launch (`fused_applies`), the
+        scenarios are solved one by one with the same noise."""
+        self.check_solvers(self._solvers)
+        first = self._solvers[0]
+        S, R, L, H = len(self._solvers), first._restarts, first._row_len, first._horizon
+        n_s, n_u = first._ssm.num_states, first._ssm.num_actions
+        if noise is None:
+            noise = self.sample_noise()
+        if not self.fused_applies():
+            self.per_model_solves += 1
+            return [m.find(noise[:, s * R:(s + 1) * R].contiguous()) for s, m in enumerate(self._solvers)]
+        best, costs, best_ok, histories, status = self.solve(noise)
+        words, found, _, host = _hand_off(self, torch.cat([best, costs], dim=1), best_ok, status, None)
+        both = _lib.SX_STATUS_NAN | _lib.SX_STATUS_ZERO_FIX
+        for s, m in enumerate(self._solvers):
+            sl = slice(s * R, (s + 1) * R)
+            st = fold_status(words[sl])
+            if (st & both) == both:
+                # (as StaticCemMpc.find: the reference's whole-batch zero fix-up, for this scenario only)
+                self.stepwise_fallbacks += 1
+                m.stepwise_fallbacks += 1
+                b, c, ok, histories[s], st_s = m.solve(noise[:, sl].contiguous(), stepwise=True)
+                w, found[sl], _, host[sl] = _hand_off(m, torch.cat([b, c], dim=1), ok, st_s, None)
+                st = fold_status(w)
+            m.last_status = st
+            m.last_rollouts = histories[s]
+        answers = []
+        for s, m in enumerate(self._solvers):
+            sl = slice(s * R, (s + 1) * R)
+            raise_for_status(m.last_status, f'MultiModelStaticCemMpc.find (scenario {s})',
+                             dump=lambda m=m: save_failure_state(m._ssm, m._mean0[:n_s], None))
+            rows = host[sl].clone()
+            m.last_rows, m.last_costs = rows[:, :L], rows[:, L:]
+            m.last_choice = e = StaticCemMpc.choose(found[sl], rows[:, L + 1])
+            answers.append(None if e is None else (rows[e, :n_s].clone(), rows[e, n_s:L].reshape(H, n_u).clone(),
+                                                   float(rows[e, L + 1])))
+        return answers
 
 
 # ---- Cautious MPC (DESIGN.md section 3.11) ----------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 // sx_stream_launch.hpp), the launch in that form through the launchers of sx_rw_launch.hpp,
 // sx_stream_launch.hpp and sx_big_launch.hpp (launch_rollout), the one host path of the entries that have the streaming
 // kernel only (stream_rollout), the GP model table, and sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi,
-// sx_cem_rollout_starts, sx_cem_rollout_starts_cons, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
+// sx_cem_rollout_starts[_cons][_multi], sx_cem_rollout_starts_multi_form, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
 // sx_cem_rollout_workspace_bytes, and the entries with the saturating cost on the safety ellipsoids,
 // sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form, and those with the SafeMPC constraint set in the step,
 // sx_cem_rollout[_elites]_cons[_multi], sx_cem_rollout_cons_form, sx_cem_rollout_cons_multi_form.  No kernel is compiled here.
@@ -317,19 +317,22 @@ int sx_cem_rollout_elites_junk(const sx_gp_model* model, const sx_env* env, int 
 
 int sx_cem_rollout_starts_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
 
-// sx_cem_rollout_starts[_cons]'s own argument checks (before anything touches the device)
-static bool starts_args_ok(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
-                           const double* std, const double* noise, const double* rows, const double* obj_cost,
-                           const double* con_cost, const int32_t* status) {
+// sx_cem_rollout_starts[_cons][_multi]'s own argument checks (before anything touches the device), over the `n_models`
+// models behind `model`: 1, or with the multi-model entries one per problem (E of them, as multi_models_ok reads them)
+static bool starts_args_ok(const sx_gp_model* model, int n_models, const sx_env* env, int E, int P, int H,
+                           const double* mean, const double* std, const double* noise, const double* rows,
+                           const double* obj_cost, const double* con_cost, const int32_t* status) {
     if (!model || !env || !rows || !obj_cost || !con_cost || !status || E <= 0 || P <= 0 || H <= 0) return false;
     if (noise && !(mean && std)) return false;
-    return model->n_s == env->n_s && model->n_u == env->n_u && model->n_train > 0 && model->n_pad > 0;
+    for (int i = 0; i < n_models; ++i)
+        if (model[i].n_s != env->n_s || model[i].n_u != env->n_u || model[i].n_train <= 0 || model[i].n_pad <= 0) return false;
+    return true;
 }
 
 int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
                           const double* std, const double* noise, double* rows, double* traj, double* sigma,
                           double* obj_cost, double* con_cost, int32_t* status, void* stream) {
-    if (!starts_args_ok(model, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    if (!starts_args_ok(model, 1, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status)) return SX_ERR_ARG;
     // (x0, q0 and the elite-row fields stay empty: the kernel reads the start of a particle from its row)
     const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
     return sx::stream_dispatch<sx::StreamStarts>(model, nullptr, env, nullptr, rp, stream);
@@ -338,10 +341,35 @@ int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, in
 int sx_cem_rollout_starts_cons(const sx_gp_model* model, const sx_env* env, const sx_con_set* cons, int E, int P, int H,
                                const double* mean, const double* std, const double* noise, double* rows, double* traj,
                                double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
-    if (!starts_args_ok(model, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    if (!starts_args_ok(model, 1, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status)) return SX_ERR_ARG;
     if (!sx::con_set_ok(cons, env->n_s)) return SX_ERR_ARG;
     const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
     return sx::stream_dispatch<sx::StreamStartsCons>(model, nullptr, env, nullptr, rp, stream, cons);
+}
+
+int sx_cem_rollout_starts_multi_form(const sx_gp_model* models, int E, int H) {
+    return sx::multi_models_ok(models, E) ? sx::stream_form(models, E, H) : -1;
+}
+
+// (problem e rolls out under models[e] and entry e of `table`; a scenario with R restarts stands R times in both)
+int sx_cem_rollout_starts_multi(const sx_gp_model* models, const void* table, const sx_env* env, int E, int P, int H,
+                                const double* mean, const double* std, const double* noise, double* rows, double* traj,
+                                double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
+    if (!starts_args_ok(models, E, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status) || !table)
+        return SX_ERR_ARG;
+    const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::stream_dispatch<sx::StreamStartsMulti>(models, table, env, nullptr, rp, stream);
+}
+
+int sx_cem_rollout_starts_cons_multi(const sx_gp_model* models, const void* table, const sx_env* env,
+                                     const sx_con_set* cons, int E, int P, int H, const double* mean, const double* std,
+                                     const double* noise, double* rows, double* traj, double* sigma, double* obj_cost,
+                                     double* con_cost, int32_t* status, void* stream) {
+    if (!starts_args_ok(models, E, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status) || !table)
+        return SX_ERR_ARG;
+    if (!sx::con_set_ok(cons, env->n_s)) return SX_ERR_ARG;
+    const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::stream_dispatch<sx::StreamStartsConsMulti>(models, table, env, nullptr, rp, stream, cons);
 }
 
 int64_t sx_gp_model_table_bytes(int n_s, int n_u, int E) {

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
     constexpr int SH = V::SH;
     constexpr bool MM = V::MM;
     static_assert(sizeof...(X) == (V::CONS ? 1 : 0) + (V::SAT ? 1 : 0), "X... is [ConConst<NS>][, SatConst<NS>]");
-    static_assert(!V::PS || (SH == 0 && !MM && !V::SAT), "the per-particle starts: plain models, one GP, the quadratic cost");
+    static_assert(!V::PS || (SH == 0 && !V::SAT), "the per-particle starts: plain models, the quadratic cost");
     static_assert(!(V::SAT || V::CONS) || SH == 0, "the saturating cost and the constraint set: no query shift");
     static_assert(kernel_arg_bytes<decltype(gc_arg), const int4*, ReachConst<NS, NU>, CostConst<SX_MAX_M, NS, NU>, RolloutPtrs,
                                    X...>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");

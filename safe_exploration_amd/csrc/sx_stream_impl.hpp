@@ -1,7 +1,7 @@
 // Body of launch_stream<V, NS, NU> (sx_stream_launch.hpp), the one launcher of the streaming rollout kernels; included by
 // sx_stream_ns*.hip, sx_stream_multi.hip, sx_stream_starts.hip, sx_stream_sat.hip, sx_stream_sat_multi.hip,
-// sx_stream_cons.hip, sx_stream_cons_sat.hip, sx_stream_cons_multi.hip, sx_stream_cons_sat_multi.hip and
-// sx_stream_starts_cons.hip, which instantiate it for their variant V and so compile that variant's kernels.
+// sx_stream_cons.hip, sx_stream_cons_sat.hip, sx_stream_cons_multi.hip, sx_stream_cons_sat_multi.hip,
+// sx_stream_starts_cons.hip, sx_stream_starts_multi.hip and sx_stream_starts_cons_multi.hip, which instantiate it for their variant V and so compile that variant's kernels.
 #pragma once
 #include <climits>
 #include <tuple>
@@ -53,7 +53,7 @@ int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc
 }  // namespace sx
 
 // launch_stream of variant V (the trailing argument: StreamPlain<SH>, StreamPlain<0, true>, StreamStarts, StreamSat<MM>,
-// StreamCons<SAT, MM>, StreamStartsCons)
+// StreamCons<SAT, MM>, StreamStartsCons, StreamStartsMulti, StreamStartsConsMulti)
 #define SX_STREAM_INSTANTIATE(NS, NU, ...)                                                                            \
     template int sx::launch_stream<sx::__VA_ARGS__, NS, NU>(                                                          \
         const sx::StreamGpArg<sx::__VA_ARGS__, NS, NU>&, const sx::ReachConst<NS, NU>&,                               \

@@ -5,7 +5,8 @@
 // mode in sx_stream_multi.hip, the per-particle starts in sx_stream_starts.hip, the saturating-cost objective in
 // sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip, in the
 // multi-model mode in sx_stream_cons_multi.hip and sx_stream_cons_sat_multi.hip, on the per-particle starts in
-// sx_stream_starts_cons.hip; built in parallel with the rest);
+// sx_stream_starts_cons.hip, the per-particle starts in the multi-model mode in sx_stream_starts_multi.hip and
+// sx_stream_starts_cons_multi.hip; built in parallel with the rest);
 // sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -104,7 +105,7 @@ inline StreamPlan plan_stream_multi(const sx_gp_model* models, int E, int steps,
 // in every variant.
 //   SH    the query shift (sx_cem_rollout_junk; described at RolloutGpArg).
 //   MM    the first argument is the device table of the problems' GpConst (sx_gp_model_table; at RolloutGpArg too).
-//   PS    (sx_cem_rollout_starts; SH = 0, MM = false) a start state per particle: the CEM row of a particle is
+//   PS    (sx_cem_rollout_starts[_multi]; SH = 0) a start state per particle: the CEM row of a particle is
 //         [x0 (NS) | actions (H NU)], L = NS + H NU entries.  rp.mean / rp.std are [E x L], rp.noise [E x P x L] | NULL,
 //         rp.actions the rows [E x P x L] (written when noise is given, read otherwise); rp.x0, rp.q0 and the elite-row
 //         fields are unused.  The owner lane of a particle takes its start from its own row (a point, reach_point at t = 0)
@@ -135,6 +136,8 @@ using StreamSat = StreamVariant<0, MM, false, true, false>;   // sx_cem_rollout[
 template <bool SAT, bool MM = false>
 using StreamCons = StreamVariant<0, MM, false, SAT, true>;   // sx_cem_rollout[_elites]_cons[_multi], SAT: with a cost
 using StreamStartsCons = StreamVariant<0, false, true, false, true>;   // sx_cem_rollout_starts_cons
+using StreamStartsMulti = StreamVariant<0, true, true, false, false>;   // sx_cem_rollout_starts_multi
+using StreamStartsConsMulti = StreamVariant<0, true, true, false, true>;   // sx_cem_rollout_starts_cons_multi
 
 // The first kernel argument of variant V: the GpConst, or with V::MM the device table of E of them
 template <class V, int NS, int NU>

@@ -118,3 +118,37 @@ def find_max_variance_multi(explorations: Sequence[DynamicSafeMPCExploration], x
     x_0 = np.atleast_2d(x_0)
     u_apply, results = get_actions_multi([x.safempc for x in explorations], x_0)
     return x_0, u_apply, results
+
+
+def find_max_variance_static_multi(explorations: Sequence[StaticSafeMPCExploration]
+                                   ) -> List[Tuple[Optional[ndarray], Optional[ndarray]]]:
+    """``find_max_variance`` of S independent static explorations -- the reference's scenarios, each with its own model --
+    at once: entry s is what ``explorations[s].find_max_variance()`` returns, (x [n_s x 1], u [n_u x 1]) or (None, None).
+    One ``MultiModelStaticCemMpc`` over their solvers: every scenario with all of its restarts in one rollout launch and one
+    ranking launch per CEM iteration (with ``cem_static_ctrl_ellipsoid_constraint`` / ``cem_static_obstacle_constraint`` on
+    all of them, the launch with their one constraint set), each scenario drawing its own solver's noise.  The multi-model
+    solver is kept on the first exploration between calls and rebuilt when the list of solvers changes.  The models are
+    updated in lockstep with ``safempc_cem.update_models_multi([x.safempc for x in explorations], ...)``."""
+    from .cem_mpc import MultiModelStaticCemMpc
+    explorations = list(explorations)
+    if not explorations:
+        raise ValueError('find_max_variance_static_multi needs at least one exploration')
+    for x in explorations:
+        if not isinstance(x, StaticSafeMPCExploration):
+            raise TypeError(f'find_max_variance_static_multi takes StaticSafeMPCExploration instances, got '
+                            f'{type(x).__name__} (find_max_variance_multi serves the dynamic explorations)')
+    solvers = [x._solver for x in explorations]
+    cached = getattr(explorations[0], '_static_multi', None)
+    if cached is None or len(cached.solvers) != len(solvers) or any(a is not b for a, b in zip(cached.solvers, solvers)):
+        explorations[0]._static_multi = cached = MultiModelStaticCemMpc.from_solvers(solvers)
+    out = []
+    for x, found in zip(explorations, cached.find()):
+        if found is None:
+            out.append((None, None))
+            continue
+        x_best, actions, obj = found
+        if x.verbosity > 1:
+            print(f'New feasible solution with sigma sum {-obj} found')
+        out.append((np.asarray(x_best, dtype=np.float64).reshape(x.n_s, 1),
+                    np.asarray(actions[0], dtype=np.float64).reshape(x.n_u, 1)))
+    return out
