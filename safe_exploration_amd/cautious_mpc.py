@@ -15,12 +15,12 @@ import torch
 from numpy import ndarray
 
 from . import _lib
-from .cem_mpc import CautiousCemMpc, MultiModelCautiousCemMpc, Rollouts
+from .cem_mpc import CautiousCemMpc, MultiModelCautiousCemMpc, Rollouts, keep_multi
 from .costs import SaturatingCost
 from .gp_reachability_pytorch import make_env
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
-from .safempc_cem import LqrFeedbackController, MpcResult, objective_spec
+from .safempc_cem import LqrFeedbackController, MpcResult, _update_models_multi, objective_spec
 from .utils import assert_shape, get_device
 
 PERF_TRAJECTORIES = ('taylor', 'mean_equivalent')
@@ -298,11 +298,9 @@ def get_actions_multi(solvers: Sequence[CautiousCemMPC], states: ndarray) -> Tup
     starts = [s._init_controls(s.n_fail, s.k_ff_old) for s in solvers]
     flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
     if all(isinstance(m, CautiousCemMpc) for m in mpcs):
-        key = tuple(id(m) for m in mpcs)
-        cached = getattr(solvers[0], '_multi', None)
-        if cached is None or cached[0] != key or any(a is not b for a, b in zip(cached[1].solvers, mpcs)):
-            solvers[0]._multi = cached = (key, MultiModelCautiousCemMpc.from_solvers(mpcs))
-        best, found = cached[1].get_actions_multi(flat, init_mean=solvers[0]._warm(starts))
+        multi = keep_multi((getattr(solvers[0], '_multi', None) or (None, None))[1], MultiModelCautiousCemMpc, mpcs)
+        solvers[0]._multi = (tuple(id(m) for m in mpcs), multi)
+        best, found = multi.get_actions_multi(flat, init_mean=solvers[0]._warm(starts))
         rows = [best[e].detach().cpu().numpy().copy() if bool(found[e]) else None for e in range(len(solvers))]
     else:
         rows = []
@@ -325,12 +323,4 @@ def update_models_multi(solvers: Sequence[CautiousCemMPC], xs: Sequence[ndarray]
     the reference's retraining of every scenario's model after an episode (episode_runner.py:55,123): solver e's model
     learns the error of (xs[e], ys[e]) to its linear prior, as ``CautiousCemMPC.update_model``, and the exact GPs train in
     lockstep (``gp_ssm_cem.update_models_multi``)."""
-    solvers, xs, ys = list(solvers), list(xs), list(ys)
-    if not len(solvers) == len(xs) == len(ys):
-        raise ValueError(f'{len(solvers)} solvers, {len(xs)} input sets, {len(ys)} target sets')
-    xs_t, ys_t = [], []
-    for s, x, y in zip(solvers, xs, ys):
-        x_s, x_u = x[:, :s.state_dimen], x[:, s.state_dimen:]
-        xs_t.append(torch.tensor(x, device=s._device))
-        ys_t.append(torch.tensor(y - s.eval_prior(x_s, x_u), device=s._device))
-    gp_ssm_cem.update_models_multi([s._ssm for s in solvers], xs_t, ys_t, opt_hyp, replace_old)
+    _update_models_multi(solvers, xs, ys, opt_hyp, replace_old, lambda s, x_s, x_u, y: y - s.eval_prior(x_s, x_u))

@@ -12,7 +12,7 @@ rollouts)``, an action-constraint cost of 3 per violating step, 10 per state out
 """
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -106,11 +106,11 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
     family = getattr(ssm, 'kernel_family', 'rbf')
     workspace, unsupported = (), None
     if con_set is not None:
-        _require_rbf_con_set(ssm)
+        _require_exact_rbf([ssm], _CON_SET_IS)
         head = (ctypes.byref(ssm.device_model), ctypes.byref(env), _con_set_arg(con_set)) + (_cost_args(cost, ssm) or (None,))
         suffix = '_cons'
     elif cost is not None:
-        _require_rbf_cost([ssm])
+        _require_exact_rbf([ssm], _COST_IS)
         head, suffix = (ctypes.byref(ssm.device_model), ctypes.byref(env)) + _cost_args(cost, ssm), '_sat'
     elif family in ('feature', 'mlp', 'feature_junk', 'mlp_junk'):
         # 'feature': degenerate kernels ('linear', 'nn'), the weight-space rollout, one particle per lane (csrc/sx_feat.hpp);
@@ -144,20 +144,21 @@ def cem_rollout(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: int, *, act
                     elite_rows=elite_rows, want_dist=want_dist, workspace=workspace)
 
 
-def _require_rbf_cost(ssms) -> None:
-    for ssm in ssms:
+def _require_exact_rbf(ssms, what: str, numbered: bool = False) -> None:
+    """NotImplementedError unless every model is an exact RBF GP.  `what`: the feature that needs one, with its verb ('the
+    performance trajectory is'); `numbered`: the models are the solvers' of a multi-model solve, named by their index."""
+    for i, ssm in enumerate(ssms):
         family = getattr(ssm, 'kernel_family', 'rbf')
         if family != 'rbf':
-            raise NotImplementedError(f'the saturating cost on the safety trajectory is built for exact RBF GPs, not '
-                                      f'kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+            raise NotImplementedError(f'{what} built for exact RBF GPs' + (f': solver {i} has' if numbered else ', not')
+                                      + f' kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step '
+                                      f'models)')
 
 
-def _require_rbf_con_set(ssm) -> None:
-    family = getattr(ssm, 'kernel_family', 'rbf')
-    if family != 'rbf':
-        raise NotImplementedError(f'the constraint set (con_set: feedback bounds, obstacle polytope) is built for exact RBF '
-                                  f'GPs, not kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and '
-                                  f'step-by-step models)')
+# the features of the rollout wrappers that need one, as `_require_exact_rbf` names them
+_COST_IS = 'the saturating cost on the safety trajectory is'
+_CON_SET_IS = 'the constraint set (con_set: feedback bounds, obstacle polytope) is'
+_STARTS_ARE = 'per-particle start states (static exploration) are'
 
 
 def _con_set_arg(con_set):
@@ -183,11 +184,46 @@ def conset_eval(env: _lib.SxEnv, con_set, u: Tensor, q_start: Optional[Tensor], 
     return out
 
 
-def _require_rbf_starts(ssm) -> None:
-    family = getattr(ssm, 'kernel_family', 'rbf')
-    if family != 'rbf':
-        raise NotImplementedError(f'per-particle start states (static exploration) are built for exact RBF GPs, not '
-                                  f'kernel_family {family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+def _starts_rollout(suffix: str, head, ssms: Sequence, horizon: int, words: int, unsupported, *, mean, std, noise, rows,
+                    want_traj, want_sigma, status, con_set):
+    """What `cem_rollout_starts` and `cem_rollout_starts_multi` share: the checks of the rows, the outputs and the launch of
+    sx_cem_rollout_starts[_cons]<suffix>(*head(E, dev)[, con_set], E, P, H, mean, std, noise, rows, <outputs>, status, stream).
+    `head(E, dev)`: the entry's arguments in front of the set, made once the problem count and the device are known;
+    `words`: the size of a fresh status (None: one word per problem); `unsupported`: what SX_ERR_UNSUPPORTED raises."""
+    _require_exact_rbf(ssms, _STARTS_ARE)
+    cons = ()
+    if con_set is not None:
+        _require_exact_rbf(ssms, _CON_SET_IS)
+        cons = (_con_set_arg(con_set),)
+    entry = 'sx_cem_rollout_starts' + ('_cons' if cons else '') + suffix
+    n_s, n_u = ssms[0].num_states, ssms[0].num_actions
+    L = n_s + horizon * n_u
+    given = rows if noise is None else noise
+    if (noise is None) == (rows is None) or given.dim() != 3 or given.size(2) != L or not given.is_contiguous():
+        raise ValueError(f'either noise (the rows are drawn) or rows (given), a contiguous [E x P x {L}] tensor')
+    _lib.require_gpu(given, 'rows' if noise is None else 'noise')
+    E, P, dev = given.size(0), given.size(1), given.device
+    head = head(E, dev)
+    if noise is not None:
+        if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
+            raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
+        mean, std = mean.contiguous(), std.contiguous()
+        rows = torch.empty((E, P, L), dtype=torch.float64, device=dev)
+    S = n_s + n_s * n_s
+    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
+    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
+    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
+    con = torch.empty((E, P), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(E if words is None else words, dtype=torch.int32, device=dev)
+    code = getattr(_lib.lib(), entry)(*head, *cons, E, P, horizon, _lib.ptr(mean if noise is not None else None),
+                                      _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
+                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                      _lib.stream_ptr(dev))
+    if unsupported is not None and code == _lib.SX_ERR_UNSUPPORTED:
+        raise unsupported(f'{entry}: no single-launch form for the models')
+    _lib.check(code, entry)
+    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
 
 
 def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Optional[Tensor] = None,
@@ -203,36 +239,9 @@ def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Op
     the obstacle rows on every intermediate ellipsoid, and SX_STATE_VIOLATION_COST once more for a start that violates the
     obstacle rows; everything but con_cost is the launch's without the set.
     """
-    _require_rbf_starts(ssm)
-    entry, head = 'sx_cem_rollout_starts', (ctypes.byref(ssm.device_model), ctypes.byref(env))
-    if con_set is not None:
-        _require_rbf_con_set(ssm)
-        entry, head = 'sx_cem_rollout_starts_cons', head + (_con_set_arg(con_set),)
-    n_s, n_u = ssm.num_states, ssm.num_actions
-    L = n_s + horizon * n_u
-    given = rows if noise is None else noise
-    if (noise is None) == (rows is None) or given.dim() != 3 or given.size(2) != L or not given.is_contiguous():
-        raise ValueError(f'either noise (the rows are drawn) or rows (given), a contiguous [E x P x {L}] tensor')
-    _lib.require_gpu(given, 'rows' if noise is None else 'noise')
-    E, P, dev = given.size(0), given.size(1), given.device
-    if noise is not None:
-        if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
-            raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
-        mean, std = mean.contiguous(), std.contiguous()
-        rows = torch.empty((E, P, L), dtype=torch.float64, device=dev)
-    S = n_s + n_s * n_s
-    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
-    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
-    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
-    con = torch.empty((E, P), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, _lib.ptr(mean if noise is not None else None),
-                                      _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
-                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                      _lib.stream_ptr(dev))
-    _lib.check(code, entry)
-    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+    return _starts_rollout('', lambda E, dev: (ctypes.byref(ssm.device_model), ctypes.byref(env)), [ssm], horizon, 1, None,
+                           mean=mean, std=std, noise=noise, rows=rows, want_traj=want_traj, want_sigma=want_sigma,
+                           status=status, con_set=con_set)
 
 
 class FusedMultiUnsupported(_lib.SxError):
@@ -324,10 +333,9 @@ def cem_rollout_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0: Tensor, hor
     Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch): mixed
     families, JunkDimensionsSSM and step-by-step models, differing architectures, a shape without a kernel."""
     if con_set is not None:
-        for ssm in ssms:
-            _require_rbf_con_set(ssm)
+        _require_exact_rbf(ssms, _CON_SET_IS)
     if cost is not None:
-        _require_rbf_cost(ssms)
+        _require_exact_rbf(ssms, _COST_IS)
     family = multi_family(ssms)
     if family is None:
         raise FusedMultiUnsupported('the multi-model rollout takes models of one kernel_family: "rbf", "feature" or "mlp"; '
@@ -366,47 +374,18 @@ def cem_rollout_starts_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, horizon:
     sx_cem_rollout_starts_cons_multi.  Buffers as in `cem_rollout_starts` (`mean`, `std` [E x L]: a start distribution per
     problem); `status` is int32 [E], one word per problem.  `table` keeps the device table of the models between calls.
     Raises FusedMultiUnsupported where the library has no single launch for the models (before any launch)."""
-    for ssm in ssms:
-        _require_rbf_starts(ssm)
-        if con_set is not None:
-            _require_rbf_con_set(ssm)
-    n_s, n_u = ssms[0].num_states, ssms[0].num_actions
-    L = n_s + horizon * n_u
-    given = rows if noise is None else noise
-    if (noise is None) == (rows is None) or given.dim() != 3 or given.size(2) != L or not given.is_contiguous():
-        raise ValueError(f'either noise (the rows are drawn) or rows (given), a contiguous [E x P x {L}] tensor')
-    _lib.require_gpu(given, 'rows' if noise is None else 'noise')
-    E, P, dev = given.size(0), given.size(1), given.device
-    if len(ssms) != E:
-        raise ValueError(f'{len(ssms)} models for {E} problems')
-    if status is not None and status.numel() != E:
-        raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
-    if noise is not None:
-        if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
-            raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
-        mean, std = mean.contiguous(), std.contiguous()
-        rows = torch.empty((E, P, L), dtype=torch.float64, device=dev)
     if table is None or table.family != 'rbf':
-        table = GpModelTable()
-    models, tab = table.get(ssms, dev)
-    entry, head = 'sx_cem_rollout_starts_multi', (models, _lib.ptr(tab), ctypes.byref(env))
-    if con_set is not None:
-        entry, head = 'sx_cem_rollout_starts_cons_multi', head + (_con_set_arg(con_set),)
-    S = n_s + n_s * n_s
-    traj = torch.empty((E, P, horizon, S), dtype=torch.float64, device=dev) if want_traj else None
-    sigma = torch.empty((E, P, horizon, n_s), dtype=torch.float64, device=dev) if want_sigma else None
-    obj = torch.empty((E, P), dtype=torch.float64, device=dev)
-    con = torch.empty((E, P), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.zeros(E, dtype=torch.int32, device=dev)
-    code = getattr(_lib.lib(), entry)(*head, E, P, horizon, _lib.ptr(mean if noise is not None else None),
-                                      _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
-                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
-                                      _lib.stream_ptr(dev))
-    if code == _lib.SX_ERR_UNSUPPORTED:
-        raise FusedMultiUnsupported(f'{entry}: no single-launch form for the models')
-    _lib.check(code, entry)
-    return dict(rows=rows, obj_cost=obj, con_cost=con, traj=traj, sigma=sigma, status=status)
+        table = GpModelTable()      # (it owns the device table: held here until the launch is enqueued)
+
+    def head(E, dev):
+        if len(ssms) != E:
+            raise ValueError(f'{len(ssms)} models for {E} problems')
+        if status is not None and status.numel() != E:
+            raise ValueError(f'status must hold one word per problem ({E}), got {status.numel()}')
+        models, tab = table.get(ssms, dev)
+        return models, _lib.ptr(tab), ctypes.byref(env)
+    return _starts_rollout('_multi', head, ssms, horizon, None, FusedMultiUnsupported, mean=mean, std=std, noise=noise,
+                           rows=rows, want_traj=want_traj, want_sigma=want_sigma, status=status, con_set=con_set)
 
 
 class FusedJunkUnsupported(_lib.SxError):
@@ -415,10 +394,7 @@ class FusedJunkUnsupported(_lib.SxError):
 
 def _require_rbf(ssms: Sequence, x0: Tensor) -> None:
     _lib.require_gpu(x0, 'x0')
-    for ssm in ssms:
-        if getattr(ssm, 'kernel_family', 'rbf') != 'rbf':
-            raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
-                                      f'{getattr(ssm, "kernel_family", None)!r}')
+    _require_exact_rbf(ssms, 'the performance trajectory is')
 
 
 def _perf_rollout(entry: str, head: tuple, ssms: Sequence, x0: Tensor, horizon: int, n_perf: int, r: int, *, safe_actions,
@@ -849,6 +825,34 @@ def rank_chunks(num_candidates: int) -> int:
     return c
 
 
+def check_rank_limits(num_rollouts: int, num_elites: int, share: int, world: int = 1) -> None:
+    """ValueError where the ranking kernel cannot pick `num_elites` of `num_rollouts` particles, `share` of them on this GPU
+    of `world`: every rank hands in its top-k rows, and a share beyond RANK_MAX_CANDIDATES ranks in two levels
+    (`cem_rank_refit_any`)."""
+    if num_elites > num_rollouts:
+        raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
+    if num_elites > num_rollouts // world:
+        # every rank hands in its local top-k rows; a rank that owns fewer than k particles could not, and the
+        # global top-k would silently miss candidates
+        raise ValueError(f'num_elites={num_elites} exceeds the smallest per-GPU share '
+                         f'({num_rollouts // world} of {num_rollouts} particles over {world} GPUs)')
+    if num_elites > RANK_MAX_ELITES:
+        raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
+    if world > 1 and world * (num_elites + 1) > RANK_MAX_CANDIDATES:
+        raise ValueError(f'{world * (num_elites + 1)} candidate rows after the exchange exceed the ranking kernel\'s '
+                         f'limit of {RANK_MAX_CANDIDATES}')
+    chunks = rank_chunks(share)     # > 1: two-level ranking on this GPU (cem_rank_refit_any)
+    if chunks > 1 and (num_elites > share // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
+        raise ValueError(f'{share} particles per GPU rank in {chunks} chunks: num_elites={num_elites} is '
+                         f'too large for it (limit {min(share // chunks, RANK_MAX_CANDIDATES // chunks)})')
+
+
+def expand_init_std(init_std, horizon: int, n_u: int) -> Tensor:
+    """`init_std` -- a scalar, one value per step [H] or [H x n_u] -- as a float64 [H x n_u] tensor on the host."""
+    std = torch.as_tensor(init_std, dtype=torch.float64).cpu()
+    return (std.reshape(horizon, -1) if std.dim() > 0 else std).expand(horizon, n_u).clone()
+
+
 def cem_rank_refit_any(con: Tensor, obj: Tensor, actions: Tensor, k: int, **kw):
     """`cem_rank_refit` for any candidate count.  Beyond the kernel's 16 384 candidates per problem (BASELINE config 3's
     65 536 particles on ONE GPU) the ranking runs in two levels, exactly like the multi-GPU exchange without the collective:
@@ -1010,7 +1014,7 @@ class FusedCemMpc:
         self._con_set = con_set
         if con_set is not None:
             _con_set_arg(con_set)
-            _require_rbf_con_set(ssm)
+            _require_exact_rbf([ssm], _CON_SET_IS)
             if int(n_perf) > 0:
                 raise NotImplementedError(f'con_set constrains the safety trajectory of a solve without a performance '
                                           f'trajectory: got n_perf={n_perf} (cem_n_perf > 0 is not built)')
@@ -1045,10 +1049,7 @@ class FusedCemMpc:
             raise ValueError(f'perf_terminal_safety checks the performance state {time_horizon + 2}: n_perf={n_perf} is too '
                              f'short (n_perf >= time_horizon + 2)')
         if self._n_perf > 0:
-            family = getattr(ssm, 'kernel_family', 'rbf')
-            if family != 'rbf':
-                raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
-                                          f'{family!r} (feature-GP, MC-dropout, junk-dimension and step-by-step models)')
+            _require_exact_rbf([ssm], 'the performance trajectory is')
             if process_group is not None:
                 raise NotImplementedError('the performance trajectory is not built for sharded particles (a process group)')
             self._check_perf_objective(env)
@@ -1058,11 +1059,9 @@ class FusedCemMpc:
         # the first iteration's sampling distribution: std is a scalar or one value per step [H] / [H x n_u];
         # warm_start 'zero' = mean 0 (the reference's cold start), 'safe_policy' = the safe controller u = k_fb x rolled
         # through the model's mean dynamics from x0 (safe_policy_plan)
-        self._init_std = torch.as_tensor(init_std, dtype=torch.float64).cpu()
-        if self._init_std.dim() > 0:
-            self._init_std = self._init_std.reshape(time_horizon, -1).expand(time_horizon, ssm.num_actions).clone()
-            if self._tail:      # the tail steps start from the last safety step's value
-                self._init_std = torch.cat([self._init_std, self._init_std[-1:].expand(self._tail, -1)])
+        self._init_std = expand_init_std(init_std, time_horizon, ssm.num_actions)
+        if self._tail:      # the tail steps start from the last safety step's value
+            self._init_std = torch.cat([self._init_std, self._init_std[-1:].expand(self._tail, -1)])
         if warm_start not in ('zero', 'safe_policy'):
             raise ValueError(f"warm_start must be 'zero' or 'safe_policy', got {warm_start!r}")
         self._warm_start = warm_start
@@ -1073,24 +1072,9 @@ class FusedCemMpc:
         self._sharded = self._world > 1 or (force_exchange and process_group is not None)
         self._num_rollouts = num_rollouts
         self._local_rollouts, _ = distributed.shard_particles(num_rollouts, self._world, self._rank)
-        if num_elites > num_rollouts:
-            raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
-        if num_elites > num_rollouts // self._world:
-            # every rank hands in its local top-k rows; a rank that owns fewer than k particles could not, and the
-            # global top-k would silently miss candidates
-            raise ValueError(f'num_elites={num_elites} exceeds the smallest per-GPU share '
-                             f'({num_rollouts // self._world} of {num_rollouts} particles over {self._world} GPUs)')
+        check_rank_limits(num_rollouts, num_elites, self._local_rollouts, self._world)
         self._num_elites = num_elites
         self._local_elites = num_elites     # the same k on every rank
-        if num_elites > RANK_MAX_ELITES:
-            raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
-        if self._sharded and self._world * (num_elites + 1) > RANK_MAX_CANDIDATES:
-            raise ValueError(f'{self._world * (num_elites + 1)} candidate rows after the exchange exceed the ranking kernel\'s '
-                             f'limit of {RANK_MAX_CANDIDATES}')
-        chunks = rank_chunks(self._local_rollouts)     # > 1: two-level ranking on this GPU (cem_rank_refit_any)
-        if chunks > 1 and (num_elites > self._local_rollouts // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
-            raise ValueError(f'{self._local_rollouts} particles per GPU rank in {chunks} chunks: num_elites={num_elites} is '
-                             f'too large for it (limit {min(self._local_rollouts // chunks, RANK_MAX_CANDIDATES // chunks)})')
         self._device = torch.device(device if device is not None else 'cuda:0')
         self._init_std = self._init_std.to(self._device)
         # the iteration's collective on the compute stream (our own RCCL communicator) where the group is an nccl one
@@ -1138,7 +1122,7 @@ class FusedCemMpc:
         read, no hook is evaluated and no trajectory is recorded for one."""
         on_safety = getattr(self, '_cost_on_safety', False)
         if cost is not None and on_safety:
-            _require_rbf_cost([self._ssm])
+            _require_exact_rbf([self._ssm], _COST_IS)
         self._cost = _checked_cost(cost, self._ssm.num_states, self._perf_kind if self._n_perf > 0 else None, on_safety)
 
     @property
@@ -1464,7 +1448,163 @@ class FusedCemMpc:
         return best[0], history
 
 
-class MultiModelCemMpc:
+class SharedPolicy(NamedTuple):
+    """What a multi-model class asks of its solvers beside the table of the settings they share."""
+    what: str                   # the solve, as the messages name it: 'a multi-model static solve'
+    con_set: str = 'none'       # the constraint set: 'none' may carry one, 'all' carry one byte-equal set, or 'all_or_none'
+    exact_rbf: bool = False     # every solver's model is an exact RBF GP
+    label: str = ''             # what stands in front of a differing setting's name
+
+
+def _setting(solver, attr):
+    """(a solver's setting as it is compared, may a message print it): tensors by value and ctypes structs (sx_env) byte for
+    byte, neither printed.  `attr`: the attribute's name -- read with a default: an injected optimiser need not be one of
+    our classes -- or a function of the solver."""
+    v = attr(solver) if callable(attr) else getattr(solver, attr, None)
+    if isinstance(v, Tensor):
+        return tuple(v.reshape(-1).tolist()), False
+    return (bytes(v), False) if isinstance(v, ctypes.Structure) else (v, True)
+
+
+def _model_shape(solver) -> tuple:
+    return solver._ssm.num_states, solver._ssm.num_actions
+
+
+def _compare_settings(solvers: Sequence, table, what: str, label: str = '') -> None:
+    """ValueError, naming the setting and the solver, unless every solver has solver 0's value of every (reported name,
+    attribute) of `table`."""
+    for name, attr in table:
+        first, printable = _setting(solvers[0], attr)
+        for e, s in enumerate(solvers[1:], start=1):
+            other = _setting(s, attr)[0]
+            if other != first:
+                raise ValueError(f'the solvers of {what} must share {label}{name}: '
+                                 + (f'solver 0 has {first!r}, solver {e} has {other!r}' if printable
+                                    else f'solver {e} differs from solver 0'))
+
+
+def _shared_con_set(solvers: Sequence, policy: str, what: str):
+    """The constraint set of a multi-model solve (None: no solver carries one), whose launch takes ONE: by `policy` no
+    solver may carry a set ('none'), all carry one ('all') or all or none do ('all_or_none'), and the sets are equal byte
+    for byte, as the environments are compared.  NotImplementedError, naming con_set, where the solve is not built for the
+    solvers' sets; ValueError for differing ones."""
+    sets = [getattr(m, '_con_set', None) for m in solvers]
+    have = sum(c is not None for c in sets)
+    if have and policy == 'none':
+        raise NotImplementedError(f'{what} is not built for con_set: MultiModelConsCemMpc solves over solvers that all '
+                                  f'carry one set')
+    if have not in (0, len(sets)):
+        raise NotImplementedError(f'the solvers of {what} all carry a constraint set (con_set) or none does: {have} of '
+                                  f'{len(sets)} have one; the ones without act in a multi-model solve of their own')
+    if not have and policy == 'all':
+        raise NotImplementedError(f'{what} needs solvers with a constraint set (con_set); MultiModelCemMpc solves the others')
+    for e, c in enumerate(sets[:have]):
+        _con_set_arg(c)
+        if bytes(c) != bytes(sets[0]):
+            raise ValueError(f'the solvers of {what} must share one constraint set (con_set: the obstacle rows and the '
+                             f'feedback bounds of the environment they share): solver {e} differs from solver 0')
+    return sets[0]
+
+
+def check_shared_settings(solvers: Sequence, table, policy: SharedPolicy) -> None:
+    """THE comparison of the solvers of one multi-model solve: the models' family and the constraint sets by `policy`
+    (NotImplementedError), then every setting of `table` (ValueError)."""
+    if policy.exact_rbf:
+        _require_exact_rbf([m._ssm for m in solvers], policy.what + ' is', numbered=True)
+    _shared_con_set(solvers, policy.con_set, policy.what)
+    _compare_settings(solvers, table, policy.what, policy.label)
+
+
+class MultiModelCem:
+    """What the multi-model solvers share.  Problem (or scenario) e keeps a single-model solver of its own, ``solvers[e]``:
+    it supplies the problem's noise draws and start distribution, so a multi-model solve samples exactly what the solvers'
+    own solves would, and it takes over where the single launch does not apply (``fused_applies``; ``per_model_solves``
+    counts those solves) and for the step-by-step repeat of one problem (``stepwise_fallbacks``).  The solvers agree on
+    the class's ``_SHARED`` settings and ``_POLICY`` (``check_solvers``).  The device table of the models is kept between
+    solves.
+
+    A subclass supplies the two, how problem e draws its noise and starts, the rollout call of ``solve`` and the form
+    query ``fused_applies``."""
+
+    _SHARED: tuple = ()         # (reported name, attribute) of every setting the solvers of one solve share
+    _POLICY: SharedPolicy
+
+    def __init__(self, solvers: Sequence, family: Optional[str] = 'rbf', table: Optional[tuple] = None):
+        """`table`: the settings compared here, where they are fewer than `check_solvers` compares."""
+        solvers = list(solvers)
+        if not solvers:
+            raise ValueError(f'{type(self).__name__} needs at least one solver')
+        check_shared_settings(solvers, self._SHARED if table is None else table, self._POLICY)
+        self._solvers = solvers
+        self._table = GpModelTable(family) if family is not None else None
+        self._last_noise = self._last_actions = None
+        self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path (what _check_solve counts)
+        self.per_model_solves = 0       # solves that went one solver at a time (single launch not applicable)
+
+    @classmethod
+    def check_solvers(cls, solvers: Sequence) -> None:
+        """ValueError, naming the setting and the solver, unless the solvers share every setting of the class's `_SHARED`;
+        NotImplementedError where the class is not built for the solvers' constraint sets or models (`_POLICY`)."""
+        check_shared_settings(solvers, cls._SHARED, cls._POLICY)
+
+    @property
+    def solvers(self) -> list:
+        return self._solvers
+
+    @property
+    def last_status(self) -> List[int]:
+        """The status word of every problem's last solve."""
+        return [s.last_status for s in self._solvers]
+
+    @property
+    def _env(self) -> _lib.SxEnv:
+        return self._solvers[0]._env      # (ONE sx_env: check_solvers compares the solvers')
+
+    @property
+    def _device(self):
+        return self._solvers[0]._device
+
+    def set_env(self, env: _lib.SxEnv) -> None:
+        """`set_env` on every solver."""
+        for s in self._solvers:
+            s.set_env(env)
+
+    def set_cost(self, cost) -> None:
+        """`set_cost` on every solver."""
+        for s in self._solvers:
+            s.set_cost(cost)
+
+    def _get_actions_multi(self, states: Tensor, where: str, **init) -> Tuple[Tensor, Tensor]:
+        """`get_actions_multi` of the classes that solve from given states (problem e over `self._ssms[e]`): flat start
+        states [E x (n_s + n_s^2)], all points.  One solve per solver, each with its own checks (and its own step-by-step
+        repeat), where `fused_applies` is False; else ONE `solve` and `_check_solve` with a status word per problem.
+        `init`: per-problem tensors [E x ...] for `solve`, handed row by row to the solvers' own solves.  Returns (best
+        rows on the host, found bool [E] on the host)."""
+        E, n_s = len(self._ssms), self._ssms[0].num_states
+        if states.dim() != 2 or states.shape != (E, n_s + n_s * n_s):
+            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(states.shape)}')
+        states = states.to(self._device, torch.float64)
+        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
+        if not self.fused_applies():
+            self.per_model_solves += 1
+            per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1],
+                                    **{key: v[e:e + 1] for key, v in init.items()}) for e, s in enumerate(self._solvers)]
+            return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
+        best, best_ok, status = self.solve(x0, **init)
+        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
+                                           [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
+        return best_host, found
+
+
+def keep_multi(cached, cls, solvers: Sequence):
+    """`cached` where it is a `cls` over exactly `solvers`, else a new one (`cls.from_solvers`): how a front end keeps the
+    multi-model solver, and with it the device table, between calls."""
+    if type(cached) is cls and len(cached.solvers) == len(solvers) and all(a is b for a, b in zip(cached.solvers, solvers)):
+        return cached
+    return cls.from_solvers(solvers)
+
+
+class MultiModelCemMpc(MultiModelCem):
     """E independent problems with a model each -- the reference's exploration scenarios, each with its own training set,
     hyper-parameters or network -- solved together: one multi-model rollout launch and one ``sx_cem_rank_refit`` launch per
     CEM iteration for all of them, where ``FusedCemMpc`` needs one solve per model.  The models share one kernel_family:
@@ -1472,20 +1612,32 @@ class MultiModelCemMpc:
     MC-dropout ensembles (``sx_cem_rollout_mlp_multi``); the last two share their architecture too, and have no elite-row
     form (the ranking kernel refits).
 
-    Problem e keeps a ``FusedCemMpc`` of its own (``solvers[e]``, built here from the same settings with seed ``seed + e``
-    unless given): it supplies the problem's noise draws and warm start, so a multi-model solve samples exactly what E
-    sequential ``get_actions`` calls would, and it takes over where the single launch does not apply -- mixed families,
-    JunkDimensionsSSM and step-by-step models, differing architectures, an exact-GP training set that needs the workspace
-    path (one solve per model then), and the per-problem step-by-step repeat of ``_check_solve``.  The problems share
-    `env` and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
+    Problem e keeps a ``FusedCemMpc`` (built here from the same settings with seed ``seed + e`` unless given), which also
+    supplies its warm start.  The single launch does not apply to mixed families, JunkDimensionsSSM and step-by-step
+    models, differing architectures and an exact-GP training set that needs the workspace path.  The problems share `env`
+    and the CEM settings; sharded (multi-GPU) multi-model solves are out of scope.
 
     Solvers built with ``cost_on_safety=True`` carry their ``SaturatingCost`` into the launch (``sx_cem_rollout_sat_multi`` /
     ``sx_cem_rollout_elites_sat_multi``): equal costs on all solvers, or none on any of them.  Solvers with a constraint set
     (``con_set``) are refused here: ``MultiModelConsCemMpc`` solves those.
     """
 
-    _perf_solvers = False   # MultiModelPerfCemMpc: the solvers carry a performance trajectory
-    _cons_solvers = False   # MultiModelConsCemMpc: the solvers carry a constraint set
+    # what one launch needs of its solvers: compared at construction.  (The start distributions are the solvers' own:
+    # `solve` takes problem e's from solvers[e].)
+    _LAUNCH = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
+               ('num_iterations', '_num_iterations'), ('n_perf', '_n_perf'), ('perf_r', '_perf_r'),
+               ('perf_variance', '_perf_variance'), ('perf_type', '_perf_type'),
+               ('perf_terminal_safety', '_perf_terminal_safety'))
+    # what the solvers of a front end's get_actions_multi share (`check_solvers`)
+    _SHARED = (('the solver type', '__class__'),) + _LAUNCH + (
+        ('warm_start', '_warm_start'), ('device', '_device'), ('the world size', '_world'),
+        ('cost_on_safety', '_cost_on_safety'), ('init_std', '_init_std'), ('the environment constants (sx_env)', '_env'))
+    _POLICY = SharedPolicy('a multi-model solve', label='the CEM settings (horizon, rollouts, elites, iterations, initial '
+                           'distribution, device, the performance trajectory\'s n_perf, perf_r, perf_variance, perf_type, '
+                           'perf_terminal_safety, and cost_on_safety) and the environment constants; of these, ')
+    _FORM = 'sx_cem_rollout_multi_form'     # the form query of exact RBF GPs: < 0 where they have no single launch
+    # the kernel-form cost: equal on all solvers or on none, compared before every solve
+    _COST = (('the cost (equal costs on all of the solvers, or none on any of them)', '_cost'),)
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
@@ -1501,42 +1653,29 @@ class MultiModelCemMpc:
             solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
                                    seed=seed + e, init_std=init_std, warm_start=warm_start)
                        for e, ssm in enumerate(self._ssms)]
-        if len(solvers) != len(self._ssms) or any(
-                (s._horizon, s._num_rollouts, s._num_elites, s._num_iterations, s._sharded)
-                != (time_horizon, num_rollouts, num_elites, num_iterations, False) for s in solvers):
-            raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: one per model, unsharded, with this '
+        super().__init__(solvers, multi_family(self._ssms), self._LAUNCH)
+        first = self._solvers[0]
+        if (len(self._solvers) != len(self._ssms) or any(s._sharded for s in self._solvers)
+                or (first._horizon, first._num_rollouts, first._num_elites, first._num_iterations)
+                != (time_horizon, num_rollouts, num_elites, num_iterations)):
+            raise ValueError(f'{len(self._solvers)} solvers for {len(self._ssms)} models: one per model, unsharded, with this '
                              f'solve\'s horizon, particles, elites and iterations')
-        if not self._perf_solvers and any(getattr(s, '_n_perf', 0) > 0 for s in solvers):
-            raise NotImplementedError('MultiModelCemMpc solves have no performance trajectory (solvers with n_perf > 0): '
-                                      'MultiModelPerfCemMpc solves those')
-        if not self._cons_solvers and any(getattr(s, '_con_set', None) is not None for s in solvers):
-            raise NotImplementedError(f'{type(self).__name__} solves without a constraint set (solvers with con_set): '
-                                      f'MultiModelConsCemMpc solves those')
-        self._solvers = list(solvers)
-        self._env = env
+        self._check_trajectories()
         self._horizon = time_horizon
         self._num_elites = num_elites
         self._num_iterations = num_iterations
-        self._device = self._solvers[0]._device
-        family = multi_family(self._ssms)
-        self._table = GpModelTable(family) if family is not None else None
-        self._last_noise = None
-        self.stepwise_fallbacks = 0     # problems repeated through the step-by-step path
-        self.per_model_solves = 0       # solves that went one model at a time (single launch not applicable)
         self._solver_cost()
+
+    def _check_trajectories(self) -> None:
+        """The trajectories of the solvers this class solves over: the safety trajectory alone."""
+        if any(getattr(s, '_n_perf', 0) > 0 for s in self._solvers):
+            raise NotImplementedError('MultiModelCemMpc solves have no performance trajectory (solvers with n_perf > 0): '
+                                      'MultiModelPerfCemMpc solves those')
 
     def _solver_cost(self):
         """The kernel-form cost of the solve: the solvers' (`FusedCemMpc.set_cost`), equal on all of them or on none."""
-        costs = [getattr(s, '_cost', None) for s in self._solvers]
-        if any(c != costs[0] for c in costs):
-            raise ValueError(f'a multi-model solve needs equal costs on all of its solvers, or none on any of them; got '
-                             f'{costs}')
-        return costs[0]
-
-    def set_cost(self, cost) -> None:
-        """`FusedCemMpc.set_cost` on every solver."""
-        for s in self._solvers:
-            s.set_cost(cost)
+        _compare_settings(self._solvers, self._COST, self._POLICY.what)
+        return getattr(self._solvers[0], '_cost', None)
 
     def _con_set_kw(self) -> dict:
         """What the rollout call takes for the solvers' constraint set: nothing here (MultiModelConsCemMpc: the set)."""
@@ -1550,44 +1689,6 @@ class MultiModelCemMpc:
         return cls([s._ssm for s in solvers], first._env, first._horizon, first._num_rollouts, first._num_elites,
                    first._num_iterations, device=first._device, solvers=solvers)
 
-    @staticmethod
-    def check_solvers(solvers: Sequence, check_con_set: bool = True) -> None:
-        """ValueError unless the solvers share the CEM settings and the environment constants (sx_env).  (Read with
-        defaults: an injected optimiser need not be a FusedCemMpc.)  NotImplementedError for solvers with a constraint
-        set (`check_con_set`; MultiModelConsCemMpc.check_solvers compares the sets itself)."""
-        def settings(m):
-            init, env = getattr(m, '_init_std', None), getattr(m, '_env', None)
-            names = ('_horizon', '_num_rollouts', '_num_elites', '_num_iterations', '_warm_start', '_device', '_world',
-                     '_n_perf', '_perf_r', '_perf_variance', '_perf_type', '_perf_terminal_safety', '_cost_on_safety')
-            return ((type(m),) + tuple(getattr(m, a, None) for a in names)
-                    + (None if init is None else tuple(init.reshape(-1).tolist()),), None if env is None else bytes(env))
-
-        if check_con_set and any(getattr(m, '_con_set', None) is not None for m in solvers):
-            raise NotImplementedError('a multi-model solve (MultiModelCemMpc) is not built for con_set: '
-                                      'MultiModelConsCemMpc solves over solvers that all carry one set')
-        (cem0, env0), *rest = [settings(m) for m in solvers]
-        for cem, env in rest:
-            if cem != cem0:
-                raise ValueError('the solvers of a multi-model solve must share the CEM settings (horizon, rollouts, '
-                                 'elites, iterations, initial distribution, device, the performance trajectory\'s '
-                                 'n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety, and cost_on_safety)')
-            if env != env0:
-                raise ValueError('the solvers of a multi-model solve must share the environment constants (sx_env)')
-
-    @property
-    def solvers(self) -> List[FusedCemMpc]:
-        return self._solvers
-
-    @property
-    def last_status(self) -> List[int]:
-        """The status word of every problem's last solve."""
-        return [s.last_status for s in self._solvers]
-
-    def set_env(self, env: _lib.SxEnv) -> None:
-        self._env = env
-        for s in self._solvers:
-            s.set_env(env)
-
     def fused_applies(self) -> bool:
         """Does one multi-model launch serve the models?  Exact RBF GPs without the workspace path
         (sx_cem_rollout_multi_form); feature-space GPs or MC-dropout ensembles of one shape and architecture (the sign of
@@ -1597,15 +1698,13 @@ class MultiModelCemMpc:
             return False
         models = model_array(self._ssms, family)
         if family == 'rbf':
-            return int(_lib.lib().sx_cem_rollout_multi_form(models, len(self._ssms), self._horizon)) >= 0
+            return int(getattr(_lib.lib(), self._FORM)(models, len(self._ssms), self._horizon)) >= 0
         return model_table_bytes(models, family) >= 0
 
-    def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
-        """E = len(models) solves from x0 [E x n_s] (points) in one launch per step of the loop.  Nothing synchronises.
-        noise: optional [iters x E x P x H x n_u] standard normals; by default problem e draws from solvers[e].
-        Returns (best [E x H x n_u], best_ok int32 [E], status int32 [E]: one word per problem).
-        Raises FusedMultiUnsupported (before any launch) where the single launch does not apply."""
-        E, H, n_s, n_u = len(self._ssms), self._horizon, self._ssms[0].num_states, self._ssms[0].num_actions
+    def _begin(self, x0: Tensor, noise: Optional[Tensor]):
+        """What opens a solve: x0's shape, then per problem e what solvers[e] would draw and start from alone -- its noise
+        (unless given) and its start distribution -- and a status word.  Returns (noise, mean, std, status)."""
+        E, n_s = len(self._ssms), self._ssms[0].num_states
         if x0.shape != (E, n_s):
             raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
         if noise is None:
@@ -1613,7 +1712,15 @@ class MultiModelCemMpc:
         self._last_noise = noise
         starts = [s.start_distribution(x0[e:e + 1]) for e, s in enumerate(self._solvers)]
         mean, std = torch.cat([m for m, _ in starts]), torch.cat([sd for _, sd in starts])
-        status = torch.zeros(E, dtype=torch.int32, device=x0.device)
+        return noise, mean, std, torch.zeros(E, dtype=torch.int32, device=x0.device)
+
+    def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """E = len(models) solves from x0 [E x n_s] (points) in one launch per step of the loop.  Nothing synchronises.
+        noise: optional [iters x E x P x H x n_u] standard normals; by default problem e draws from solvers[e].
+        Returns (best [E x H x n_u], best_ok int32 [E], status int32 [E]: one word per problem).
+        Raises FusedMultiUnsupported (before any launch) where the single launch does not apply."""
+        E, H, n_u = len(self._ssms), self._horizon, self._ssms[0].num_actions
+        noise, mean, std, status = self._begin(x0, noise)
         # (solver 0 stands for all: the solvers share this solve's settings, and a model on the workspace path has no
         # multi-model launch at all)
         in_prologue = self._solvers[0]._refit_in_prologue(E)
@@ -1637,21 +1744,8 @@ class MultiModelCemMpc:
         host, found bool [E] on the host); ``found[e] == False`` is the ``get_actions`` ``None`` of problem e.  Raises like
         ``FusedCemMpc.get_actions`` if any problem hit a numerical failure; the step-by-step repeat of a solve that reports
         both SX_STATUS_NAN and SX_STATUS_ZERO_FIX is made for that problem only."""
-        E, n_s = len(self._ssms), self._ssms[0].num_states
-        if states.dim() != 2 or states.shape != (E, n_s + n_s * n_s):
-            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(states.shape)}')
         self._solver_cost()      # mixed costs raise before anything is solved, one model at a time included
-        states = states.to(self._device, torch.float64)
-        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
-        if not self.fused_applies():
-            # one solve per model, each with its own checks (and its own step-by-step repeat)
-            self.per_model_solves += 1
-            per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1]) for e, s in enumerate(self._solvers)]
-            return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
-        best, best_ok, status = self.solve(x0)
-        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
-                                           [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
-        return best_host, found
+        return self._get_actions_multi(states, where)
 
 
 class MultiModelConsCemMpc(MultiModelCemMpc):
@@ -1662,7 +1756,8 @@ class MultiModelConsCemMpc(MultiModelCemMpc):
     repeat of ``_check_solve`` and the one-solve-per-model fallback (a training set on the workspace path) are the
     solvers' own, which carry the set already.
     """
-    _cons_solvers = True
+    _POLICY = MultiModelCemMpc._POLICY._replace(con_set='all')
+    _FORM = 'sx_cem_rollout_cons_multi_form'
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, con_set=None, device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero',
@@ -1675,48 +1770,15 @@ class MultiModelConsCemMpc(MultiModelCemMpc):
             solvers = [FusedCemMpc(ssm, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device,
                                    seed=seed + e, init_std=init_std, warm_start=warm_start, con_set=con_set)
                        for e, ssm in enumerate(ssms)]
-        solvers = list(solvers)
-        self._con_set = self._solver_con_set(solvers)
-        if con_set is not None and bytes(con_set) != bytes(self._con_set):
-            raise ValueError('the solvers carry another constraint set than the con_set given')
         super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
                          init_std=init_std, warm_start=warm_start, solvers=solvers)
-        for ssm in self._ssms:
-            _require_rbf_con_set(ssm)
-
-    @staticmethod
-    def _solver_con_set(solvers: Sequence):
-        """The one set of the solvers: byte-equal on all of them (as the environments are compared)."""
-        sets = [getattr(m, '_con_set', None) for m in solvers]
-        if any(c is None for c in sets):
-            raise NotImplementedError('MultiModelConsCemMpc takes solvers that all carry a constraint set (con_set): '
-                                      'the ones without act in a MultiModelCemMpc of their own'
-                                      if any(c is not None for c in sets) else
-                                      'MultiModelConsCemMpc needs solvers with a constraint set (con_set); '
-                                      'MultiModelCemMpc solves the others')
-        for c in sets:
-            _con_set_arg(c)
-        if any(bytes(c) != bytes(sets[0]) for c in sets[1:]):
-            raise ValueError('the solvers of a multi-model solve must share one constraint set (con_set: the obstacle '
-                             'rows and the feedback bounds of the environment they share)')
-        return sets[0]
-
-    @staticmethod
-    def check_solvers(solvers: Sequence) -> None:
-        """`MultiModelCemMpc.check_solvers` for solvers that all carry one constraint set: ValueError for differing sets,
-        NotImplementedError (naming con_set) where only some solvers carry one."""
-        MultiModelConsCemMpc._solver_con_set(solvers)
-        MultiModelCemMpc.check_solvers(solvers, check_con_set=False)
+        if con_set is not None and bytes(con_set) != bytes(self._solvers[0]._con_set):
+            raise ValueError('the solvers carry another constraint set than the con_set given')
+        _require_exact_rbf(self._ssms, _CON_SET_IS)
 
     def _con_set_kw(self) -> dict:
-        return dict(con_set=self._solver_con_set(self._solvers))
+        return dict(con_set=_shared_con_set(self._solvers, 'all', self._POLICY.what))
 
-    def fused_applies(self) -> bool:
-        """Does one sx_cem_rollout_cons_multi launch serve the models (sx_cem_rollout_cons_multi_form)?  Host only."""
-        if multi_family(self._ssms) != 'rbf':
-            return False
-        models = model_array(self._ssms, 'rbf')
-        return int(_lib.lib().sx_cem_rollout_cons_multi_form(models, len(self._ssms), self._horizon)) >= 0
 
 
 class MultiModelPerfCemMpc(MultiModelCemMpc):
@@ -1731,8 +1793,6 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
     Where either launch has no form for the models (``fused_applies`` is False) the problems are solved one model at a
     time (``per_model_solves``).
     """
-    _perf_solvers = True
-
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, n_perf: Optional[int] = None, perf_r: int = 1, perf_variance: bool = False,
                  device=None, seed: int = 0, init_std=1.0, warm_start: str = 'zero', process_group=None,
@@ -1748,36 +1808,32 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                                    seed=seed + e, init_std=init_std, warm_start=warm_start, n_perf=n_perf, perf_r=perf_r,
                                    perf_variance=perf_variance, perf_type=perf_type,
                                    perf_terminal_safety=perf_terminal_safety) for e, ssm in enumerate(ssms)]
-        solvers = list(solvers)
-        settings = {(getattr(s, '_n_perf', 0), getattr(s, '_perf_r', 1), getattr(s, '_perf_variance', False))
-                    for s in solvers}
-        if len(settings) != 1:
-            raise ValueError(f'the solvers of a multi-model solve with a performance trajectory must share (n_perf, perf_r, '
-                             f'perf_variance), got {sorted(settings)}')
-        (self._n_perf, self._perf_r, self._perf_variance), = settings
-        if self._n_perf <= 0:
-            raise ValueError('MultiModelPerfCemMpc needs solvers with a performance trajectory (n_perf > 0); '
-                             'MultiModelCemMpc solves the others')
+        super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
+                         init_std=init_std, warm_start=warm_start, solvers=solvers)
+        # (check_solvers compares the five between the solvers)
+        first = self._solvers[0]
+        self._n_perf, self._perf_r, self._perf_variance = first._n_perf, first._perf_r, first._perf_variance
         if n_perf is not None and (int(n_perf), int(perf_r), bool(perf_variance)) != (self._n_perf, self._perf_r,
                                                                                       self._perf_variance):
             raise ValueError(f'the solvers have (n_perf, perf_r, perf_variance) = {(self._n_perf, self._perf_r, self._perf_variance)}'
                              f', not {(n_perf, perf_r, perf_variance)}')
-        if any(getattr(s, '_objective_hook', None) is not None and getattr(s, '_cost', None) is None for s in solvers):
-            raise NotImplementedError('a multi-model solve with a performance trajectory has no objective hook: solvers '
-                                      'with one act one at a time (get_actions)')
-        super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
-                         init_std=init_std, warm_start=warm_start, solvers=solvers)
-        if multi_family(self._ssms) != 'rbf':
-            raise NotImplementedError(f'the performance trajectory is built for exact RBF GPs, not kernel_family '
-                                      f'{[getattr(s, "kernel_family", None) for s in self._ssms]}')
+        _require_exact_rbf(self._ssms, 'the performance trajectory is', numbered=True)
         self._tail = self._n_perf - self._perf_r
-        # (check_solvers compares the two between the solvers)
-        self._perf_type = getattr(solvers[0], '_perf_type', 'mean_equivalent')
-        self._perf_terminal_safety = bool(getattr(solvers[0], '_perf_terminal_safety', False))
+        self._perf_type = getattr(first, '_perf_type', 'mean_equivalent')
+        self._perf_terminal_safety = bool(getattr(first, '_perf_terminal_safety', False))
         self._perf_kind = perf_kind(self._perf_variance, self._perf_type)
         self._taylor = self._perf_kind == 'taylor'
         # the device table the performance launch reads: alpha per model for the mean-only form, else the safety launch's
         self._perf_table = PerfModelTable() if self._perf_kind == 'mean' else self._table
+
+    def _check_trajectories(self) -> None:
+        """The solvers carry a performance trajectory, and no objective hook that would have to be evaluated."""
+        if getattr(self._solvers[0], '_n_perf', 0) <= 0:
+            raise ValueError('MultiModelPerfCemMpc needs solvers with a performance trajectory (n_perf > 0); '
+                             'MultiModelCemMpc solves the others')
+        if any(getattr(s, '_objective_hook', None) is not None and getattr(s, '_cost', None) is None for s in self._solvers):
+            raise NotImplementedError('a multi-model solve with a performance trajectory has no objective hook: solvers '
+                                      'with one act one at a time (get_actions)')
 
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         if objective_hook is not None:
@@ -1802,22 +1858,14 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """As `MultiModelCemMpc.solve` with rows of H + T steps: noise [iters x E x P x (H + T) x n_u], and the returned
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
-        E, H, T = len(self._ssms), self._horizon, self._tail
-        n_s, n_u = self._ssms[0].num_states, self._ssms[0].num_actions
+        E, H, T, n_u = len(self._ssms), self._horizon, self._tail, self._ssms[0].num_actions
         cost = self._solver_cost()
         if self._perf_kind == 'taylor' and self._perf_form() < 0:
             raise FusedMultiUnsupported(f"perf_type='taylor' has no multi-model launch for these models (N = "
                                         f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {self._n_perf}): '
                                         f'the solvers act one model at a time')
-        if x0.shape != (E, n_s):
-            raise ValueError(f'x0 must be [{E} x {n_s}], got {tuple(x0.shape)}')
-        if noise is None:
-            noise = torch.stack([s._next_noise(1)[:, 0] for s in self._solvers], dim=1)
-        self._last_noise = noise
+        noise, mean, std, status = self._begin(x0, noise)
         noise_safe, noise_tail = noise[:, :, :, :H].contiguous(), noise[:, :, :, H:].contiguous()
-        starts = [s.start_distribution(x0[e:e + 1]) for e, s in enumerate(self._solvers)]
-        mean, std = torch.cat([m for m, _ in starts]), torch.cat([sd for _, sd in starts])
-        status = torch.zeros(E, dtype=torch.int32, device=x0.device)
 
         def rollout(it, mean, std, rows):
             r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean[:, :H].contiguous(), std=std[:, :H].contiguous(),
@@ -1871,35 +1919,23 @@ class StaticCemMpc:
         self._con_set = con_set
         if con_set is not None:
             _con_set_arg(con_set)
-            _require_rbf_con_set(ssm)
-        family = getattr(ssm, 'kernel_family', 'rbf')
-        if family != 'rbf':
-            raise NotImplementedError(f'static exploration is built for exact RBF GPs, not kernel_family {family!r} '
-                                      f'(feature-GP, MC-dropout, JunkDimensionsSSM and step-by-step models)')
+            _require_exact_rbf([ssm], _CON_SET_IS)
+        _require_exact_rbf([ssm], 'static exploration is')
         if process_group is not None:
             raise NotImplementedError('static exploration is not built for sharded particles (a process group)')
         n_s, n_u = ssm.num_states, ssm.num_actions
         if n_restarts < 1:
             raise ValueError(f'n_restarts={n_restarts} must be at least 1')
-        if num_elites > num_rollouts:
-            raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
-        if num_elites > RANK_MAX_ELITES:
-            raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
-        chunks = rank_chunks(num_rollouts)
-        if chunks > 1 and (num_elites > num_rollouts // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
-            raise ValueError(f'{num_rollouts} particles rank in {chunks} chunks: num_elites={num_elites} is too large for it')
+        check_rank_limits(num_rollouts, num_elites, num_rollouts)
         self._ssm = ssm
         self._horizon, self._num_rollouts, self._num_elites = time_horizon, num_rollouts, num_elites
         self._num_iterations, self._restarts, self._record = num_iterations, int(n_restarts), record_rollouts
         self._row_len = n_s + time_horizon * n_u
         self._device = torch.device(device if device is not None else 'cuda:0')
         as_row = lambda v, n: torch.as_tensor(v, dtype=torch.float64).reshape(-1).expand(n).clone()
-        act_std = torch.as_tensor(init_std, dtype=torch.float64)
-        act_std = (act_std.reshape(time_horizon, -1).expand(time_horizon, n_u) if act_std.dim() > 0
-                   else act_std.expand(time_horizon, n_u))
         # the first iteration's distribution of the row: [start_mean | 0], [start_std | init_std]
         self._mean0 = torch.cat([as_row(start_mean, n_s), torch.zeros(time_horizon * n_u, dtype=torch.float64)])
-        self._std0 = torch.cat([as_row(start_std, n_s), act_std.reshape(-1)])
+        self._std0 = torch.cat([as_row(start_std, n_s), expand_init_std(init_std, time_horizon, n_u).reshape(-1)])
         self._mean0, self._std0 = self._mean0.to(self._device), self._std0.to(self._device)
         self._seed = int(seed)
         self._gens = None       # one generator per restart (seed + e), made with the first draw
@@ -2034,7 +2070,7 @@ class StaticCemMpc:
         return host[e, :n_s].clone(), host[e, n_s:L].reshape(self._horizon, n_u).clone(), float(host[e, L + 1])
 
 
-class MultiModelStaticCemMpc:
+class MultiModelStaticCemMpc(MultiModelCem):
     """S independent static-exploration problems with an exact GP each -- the reference's scenarios, one model per scenario
     (sacred_helper.py's n_scenarios runs of StaticSafeMPCExploration) -- solved together: scenario s with its R restarts is
     the problems e = s R .. s R + R - 1 of ONE ``sx_cem_rollout_starts_multi`` launch (``sx_cem_rollout_starts_cons_multi``
@@ -2046,71 +2082,19 @@ class MultiModelStaticCemMpc:
     as in a solve of its own), decides among its restarts (``StaticCemMpc.choose``), takes the step-by-step repeat of a
     scenario whose status has SX_STATUS_NAN | SX_STATUS_ZERO_FIX, and solves alone where the models have no single launch
     (``fused_applies``).  The solvers share (n_s, n_u), the horizon, particles, elites, iterations, restarts, the device, ONE
-    sx_env and ONE constraint set (or none)."""
+    sx_env (byte for byte) and ONE constraint set (or none); ``check_solvers`` runs before every ``solve`` and ``find``."""
 
-    # what the solvers of one solve share, by the name a disagreement is reported under
-    _SHARED = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
-               ('num_iterations', '_num_iterations'), ('n_restarts', '_restarts'), ('device', '_device'),
-               ('record_rollouts', '_record'))
-
-    def __init__(self, solvers: Sequence[StaticCemMpc]):
-        solvers = list(solvers)
-        if not solvers:
-            raise ValueError('MultiModelStaticCemMpc needs at least one solver')
-        self.check_solvers(solvers)
-        self._solvers = solvers
-        self._table = GpModelTable()
-        self.stepwise_fallbacks = 0     # scenarios repeated step by step
-        self.per_model_solves = 0       # finds that went one scenario at a time (single launch not applicable)
+    _SHARED = (('(n_s, n_u)', _model_shape), ('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'),
+               ('num_elites', '_num_elites'), ('num_iterations', '_num_iterations'), ('n_restarts', '_restarts'),
+               ('device', '_device'), ('record_rollouts', '_record'),
+               ('the environment constants (env: one sx_env)', '_env'))
+    _POLICY = SharedPolicy('a multi-model static solve', con_set='all_or_none', exact_rbf=True)
 
     @classmethod
     def from_solvers(cls, solvers: Sequence[StaticCemMpc]) -> 'MultiModelStaticCemMpc':
         """The multi-model solve over existing single-model solvers, solvers[s] for scenario s, with their settings (which
         `check_solvers` compares)."""
         return cls(solvers)
-
-    @staticmethod
-    def check_solvers(solvers: Sequence) -> None:
-        """ValueError, naming the mismatch, unless the solvers share (n_s, n_u), time_horizon, num_rollouts, num_elites,
-        num_iterations, n_restarts, device, the environment constants (sx_env, byte for byte) and the constraint set (byte
-        for byte); NotImplementedError where only some solvers carry a set (naming con_set), or for a model that is not an
-        exact RBF GP."""
-        for s, m in enumerate(solvers):
-            family = getattr(m._ssm, 'kernel_family', 'rbf')
-            if family != 'rbf':
-                raise NotImplementedError(f'a multi-model static solve is built for exact RBF GPs: solver {s} has '
-                                          f'kernel_family {family!r}')
-        first = solvers[0]
-        shape0 = (first._ssm.num_states, first._ssm.num_actions)
-        sets = [getattr(m, '_con_set', None) for m in solvers]
-        if any(c is None for c in sets) and any(c is not None for c in sets):
-            raise NotImplementedError(f'the solvers of a multi-model static solve all carry a constraint set (con_set) or '
-                                      f'none does: {sum(c is not None for c in sets)} of {len(sets)} have one')
-        for s, m in enumerate(solvers[1:], start=1):
-            shape = (m._ssm.num_states, m._ssm.num_actions)
-            if shape != shape0:
-                raise ValueError(f'the solvers of a multi-model static solve must share (n_s, n_u): solver 0 has {shape0}, '
-                                 f'solver {s} has {shape}')
-            for name, attr in MultiModelStaticCemMpc._SHARED:
-                a, b = getattr(first, attr, None), getattr(m, attr, None)
-                if a != b:
-                    raise ValueError(f'the solvers of a multi-model static solve must share {name}: solver 0 has {a!r}, '
-                                     f'solver {s} has {b!r}')
-            if bytes(first._env) != bytes(m._env):
-                raise ValueError(f'the solvers of a multi-model static solve must share the environment constants (env: '
-                                 f'one sx_env): solver {s} differs from solver 0')
-            if sets[0] is not None and bytes(sets[0]) != bytes(sets[s]):
-                raise ValueError(f'the solvers of a multi-model static solve must share one constraint set (con_set): '
-                                 f'solver {s} differs from solver 0')
-
-    @property
-    def solvers(self) -> List[StaticCemMpc]:
-        return self._solvers
-
-    @property
-    def last_status(self) -> List[int]:
-        """The status word of every scenario's last find."""
-        return [s.last_status for s in self._solvers]
 
     def _models(self) -> List[GpCemSSM]:
         """The model of every problem: scenario s's, once per restart."""
@@ -2330,29 +2314,17 @@ class CautiousCemMpc:
         if isinstance(ssm, (list, tuple)):
             raise ValueError('CautiousCemMpc solves its problems over ONE model: MultiModelCautiousCemMpc solves over a GP per '
                              'problem')
-        family = getattr(ssm, 'kernel_family', 'rbf')
-        if family != 'rbf':
-            raise NotImplementedError(f'Cautious MPC is built for exact RBF GPs, not kernel_family {family!r} '
-                                      f'(feature-GP, MC-dropout, JunkDimensionsSSM and step-by-step models)')
+        _require_exact_rbf([ssm], 'Cautious MPC is')
         if process_group is not None:
             raise NotImplementedError('Cautious MPC is not built for sharded particles (a process group)')
         if time_horizon < 1:
             raise ValueError(f'time_horizon={time_horizon} must be at least 1')
-        if num_elites > num_rollouts:
-            raise ValueError(f'num_elites={num_elites} exceeds num_rollouts={num_rollouts}')
-        if num_elites > RANK_MAX_ELITES:
-            raise ValueError(f'num_elites={num_elites} exceeds the ranking kernel\'s limit of {RANK_MAX_ELITES}')
-        chunks = rank_chunks(num_rollouts)
-        if chunks > 1 and (num_elites > num_rollouts // chunks or chunks * num_elites > RANK_MAX_CANDIDATES):
-            raise ValueError(f'{num_rollouts} particles rank in {chunks} chunks: num_elites={num_elites} is too large for it')
+        check_rank_limits(num_rollouts, num_elites, num_rollouts)
         self._ssm = ssm
         self._horizon, self._num_rollouts, self._num_elites = int(time_horizon), int(num_rollouts), int(num_elites)
         self._num_iterations, self._record, self._propagate = int(num_iterations), bool(record_rollouts), bool(propagate)
         self._device = torch.device(device if device is not None else 'cuda:0')
-        std = torch.as_tensor(init_std, dtype=torch.float64)
-        n_u = ssm.num_actions
-        self._init_std = (std.reshape(self._horizon, -1).expand(self._horizon, n_u) if std.dim() > 0
-                          else std.expand(self._horizon, n_u)).clone().to(self._device)
+        self._init_std = expand_init_std(init_std, self._horizon, ssm.num_actions).to(self._device)
         self._gen = torch.Generator(device=self._device)
         self._gen.manual_seed(int(seed))
         self._objective_hook = None
@@ -2467,7 +2439,7 @@ class CautiousCemMpc:
                                     **({} if self._cost is None else dict(cost=self._cost)))
 
 
-class MultiModelCautiousCemMpc:
+class MultiModelCautiousCemMpc(MultiModelCem):
     """E independent Cautious MPC problems with an exact GP each -- the cautious arm of the reference's experiments, one
     scenario per model (episode_runner.py:40-123) -- solved together: one ``sx_cem_cautious_rollout_multi`` launch
     (``sx_cem_cautious_rollout_sat_multi`` where the solvers carry a ``SaturatingCost``) and one ranking launch per CEM
@@ -2481,9 +2453,12 @@ class MultiModelCautiousCemMpc:
     initial spread, the environment constants (there is ONE sx_env: k_fb, the box, the polytope, beta) and the cost.
     """
 
-    # what the solvers of one solve share, by the name a disagreement is reported under
     _SHARED = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
-               ('num_iterations', '_num_iterations'), ('propagate', '_propagate'), ('device', '_device'))
+               ('num_iterations', '_num_iterations'), ('propagate', '_propagate'), ('device', '_device'),
+               ('init_std', '_init_std'),
+               ('the environment constants (env: one sx_env with k_fb, the box, the polytope and beta)', '_env'),
+               ('the cost (equal SaturatingCosts on all of them, or none on any)', '_cost'))
+    _POLICY = SharedPolicy('a multi-model cautious solve')
 
     def __init__(self, ssms: Sequence[GpCemSSM], env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, propagate: bool = True, device=None, seed: int = 0, init_std=1.0,
@@ -2501,12 +2476,7 @@ class MultiModelCautiousCemMpc:
         solvers = list(solvers)
         if len(solvers) != len(self._ssms) or any(s._ssm is not m for s, m in zip(solvers, self._ssms)):
             raise ValueError(f'{len(solvers)} solvers for {len(self._ssms)} models: solvers[e] solves over ssms[e]')
-        self.check_solvers(solvers)
-        self._solvers = solvers
-        self._table = GpModelTable()
-        self._last_noise = self._last_actions = None
-        self.stepwise_fallbacks = 0     # (what _check_solve counts; the cautious kernel has no step-by-step repeat)
-        self.per_model_solves = 0       # solves that went one solver at a time (single launch not applicable)
+        super().__init__(solvers)
 
     @classmethod
     def from_solvers(cls, solvers: Sequence[CautiousCemMpc]) -> 'MultiModelCautiousCemMpc':
@@ -2516,54 +2486,10 @@ class MultiModelCautiousCemMpc:
         return cls([s._ssm for s in solvers], first._env, first._horizon, first._num_rollouts, first._num_elites,
                    first._num_iterations, propagate=first._propagate, device=first._device, solvers=solvers)
 
-    @staticmethod
-    def check_solvers(solvers: Sequence) -> None:
-        """ValueError, naming the setting, unless the solvers share time_horizon, num_rollouts, num_elites, num_iterations,
-        propagate, device, init_std, the environment constants (env) and the cost.  (Read with defaults: an injected
-        optimiser need not be a CautiousCemMpc.)"""
-        def flat(t):
-            return None if t is None else tuple(torch.as_tensor(t).reshape(-1).tolist())
-
-        first = solvers[0]
-        for e, s in enumerate(solvers[1:], start=1):
-            for name, attr in MultiModelCautiousCemMpc._SHARED:
-                a, b = getattr(first, attr, None), getattr(s, attr, None)
-                if a != b:
-                    raise ValueError(f'the solvers of a multi-model cautious solve must share {name}: solver 0 has {a!r}, '
-                                     f'solver {e} has {b!r}')
-            if flat(getattr(first, '_init_std', None)) != flat(getattr(s, '_init_std', None)):
-                raise ValueError(f'the solvers of a multi-model cautious solve must share init_std: solver {e} differs from '
-                                 f'solver 0')
-            env0, env = getattr(first, '_env', None), getattr(s, '_env', None)
-            if (None if env0 is None else bytes(env0)) != (None if env is None else bytes(env)):
-                raise ValueError(f'the solvers of a multi-model cautious solve must share the environment constants (env: '
-                                 f'one sx_env with k_fb, the box, the polytope and beta): solver {e} differs from solver 0')
-            if getattr(first, '_cost', None) != getattr(s, '_cost', None):
-                raise ValueError(f'the solvers of a multi-model cautious solve must share the cost (equal SaturatingCosts '
-                                 f'on all of them, or none on any): solver {e} differs from solver 0')
-
-    @property
-    def solvers(self) -> List[CautiousCemMpc]:
-        return self._solvers
-
-    @property
-    def last_status(self) -> List[int]:
-        """The status word of every problem's last solve."""
-        return [s.last_status for s in self._solvers]
-
-    @property
-    def _env(self) -> _lib.SxEnv:
-        return self._solvers[0]._env      # (check_solvers compares the solvers' before every solve)
-
     def set_env(self, env: _lib.SxEnv, objective_hook=None) -> None:
         """`CautiousCemMpc.set_env` on every solver."""
         for s in self._solvers:
             s.set_env(env, objective_hook=objective_hook)
-
-    def set_cost(self, cost) -> None:
-        """`CautiousCemMpc.set_cost` on every solver."""
-        for s in self._solvers:
-            s.set_cost(cost)
 
     def form(self) -> int:
         """sx_cem_cautious_rollout_multi_form of the models: < 0 where they have no single launch.  Host only."""
@@ -2627,24 +2553,9 @@ class MultiModelCautiousCemMpc:
         is the ``get_actions`` ``None`` of problem e.  Raises like ``CautiousCemMpc.get_actions`` where a problem hit a
         numerical failure, for that problem only (one status word per problem)."""
         self.check_solvers(self._solvers)
-        E, n_s = len(self._ssms), self._ssms[0].num_states
-        if flat_states.dim() != 2 or flat_states.shape != (E, n_s + n_s * n_s):
-            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(flat_states.shape)}')
-        dev = self._solvers[0]._device
-        states = flat_states.to(dev, torch.float64)
-        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
-        if init_mean is not None:
-            init_mean = init_mean.to(dev, torch.float64).reshape(E, self._solvers[0]._horizon, -1)
-        if not self.fused_applies():
-            # one solve per solver, each with its own checks
-            self.per_model_solves += 1
-            per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1],
-                                    init_mean=None if init_mean is None else init_mean[e:e + 1])
-                   for e, s in enumerate(self._solvers)]
-            return torch.cat([p[0] for p in per]), torch.cat([p[1] for p in per])
-        best, best_ok, status = self.solve(x0, init_mean=init_mean)
-        best_host, found, _ = _check_solve(self, x0, q_block, best, best_ok, status, where,
-                                           [(s, slice(e, e + 1)) for e, s in enumerate(self._solvers)])
+        init = {} if init_mean is None else dict(init_mean=init_mean.to(self._device, torch.float64).reshape(
+            len(self._ssms), self._solvers[0]._horizon, -1))
+        best_host, found = self._get_actions_multi(flat_states, where, **init)
         for s in self._solvers:
             s.last_rollouts = []
         return best_host, found

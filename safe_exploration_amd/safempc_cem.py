@@ -17,7 +17,7 @@ from torch import Tensor
 from . import _lib, gp_reachability_pytorch
 from .costs import SaturatingCost
 from .cem_mpc import (FusedCemMpc, MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc,
-                      multi_family)
+                      keep_multi, multi_family)
 from .gp_reachability_pytorch import make_con_set, make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
@@ -648,14 +648,9 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
     (MultiModelConsCemMpc if with_set else MultiModelCemMpc).check_solvers(mpcs)
     flat = torch.cat([s._flat_points(states[e:e + 1]) for e, s in enumerate(solvers)])
     if multi_solve_applies(mpcs):
-        key = tuple(id(m) for m in mpcs)
-        cached = getattr(solvers[0], '_multi', None)
         cls = MultiModelPerfCemMpc if with_perf else MultiModelConsCemMpc if with_set else MultiModelCemMpc
-        if (cached is None or cached[0] != key or type(cached[1]) is not cls
-                or any(a is not b for a, b in zip(cached[1].solvers, mpcs))):
-            solvers[0]._multi = cached = (key, cls.from_solvers(mpcs))
-        multi = cached[1]
-        multi._env = mpcs[0]._env
+        multi = keep_multi((getattr(solvers[0], '_multi', None) or (None, None))[1], cls, mpcs)
+        solvers[0]._multi = (tuple(id(m) for m in mpcs), multi)
         best, found = multi.get_actions_multi(flat)
         best = best.detach().cpu().numpy()
     else:
@@ -679,13 +674,18 @@ def update_models_multi(solvers: Sequence[CemSafeMPC], xs: Sequence[ndarray], ys
     the error of (xs[e], ys[e]) to its linear prior, as ``CemSafeMPC.update_model``.  Exact RBF GPs of one shape train in
     lockstep (``gp_ssm_cem.update_models_multi``: one fit and one MLL-gradient launch sequence per Adam step for all of
     them), with the results of one update_model per solver; other models are updated one at a time."""
+    _update_models_multi(solvers, xs, ys, opt_hyp, replace_old,
+                         lambda s, x_s, x_u, y: y - s.eval_prior(x_s, x_u) if s._use_prior_model else y)
+
+
+def _update_models_multi(solvers, xs, ys, opt_hyp, replace_old, prior_error) -> None:
+    """`update_models_multi` of this module and of cautious_mpc: solver e's model learns `prior_error(solver, states,
+    actions, targets)` of (xs[e], ys[e])."""
     solvers, xs, ys = list(solvers), list(xs), list(ys)
     if not len(solvers) == len(xs) == len(ys):
         raise ValueError(f'{len(solvers)} solvers, {len(xs)} input sets, {len(ys)} target sets')
     xs_t, ys_t = [], []
     for s, x, y in zip(solvers, xs, ys):
-        x_s, x_u = x[:, :s.state_dimen], x[:, s.state_dimen:]
-        y_error = y - s.eval_prior(x_s, x_u) if s._use_prior_model else y
         xs_t.append(torch.tensor(x, device=s._device))
-        ys_t.append(torch.tensor(y_error, device=s._device))
+        ys_t.append(torch.tensor(prior_error(s, x[:, :s.state_dimen], x[:, s.state_dimen:], y), device=s._device))
     gp_ssm_cem.update_models_multi([s._ssm for s in solvers], xs_t, ys_t, opt_hyp, replace_old)

@@ -129,7 +129,7 @@ def find_max_variance_static_multi(explorations: Sequence[StaticSafeMPCExplorati
     all of them, the launch with their one constraint set), each scenario drawing its own solver's noise.  The multi-model
     solver is kept on the first exploration between calls and rebuilt when the list of solvers changes.  The models are
     updated in lockstep with ``safempc_cem.update_models_multi([x.safempc for x in explorations], ...)``."""
-    from .cem_mpc import MultiModelStaticCemMpc
+    from .cem_mpc import MultiModelStaticCemMpc, keep_multi
     explorations = list(explorations)
     if not explorations:
         raise ValueError('find_max_variance_static_multi needs at least one exploration')
@@ -138,9 +138,8 @@ def find_max_variance_static_multi(explorations: Sequence[StaticSafeMPCExplorati
             raise TypeError(f'find_max_variance_static_multi takes StaticSafeMPCExploration instances, got '
                             f'{type(x).__name__} (find_max_variance_multi serves the dynamic explorations)')
     solvers = [x._solver for x in explorations]
-    cached = getattr(explorations[0], '_static_multi', None)
-    if cached is None or len(cached.solvers) != len(solvers) or any(a is not b for a, b in zip(cached.solvers, solvers)):
-        explorations[0]._static_multi = cached = MultiModelStaticCemMpc.from_solvers(solvers)
+    explorations[0]._static_multi = cached = keep_multi(getattr(explorations[0], '_static_multi', None),
+                                                        MultiModelStaticCemMpc, solvers)
     out = []
     for x, found in zip(explorations, cached.find()):
         if found is None:

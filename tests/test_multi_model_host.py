@@ -133,3 +133,93 @@ def test_multi_form_rejects_bad_arguments_and_shapes_without_a_kernel():
     assert lib.sx_cem_rollout_multi_form(None, 2, 15) < 0
     assert lib.sx_cem_rollout_multi_form(_models([(2, 1, 60), (2, 2, 60)]), 2, 15) < 0
     assert lib.sx_cem_rollout_multi_form(_models([(3, 2, 77)]), 1, 15) < 0       # (3, 2): no rollout kernel
+
+
+# ---- the host layer: one base class, one comparison of the solvers' settings ---------------------------------------------------------
+def _fused_solvers(cls, n=2):
+    """Solvers of the kind `cls` solves over (a FusedCemMpc each), equal in every setting."""
+    from safe_exploration_amd.cem_mpc import FusedCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc
+    from test_conset_host import _set
+    from test_perf_multi_host import _Ssm, _env as solver_env
+    kw = dict(con_set=_set()) if cls is MultiModelConsCemMpc else dict(n_perf=6) if cls is MultiModelPerfCemMpc else {}
+    return [FusedCemMpc(_Ssm(20 + 50 * e), solver_env(), 5, 64, 8, 3, device='cpu', init_std=0.2, seed=e, **kw)
+            for e in range(n)]
+
+
+def _cem_classes():
+    from safe_exploration_amd.cem_mpc import MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc
+    return [MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc]
+
+
+@pytest.mark.parametrize('cls', _cem_classes())
+def test_check_solvers_names_the_setting_and_the_solver(cls):
+    import re
+    import torch
+    from test_perf_multi_host import _env as solver_env
+    cls.check_solvers(_fused_solvers(cls))
+    cls.from_solvers(_fused_solvers(cls))
+    assert len(cls._SHARED) == 16 and {'__class__', '_init_std', '_env'} < {attr for _, attr in cls._SHARED}
+
+    def refused(solvers, name):
+        named = re.escape(name) + r': solver (0 has .*, solver 1 has|1 differs from solver 0)'
+        with pytest.raises(ValueError, match='CEM settings.*of these, ' + named):
+            cls.check_solvers(solvers)
+
+    # every entry of the table, solver 1 holding another value than solver 0
+    for name, attr in cls._SHARED:
+        solvers = _fused_solvers(cls)
+        if attr == '__class__':
+            solvers[1].__class__ = type('Other', (type(solvers[1]),), {})
+        else:
+            setattr(solvers[1], attr, object())
+        refused(solvers, name)
+    # init_std and the environment by their values
+    solvers = _fused_solvers(cls)
+    solvers[1]._init_std = solvers[1]._init_std + 0.25
+    refused(solvers, 'init_std')
+    solvers = _fused_solvers(cls)
+    moved = solver_env()
+    moved.beta = 7.0
+    solvers[1].set_env(moved)
+    refused(solvers, 'the environment constants (sx_env)')
+    # what differs is printed where it prints
+    solvers = _fused_solvers(cls)
+    solvers[1]._num_rollouts = 128
+    with pytest.raises(ValueError, match='num_rollouts: solver 0 has 64, solver 1 has 128'):
+        cls.check_solvers(solvers)
+    third = _fused_solvers(cls, 3)
+    third[2]._init_std = torch.full_like(third[2]._init_std, 0.5)
+    with pytest.raises(ValueError, match='init_std: solver 2 differs from solver 0'):
+        cls.check_solvers(third)
+
+
+def _all_classes():
+    from safe_exploration_amd.cem_mpc import MultiModelCautiousCemMpc, MultiModelStaticCemMpc
+    return _cem_classes() + [MultiModelStaticCemMpc, MultiModelCautiousCemMpc]
+
+
+@pytest.mark.parametrize('cls', _all_classes())
+def test_every_multi_model_class_stands_on_the_one_base(cls):
+    import inspect
+    from safe_exploration_amd import cem_mpc
+    base = cem_mpc.MultiModelCem
+    assert issubclass(cls, base) and cls is not base
+    for name in ('solvers', 'last_status', 'check_solvers'):
+        assert all(name not in vars(k) for k in cls.__mro__ if k not in (base, object)), name
+    assert cls.solvers is base.solvers and cls.last_status is base.last_status
+    assert cls.check_solvers.__func__ is base.check_solvers.__func__
+    assert cls._SHARED and cls._POLICY.what
+    # the counters are the base constructor's: no subclass sets them
+    for k in cls.__mro__[:-2]:
+        assert all(name not in inspect.getsource(k) for name in ('per_model_solves = ', 'stepwise_fallbacks = ')), k.__name__
+    if cls is cem_mpc.MultiModelStaticCemMpc:
+        from test_static_multi_host import _solver
+        solvers = [_solver(20), _solver(70)]
+    elif cls is cem_mpc.MultiModelCautiousCemMpc:
+        from test_cautious_multi_host import _solvers
+        solvers = _solvers(2)
+    else:
+        solvers = _fused_solvers(cls)
+    mpc = cls.from_solvers(solvers)
+    assert mpc.per_model_solves == 0 and mpc.stepwise_fallbacks == 0
+    assert mpc.solvers is mpc._solvers and mpc.solvers == solvers and mpc.last_status == [0, 0]
