@@ -168,6 +168,38 @@ def _con_set_arg(con_set):
     return ctypes.byref(con_set)
 
 
+def _checked_con_set(con_set, ssm):
+    """`con_set` as the constructors of `FusedCemMpc` and `StaticCemMpc` keep it: None, or a set over an exact RBF GP."""
+    if con_set is not None:
+        _con_set_arg(con_set)
+        _require_exact_rbf([ssm], _CON_SET_IS)
+    return con_set
+
+
+def _con_set_kw(con_set) -> dict:
+    """The constraint set as the rollouts' keyword; empty without one, so that they are called as before."""
+    return {} if con_set is None else dict(con_set=con_set)
+
+
+def hook_objective(hook, means: Tensor, steps: int, n_s: int, like: Tensor) -> Tensor:
+    """An objective hook (an ``Environment.objective_cost_function`` without a kernel form) summed over the recorded means
+    [E x P x steps x n_s], step by step in that order: a contiguous tensor shaped `like`."""
+    obj = torch.zeros_like(like)
+    for t in range(steps):
+        obj += hook(means[:, :, t].reshape(-1, n_s)).reshape(obj.shape)
+    return obj.contiguous()
+
+
+def split_flat_states(states: Tensor, n_s: int, device, episodes=None) -> Tuple[Tensor, Tensor]:
+    """Flat start states [E x (n_s + n_s^2)] as (x0 [E x n_s] contiguous, the Q block [E x n_s^2]) in float64 on `device`.
+    `episodes`: the E the caller wants (None: any); ValueError for another shape."""
+    S = n_s + n_s * n_s
+    if states.dim() != 2 or states.size(1) != S or episodes not in (None, states.size(0)):
+        raise ValueError(f'Wanted shape ({"E" if episodes is None else episodes}, {S}), got {tuple(states.shape)}')
+    states = states.to(device, torch.float64)
+    return states[:, :n_s].contiguous(), states[:, n_s:]
+
+
 def conset_eval(env: _lib.SxEnv, con_set, u: Tensor, q_start: Optional[Tensor], p_next: Optional[Tensor],
                 q_next: Optional[Tensor], check_obstacle: bool = True) -> Tensor:
     """Thin wrapper over sx_conset_eval: [P], the constraint set's cost of one step of P particles -- the action cost (3)
@@ -480,10 +512,88 @@ def cem_perf_rollout_var(ssm: GpCemSSM, env: _lib.SxEnv, x0: Tensor, horizon: in
 PERF_TYPES = ('mean_equivalent', 'taylor')
 
 
-def perf_kind(perf_variance: bool, perf_type: str) -> str:
-    """The performance rollout of a solver with these two settings: 'mean' (sx_cem_perf_rollout[_multi]), 'variance'
-    (sx_cem_perf_rollout_var[_multi]) or 'taylor' (sx_cem_perf_rollout_taylor[_multi]; it carries the variance by itself)."""
-    return 'taylor' if perf_type == 'taylor' else 'variance' if perf_variance else 'mean'
+class PerfNames(NamedTuple):
+    """How a message of `PerfSpec.checked` spells the five settings and the horizon: what the caller's user typed."""
+    n_perf: str
+    r: str
+    variance: str
+    type: str
+    terminal_safety: str
+    horizon: str
+    range_last: bool = False    # the rule on (n_perf, r) is tested behind the others, not in front of them
+
+
+KEYWORD_NAMES = PerfNames('n_perf', 'perf_r', 'perf_variance', 'perf_type', 'perf_terminal_safety', 'time_horizon')
+CONF_NAMES = PerfNames('cem_n_perf', 'cem_perf_r', 'cem_perf_variance', 'cem_perf_type', 'cem_perf_terminal_safety',
+                       'mpc_time_horizon', range_last=True)
+
+
+class PerfSpec(NamedTuple):
+    """Does a solve have a performance trajectory, and which one: `n_perf` steps (0: none) that share
+    their first `r` actions with the safety trajectory; `variance`: they carry the GP's posterior variance; `type`: one of
+    PERF_TYPES; `terminal_safety`: the 'taylor' ellipsoid at step H + 2 must lie in the safe polytope."""
+    n_perf: int = 0
+    r: int = 1
+    variance: bool = False
+    type: str = 'mean_equivalent'
+    terminal_safety: bool = False
+
+    @property
+    def on(self) -> bool:
+        return self.n_perf > 0
+
+    @property
+    def kind(self) -> Optional[str]:
+        """The performance rollout: 'mean' (sx_cem_perf_rollout[_multi]), 'variance' (sx_cem_perf_rollout_var[_multi]) or
+        'taylor' (sx_cem_perf_rollout_taylor[_multi]; it carries the variance by itself); None without a trajectory."""
+        if not self.on:
+            return None
+        return 'taylor' if self.type == 'taylor' else 'variance' if self.variance else 'mean'
+
+    @property
+    def tail(self) -> int:
+        """T: the steps of a CEM row behind the H safety steps."""
+        return self.n_perf - self.r if self.on else 0
+
+    def row_steps(self, horizon: int) -> int:
+        return horizon + self.tail
+
+    def keywords(self) -> dict:
+        """The spec as `FusedCemMpc`'s keywords: n_perf, perf_r, and of the other three those that are not the default."""
+        return {k: v for k, v, d in zip(KEYWORD_NAMES, self, PERF_OFF) if v != d or k in ('n_perf', 'perf_r')}
+
+    def checked(self, horizon: int, *, names: PerfNames = KEYWORD_NAMES) -> 'PerfSpec':
+        """THE validation of the five settings against the safety horizon: the spec with its fields as int / bool, or
+        ValueError naming the setting as `names` spells it."""
+        s = PerfSpec(int(self.n_perf), int(self.r), bool(self.variance), self.type, bool(self.terminal_safety))
+        n, taylor = names, self.type == 'taylor'
+        rules = [
+            (s.n_perf < 0 or (s.on and not (1 <= s.r <= horizon and s.n_perf > s.r)),
+             f'a performance trajectory needs 1 <= {n.r} <= {n.horizon} and {n.n_perf} > {n.r}, got {n.n_perf}={s.n_perf}, '
+             f'{n.r}={s.r}, {n.horizon}={horizon}'),
+            (s.variance and not s.on, f'{n.variance}=True needs a performance trajectory ({n.n_perf} > 0)'),
+            (s.type not in PERF_TYPES, f'{n.type} must be one of {PERF_TYPES}, got {s.type!r}'),
+            (taylor and not s.on, f"{n.type}='taylor' needs a performance trajectory ({n.n_perf} > 0)"),
+            (s.terminal_safety and not taylor, f"{n.terminal_safety} needs the propagated covariance ({n.type}='taylor')"),
+            (s.terminal_safety and s.n_perf < horizon + 2,
+             f'{n.terminal_safety} checks the performance state {n.horizon} + 2 = {horizon + 2}: {n.n_perf}={s.n_perf} is too '
+             f'short ({n.n_perf} >= {n.horizon} + 2)')]
+        if n.range_last:
+            rules.append(rules.pop(0))
+        for failed, message in rules:
+            if failed:
+                raise ValueError(message)
+        return s
+
+
+PERF_OFF = PerfSpec()
+
+
+def perf_spec_of(solver) -> PerfSpec:
+    """A solver's spec; the off spec for an object that carries none (an injected optimiser, a stand-in built without the
+    constructor).  The one place where the five settings have a default."""
+    spec = getattr(solver, '_perf', None)
+    return spec if isinstance(spec, PerfSpec) else PERF_OFF
 
 
 def _cost_args(cost, ssm) -> tuple:
@@ -628,16 +738,17 @@ def cem_perf_rollout_taylor_multi(ssms: Sequence[GpCemSSM], env: _lib.SxEnv, x0:
                          unsupported=unsupported, want_cov=bool(want_cov), terminal_safety=terminal_safety)
 
 
-def _launch_perf(kind: str, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon: int, n_perf: int, r: int, safety: dict,
-                 mean: Tensor, std: Tensor, tail_noise: Tensor, status: Tensor, *, multi: bool = False,
-                 want_traj: bool = False, record: bool = False, terminal_safety: bool = False, table=None, cost=None):
+def _launch_perf(perf: PerfSpec, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon: int, safety: dict, mean: Tensor,
+                 std: Tensor, tail_noise: Tensor, status: Tensor, *, multi: bool = False, want_traj: bool = False,
+                 record: bool = False, table=None, cost=None):
     """The one performance launch of a CEM iteration, for `FusedCemMpc.solve` (ssms = [the model]) and
     `MultiModelPerfCemMpc.solve` (`multi`: a model per problem, and the solver's `table` for the kind): the rollout of
-    `kind` (`perf_kind`) behind the safety rollout's result `safety`, its tail drawn from the columns past `horizon` of the
+    `perf.kind` behind the safety rollout's result `safety`, its tail drawn from the columns past `horizon` of the
     full-row `mean` / `std` with `tail_noise`.  `want_traj` asks for the means; `record` for all the variance and Taylor
     forms carry (means, variances, covariances).  A multi-model solve asks for neither.  `cost` (Taylor only): the
     saturating cost as the kernel's objective.  The wrappers are looked up on the module when called.  Returns the
     wrapper's dict."""
+    kind = perf.kind
     kw = dict(safe_actions=safety['actions'], obj_cost=safety['obj_cost'].contiguous(),
               con_cost=safety['con_cost'].contiguous(), status=status, tail_mean=mean[:, horizon:].contiguous(),
               tail_std=std[:, horizon:].contiguous(), tail_noise=tail_noise)
@@ -648,11 +759,11 @@ def _launch_perf(kind: str, ssms: Sequence, env: _lib.SxEnv, x0: Tensor, horizon
     else:
         kw.update(want_traj=want_traj or record, want_sigma=record, **(dict(want_cov=record) if kind == 'taylor' else {}))
     if kind == 'taylor':
-        kw.update(terminal_safety=terminal_safety, **({} if cost is None else dict(cost=cost)))
+        kw.update(terminal_safety=perf.terminal_safety, **({} if cost is None else dict(cost=cost)))
     name = 'cem_perf_rollout' + {'mean': '', 'variance': '_var', 'taylor': '_taylor'}[kind]
     if multi:
         name = 'cem_perf_rollout_taylor_multi' if kind == 'taylor' else 'cem_perf_rollout_multi'
-    return globals()[name](ssms if multi else ssms[0], env, x0, horizon, n_perf, r, **kw)
+    return globals()[name](ssms if multi else ssms[0], env, x0, horizon, perf.n_perf, perf.r, **kw)
 
 
 def fused_refit_applies(ssm, episodes: int, particles: int, horizon: int, candidates: Optional[int] = None) -> bool:
@@ -1011,10 +1122,8 @@ class FusedCemMpc:
                  perf_r: int = 1, perf_variance: bool = False, perf_type: str = 'mean_equivalent',
                  perf_terminal_safety: bool = False, cost_on_safety: bool = False, con_set=None):
         self._ssm = ssm
-        self._con_set = con_set
+        self._con_set = _checked_con_set(con_set, ssm)
         if con_set is not None:
-            _con_set_arg(con_set)
-            _require_exact_rbf([ssm], _CON_SET_IS)
             if int(n_perf) > 0:
                 raise NotImplementedError(f'con_set constrains the safety trajectory of a solve without a performance '
                                           f'trajectory: got n_perf={n_perf} (cem_n_perf > 0 is not built)')
@@ -1028,27 +1137,8 @@ class FusedCemMpc:
         self._env = env
         self._horizon = time_horizon
         # the performance trajectory (off with n_perf = 0): T tail steps behind the H safety steps of a row
-        self._n_perf, self._perf_r = int(n_perf), int(perf_r)
-        if self._n_perf < 0 or (self._n_perf > 0 and not (1 <= self._perf_r <= time_horizon and self._n_perf > self._perf_r)):
-            raise ValueError(f'a performance trajectory needs 1 <= perf_r <= time_horizon and n_perf > perf_r, got '
-                             f'n_perf={n_perf}, perf_r={perf_r}, time_horizon={time_horizon}')
-        self._tail = self._n_perf - self._perf_r if self._n_perf > 0 else 0
-        self._row_steps = time_horizon + self._tail
-        self._perf_variance = bool(perf_variance)
-        if self._perf_variance and self._n_perf <= 0:
-            raise ValueError('perf_variance=True needs a performance trajectory (n_perf > 0)')
-        if perf_type not in PERF_TYPES:
-            raise ValueError(f'perf_type must be one of {PERF_TYPES}, got {perf_type!r}')
-        self._perf_type, self._perf_terminal_safety = perf_type, bool(perf_terminal_safety)
-        self._perf_kind = perf_kind(self._perf_variance, perf_type)
-        if perf_type == 'taylor' and self._n_perf <= 0:
-            raise ValueError("perf_type='taylor' needs a performance trajectory (n_perf > 0)")
-        if self._perf_terminal_safety and perf_type != 'taylor':
-            raise ValueError("perf_terminal_safety needs the propagated covariance (perf_type='taylor')")
-        if self._perf_terminal_safety and self._n_perf < time_horizon + 2:
-            raise ValueError(f'perf_terminal_safety checks the performance state {time_horizon + 2}: n_perf={n_perf} is too '
-                             f'short (n_perf >= time_horizon + 2)')
-        if self._n_perf > 0:
+        self._perf = PerfSpec(n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety).checked(time_horizon)
+        if self._perf.on:
             _require_exact_rbf([ssm], 'the performance trajectory is')
             if process_group is not None:
                 raise NotImplementedError('the performance trajectory is not built for sharded particles (a process group)')
@@ -1060,8 +1150,8 @@ class FusedCemMpc:
         # warm_start 'zero' = mean 0 (the reference's cold start), 'safe_policy' = the safe controller u = k_fb x rolled
         # through the model's mean dynamics from x0 (safe_policy_plan)
         self._init_std = expand_init_std(init_std, time_horizon, ssm.num_actions)
-        if self._tail:      # the tail steps start from the last safety step's value
-            self._init_std = torch.cat([self._init_std, self._init_std[-1:].expand(self._tail, -1)])
+        if self._perf.on:   # the tail steps start from the last safety step's value
+            self._init_std = torch.cat([self._init_std, self._init_std[-1:].expand(self._perf.tail, -1)])
         if warm_start not in ('zero', 'safe_policy'):
             raise ValueError(f"warm_start must be 'zero' or 'safe_policy', got {warm_start!r}")
         self._warm_start = warm_start
@@ -1107,7 +1197,7 @@ class FusedCemMpc:
         """New problem constants (the pendulum's objective target moves between calls).  `objective_hook`, if given, is
         an ``Environment.objective_cost_function`` this module has no kernel form for: it is then evaluated with torch
         on the recorded trajectory centres, H small launches per iteration instead of none."""
-        if self._n_perf > 0 and objective_hook is None:
+        if self._perf.on and objective_hook is None:
             self._check_perf_objective(env)
         self._env = env
         self._objective_hook = objective_hook
@@ -1123,21 +1213,15 @@ class FusedCemMpc:
         on_safety = getattr(self, '_cost_on_safety', False)
         if cost is not None and on_safety:
             _require_exact_rbf([self._ssm], _COST_IS)
-        self._cost = _checked_cost(cost, self._ssm.num_states, self._perf_kind if self._n_perf > 0 else None, on_safety)
+        self._cost = _checked_cost(cost, self._ssm.num_states, perf_spec_of(self).kind, on_safety)
 
     @property
     def _safety_cost(self):
         """The cost where it prices the safety trajectory (cost_on_safety), else None."""
         return self._cost if getattr(self, '_cost_on_safety', False) else None
 
-    @property
-    def _con_set_kw(self) -> dict:
-        """What the constraint set adds to a rollout call (nothing without one)."""
-        con_set = getattr(self, '_con_set', None)
-        return {} if con_set is None else dict(con_set=con_set)
-
     def _check_perf_objective(self, env: _lib.SxEnv) -> None:
-        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf_kind == 'mean':
+        if env.obj_mode == _lib.SX_OBJ_NEG_VARIANCE and self._perf.kind == 'mean':
             raise ValueError('the performance trajectory propagates means only: it cannot carry the variance objective '
                              '(SX_OBJ_NEG_VARIANCE); give the environment an objective_cost_function, or pass '
                              "perf_variance=True or perf_type='taylor'")
@@ -1202,7 +1286,8 @@ class FusedCemMpc:
         this solver's generator.  They are drawn for
         up to 8 solves per generator launch (at most 256 MB): one launch per solve is 8 us + a 6 us gap in front of the first
         rollout, 1.2 % of a config-2 solve."""
-        shape = (self._num_iterations, episodes, self._local_rollouts, self._row_steps, self._ssm.num_actions)
+        shape = (self._num_iterations, episodes, self._local_rollouts, self._perf.row_steps(self._horizon),
+                 self._ssm.num_actions)
         pool = getattr(self, '_noise_pool', None)
         if pool is None or tuple(pool.shape[1:]) != shape or self._noise_next >= pool.size(0):
             per_solve = 8
@@ -1217,8 +1302,8 @@ class FusedCemMpc:
         return out
 
     def sample_noise(self, episodes: int = 1) -> Tensor:
-        return torch.randn((episodes, self._local_rollouts, self._row_steps, self._ssm.num_actions), dtype=torch.float64,
-                           device=self._device, generator=self._gen)
+        return torch.randn((episodes, self._local_rollouts, self._perf.row_steps(self._horizon), self._ssm.num_actions),
+                           dtype=torch.float64, device=self._device, generator=self._gen)
 
     def start_distribution(self, x0: Tensor, init_mean: Optional[Tensor] = None,
                            init_std: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -1226,13 +1311,14 @@ class FusedCemMpc:
         `init_mean` / `init_std` where given, else the warm start's mean and the constructor's init_std; with a performance
         trajectory H + T steps, the tail behind the safety steps (zero mean, or the safe policy's plan continued).  (The constant
         ones are kept between solves: three small launches per solve otherwise, 2 % of a config-2 solve.)"""
-        E, dev, H, n_u = x0.size(0), x0.device, self._row_steps, self._ssm.num_actions
+        perf = self._perf
+        E, dev, H, n_u = x0.size(0), x0.device, perf.row_steps(self._horizon), self._ssm.num_actions
         if init_mean is not None:
             mean = init_mean.to(dev).reshape(E, H, n_u).clone()
-        elif self._warm_start == 'safe_policy' and self._n_perf > 0:
+        elif self._warm_start == 'safe_policy' and perf.on:
             # the plan continued for n_perf steps: its first H steps, then the steps perf_r .. n_perf - 1 as the tail
-            plan = self.safe_policy_plan(x0, max(self._horizon, self._n_perf))
-            mean = torch.cat([plan[:, :self._horizon], plan[:, self._perf_r:self._n_perf]], dim=1).contiguous()
+            plan = self.safe_policy_plan(x0, max(self._horizon, perf.n_perf))
+            mean = torch.cat([plan[:, :self._horizon], plan[:, perf.r:perf.n_perf]], dim=1).contiguous()
         elif self._warm_start == 'safe_policy':
             mean = self.safe_policy_plan(x0).contiguous()
         else:
@@ -1257,7 +1343,7 @@ class FusedCemMpc:
                                       group=self._group if self._world > 1 else None,
                                       objective_hook=self._objective_hook if cost is None else None,
                                       **({} if cost is None else dict(cost=cost)),
-                                      **self._con_set_kw) for e in range(x0.size(0))]
+                                      **_con_set_kw(getattr(self, '_con_set', None))) for e in range(x0.size(0))]
         return dict(actions=acts, traj=None, obj_cost=torch.stack([q['obj_cost'] for q in per_e]),
                     con_cost=torch.stack([q['con_cost'] for q in per_e]))
 
@@ -1278,7 +1364,8 @@ class FusedCemMpc:
         actions.
         """
         n_u, H, E, dev = self._ssm.num_actions, self._horizon, x0.size(0), x0.device
-        perf, rows_steps = self._n_perf > 0, self._row_steps
+        spec = self._perf
+        perf, rows_steps = spec.on, spec.row_steps(H)
         L = rows_steps * n_u
         mean, std = self.start_distribution(x0, init_mean, init_std)
         status = self._fresh_status(dev)
@@ -1296,7 +1383,7 @@ class FusedCemMpc:
         in_prologue = (not stepwise) and (not perf) and self._refit_in_prologue(E)
         # (a cost on the safety trajectory rides in the rollout call: no hook is evaluated, no trajectory recorded for one)
         safety_cost = self._safety_cost
-        cost_kw = dict({} if safety_cost is None else dict(cost=safety_cost), **self._con_set_kw)
+        cost_kw = dict({} if safety_cost is None else dict(cost=safety_cost), **_con_set_kw(getattr(self, '_con_set', None)))
         want_traj = self._record or (self._objective_hook is not None and not perf and safety_cost is None)
         if perf and noise is not None:
             # the draws of the safety steps and of the tail, each contiguous: two copies per solve
@@ -1334,23 +1421,15 @@ class FusedCemMpc:
                 # the constraint cost, and the rows [safety actions | tail] are what the ranking sees
                 # (with a kernel-form cost no hook is evaluated)
                 hook, n_s = (self._objective_hook if self._cost is None else None), self._ssm.num_states
-                pr = _launch_perf(self._perf_kind, [self._ssm], self._env, x0, H, self._n_perf, self._perf_r, r, full_mean,
-                                  full_std, eps_tail, status, want_traj=hook is not None, record=self._record,
-                                  terminal_safety=self._perf_terminal_safety, cost=self._cost)
+                pr = _launch_perf(spec, [self._ssm], self._env, x0, H, r, full_mean, full_std, eps_tail, status,
+                                  want_traj=hook is not None, record=self._record, cost=self._cost)
                 r.update({key: pr[key] for key in ('perf_traj', 'perf_sigma', 'perf_cov') if key in pr})
                 r.update(safe_actions=r['actions'], actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
                 if hook is not None:
-                    obj = torch.zeros_like(pr['obj_cost'])
-                    for t in range(self._n_perf):
-                        obj += hook(pr['perf_traj'][:, :, t].reshape(-1, n_s)).reshape(obj.shape)
-                    r['obj_cost'] = obj.contiguous()
+                    r['obj_cost'] = hook_objective(hook, pr['perf_traj'], spec.n_perf, n_s, pr['obj_cost'])
             elif self._objective_hook is not None and not stepwise and safety_cost is None:
-                n_s = self._ssm.num_states
-                centres = r['traj'][..., :n_s]                                   # [E x P x H x n_s]
-                obj = torch.zeros_like(r['obj_cost'])
-                for t in range(H):
-                    obj += self._objective_hook(centres[:, :, t].reshape(-1, n_s)).reshape(obj.shape)
-                r['obj_cost'] = obj.contiguous()
+                n_s = self._ssm.num_states      # (the hook sees the trajectory centres [E x P x H x n_s])
+                r['obj_cost'] = hook_objective(self._objective_hook, r['traj'][..., :n_s], H, n_s, r['obj_cost'])
             if self.rollout_events is not None:
                 ev[1].record(torch.cuda.current_stream(dev))
                 self.rollout_events.append(ev)
@@ -1415,7 +1494,7 @@ class FusedCemMpc:
             q_block = q_block.contiguous()
         best, best_ok, history, status = self.solve(x0)
         best_host, found, repeated = _check_solve(self, x0, q_block, best, best_ok, status, where, [(self, slice(None))])
-        if self._n_perf > 0:
+        if self._perf.on:
             # the callers' plan is the safety actions of the best row; its tail stays readable
             self.last_perf_actions = best_host[:, self._horizon:]
             best_host = best_host[:, :self._horizon]
@@ -1428,21 +1507,14 @@ class FusedCemMpc:
         Returns (actions [E x H x n_u] on the host, found bool [E] on the host, rollouts); ``found[e] == False`` is the
         ``get_actions`` ``None`` of episode e.  Raises like ``get_actions`` if any episode hit a numerical failure.
         """
-        n_s = self._ssm.num_states
-        if states.dim() != 2 or states.size(1) != n_s + n_s * n_s:
-            raise ValueError(f'Wanted shape (E, {n_s + n_s * n_s}), got {tuple(states.shape)}')
-        states = states.to(self._device, torch.float64)
-        return self._solve_checked(states[:, :n_s].contiguous(), 'get_actions_batch', q_block=states[:, n_s:])
+        x0, q_block = split_flat_states(states, self._ssm.num_states, self._device)
+        return self._solve_checked(x0, 'get_actions_batch', q_block=q_block)
 
     def get_actions(self, state: Tensor) -> Tuple[Optional[Tensor], List[Rollouts]]:
         """state: the flat start state [1 x (n_s + n_s^2)] with an all-zero Q block (a point, safempc_cem.py:234-235).
         The selected actions come back on the host (they travel with the solve's one device->host hand-off)."""
-        n_s = self._ssm.num_states
-        flat = state.reshape(1, -1)
-        if flat.size(1) != n_s + n_s * n_s:
-            raise ValueError(f'Wanted shape (1, {n_s + n_s * n_s}), got {tuple(state.shape)}')
-        flat = flat.to(self._device, torch.float64)
-        best, found, history = self._solve_checked(flat[:, :n_s].contiguous(), 'get_actions', q_block=flat[:, n_s:])
+        x0, q_block = split_flat_states(state.reshape(1, -1), self._ssm.num_states, self._device, episodes=1)
+        best, found, history = self._solve_checked(x0, 'get_actions', q_block=q_block)
         if not bool(found[0]):
             return None, history
         return best[0], history
@@ -1580,11 +1652,8 @@ class MultiModelCem:
         repeat), where `fused_applies` is False; else ONE `solve` and `_check_solve` with a status word per problem.
         `init`: per-problem tensors [E x ...] for `solve`, handed row by row to the solvers' own solves.  Returns (best
         rows on the host, found bool [E] on the host)."""
-        E, n_s = len(self._ssms), self._ssms[0].num_states
-        if states.dim() != 2 or states.shape != (E, n_s + n_s * n_s):
-            raise ValueError(f'Wanted shape ({E}, {n_s + n_s * n_s}), got {tuple(states.shape)}')
-        states = states.to(self._device, torch.float64)
-        x0, q_block = states[:, :n_s].contiguous(), states[:, n_s:].contiguous()
+        x0, q_block = split_flat_states(states, self._ssms[0].num_states, self._device, episodes=len(self._ssms))
+        q_block = q_block.contiguous()
         if not self.fused_applies():
             self.per_model_solves += 1
             per = [s._solve_checked(x0[e:e + 1], where, q_block=q_block[e:e + 1],
@@ -1625,9 +1694,8 @@ class MultiModelCemMpc(MultiModelCem):
     # what one launch needs of its solvers: compared at construction.  (The start distributions are the solvers' own:
     # `solve` takes problem e's from solvers[e].)
     _LAUNCH = (('time_horizon', '_horizon'), ('num_rollouts', '_num_rollouts'), ('num_elites', '_num_elites'),
-               ('num_iterations', '_num_iterations'), ('n_perf', '_n_perf'), ('perf_r', '_perf_r'),
-               ('perf_variance', '_perf_variance'), ('perf_type', '_perf_type'),
-               ('perf_terminal_safety', '_perf_terminal_safety'))
+               ('num_iterations', '_num_iterations'),
+               ('the performance trajectory (n_perf, perf_r, perf_variance, perf_type, perf_terminal_safety)', perf_spec_of))
     # what the solvers of a front end's get_actions_multi share (`check_solvers`)
     _SHARED = (('the solver type', '__class__'),) + _LAUNCH + (
         ('warm_start', '_warm_start'), ('device', '_device'), ('the world size', '_world'),
@@ -1668,7 +1736,7 @@ class MultiModelCemMpc(MultiModelCem):
 
     def _check_trajectories(self) -> None:
         """The trajectories of the solvers this class solves over: the safety trajectory alone."""
-        if any(getattr(s, '_n_perf', 0) > 0 for s in self._solvers):
+        if any(perf_spec_of(s).on for s in self._solvers):
             raise NotImplementedError('MultiModelCemMpc solves have no performance trajectory (solvers with n_perf > 0): '
                                       'MultiModelPerfCemMpc solves those')
 
@@ -1677,9 +1745,9 @@ class MultiModelCemMpc(MultiModelCem):
         _compare_settings(self._solvers, self._COST, self._POLICY.what)
         return getattr(self._solvers[0], '_cost', None)
 
-    def _con_set_kw(self) -> dict:
-        """What the rollout call takes for the solvers' constraint set: nothing here (MultiModelConsCemMpc: the set)."""
-        return {}
+    def _shared_set(self):
+        """The solvers' constraint set as the rollout call takes it: none here (MultiModelConsCemMpc: the set)."""
+        return None
 
     @classmethod
     def from_solvers(cls, solvers: Sequence[FusedCemMpc]) -> 'MultiModelCemMpc':
@@ -1726,7 +1794,7 @@ class MultiModelCemMpc(MultiModelCem):
         in_prologue = self._solvers[0]._refit_in_prologue(E)
         # the solvers' cost where it prices the safety trajectory (cost_on_safety): it rides in the rollout call
         cost = self._solver_cost() if getattr(self._solvers[0], '_cost_on_safety', False) else None
-        cost_kw = dict({} if cost is None else dict(cost=cost), **self._con_set_kw())
+        cost_kw = dict({} if cost is None else dict(cost=cost), **_con_set_kw(self._shared_set()))
 
         def rollout(it, mean, std, rows):
             return cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean, std=std, elite_rows=rows,
@@ -1776,8 +1844,8 @@ class MultiModelConsCemMpc(MultiModelCemMpc):
             raise ValueError('the solvers carry another constraint set than the con_set given')
         _require_exact_rbf(self._ssms, _CON_SET_IS)
 
-    def _con_set_kw(self) -> dict:
-        return dict(con_set=_shared_con_set(self._solvers, 'all', self._POLICY.what))
+    def _shared_set(self):
+        return _shared_con_set(self._solvers, 'all', self._POLICY.what)
 
 
 
@@ -1810,25 +1878,17 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
                                    perf_terminal_safety=perf_terminal_safety) for e, ssm in enumerate(ssms)]
         super().__init__(ssms, env, time_horizon, num_rollouts, num_elites, num_iterations, device=device, seed=seed,
                          init_std=init_std, warm_start=warm_start, solvers=solvers)
-        # (check_solvers compares the five between the solvers)
-        first = self._solvers[0]
-        self._n_perf, self._perf_r, self._perf_variance = first._n_perf, first._perf_r, first._perf_variance
-        if n_perf is not None and (int(n_perf), int(perf_r), bool(perf_variance)) != (self._n_perf, self._perf_r,
-                                                                                      self._perf_variance):
-            raise ValueError(f'the solvers have (n_perf, perf_r, perf_variance) = {(self._n_perf, self._perf_r, self._perf_variance)}'
+        self._perf = perf_spec_of(self._solvers[0])     # (the base has compared the solvers' specs)
+        if n_perf is not None and (int(n_perf), int(perf_r), bool(perf_variance)) != self._perf[:3]:
+            raise ValueError(f'the solvers have (n_perf, perf_r, perf_variance) = {tuple(self._perf[:3])}'
                              f', not {(n_perf, perf_r, perf_variance)}')
         _require_exact_rbf(self._ssms, 'the performance trajectory is', numbered=True)
-        self._tail = self._n_perf - self._perf_r
-        self._perf_type = getattr(first, '_perf_type', 'mean_equivalent')
-        self._perf_terminal_safety = bool(getattr(first, '_perf_terminal_safety', False))
-        self._perf_kind = perf_kind(self._perf_variance, self._perf_type)
-        self._taylor = self._perf_kind == 'taylor'
         # the device table the performance launch reads: alpha per model for the mean-only form, else the safety launch's
-        self._perf_table = PerfModelTable() if self._perf_kind == 'mean' else self._table
+        self._perf_table = PerfModelTable() if self._perf.kind == 'mean' else self._table
 
     def _check_trajectories(self) -> None:
         """The solvers carry a performance trajectory, and no objective hook that would have to be evaluated."""
-        if getattr(self._solvers[0], '_n_perf', 0) <= 0:
+        if not perf_spec_of(self._solvers[0]).on:
             raise ValueError('MultiModelPerfCemMpc needs solvers with a performance trajectory (n_perf > 0); '
                              'MultiModelCemMpc solves the others')
         if any(getattr(s, '_objective_hook', None) is not None and getattr(s, '_cost', None) is None for s in self._solvers):
@@ -1847,22 +1907,23 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         LDS, which holds every training set the multi-model safety rollout takes (n_pad <= 1024).  Host only."""
         if not super().fused_applies():
             return False
-        return self._perf_kind == 'mean' or self._perf_form() >= 0
+        return self._perf.kind == 'mean' or self._perf_form() >= 0
 
     def _perf_form(self) -> int:
         """sx_cem_perf_rollout_{var,taylor}_multi_form of the models: < 0 where they have no single launch.  Host only."""
         query = {'variance': 'sx_cem_perf_rollout_var_multi_form', 'taylor': 'sx_cem_perf_rollout_taylor_multi_form'}
         models = model_array(self._ssms, 'rbf')
-        return int(getattr(_lib.lib(), query[self._perf_kind])(models, len(self._ssms), self._n_perf))
+        return int(getattr(_lib.lib(), query[self._perf.kind])(models, len(self._ssms), self._perf.n_perf))
 
     def solve(self, x0: Tensor, noise: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
         """As `MultiModelCemMpc.solve` with rows of H + T steps: noise [iters x E x P x (H + T) x n_u], and the returned
         best rows [E x (H + T) x n_u] carry the tail behind the safety actions."""
-        E, H, T, n_u = len(self._ssms), self._horizon, self._tail, self._ssms[0].num_actions
+        perf = self._perf
+        E, H, T, n_u = len(self._ssms), self._horizon, perf.tail, self._ssms[0].num_actions
         cost = self._solver_cost()
-        if self._perf_kind == 'taylor' and self._perf_form() < 0:
+        if perf.kind == 'taylor' and self._perf_form() < 0:
             raise FusedMultiUnsupported(f"perf_type='taylor' has no multi-model launch for these models (N = "
-                                        f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {self._n_perf}): '
+                                        f'{[ssm.device_model.n_train for ssm in self._ssms]}, n_perf = {perf.n_perf}): '
                                         f'the solvers act one model at a time')
         noise, mean, std, status = self._begin(x0, noise)
         noise_safe, noise_tail = noise[:, :, :, :H].contiguous(), noise[:, :, :, H:].contiguous()
@@ -1870,8 +1931,7 @@ class MultiModelPerfCemMpc(MultiModelCemMpc):
         def rollout(it, mean, std, rows):
             r = cem_rollout_multi(self._ssms, self._env, x0, H, mean=mean[:, :H].contiguous(), std=std[:, :H].contiguous(),
                                   noise=noise_safe[it], status=status, table=self._table)
-            pr = _launch_perf(self._perf_kind, self._ssms, self._env, x0, H, self._n_perf, self._perf_r, r, mean, std,
-                              noise_tail[it], status, multi=True, terminal_safety=self._perf_terminal_safety,
+            pr = _launch_perf(perf, self._ssms, self._env, x0, H, r, mean, std, noise_tail[it], status, multi=True,
                               table=self._perf_table, cost=cost)
             return dict(actions=pr['rows'], obj_cost=pr['obj_cost'], con_cost=pr['con_cost'])
 
@@ -1916,10 +1976,7 @@ class StaticCemMpc:
     def __init__(self, ssm: GpCemSSM, env: _lib.SxEnv, time_horizon: int, num_rollouts: int, num_elites: int,
                  num_iterations: int, *, start_mean, start_std, n_restarts: int = 1, seed: int = 0, init_std=1.0,
                  device=None, record_rollouts: bool = False, process_group=None, con_set=None):
-        self._con_set = con_set
-        if con_set is not None:
-            _con_set_arg(con_set)
-            _require_exact_rbf([ssm], _CON_SET_IS)
+        self._con_set = _checked_con_set(con_set, ssm)
         _require_exact_rbf([ssm], 'static exploration is')
         if process_group is not None:
             raise NotImplementedError('static exploration is not built for sharded particles (a process group)')
@@ -1972,12 +2029,6 @@ class StaticCemMpc:
         return torch.stack([torch.randn(shape, dtype=torch.float64, device=self._device, generator=g) for g in self._gens],
                            dim=1)
 
-    @property
-    def _con_set_kw(self) -> dict:
-        """The constraint set as the rollouts' keyword; empty without one, so that they are called as before."""
-        con_set = getattr(self, '_con_set', None)
-        return {} if con_set is None else dict(con_set=con_set)
-
     def _rollout_stepwise(self, mean: Tensor, std: Tensor, eps: Tensor, status: Tensor):
         """One iteration's rollout through `cem_rollout_stepwise` with a start per particle, restart by restart; with a
         constraint set the steps are charged by sx_conset_eval and the start by `start_obstacle_cost`."""
@@ -1987,7 +2038,7 @@ class StaticCemMpc:
         for e in range(rows.size(0)):
             x0 = rows[e, :, :n_s].contiguous()
             acts = rows[e, :, n_s:].reshape(-1, self._horizon, n_u).contiguous()
-            r = cem_rollout_stepwise(self._ssm, self._env, x0, acts, status=status, **self._con_set_kw)
+            r = cem_rollout_stepwise(self._ssm, self._env, x0, acts, status=status, **_con_set_kw(self._con_set))
             obj.append(r['obj_cost'])
             start = start_constraint_cost(self._env, x0)
             if self._con_set is not None:
@@ -2018,7 +2069,7 @@ class StaticCemMpc:
             if stepwise:
                 return self._rollout_stepwise(mean, std, eps, status)
             r = cem_rollout_starts(self._ssm, self._env, self._horizon, mean=mean, std=std, noise=eps,
-                                   want_traj=self._record, status=status, **self._con_set_kw)
+                                   want_traj=self._record, status=status, **_con_set_kw(getattr(self, '_con_set', None)))
             if self._record:
                 for e in range(E):
                     history.append(Rollouts(r['traj'][e], r['rows'][e, :, n_s:].reshape(P, self._horizon, n_u),
@@ -2136,7 +2187,7 @@ class MultiModelStaticCemMpc(MultiModelCem):
         std = torch.cat([m._std0.expand(R, L) for m in self._solvers]).contiguous()
         status = torch.zeros(E, dtype=torch.int32, device=dev)
         histories: List[List[Rollouts]] = [[] for _ in range(S)]
-        con_kw = first._con_set_kw
+        con_kw = _con_set_kw(getattr(first, '_con_set', None))
 
         def rollout(it, mean, std, rows):
             r = cem_rollout_starts_multi(ssms, first._env, H, mean=mean, std=std, noise=noise[it].contiguous(),
@@ -2385,10 +2436,7 @@ class CautiousCemMpc:
                                      want_cov=self._record, status=status,
                                      **({} if self._cost is None else dict(cost=self._cost)))
             if hook is not None:
-                obj = torch.zeros_like(r['obj_cost'])
-                for t in range(T):
-                    obj += hook(r['traj'][:, :, t].reshape(-1, n_s)).reshape(obj.shape)
-                r['obj_cost'] = obj.contiguous()
+                r['obj_cost'] = hook_objective(hook, r['traj'], T, n_s, r['obj_cost'])
             self._last_actions = r['rows']
             if self._record:
                 for e in range(E):
@@ -2416,12 +2464,8 @@ class CautiousCemMpc:
         """E independent problems at once: flat start states [E x (n_s + n_s^2)], all points (as
         ``FusedCemMpc.get_actions_batch``).  `init_mean` [E x T x n_u]: the warm start.  Returns (rows [E x T x n_u] on the
         host, found bool [E] on the host, rollouts)."""
-        n_s = self._ssm.num_states
-        if states.dim() != 2 or states.size(1) != n_s + n_s * n_s:
-            raise ValueError(f'Wanted shape (E, {n_s + n_s * n_s}), got {tuple(states.shape)}')
-        states = states.to(self._device, torch.float64)
-        return self._solve_checked(states[:, :n_s].contiguous(), 'get_actions_batch', q_block=states[:, n_s:],
-                                   init_mean=init_mean)
+        x0, q_block = split_flat_states(states, self._ssm.num_states, self._device)
+        return self._solve_checked(x0, 'get_actions_batch', q_block=q_block, init_mean=init_mean)
 
     def get_actions(self, state: Tensor, init_mean: Optional[Tensor] = None) -> Tuple[Optional[Tensor], List[Rollouts]]:
         """state: the flat start state [1 x (n_s + n_s^2)] with an all-zero Q block.  Returns (row [T x n_u] on the host

@@ -16,8 +16,8 @@ from torch import Tensor
 
 from . import _lib, gp_reachability_pytorch
 from .costs import SaturatingCost
-from .cem_mpc import (FusedCemMpc, MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc, Rollouts, StaticCemMpc,
-                      keep_multi, multi_family)
+from .cem_mpc import (CONF_NAMES, FusedCemMpc, MultiModelCemMpc, MultiModelConsCemMpc, MultiModelPerfCemMpc, PerfSpec,
+                      Rollouts, StaticCemMpc, keep_multi, multi_family, perf_spec_of)
 from .gp_reachability_pytorch import make_con_set, make_env, onestep_reachability
 from .safempc import SafeMPC
 from .ssm_cem import gp_ssm_cem
@@ -227,38 +227,23 @@ class CemSafeMPC(SafeMPC):
         # The performance trajectory (FusedCemMpc): cem_n_perf steps (0 = off) sharing their first
         # cem_perf_r actions with the safety trajectory.  Settings of their own: the reference's CEM configs inherit
         # n_perf / r / type_perf_traj from the casadi defaults and must keep solving without one.
-        self._cem_n_perf = int(getattr(conf, 'cem_n_perf', 0) or 0)
-        self._cem_perf_r = int(getattr(conf, 'cem_perf_r', 1))
-        # cem_perf_variance: the performance trajectory carries the GP's posterior variance (sx_cem_perf_rollout_var), and
-        # with it the exploration objective of an environment without an objective_cost_function
-        self._cem_perf_variance = bool(getattr(conf, 'cem_perf_variance', False))
-        if self._cem_perf_variance and not self._cem_n_perf:
-            raise ValueError('cem_perf_variance needs a performance trajectory (cem_n_perf > 0)')
-        # cem_perf_type: 'mean_equivalent' (a point is propagated) or 'taylor' (sx_cem_perf_rollout_taylor: the state
-        # covariance is propagated to first order under the LQR feedback, and the variance objective includes it);
-        # cem_perf_terminal_safety: the performance ellipsoid at step mpc_time_horizon + 2 must lie in the safe polytope.
-        # Settings of their own, like cem_n_perf: the casadi solver's type_perf_traj / perf_safety_constr stay unread.
-        self._cem_perf_type = getattr(conf, 'cem_perf_type', None) or 'mean_equivalent'
-        self._cem_perf_terminal_safety = bool(getattr(conf, 'cem_perf_terminal_safety', False))
-        if self._cem_perf_type not in ('mean_equivalent', 'taylor'):
-            raise ValueError(f"cem_perf_type must be 'mean_equivalent' or 'taylor', got {self._cem_perf_type!r}")
-        taylor = self._cem_perf_type == 'taylor'
-        if taylor and not self._cem_n_perf:
-            raise ValueError("cem_perf_type='taylor' needs a performance trajectory (cem_n_perf > 0)")
-        if self._cem_perf_terminal_safety and not taylor:
-            raise ValueError("cem_perf_terminal_safety needs the propagated covariance (cem_perf_type='taylor')")
-        if self._cem_perf_terminal_safety and self._cem_n_perf < self._mpc_time_horizon + 2:
-            raise ValueError(f'cem_perf_terminal_safety checks the performance state mpc_time_horizon + 2 = '
-                             f'{self._mpc_time_horizon + 2}: cem_n_perf={self._cem_n_perf} is too short')
-        if self._cem_n_perf:
-            if not (1 <= self._cem_perf_r <= self._mpc_time_horizon and self._cem_n_perf > self._cem_perf_r):
-                raise ValueError(f'cem_n_perf={self._cem_n_perf} needs 1 <= cem_perf_r <= mpc_time_horizon and cem_n_perf > '
-                                 f'cem_perf_r, got cem_perf_r={self._cem_perf_r}, mpc_time_horizon={self._mpc_time_horizon}')
+        # cem_perf_variance: the trajectory carries the GP's posterior variance (sx_cem_perf_rollout_var), and with it the
+        # exploration objective of an environment without an objective_cost_function.  cem_perf_type: 'mean_equivalent' (a
+        # point is propagated) or 'taylor' (sx_cem_perf_rollout_taylor: the state covariance is propagated to first order
+        # under the LQR feedback, and the variance objective includes it); cem_perf_terminal_safety: the performance
+        # ellipsoid at step mpc_time_horizon + 2 must lie in the safe polytope.  The casadi solver's type_perf_traj /
+        # perf_safety_constr stay unread.  One PerfSpec, validated here in the settings' names and handed to the optimiser.
+        self._perf = PerfSpec(getattr(conf, 'cem_n_perf', 0) or 0, getattr(conf, 'cem_perf_r', 1),
+                              getattr(conf, 'cem_perf_variance', False),
+                              getattr(conf, 'cem_perf_type', None) or 'mean_equivalent',
+                              getattr(conf, 'cem_perf_terminal_safety', False)).checked(self._mpc_time_horizon,
+                                                                                        names=CONF_NAMES)
+        if self._perf.on:
             family = getattr(ssm, 'kernel_family', None)
             if mpc is None and family != 'rbf':
                 raise NotImplementedError(f'cem_n_perf > 0 needs an exact RBF GP (GpCemSSM); kernel_family {family!r} has no '
                                           f'performance trajectory')
-            if (not self._cem_perf_variance and not taylor
+            if (self._perf.kind == 'mean'
                     and env.objective_cost_function(torch.zeros((1, env.n_s), dtype=torch.float64)) is None):
                 raise ValueError('cem_n_perf > 0 needs an environment objective: the performance trajectory propagates '
                                  'means only and cannot carry the variance objective (set cem_perf_variance or '
@@ -268,9 +253,9 @@ class CemSafeMPC(SafeMPC):
         # SaturatingCost prices the safety ellipsoids in the rollout kernel (FusedCemMpc(cost_on_safety=True), DESIGN.md
         # section 3.13).  The cost belongs to one trajectory, chosen by cem_n_perf as the reference's config chooses.
         self._cem_cost_on_safety = bool(getattr(conf, 'cem_cost_on_safety', False))
-        if self._cem_cost_on_safety and self._cem_n_perf:
+        if self._cem_cost_on_safety and self._perf.on:
             raise ValueError(f'cem_cost_on_safety prices the safety trajectory, which carries the objective only without a '
-                             f'performance trajectory: got cem_n_perf={self._cem_n_perf}')
+                             f'performance trajectory: got cem_n_perf={self._perf.n_perf}')
         if self._cem_cost_on_safety and mpc is None and getattr(ssm, 'kernel_family', None) != 'rbf':
             raise NotImplementedError(f'cem_cost_on_safety needs an exact RBF GP (GpCemSSM), not kernel_family '
                                       f'{getattr(ssm, "kernel_family", None)!r}')
@@ -285,9 +270,9 @@ class CemSafeMPC(SafeMPC):
         if ctrl_ellipsoid or obstacle:
             setting = ' / '.join(name for name, on in (('cem_ctrl_ellipsoid_constraint', ctrl_ellipsoid),
                                                        ('cem_obstacle_constraint', obstacle)) if on)
-            if self._cem_n_perf:
+            if self._perf.on:
                 raise NotImplementedError(f'{setting} constrains the safety trajectory of a solve without a performance '
-                                          f'trajectory: got cem_n_perf={self._cem_n_perf}')
+                                          f'trajectory: got cem_n_perf={self._perf.n_perf}')
             if mpc is None and getattr(ssm, 'kernel_family', None) != 'rbf':
                 raise NotImplementedError(f'{setting} needs an exact RBF GP (GpCemSSM), not kernel_family '
                                           f'{getattr(ssm, "kernel_family", None)!r}')
@@ -345,7 +330,7 @@ class CemSafeMPC(SafeMPC):
     @property
     def performance_trajectory_length(self) -> int:
         """conf.cem_n_perf: 0 (the reference's CEM solver has none, safempc_cem.py:212-215) unless that setting asks."""
-        return self._cem_n_perf
+        return self._perf.n_perf
 
     @property
     def x_train(self) -> ndarray:
@@ -362,11 +347,12 @@ class CemSafeMPC(SafeMPC):
         configs).  Any other value is ignored: the objective is then the environment's."""
         if not isinstance(cost_func, SaturatingCost):
             return
-        on_safety = getattr(self, '_cem_cost_on_safety', False) and self._cem_n_perf <= 0
-        if not on_safety and (self._cem_perf_type != 'taylor' or self._cem_n_perf <= 0):
+        perf = perf_spec_of(self)
+        on_safety = getattr(self, '_cem_cost_on_safety', False) and not perf.on
+        if not on_safety and perf.kind != 'taylor':
             raise ValueError("a SaturatingCost prices (mean, covariance) pairs of the performance trajectory: it needs "
-                             f"cem_perf_type='taylor' with cem_n_perf > 0, got cem_perf_type={self._cem_perf_type!r}, "
-                             f'cem_n_perf={self._cem_n_perf}; without a performance trajectory, cem_cost_on_safety prices '
+                             f"cem_perf_type='taylor' with cem_n_perf > 0, got cem_perf_type={perf.type!r}, "
+                             f'cem_n_perf={perf.n_perf}; without a performance trajectory, cem_cost_on_safety prices '
                              f'the safety ellipsoids')
         self._cost = cost_func
         if self._mpc is not None:
@@ -387,7 +373,7 @@ class CemSafeMPC(SafeMPC):
         state_c = next(c for c in self._constraints if hasattr(c, 'polytope_a'))
         spec = objective_spec(self._env)
         mode, w_abs, target, w_lin = spec if spec is not None else (_lib.SX_OBJ_NEG_VARIANCE, None, None, None)
-        if spec is None and self._cem_n_perf:
+        if spec is None and self._perf.on:
             # the hook is evaluated on the performance trajectory's recorded means; the kernels' own objective (all-zero
             # weights here) is overwritten
             mode = _lib.SX_OBJ_AFFINE_ABS
@@ -420,10 +406,7 @@ class CemSafeMPC(SafeMPC):
                                     seed=int(getattr(self._conf, 'cem_seed', 0)),
                                     init_std=getattr(self._conf, 'cem_init_std', 1.0),
                                     warm_start=getattr(self._conf, 'cem_warm_start', None) or 'zero',
-                                    record_rollouts=self._record_rollouts, n_perf=self._cem_n_perf,
-                                    perf_r=self._cem_perf_r, **({'perf_variance': True} if self._cem_perf_variance else {}),
-                                    **({'perf_type': 'taylor', 'perf_terminal_safety': self._cem_perf_terminal_safety}
-                                       if self._cem_perf_type == 'taylor' else {}),
+                                    record_rollouts=self._record_rollouts, **self._perf.keywords(),
                                     **({'cost_on_safety': True} if getattr(self, '_cem_cost_on_safety', False) else {}),
                                     **({} if getattr(self, '_con_set', None) is None else {'con_set': self._con_set}))
             if self._cost is not None:
@@ -623,18 +606,17 @@ def get_actions_multi(solvers: Sequence[CemSafeMPC], states: ndarray) -> Tuple[n
         raise NotImplementedError(f'get_actions_multi takes solvers that all have a constraint set or all have none: '
                                   f'{len(with_set)} of {len(solvers)} have {with_set[0]._con_set_setting}; those act one at '
                                   f'a time (get_action), or together in a call of their own')
-    # the performance trajectory (cem_n_perf > 0): all solvers or none, with one (cem_n_perf, cem_perf_r, cem_perf_variance)
-    perf = [(getattr(s, '_cem_n_perf', 0), getattr(s, '_cem_perf_r', 1), getattr(s, '_cem_perf_variance', False),
-             getattr(s, '_cem_perf_type', 'mean_equivalent'), getattr(s, '_cem_perf_terminal_safety', False))
-            for s in solvers]
-    with_perf = any(p[0] > 0 for p in perf)
-    if with_perf and not all(p[0] > 0 for p in perf):
+    # the performance trajectory (cem_n_perf > 0): all solvers or none, with one spec
+    perf = [perf_spec_of(s) for s in solvers]
+    with_perf = any(p.on for p in perf)
+    if with_perf and not all(p.on for p in perf):
         raise NotImplementedError('get_actions_multi takes solvers that all have a performance trajectory or all have none: '
-                                  f'got cem_n_perf = {[p[0] for p in perf]}; the ones with cem_n_perf > 0 act one at a time '
+                                  f'got cem_n_perf = {[p.n_perf for p in perf]}; the ones with cem_n_perf > 0 act one at a time '
                                   f'(get_action), or together in a call of their own')
     if with_perf and len(set(perf)) != 1:
         raise ValueError('the solvers of get_actions_multi must share the performance trajectory\'s settings: got '
-                         f'(cem_n_perf, cem_perf_r, cem_perf_variance, cem_perf_type, cem_perf_terminal_safety) = {perf}')
+                         f'(cem_n_perf, cem_perf_r, cem_perf_variance, cem_perf_type, cem_perf_terminal_safety) = '
+                         f'{[tuple(p) for p in perf]}')
     n_s, n_u = solvers[0].state_dimen, solvers[0].action_dimen
     if states.ndim != 2 or states.shape != (len(solvers), n_s):
         raise ValueError(f'Wanted shape ({len(solvers)}, {n_s}), got {states.shape}')

@@ -319,7 +319,7 @@ def test_get_action_over_an_exploration_environment():
     action, result = solver.get_action(np.array([0.02, -0.03]))
     assert action.shape == (1,) and result == MpcResult.FOUND_SOLUTION
     mpc = solver._solver()
-    assert mpc._perf_type == 'taylor' and mpc._perf_terminal_safety and not mpc._perf_variance
+    assert mpc._perf.type == 'taylor' and mpc._perf.terminal_safety and not mpc._perf.variance
     assert mpc._env.obj_mode == VAR and mpc._objective_hook is None
     assert tuple(mpc.last_perf_actions.shape) == (1, 10 - 1, 1) and mpc.last_status == 0
     assert bool((np.abs(solver._last_mpc_actions) <= 1.0).all())    # feasible: inside the action box

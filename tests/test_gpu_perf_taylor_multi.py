@@ -349,9 +349,9 @@ def test_lockstep_runner_with_one_taylor_solver_per_scenario_matches_do_rollout(
     solvers, envs = [p[0] for p in pairs], [p[1] for p in pairs]
     res = do_rollout_batch(envs, steps, solvers)
     multi = solvers[0]._multi[1]
-    assert isinstance(multi, MultiModelPerfCemMpc) and multi._taylor and multi.per_model_solves == 0
+    assert isinstance(multi, MultiModelPerfCemMpc) and multi._perf.kind == 'taylor' and multi.per_model_solves == 0
     for s in solvers:
-        assert s._solver()._perf_type == 'taylor'
+        assert s._solver()._perf.type == 'taylor'
         assert tuple(s._solver().last_perf_actions.shape) == (1, Conf.cem_n_perf - 1, 1)
     for e, (r, (xx, yy, cc, codes, failed)) in enumerate(zip(res, seq)):
         assert r.safety_failure == failed and r.xx.shape == xx.shape, e
@@ -376,4 +376,4 @@ def test_find_max_variance_multi_gives_what_the_explorations_give_one_by_one():
     print(f'max |multi - one by one| = {float(np.abs(u - np.stack(one_by_one)).max()):.3e}; tolerance 1e-9')
     np.testing.assert_allclose(u, np.stack(one_by_one), rtol=0, atol=1e-9)
     multi = explorations[0].safempc._multi[1]
-    assert isinstance(multi, MultiModelPerfCemMpc) and multi._taylor and multi.per_model_solves == 0
+    assert isinstance(multi, MultiModelPerfCemMpc) and multi._perf.kind == 'taylor' and multi.per_model_solves == 0

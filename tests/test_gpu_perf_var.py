@@ -347,7 +347,7 @@ def test_get_action_and_find_max_variance_over_an_exploration_environment():
     assert action.shape == (1,) and result == MpcResult.FOUND_SOLUTION
     assert solver._last_mpc_actions.shape == (Conf.mpc_time_horizon, 1)
     mpc = solver._solver()
-    assert mpc._perf_variance and mpc._env.obj_mode == VAR and mpc._objective_hook is None
+    assert mpc._perf.variance and mpc._env.obj_mode == VAR and mpc._objective_hook is None
     assert tuple(mpc.last_perf_actions.shape) == (1, 10 - 1, 1) and mpc.last_status == 0
     explorer = DynamicSafeMPCExploration(solver, env)
     assert (explorer.n_safe, explorer.n_perf) == (5, 10)

@@ -390,7 +390,7 @@ def test_safempc_get_action_after_init_solver():
     assert solver._cost is None
     solver.init_solver(cost)
     mpc = solver._solver()
-    assert mpc._safety_cost is cost and mpc._n_perf == 0
+    assert mpc._safety_cost is cost and mpc._perf.n_perf == 0
     mpc._next_noise = lambda episodes: T(noise[:, None])      # the oracle's draws
     counting = CountingLib(_lib.lib())
     with mock.patch.object(_lib, 'lib', lambda: counting):

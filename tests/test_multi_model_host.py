@@ -155,10 +155,11 @@ def _cem_classes():
 def test_check_solvers_names_the_setting_and_the_solver(cls):
     import re
     import torch
+    from safe_exploration_amd import cem_mpc
     from test_perf_multi_host import _env as solver_env
     cls.check_solvers(_fused_solvers(cls))
     cls.from_solvers(_fused_solvers(cls))
-    assert len(cls._SHARED) == 16 and {'__class__', '_init_std', '_env'} < {attr for _, attr in cls._SHARED}
+    assert len(cls._SHARED) == 12 and {'__class__', '_init_std', '_env', cem_mpc.perf_spec_of} < {attr for _, attr in cls._SHARED}
 
     def refused(solvers, name):
         named = re.escape(name) + r': solver (0 has .*, solver 1 has|1 differs from solver 0)'
@@ -170,6 +171,13 @@ def test_check_solvers_names_the_setting_and_the_solver(cls):
         solvers = _fused_solvers(cls)
         if attr == '__class__':
             solvers[1].__class__ = type('Other', (type(solvers[1]),), {})
+        elif attr is cem_mpc.perf_spec_of:      # the five settings of the performance trajectory: one row, one value
+            for field in cem_mpc.PerfSpec._fields:
+                solvers = _fused_solvers(cls)
+                solvers[1]._perf = solvers[1]._perf._replace(**{field: object()})
+                refused(solvers, name)
+                assert all(n in name for n in cem_mpc.KEYWORD_NAMES[:5])
+            continue
         else:
             setattr(solvers[1], attr, object())
         refused(solvers, name)

@@ -183,8 +183,8 @@ def test_fused_cem_mpc_settings_raise_what_they_must():
     mpc = mk(n_perf=6, perf_type='taylor')                       # carries the variance objective by itself
     mpc.set_env(_env(obj_mode=ABS))
     mpc.set_env(_env(obj_mode=VAR))
-    assert mpc._perf_type == 'taylor' and not mpc._perf_terminal_safety and not mpc._perf_variance
-    assert mk(n_perf=7, perf_type='taylor', perf_terminal_safety=True)._perf_terminal_safety
+    assert mpc._perf.type == 'taylor' and not mpc._perf.terminal_safety and not mpc._perf.variance
+    assert mk(n_perf=7, perf_type='taylor', perf_terminal_safety=True)._perf.terminal_safety
     with pytest.raises(ValueError, match='perf_type'):
         mk(n_perf=6, perf_type='unscented')
     for kw in (dict(), dict(n_perf=0)):
@@ -283,12 +283,12 @@ def test_without_the_settings_a_solve_calls_what_it_called(monkeypatch, kw):
 # ---- CemSafeMPC and get_actions_multi --------------------------------------------------------------------------------------
 def test_cem_safempc_reads_the_settings():
     solver = _safempc(conf(cem_n_perf=6, cem_perf_type='taylor'), objective_target=None)      # exploration: no objective
-    assert solver.performance_trajectory_length == 6 and solver._cem_perf_type == 'taylor'
-    assert _safempc(conf(cem_n_perf=7, cem_perf_type='taylor', cem_perf_terminal_safety=True))._cem_perf_terminal_safety
+    assert solver.performance_trajectory_length == 6 and solver._perf.type == 'taylor'
+    assert _safempc(conf(cem_n_perf=7, cem_perf_type='taylor', cem_perf_terminal_safety=True))._perf.terminal_safety
     plain = _safempc(conf(cem_n_perf=6))
-    assert plain._cem_perf_type == 'mean_equivalent' and not plain._cem_perf_terminal_safety
+    assert plain._perf.type == 'mean_equivalent' and not plain._perf.terminal_safety
     # the casadi solver's settings stay unread
-    assert _safempc(conf(type_perf_traj='taylor', perf_safety_constr=True))._cem_perf_type == 'mean_equivalent'
+    assert _safempc(conf(type_perf_traj='taylor', perf_safety_constr=True))._perf.type == 'mean_equivalent'
     with pytest.raises(ValueError, match='cem_perf_type'):
         _safempc(conf(cem_n_perf=6, cem_perf_type='unscented'))
     with pytest.raises(ValueError, match='cem_n_perf'):

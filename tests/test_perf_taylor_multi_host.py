@@ -181,7 +181,7 @@ def test_every_iteration_is_one_safety_launch_one_taylor_launch_and_one_ranking(
     T = n_perf - r
     mpc = MultiModelPerfCemMpc([_Ssm(7), _Ssm(200), _Ssm(590)], _env(obj_mode=VAR), H, P, 8, iters, device='cpu',
                                init_std=0.2, n_perf=n_perf, perf_r=r, perf_type='taylor', perf_terminal_safety=safety)
-    assert all(s._perf_type == 'taylor' and s._perf_terminal_safety == safety for s in mpc.solvers)
+    assert all(s._perf.type == 'taylor' and s._perf.terminal_safety == safety for s in mpc.solvers)
     assert mpc.fused_applies() is True
     noise = torch.randn((iters, E, P, H + T, 1), dtype=torch.float64)
     fake.calls.clear()

@@ -295,7 +295,7 @@ class _Mpc:
 def test_init_solver_with_and_without_cem_cost_on_safety(monkeypatch):
     # objects built by __new__ may lack the setting: it reads as off
     solver = CemSafeMPC.__new__(CemSafeMPC)
-    solver._mpc, solver._cost, solver._cem_perf_type, solver._cem_n_perf = _Mpc(), None, 'mean_equivalent', 0
+    solver._mpc, solver._cost, solver._perf = _Mpc(), None, cem_mpc.PerfSpec(0, type='mean_equivalent')
     with pytest.raises(ValueError, match="cem_perf_type='taylor'"):
         solver.init_solver(COST2)
     solver._cem_cost_on_safety = True

@@ -362,7 +362,7 @@ class _Mpc:
 def test_init_solver_hands_a_saturating_cost_to_the_optimiser():
     from safe_exploration_amd.cautious_mpc import CautiousCemMPC
     from safe_exploration_amd.safempc_cem import CemSafeMPC
-    for cls, attrs in ((CautiousCemMPC, {}), (CemSafeMPC, dict(_cem_perf_type='taylor', _cem_n_perf=10))):
+    for cls, attrs in ((CautiousCemMPC, {}), (CemSafeMPC, dict(_perf=cem_mpc.PerfSpec(10, type='taylor')))):
         solver = cls.__new__(cls)
         solver._mpc, solver._cost = _Mpc(), None
         for k, v in attrs.items():
@@ -375,7 +375,7 @@ def test_init_solver_hands_a_saturating_cost_to_the_optimiser():
         solver._mpc = None                                              # before the optimiser exists the cost is kept for it
         solver.init_solver(COST2)
         assert solver._cost is COST2
-    for attrs in (dict(_cem_perf_type='mean_equivalent', _cem_n_perf=10), dict(_cem_perf_type='taylor', _cem_n_perf=0)):
+    for attrs in (dict(_perf=cem_mpc.PerfSpec(10, type='mean_equivalent')), dict(_perf=cem_mpc.PerfSpec(0, type='taylor'))):
         solver = CemSafeMPC.__new__(CemSafeMPC)
         solver._mpc, solver._cost = _Mpc(), None
         for k, v in attrs.items():
