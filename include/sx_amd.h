@@ -229,6 +229,31 @@ int sx_gp_fit(const sx_gp_model* model, const double* y_train, double* work, dou
 int sx_gp_mll_grad(const sx_gp_model* model, const double* y_train, const double* linv, const double* alpha,
                    const double* logdet, double* work, double* mll, double* grad, void* stream);
 
+/* ---- k <= 64 rows appended to a fitted exact GP without refactorising the old ones ----
+ * model->{n_s,n_u,n_train,inv_ls2,outputscale,noise,x_train} set as for sx_gp_fit with n_train = N + k and x_train dev
+ * [(N + k) x D], whose first n_old = N rows are the fitted ones; y_train dev [(N + k) x n_s]; linv_old dev [n_s x N x N],
+ * alpha_old dev [n_s x N] and logdet_old dev [n_s] as sx_gp_fit (or this entry) wrote them for those N rows and these
+ * hyper-parameters.  Per output, with K_c = k(X, X_c), K_cc = k(X_c, X_c) + noise I and B = W K_c:
+ *     S = K_cc - B^T B = L_s L_s^T,  W_s = L_s^-1,  new rows of W: [ -W_s B^T W | W_s ],  old rows: W with k zeros appended,
+ *     alpha' = [alpha; 0] + W_bot^T (W_bot y'),  logdet' = logdet + sum log diag L_s.
+ * linv dev [n_s x (N + k) x (N + k)], alpha dev [n_s x (N + k)] and logdet dev [n_s] get exactly the layout sx_gp_fit leaves
+ * for N + k rows (zeros above the diagonal included), so sx_gp_pack, sx_gp_mll_grad, sx_gp_predict_var_jac and a further
+ * sx_gp_append take them unchanged; the old rows of linv are linv_old's bit for bit.  The old and the new buffers must be
+ * DISTINCT (the row stride changes).  status dev int32, or-ed into: SX_STATUS_NOT_PD where a pivot of S is not > 0 (NaN
+ * included); the outputs are then unspecified.  workspace dev, sx_gp_append_workspace_bytes(n_s, N + k, k) bytes.  Six
+ * launches on `stream`, O(N^2 k) work, every sum in an order that depends on N and k only; nothing is waited for.
+ * SX_ERR_ARG (before any device access) for a null pointer, a shape sx_gp_fit refuses, n_old < 1, n_train - n_old outside
+ * 1 .. 64 or a workspace that is too small; SX_ERR_UNSUPPORTED for n_train > 4096.
+ * Replaces: the refit gpytorch's ExactGP runs when GpCemSSM gets new training data (ssm_cem/gp_ssm_cem.py:96-101), where
+ * the new data extend the old and the hyper-parameters have not changed: exploration_runner adds one pair per iteration
+ * (exploration_runner.py), episode_runner one episode's rows.
+ *
+ * Bytes of the workspace; < 0 for n_s outside 1 .. SX_MAX_NS, k outside 1 .. 64, n_train - k < 1 or n_train > 4096. */
+int64_t sx_gp_append_workspace_bytes(int n_s, int n_train, int k);
+int sx_gp_append(const sx_gp_model* model, int n_old, const double* y_train, const double* linv_old, const double* alpha_old,
+                 const double* logdet_old, double* linv, double* alpha, double* logdet, int32_t* status,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- E exact GPs' fit and MLL gradient in one launch sequence (batched hyper-parameter training) ----
  * Every problem e has its own training set (its own N <= 4096) and hyper-parameters; all share (n_s, n_u).  Problem e's
  * linv, alpha, logdet, mll and gradient are bit-identical to what sx_gp_fit / sx_gp_mll_grad give for that model alone.

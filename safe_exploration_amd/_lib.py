@@ -80,6 +80,8 @@ SIGNATURES = {
     'sx_gp_pack_sizes': (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     'sx_gp_fit': (c_int, [POINTER(SxGpModel)] + [c_void_p] * 7),
     'sx_gp_mll_grad': (c_int, [POINTER(SxGpModel)] + [c_void_p] * 8),
+    'sx_gp_append_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
+    'sx_gp_append': (c_int, [POINTER(SxGpModel), c_int] + [c_void_p] * 9 + [c_int64, c_void_p]),
     'sx_gp_fit_table_bytes': (c_int64, [c_int]),
     'sx_gp_fit_table': (c_int, [POINTER(SxGpModel), c_int] + [POINTER(c_void_p)] * 5 + [c_void_p] * 4),
     'sx_gp_fit_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),

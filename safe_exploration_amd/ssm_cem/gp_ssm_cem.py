@@ -30,12 +30,16 @@ _NOISE_FLOOR = 1e-4
 MAX_TRAINING_POINTS = 4096
 # csrc/sx_gp_select.hpp kSelMaxN: the pool a max-variance subset is chosen from (conf.cem_gp_subset_size)
 MAX_POOL_POINTS = 65536
+# csrc/sx_gp_append.hpp kAppendMaxK: the rows one sx_gp_append call adds (conf.cem_gp_incremental)
+MAX_APPEND_ROWS = 64
 
 
 class GpCemSSM(CemSSM):
     kernel_family = 'rbf'   # 'feature' for the degenerate kernels ('linear', 'nn'): feature_gp_ssm_cem.FeatureGpCemSSM
     _subset_size: Optional[int] = None     # conf.cem_gp_subset_size (set by __init__; the weight-space subclass has none)
     _subset_idx: Optional[Tensor] = None
+    _incremental = False                   # conf.cem_gp_incremental (set by __init__; the weight-space subclass has none)
+    _append_ok = False
 
     def __new__(cls, conf=None, *args, **kwargs):
         # one class name for every kernel, as in the reference (gp_ssm_cem.py:45-57): the 'linear' and 'nn' kernels are
@@ -67,6 +71,19 @@ class GpCemSSM(CemSSM):
         if self._subset_size is not None and not 1 <= self._subset_size <= MAX_TRAINING_POINTS:
             raise ValueError(f'cem_gp_subset_size={subset}: the fitted subset holds 1 .. {MAX_TRAINING_POINTS} points')
         self._subset_idx: Optional[Tensor] = None   # rows of the stored pool the device model is fitted on (None: all)
+        # conf.cem_gp_incremental: an update whose data extend the fitted rows by 1 .. 64 under unchanged hyper-parameters
+        # appends to the factorisation (sx_gp_append, O(N^2 k)) instead of refitting (O(N^3)); off: every update is a full fit.
+        # conf.cem_gp_incremental_max_chain: at most that many rows are appended between two full fits (None: no limit --
+        # 64 single-row appends stay within the fit's own error allowance).
+        self._incremental = bool(getattr(conf, 'cem_gp_incremental', False))
+        chain = getattr(conf, 'cem_gp_incremental_max_chain', None)
+        self._max_chain: Optional[int] = None if chain is None else int(chain)
+        if self._max_chain is not None and self._max_chain < 0:
+            raise ValueError(f'cem_gp_incremental_max_chain={chain}: a row count, or None')
+        self._append_ok = False      # may the next update append to the installed fit?  (False after anything but a plain update)
+        self._appended = 0           # rows appended since the last full fit
+        self._fit_state = None       # the installed fit: (y, logdet on the device, the raw hyper-parameters and the floor)
+        self._append_ws: Optional[Tensor] = None
         d_in = state_dimen + action_dimen
         self._raw_lengthscale = torch.zeros((state_dimen, d_in), dtype=torch.float64)
         self._raw_outputscale = torch.zeros((state_dimen,), dtype=torch.float64)
@@ -112,6 +129,7 @@ class GpCemSSM(CemSSM):
             if (nz <= self._noise_floor).any():
                 self._noise_floor = 0.0   # explicit values below gpytorch's default floor: drop the floor
             self._raw_noise = self._inv_softplus(nz - self._noise_floor)
+        self._append_ok = False
         if self._x_train is not None:
             self._update_model(self._x_train, self._y_train)
 
@@ -126,6 +144,7 @@ class GpCemSSM(CemSSM):
         self._raw_outputscale = state['gp_model']['raw_outputscale'].clone()
         self._raw_noise = state['gp_likelihood']['raw_noise'].clone()
         self._noise_floor = float(state['gp_likelihood']['noise_floor'])
+        self._append_ok = False
         if self._x_train is not None:
             self._update_model(self._x_train, self._y_train)
 
@@ -166,6 +185,31 @@ class GpCemSSM(CemSSM):
                                  _lib.ptr(logdet), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_gp_fit')
         return m, linv, alpha, logdet, status
 
+    def _appends_next(self, new_x: Tensor, new_y: Tensor):
+        """Would update_model(new_x, new_y) append to the installed fit?  None, or the merged training set (train_x,
+        train_y) that update_model would store: the decision is made once here (the comparison of the fitted rows is a
+        device round trip) and `_update_appending` acts on it."""
+        if not (self._incremental and self._append_ok and self._x_train is not None and self._y_train is not None
+                and new_x.dim() == 2 and new_y.dim() == 2 and new_x.size(0) == new_y.size(0)
+                and new_x.shape[1:] == self._x_train.shape[1:] and new_y.shape[1:] == self._y_train.shape[1:]
+                and new_x.device == self._x_train.device and new_y.device == self._y_train.device):
+            return None
+        if not 1 <= new_x.size(0) <= MAX_APPEND_ROWS:
+            return None
+        train_x, train_y = torch.cat((self._x_train, new_x), dim=0), torch.cat((self._y_train, new_y), dim=0)
+        if self._append_rows(train_x.detach().contiguous(), train_y.detach().contiguous()) == 0:
+            return None
+        return train_x, train_y
+
+    def _update_appending(self, train_x: Tensor, train_y: Tensor) -> None:
+        """update_model of the new rows behind `_appends_next`'s answer (train_x, train_y), without asking again."""
+        _lib.require_gpu(train_x, 'train_x')
+        _lib.require_gpu(train_y, 'train_y')
+        self._x_train, self._y_train = train_x, train_y
+        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
+        if not self._append(x, y, x.size(0) - self._buffers[0].size(0)):
+            self._update_model(train_x, train_y, may_append=False)
+
     def _selects(self, n: int) -> bool:
         """Is a pool of n points cut down to conf.cem_gp_subset_size before it is fitted?"""
         return self._subset_size is not None and n > self._subset_size
@@ -196,12 +240,79 @@ class GpCemSSM(CemSSM):
             x, y = x[self._subset_idx].contiguous(), y[self._subset_idx].contiguous()
         return x, y
 
-    def _update_model(self, x_train: Tensor, y_train: Tensor) -> None:
+    def update_model(self, train_x: Tensor, train_y: Tensor, opt_hyp=False, replace_old=False) -> None:
+        # conf.cem_gp_incremental: only a plain update may append, and only to the fit a plain update left
+        if opt_hyp or replace_old or self.parametric:
+            self._append_ok = False
+        super().update_model(train_x, train_y, opt_hyp, replace_old)
+        if opt_hyp or self.parametric:
+            self._append_ok = False
+
+    def _hyper_state(self):
+        return (self._raw_lengthscale, self._raw_outputscale, self._raw_noise, self._noise_floor)
+
+    def _append_rows(self, x: Tensor, y: Tensor) -> int:
+        """k, the rows by which (x, y) (device, contiguous) extend the installed fit where the update may append them
+        (conf.cem_gp_incremental); 0: a full fit."""
+        if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
+                and self._fit_state is not None and self._subset_idx is None):
+            return 0
+        fit_x, (fit_y, _, hyper) = self._buffers[0], self._fit_state
+        n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
+        if not 1 <= k <= MAX_APPEND_ROWS or n + k > MAX_TRAINING_POINTS or self._selects(n + k):
+            return 0
+        if self._max_chain is not None and self._appended + k > self._max_chain:
+            return 0
+        if x.device != fit_x.device or self._fit_ws[1].size(1) != n:
+            return 0
+        now = self._hyper_state()
+        if now[3] != hyper[3] or not all(torch.equal(a, b) for a, b in zip(now[:3], hyper[:3])):
+            return 0
+        # the fitted rows themselves, compared where they live
+        if not (torch.equal(x[:n], fit_x) and torch.equal(y[:n], fit_y)):
+            return 0
+        return k
+
+    def _append(self, x: Tensor, y: Tensor, k: int) -> bool:
+        """sx_gp_append of the last k rows of (x, y) to the installed fit, into fresh buffers that become the fit workspace,
+        then the usual pack and install.  False (and nothing changed) where S is not positive definite."""
+        lib = _lib.lib()
+        dev = x.device
+        n_s, n2 = self.num_states, x.size(0)
+        _, logdet_old, _ = self._fit_state
+        m = self._fit_struct(x)
+        nbytes = int(lib.sx_gp_append_workspace_bytes(n_s, n2, k))
+        if nbytes < 0:
+            raise _lib.SxError('sx_gp_append_workspace_bytes: bad argument')
+        if self._append_ws is None or self._append_ws.numel() * 8 < nbytes or self._append_ws.device != dev:
+            self._append_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        linv = torch.empty((n_s, n2, n2), dtype=torch.float64, device=dev)
+        alpha = torch.empty((n_s, n2), dtype=torch.float64, device=dev)
+        logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.sx_gp_append(ctypes.byref(m), n2 - k, _lib.ptr(y), _lib.ptr(self._fit_ws[1]), _lib.ptr(self._alpha),
+                                    _lib.ptr(logdet_old), _lib.ptr(linv), _lib.ptr(alpha), _lib.ptr(logdet),
+                                    _lib.ptr(status), _lib.ptr(self._append_ws), nbytes, _lib.stream_ptr(dev)), 'sx_gp_append')
+        # (the status first: where S is not positive definite the outputs are unspecified and nothing is packed from them)
+        if int(status.item()) & _lib.SX_STATUS_NOT_PD:
+            return False
+        packed = self._pack(m, linv, alpha)
+        # (no `work` of this size exists: the next full fit allocates its own)
+        self._fit_ws = (linv.new_empty((n_s, 0, 0)), linv)
+        self._install(x, m, packed, alpha, logdet.cpu(), y=y, logdet_dev=logdet)
+        self._appended += k
+        return True
+
+    def _update_model(self, x_train: Tensor, y_train: Tensor, may_append: bool = True) -> None:
         self._check_pool_size(x_train.size(0))
         _lib.require_gpu(x_train, 'train_x')
         _lib.require_gpu(y_train, 'train_y')
         x = x_train.detach().contiguous()
         y = y_train.detach().contiguous()
+        if self._incremental and may_append:
+            k = self._append_rows(x, y)
+            if k and self._append(x, y, k):
+                return
         # conf.cem_gp_subset_size: the max-variance subset of a larger pool (sx_gp_select) is what gets fitted
         x, y = self._subset_of(x, y)
         # factorise on the device (sx_gp_fit), then lay the operands out for the matrix cores (sx_gp_pack)
@@ -209,7 +320,8 @@ class GpCemSSM(CemSSM):
         packed = self._pack(m, linv, alpha)
         if int(status.item()) & _lib.SX_STATUS_NOT_PD:
             raise RuntimeError('the kernel matrix K + noise I is not positive definite for the current hyper-parameters')
-        self._install(x, m, packed, alpha, logdet.cpu())
+        self._install(x, m, packed, alpha, logdet.cpu(), y=y, logdet_dev=logdet)
+        self._appended = 0
 
     def _pack(self, m: _lib.SxGpModel, linv: Tensor, alpha: Tensor) -> Tuple[Tensor, Tensor]:
         """sx_gp_pack of a fitted model into new buffers: (a_pack, stage_tab), which `m` then points at."""
@@ -223,12 +335,18 @@ class GpCemSSM(CemSSM):
         _lib.check(lib.sx_gp_pack(ctypes.byref(m), _lib.ptr(linv), _lib.ptr(alpha), _lib.stream_ptr(dev)), 'sx_gp_pack')
         return a_pack, stage_tab
 
-    def _install(self, x: Tensor, m: _lib.SxGpModel, packed: Tuple[Tensor, Tensor], alpha: Tensor, logdet: Tensor) -> None:
-        """Makes the packed fit of x the model's (logdet: host [n_s]); the fit workspace holds its W."""
+    def _install(self, x: Tensor, m: _lib.SxGpModel, packed: Tuple[Tensor, Tensor], alpha: Tensor, logdet: Tensor,
+                 y: Optional[Tensor] = None, logdet_dev: Optional[Tensor] = None) -> None:
+        """Makes the packed fit of x the model's (logdet: host [n_s]); the fit workspace holds its W.  y, logdet_dev: the
+        fitted targets and the device copy of logdet, which a later update needs to append to this fit
+        (conf.cem_gp_incremental)."""
         self._model = m
         self._buffers = (x,) + tuple(packed)
         self._alpha = alpha
         self._linv_current = True
+        self._append_ok = self._incremental and y is not None and logdet_dev is not None
+        self._fit_state = (y, logdet_dev, tuple(t.clone() if isinstance(t, Tensor) else t for t in self._hyper_state())) \
+            if self._append_ok else None
         # 1/2 log det(I + K_d / noise_d) = sum log diag L_d - N/2 log noise_d
         self._info_gain = (logdet - 0.5 * x.size(0) * torch.log(self.noise)).numpy()
 
@@ -236,6 +354,7 @@ class GpCemSSM(CemSSM):
         """Exact marginal log likelihood per output [n_s] and its gradient [n_s x (D + 2)] w.r.t.
         (lengthscale, outputscale, noise), at the current hyper-parameters (host tensors)."""
         x, y = x_train.detach().contiguous(), y_train.detach().contiguous()
+        self._append_ok = False
         m, linv, alpha, logdet, status = self._fit(x, y)
         d_in = self.num_states + self.num_actions
         mll = torch.empty((self.num_states,), dtype=torch.float64, device=x.device)
@@ -527,6 +646,18 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
         for m, x, y in zip(ssms, xs, ys):
             m.update_model(x, y, opt_hyp, replace_old)
         return
+    # conf.cem_gp_incremental: the models whose update appends to their fit (sx_gp_append) do so one by one, after the
+    # others have been fitted together as below
+    if not opt_hyp and not replace_old and any(m._incremental for m in ssms):
+        appends = [m._appends_next(x, y) for m, x, y in zip(ssms, xs, ys)]
+        if any(a is not None for a in appends):
+            rest = [i for i, a in enumerate(appends) if a is None]
+            if rest:
+                update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest])
+            for i, a in enumerate(appends):
+                if a is not None:
+                    ssms[i]._update_appending(*a)
+            return
     # the merged training sets, checked before anything changes
     merged = []
     for m, x, y in zip(ssms, xs, ys):
@@ -600,4 +731,7 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
             m._last_training_losses = losses[e]
         model = _lib.SxGpModel.from_buffer_copy(models[e])
         packed = m._pack(model, fit.ws[e][1], fit.alpha[e])
-        m._install(fit.xs[e], model, packed, fit.alpha[e], logdets[e].clone())
+        m._install(fit.xs[e], model, packed, fit.alpha[e], logdets[e].clone(), y=fit.ys[e], logdet_dev=fit.logdet[e])
+        m._appended = 0
+        if opt_hyp or m.parametric:
+            m._append_ok = False    # as update_model: the update after hyper-parameter training is a full fit
