@@ -466,6 +466,29 @@ int sx_cem_rollout_starts(const sx_gp_model* model, const sx_env* env, int E, in
  * Replaces: nothing in safempc_exploration.py:100-163,281-330, whose NLP has one form. */
 int sx_cem_rollout_starts_form(const sx_gp_model* model, int H);
 
+/* sx_cem_rollout_starts under a feedback gain per particle and step (multi-step reachability, u = K_t (x - p_t) + k_ff_t):
+ *   gains   dev [E x P x (H-1) x n_u x n_s]   K_t of particle (e, c) for step t = 1 .. H-1 at index t - 1, row-major
+ *                                             [n_u x n_s]; required for H > 1, may be NULL for H == 1
+ *   every other argument as in sx_cem_rollout_starts (the rows [x0 | k_ff_0 .. k_ff_{H-1}], drawn or given)
+ * Step 0 starts from the point x0 of the particle's row and reads no gain (the reference's k_fb_init = None); step t >= 1
+ * propagates the ellipsoid (p_t, Q_t) under K_t: the lane that owns the particle forms the lower Cholesky factor of
+ * I + K_t^T K_t for itself.  env->k_fb is NOT read by this entry.  traj, sigma, obj_cost, con_cost (the objective, the
+ * action box on the rows' actions, the polytope mode, SX_STATE_VIOLATION_COST for a start outside the polytope) and status
+ * are sx_cem_rollout_starts' otherwise.  A non-finite gain sets SX_STATUS_NAN for the launch and leaves every other
+ * particle's outputs as they are without it; a gain is data only, never an index.
+ * The streaming kernel only (SX_FORM_STREAM or SX_FORM_BYOUT, sx_cem_rollout_gains_form): no workspace path.
+ * SX_ERR_ARG and SX_ERR_UNSUPPORTED (both before any device access) as sx_cem_rollout_starts, and SX_ERR_ARG for NULL gains
+ * with H > 1.
+ * Replaces: multistep_reachability (gp_reachability.py:168-221), one onestep_reachability per rollout and step, as
+ * run_uncertainty_propagation calls it per rollout (uncertainty_propagation_runner.py:28-41). */
+int sx_cem_rollout_gains(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
+                         const double* std, const double* noise, double* rows, const double* gains, double* traj,
+                         double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream);
+/* The form sx_cem_rollout_gains launches for this model and horizon (no launch, no device access): the answer, and the
+ * contract, of sx_cem_rollout_starts_form.
+ * Replaces: nothing in gp_reachability.py:168-221, which has one form. */
+int sx_cem_rollout_gains_form(const sx_gp_model* model, int H);
+
 /* ---- E problems with an exact GP each in one rollout launch (independent exploration runs) ----
  * Every problem e of the launch has its own training set (its own N) and hyper-parameters; all models share (n_s, n_u),
  * the sx_env and the buffer shapes of sx_cem_rollout.  The per-problem GP constants live in a device table that is built

@@ -117,6 +117,8 @@ SIGNATURES = {
     'sx_cem_rollout_workspace_bytes': (c_int64, [POINTER(SxGpModel), c_int, c_int, c_int]),
     'sx_cem_rollout_starts': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 10),
     'sx_cem_rollout_starts_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_cem_rollout_gains': (c_int, [POINTER(SxGpModel), POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 11),
+    'sx_cem_rollout_gains_form': (c_int, [POINTER(SxGpModel), c_int]),
     'sx_gp_model_table_bytes': (c_int64, [c_int, c_int, c_int]),
     'sx_gp_model_table': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),
     'sx_cem_rollout_multi': (c_int, [POINTER(SxGpModel), c_void_p, POINTER(SxEnv), c_int, c_int, c_int] + [c_void_p] * 12),

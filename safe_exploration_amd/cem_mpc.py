@@ -159,6 +159,7 @@ def _require_exact_rbf(ssms, what: str, numbered: bool = False) -> None:
 _COST_IS = 'the saturating cost on the safety trajectory is'
 _CON_SET_IS = 'the constraint set (con_set: feedback bounds, obstacle polytope) is'
 _STARTS_ARE = 'per-particle start states (static exploration) are'
+_GAINS_ARE = 'per-particle, per-step feedback gains (multi-step reachability) are'
 
 
 def _con_set_arg(con_set):
@@ -217,17 +218,19 @@ def conset_eval(env: _lib.SxEnv, con_set, u: Tensor, q_start: Optional[Tensor], 
 
 
 def _starts_rollout(suffix: str, head, ssms: Sequence, horizon: int, words: int, unsupported, *, mean, std, noise, rows,
-                    want_traj, want_sigma, status, con_set):
-    """What `cem_rollout_starts` and `cem_rollout_starts_multi` share: the checks of the rows, the outputs and the launch of
-    sx_cem_rollout_starts[_cons]<suffix>(*head(E, dev)[, con_set], E, P, H, mean, std, noise, rows, <outputs>, status, stream).
+                    want_traj, want_sigma, status, con_set, gains=None, with_gains: bool = False):
+    """What `cem_rollout_starts`, `cem_rollout_starts_multi` and `cem_rollout_gains` share: the checks of the rows, the
+    outputs and the launch of
+    sx_cem_rollout_starts[_cons]<suffix>(*head(E, dev)[, con_set], E, P, H, mean, std, noise, rows, <outputs>, status, stream)
+    or, `with_gains`, of sx_cem_rollout_gains (the same arguments with `gains` behind `rows`).
     `head(E, dev)`: the entry's arguments in front of the set, made once the problem count and the device are known;
     `words`: the size of a fresh status (None: one word per problem); `unsupported`: what SX_ERR_UNSUPPORTED raises."""
-    _require_exact_rbf(ssms, _STARTS_ARE)
+    _require_exact_rbf(ssms, _GAINS_ARE if with_gains else _STARTS_ARE)
     cons = ()
     if con_set is not None:
         _require_exact_rbf(ssms, _CON_SET_IS)
         cons = (_con_set_arg(con_set),)
-    entry = 'sx_cem_rollout_starts' + ('_cons' if cons else '') + suffix
+    entry = 'sx_cem_rollout_gains' if with_gains else 'sx_cem_rollout_starts' + ('_cons' if cons else '') + suffix
     n_s, n_u = ssms[0].num_states, ssms[0].num_actions
     L = n_s + horizon * n_u
     given = rows if noise is None else noise
@@ -236,6 +239,13 @@ def _starts_rollout(suffix: str, head, ssms: Sequence, horizon: int, words: int,
     _lib.require_gpu(given, 'rows' if noise is None else 'noise')
     E, P, dev = given.size(0), given.size(1), given.device
     head = head(E, dev)
+    extra = ()
+    if with_gains:
+        shape = (E, P, horizon - 1, n_u, n_s)
+        if horizon > 1 and (gains is None or tuple(gains.shape) != shape or not gains.is_contiguous()
+                            or gains.dtype != torch.float64 or gains.device != dev):
+            raise ValueError(f'gains must be a contiguous float64 [E x P x (H - 1) x n_u x n_s] = {shape} tensor on {dev}')
+        extra = (_lib.ptr(gains if horizon > 1 else None),)
     if noise is not None:
         if mean is None or std is None or tuple(mean.shape) != (E, L) or tuple(std.shape) != (E, L):
             raise ValueError(f'noise needs the sampling distribution: mean and std [{E} x {L}]')
@@ -250,7 +260,7 @@ def _starts_rollout(suffix: str, head, ssms: Sequence, horizon: int, words: int,
         status = torch.zeros(E if words is None else words, dtype=torch.int32, device=dev)
     code = getattr(_lib.lib(), entry)(*head, *cons, E, P, horizon, _lib.ptr(mean if noise is not None else None),
                                       _lib.ptr(std if noise is not None else None), _lib.ptr(noise), _lib.ptr(rows),
-                                      _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
+                                      *extra, _lib.ptr(traj), _lib.ptr(sigma), _lib.ptr(obj), _lib.ptr(con), _lib.ptr(status),
                                       _lib.stream_ptr(dev))
     if unsupported is not None and code == _lib.SX_ERR_UNSUPPORTED:
         raise unsupported(f'{entry}: no single-launch form for the models')
@@ -274,6 +284,22 @@ def cem_rollout_starts(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, mean: Op
     return _starts_rollout('', lambda E, dev: (ctypes.byref(ssm.device_model), ctypes.byref(env)), [ssm], horizon, 1, None,
                            mean=mean, std=std, noise=noise, rows=rows, want_traj=want_traj, want_sigma=want_sigma,
                            status=status, con_set=con_set)
+
+
+class FusedGainsUnsupported(_lib.SxError):
+    """sx_cem_rollout_gains answered SX_ERR_UNSUPPORTED (before any launch): propagate step by step."""
+
+
+def cem_rollout_gains(ssm: GpCemSSM, env: _lib.SxEnv, horizon: int, *, gains: Optional[Tensor], mean: Optional[Tensor] = None,
+                      std: Optional[Tensor] = None, noise: Optional[Tensor] = None, rows: Optional[Tensor] = None,
+                      want_traj: bool = False, want_sigma: bool = False, status: Optional[Tensor] = None):
+    """Thin wrapper over sx_cem_rollout_gains: `cem_rollout_starts` under a feedback gain per particle and step (multi-step
+    reachability).  `gains` [E x P x (H - 1) x n_u x n_s]: K_t of step t = 1 .. H - 1 at index
+    t - 1 (None allowed for H = 1); step 0 starts from the point of the row.  env.k_fb is not read.  Rows, outputs and costs
+    as in `cem_rollout_starts`; SX_ERR_UNSUPPORTED raises `FusedGainsUnsupported`."""
+    return _starts_rollout('', lambda E, dev: (ctypes.byref(ssm.device_model), ctypes.byref(env)), [ssm], horizon, 1,
+                           FusedGainsUnsupported, mean=mean, std=std, noise=noise, rows=rows, want_traj=want_traj,
+                           want_sigma=want_sigma, status=status, con_set=None, gains=gains, with_gains=True)
 
 
 class FusedMultiUnsupported(_lib.SxError):

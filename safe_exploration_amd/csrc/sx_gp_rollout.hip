@@ -2,7 +2,7 @@
 // sx_stream_launch.hpp), the launch in that form through the launchers of sx_rw_launch.hpp,
 // sx_stream_launch.hpp and sx_big_launch.hpp (launch_rollout), the one host path of the entries that have the streaming
 // kernel only (stream_rollout), the GP model table, and sx_cem_rollout[_elites][_junk], sx_cem_rollout[_elites]_multi,
-// sx_cem_rollout_starts[_cons][_multi], sx_cem_rollout_starts_multi_form, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
+// sx_cem_rollout_starts[_cons][_multi], sx_cem_rollout_gains, sx_cem_rollout_gains_form, sx_cem_rollout_starts_multi_form, sx_cem_rollout_form, sx_cem_rollout_multi_form, sx_cem_rollout_starts_form,
 // sx_cem_rollout_workspace_bytes, and the entries with the saturating cost on the safety ellipsoids,
 // sx_cem_rollout[_elites]_sat[_multi], sx_cem_rollout_sat_form, and those with the SafeMPC constraint set in the step,
 // sx_cem_rollout[_elites]_cons[_multi], sx_cem_rollout_cons_form, sx_cem_rollout_cons_multi_form.  No kernel is compiled here.
@@ -130,34 +130,45 @@ static int launch_rollout(const sx_gp_model* m, const sx_env* env, const Rollout
 // The entries that have the streaming kernel only -- the multi-model rollouts, the per-particle starts, the saturating
 // cost on the safety ellipsoids -- from their checked arguments to the launch of variant V, for one model or (V::MM) rp.E
 // of them behind their device `table`: the streaming plan with the elite-row bound (no workspace path, no resident form,
-// no override), the constants of `env`, those of `cost` (V::SAT) and of `cons` (V::CONS), the GP argument, the launcher.
+// no override), the constants of `env`, those of `cost` (V::SAT) and of `cons` (V::CONS), the device `gains` (V::KF), the GP
+// argument, the launcher.
 template <class V, int NS, int NU>
 static int stream_rollout(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                          const sx_con_set* cons, const RolloutPtrs& rp, hipStream_t stream) {
+                          const sx_con_set* cons, const double* gains, const RolloutPtrs& rp, hipStream_t stream) {
     const StreamPlan plan = plan_stream_multi(models, V::MM ? rp.E : 1, rp.H);
     if (plan.form < 0 || (rp.elite_rows && !elite_rows_fit(NS, NU, rp.H))) return SX_ERR_UNSUPPORTED;
     ReachConst<NS, NU> rc;
     CostConst<SX_MAX_M, NS, NU> cc;
-    if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    if constexpr (V::KF) {
+        // env->k_fb is not read: the constants are those of a zero gain, and no lane of the variant reads rc.kfb / rc.cholB
+        sx_env no_gain = *env;
+        for (double& k : no_gain.k_fb) k = 0.0;
+        if (int r = env_consts<NS, NU>(&no_gain, rc, cc)) return r;
+    } else {
+        if (int r = env_consts<NS, NU>(env, rc, cc)) return r;
+    }
     SatConst<NS> sat;
     if constexpr (V::SAT) make_sat_const<NS>(cost, sat);
     const SatConst<NS>* satp = V::SAT ? &sat : nullptr;
     ConConst<NS> con;
     if constexpr (V::CONS) make_con_const<NS>(cons, con);
     const ConConst<NS>* conp = V::CONS ? &con : nullptr;
+    const GainConst kf{gains};
+    const GainConst* kfp = V::KF ? &kf : nullptr;
     const bool byout = plan.form == SX_FORM_BYOUT;
     if constexpr (V::MM)
         return launch_stream<V, NS, NU>(static_cast<const GpConst<NS, NS + NU>*>(table), rc, cc, rp, satp, byout, plan.lds,
-                                        stream, conp);
+                                        stream, conp, kfp);
     else
         return launch_stream<V, NS, NU>(make_gp_const<NS, NU>(models, kRolloutThreads / 64), rc, cc, rp, satp, byout,
-                                        plan.lds, stream, conp);
+                                        plan.lds, stream, conp, kfp);
 }
 
 template <class V>
 static int stream_dispatch(const sx_gp_model* models, const void* table, const sx_env* env, const sx_sat_cost* cost,
-                           const RolloutPtrs& rp, void* stream, const sx_con_set* cons = nullptr) {
-#define CALL(NS, NU) stream_rollout<V, NS, NU>(models, table, env, cost, cons, rp, (hipStream_t)stream)
+                           const RolloutPtrs& rp, void* stream, const sx_con_set* cons = nullptr,
+                           const double* gains = nullptr) {
+#define CALL(NS, NU) stream_rollout<V, NS, NU>(models, table, env, cost, cons, gains, rp, (hipStream_t)stream)
     SX_DISPATCH(env->n_s, env->n_u, CALL);
 #undef CALL
 }
@@ -345,6 +356,17 @@ int sx_cem_rollout_starts_cons(const sx_gp_model* model, const sx_env* env, cons
     if (!sx::con_set_ok(cons, env->n_s)) return SX_ERR_ARG;
     const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
     return sx::stream_dispatch<sx::StreamStartsCons>(model, nullptr, env, nullptr, rp, stream, cons);
+}
+
+int sx_cem_rollout_gains_form(const sx_gp_model* model, int H) { return sx::stream_form(model, 1, H); }
+
+int sx_cem_rollout_gains(const sx_gp_model* model, const sx_env* env, int E, int P, int H, const double* mean,
+                         const double* std, const double* noise, double* rows, const double* gains, double* traj,
+                         double* sigma, double* obj_cost, double* con_cost, int32_t* status, void* stream) {
+    if (!starts_args_ok(model, 1, env, E, P, H, mean, std, noise, rows, obj_cost, con_cost, status)) return SX_ERR_ARG;
+    if (H > 1 && !gains) return SX_ERR_ARG;   // (step 0 starts from a point and reads none)
+    const sx::RolloutPtrs rp{nullptr, nullptr, mean, std, noise, rows, traj, sigma, obj_cost, con_cost, status, E, P, H};
+    return sx::stream_dispatch<sx::StreamGains>(model, nullptr, env, nullptr, rp, stream, nullptr, gains);
 }
 
 int sx_cem_rollout_starts_multi_form(const sx_gp_model* models, int E, int H) {

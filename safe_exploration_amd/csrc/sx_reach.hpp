@@ -178,6 +178,35 @@ __device__ __forceinline__ double remainder_r2(const ReachConst<NS, NU>& rc, con
     return sym_lambda_max<NS>(S);
 }
 
+// The lower Cholesky factor L [NS x NS] of B = I + k^T k for a gain k [NU x NS] of the lane's own (the streaming rollout
+// with a gain per particle and step, StreamVariant::KF): make_reach_const's recurrence (sx_host.hpp), in registers.  B has
+// eigenvalues >= 1: no pivot, no jitter.  A non-finite gain gives a non-finite factor, which reach_ellipsoid's checks
+// report (SX_STATUS_NAN); nothing here branches on the data.  The strict upper triangle is zero and is never read.
+template <int NS, int NU>
+__device__ __forceinline__ void gain_chol(const double (&k)[NU * NS], double (&L)[NS * NS]) {
+#pragma unroll
+    for (int i = 0; i < NS * NS; ++i) L[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        double s = 1.0;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) s += k[c * NS + j] * k[c * NS + j];
+#pragma unroll
+        for (int m = 0; m < j; ++m) s -= L[j * NS + m] * L[j * NS + m];
+        const double ljj = sqrt(s);
+        L[j * NS + j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < NS; ++i) {
+            double t = 0.0;
+#pragma unroll
+            for (int c = 0; c < NU; ++c) t += k[c * NS + i] * k[c * NS + j];
+#pragma unroll
+            for (int m = 0; m < j; ++m) t -= L[i * NS + m] * L[j * NS + m];
+            L[i * NS + j] = t / ljj;
+        }
+    }
+}
+
 // Point branch (gp_reachability_pytorch.py:65-99).  var is fixed up in place and is what the caller reports as sigma.
 template <int NS, int NU>
 __device__ __forceinline__ void reach_point(const ReachConst<NS, NU>& rc, const double (&p)[NS], const double (&u)[NU],

@@ -91,6 +91,12 @@ constexpr size_t kernel_arg_bytes() {
     return (size_t(0) + ... + ((sizeof(A) + 7) / 8 * 8));
 }
 
+// The trailing kernel argument of StreamVariant::KF (sx_cem_rollout_gains): the feedback gains of every particle and step,
+// dev [E x P x (H - 1) x NU x NS], K_t of step t >= 1 at index t - 1 (step 0 starts from a point and has none)
+struct GainConst {
+    const double* gains;
+};
+
 // The constants of a mode: the I-th of the kernel's trailing arguments, or a placeholder with I < 0 (a mode the variant
 // has not)
 struct NoConst {};
@@ -102,8 +108,10 @@ __device__ __forceinline__ decltype(auto) rollout_extra(const X&... x) {
 
 // The one streaming rollout kernel.  V is a StreamVariant (sx_stream_launch.hpp, which describes its flags): the query
 // shift V::SH and the multi-model mode V::MM as above, the per-particle starts V::PS, the saturating cost V::SAT and the
-// constraint set V::CONS.  X... is [ConConst<NS>][, SatConst<NS>], the constants of the modes V has: kernel arguments of
-// their own, uniform and read by scalar loads on the owner lanes, so that the LDS plan is the same in every variant.  The
+// constraint set V::CONS, a feedback gain per particle and step V::KF (the gain enters in finish(t), on the owner lane,
+// which forms the factor of I + K^T K for itself).  X... is [ConConst<NS>][, SatConst<NS>], or GainConst with V::KF, the
+// constants of the modes V has: kernel arguments of their own, uniform and read by scalar loads on the owner lanes (the
+// gains through the pointer GainConst holds), so that the LDS plan is the same in every variant.  The
 // sections of a mode are `if constexpr`, directly in this body: an instantiation holds what its variant's kernel held when
 // each was a definition of its own (tools/device_code_diff.py).
 template <class V, int NS, int NU, bool BYOUT, class... X>
@@ -112,13 +120,18 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
     ReachConst<NS, NU> rc, CostConst<SX_MAX_M, NS, NU> cc, RolloutPtrs rp, const X... extras) {
     constexpr int SH = V::SH;
     constexpr bool MM = V::MM;
-    static_assert(sizeof...(X) == (V::CONS ? 1 : 0) + (V::SAT ? 1 : 0), "X... is [ConConst<NS>][, SatConst<NS>]");
+    static_assert(sizeof...(X) == (V::CONS ? 1 : 0) + (V::SAT ? 1 : 0) + (V::KF ? 1 : 0),
+                  "X... is [ConConst<NS>][, SatConst<NS>] | GainConst");
     static_assert(!V::PS || (SH == 0 && !V::SAT), "the per-particle starts: plain models, the quadratic cost");
+    static_assert(!V::KF || (V::PS && SH == 0 && !V::MM && !V::SAT && !V::CONS),
+                  "a gain per particle and step: on the per-particle starts of one model, no cost, no set (its control "
+                  "ellipsoid reads rc.kfb)");
     static_assert(!(V::SAT || V::CONS) || SH == 0, "the saturating cost and the constraint set: no query shift");
     static_assert(kernel_arg_bytes<decltype(gc_arg), const int4*, ReachConst<NS, NU>, CostConst<SX_MAX_M, NS, NU>, RolloutPtrs,
                                    X...>() <= kMaxKernelArgBytes, "the kernel arguments exceed a launch's limit");
     const auto& cons = rollout_extra<V::CONS ? 0 : -1>(extras...);
     const auto& sat = rollout_extra<V::SAT ? (V::CONS ? 1 : 0) : -1>(extras...);
+    const auto& kf = rollout_extra<V::KF ? 0 : -1>(extras...);
     constexpr int D = NS + NU + SH;
     constexpr int UC = NS + SH;   // first action column of a query row
     constexpr int S = NS + NS * NS;
@@ -317,6 +330,16 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
             z[UC + cidx] = u[cidx];
         }
         int st_step = 0;
+        // V::KF: the gain K_t of this lane's particle at step t >= 1 (a step that starts from an ellipsoid), requested here so
+        // that it travels during the GP collect; a lane past P reads through the problem's first particle
+        double kt[V::KF ? NU * NS : 1];
+        if constexpr (V::KF) {
+            if (have_q) {
+                const double* gt = kf.gains + (((int64_t)e * rp.P + (valid ? c0 + tid : 0)) * (H - 1) + (t - 1)) * (NU * NS);
+#pragma unroll
+                for (int i = 0; i < NU * NS; ++i) kt[i] = gt[i];
+            }
+        }
         // the feedback bounds, from the ellipsoid the step starts from (before p, Q are overwritten below)
         bool eviol = false;
         if constexpr (V::CONS) {
@@ -324,7 +347,15 @@ __global__ __launch_bounds__(kRolloutThreads) void cem_rollout_kernel(
         }
         if (have_q) {
             gp_collect<NS, D, true>(gc, lds, nw, tid, z, mean, var, jac);
-            if constexpr (SH == 0) {
+            if constexpr (V::KF) {
+                // the step under the lane's own gain: a lane-local copy of rc with K_t and the factor of I + K_t^T K_t
+                // formed here (the uniform entries stay where rc has them)
+                ReachConst<NS, NU> rl = rc;
+#pragma unroll
+                for (int i = 0; i < NU * NS; ++i) rl.kfb[i] = kt[i];
+                gain_chol<NS, NU>(kt, rl.cholB);
+                reach_ellipsoid<NS, NU>(rl, p, Q, u, mean, var, jac, p1, Q1, st_step);
+            } else if constexpr (SH == 0) {
                 reach_ellipsoid<NS, NU>(rc, p, Q, u, mean, var, jac, p1, Q1, st_step);
             } else {
                 // [A | B]: the derivatives by the TRAINING rows' state and action columns (the reference's padding)

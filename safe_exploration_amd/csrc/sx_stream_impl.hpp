@@ -1,7 +1,7 @@
 // Body of launch_stream<V, NS, NU> (sx_stream_launch.hpp), the one launcher of the streaming rollout kernels; included by
 // sx_stream_ns*.hip, sx_stream_multi.hip, sx_stream_starts.hip, sx_stream_sat.hip, sx_stream_sat_multi.hip,
 // sx_stream_cons.hip, sx_stream_cons_sat.hip, sx_stream_cons_multi.hip, sx_stream_cons_sat_multi.hip,
-// sx_stream_starts_cons.hip, sx_stream_starts_multi.hip and sx_stream_starts_cons_multi.hip, which instantiate it for their variant V and so compile that variant's kernels.
+// sx_stream_starts_cons.hip, sx_stream_starts_multi.hip, sx_stream_starts_cons_multi.hip and sx_stream_gains.hip, which instantiate it for their variant V and so compile that variant's kernels.
 #pragma once
 #include <climits>
 #include <tuple>
@@ -22,7 +22,7 @@ auto stream_extra(const T* p) {
 template <class V, int NS, int NU>
 int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
                   const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream,
-                  const ConConst<NS>* cons) {
+                  const ConConst<NS>* cons, const GainConst* gains) {
     static_assert(V::SH >= 0 && V::SH <= NU && NS + NU + V::SH <= SX_MAX_D, "query shift outside the junk-dimension shapes");
 #ifdef SX_STAMPS
     if constexpr (!V::MM && !V::PS && !V::SAT && !V::CONS) {
@@ -37,7 +37,7 @@ int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc
     // (the table's entries carry a stage table each)
     const int4* stage_tab = nullptr;
     if constexpr (!V::MM) stage_tab = gp.stage_tab;
-    // the trailing arguments [*cons][, *sat] of V, and its kernel over them
+    // the trailing arguments [*cons][, *sat] | *gains of V, and its kernel over them
     return std::apply(
         [&](const auto&... extras) {
             const auto kernel = byout ? cem_rollout_kernel<V, NS, NU, true, std::decay_t<decltype(extras)>...>
@@ -47,15 +47,15 @@ int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc
                    cc, rp, extras...);
             return check_launch();
         },
-        std::tuple_cat(stream_extra<V::CONS>(cons), stream_extra<V::SAT>(sat)));
+        std::tuple_cat(stream_extra<V::CONS>(cons), stream_extra<V::SAT>(sat), stream_extra<V::KF>(gains)));
 }
 
 }  // namespace sx
 
 // launch_stream of variant V (the trailing argument: StreamPlain<SH>, StreamPlain<0, true>, StreamStarts, StreamSat<MM>,
-// StreamCons<SAT, MM>, StreamStartsCons, StreamStartsMulti, StreamStartsConsMulti)
+// StreamCons<SAT, MM>, StreamStartsCons, StreamStartsMulti, StreamStartsConsMulti, StreamGains)
 #define SX_STREAM_INSTANTIATE(NS, NU, ...)                                                                            \
     template int sx::launch_stream<sx::__VA_ARGS__, NS, NU>(                                                          \
         const sx::StreamGpArg<sx::__VA_ARGS__, NS, NU>&, const sx::ReachConst<NS, NU>&,                               \
         const sx::CostConst<SX_MAX_M, NS, NU>&, const sx::RolloutPtrs&, const sx::SatConst<NS>*, bool, size_t, hipStream_t, \
-        const sx::ConConst<NS>*);
+        const sx::ConConst<NS>*, const sx::GainConst*);

@@ -6,7 +6,7 @@
 // sx_stream_sat.hip and sx_stream_sat_multi.hip, the constraint set in sx_stream_cons.hip and sx_stream_cons_sat.hip, in the
 // multi-model mode in sx_stream_cons_multi.hip and sx_stream_cons_sat_multi.hip, on the per-particle starts in
 // sx_stream_starts_cons.hip, the per-particle starts in the multi-model mode in sx_stream_starts_multi.hip and
-// sx_stream_starts_cons_multi.hip; built in parallel with the rest);
+// sx_stream_starts_cons_multi.hip, a gain per particle and step in sx_stream_gains.hip; built in parallel with the rest);
 // sx_gp_rollout.hip sees the declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -123,10 +123,15 @@ inline StreamPlan plan_stream_multi(const sx_gp_model* models, int E, int steps,
 //         constraints term for term): a particle starts from a point, so step 0 pays the box test only, and the prologue
 //         tests the start x0 itself against the obstacle rows, SX_STATE_VIOLATION_COST once, beside and independent of the
 //         safe-polytope cost of the start (section 3.10, "the constraint set").
-template <int SH_, bool MM_, bool PS_, bool SAT_, bool CONS_>
+//   KF    (sx_cem_rollout_gains; with PS, SH = 0, one model, no SAT, no CONS) a feedback gain per particle and step, from a
+//         trailing GainConst argument: dev [E x P x (H - 1) x NU x NS].  At step t >= 1 the owner lane of a particle reads
+//         its K_t, forms the lower Cholesky factor of I + K_t^T K_t in registers (gain_chol) and runs reach_ellipsoid on a
+//         lane-local copy of rc with these two; rc.kfb / rc.cholB are not read.  Step 0 starts from the point of the row
+//         and reads no gain.  Everything else in the step is StreamStarts' (DESIGN.md section 3.16).
+template <int SH_, bool MM_, bool PS_, bool SAT_, bool CONS_, bool KF_ = false>
 struct StreamVariant {
     static constexpr int SH = SH_;
-    static constexpr bool MM = MM_, PS = PS_, SAT = SAT_, CONS = CONS_;
+    static constexpr bool MM = MM_, PS = PS_, SAT = SAT_, CONS = CONS_, KF = KF_;
 };
 template <int SH, bool MM = false>
 using StreamPlain = StreamVariant<SH, MM, false, false, false>;   // sx_cem_rollout[_elites][_junk] (MM: ..._multi)
@@ -138,6 +143,7 @@ using StreamCons = StreamVariant<0, MM, false, SAT, true>;   // sx_cem_rollout[_
 using StreamStartsCons = StreamVariant<0, false, true, false, true>;   // sx_cem_rollout_starts_cons
 using StreamStartsMulti = StreamVariant<0, true, true, false, false>;   // sx_cem_rollout_starts_multi
 using StreamStartsConsMulti = StreamVariant<0, true, true, false, true>;   // sx_cem_rollout_starts_cons_multi
+using StreamGains = StreamVariant<0, false, true, false, false, true>;   // sx_cem_rollout_gains
 
 // The first kernel argument of variant V: the GpConst, or with V::MM the device table of E of them
 template <class V, int NS, int NU>
@@ -145,10 +151,10 @@ using StreamGpArg = typename RolloutGpArg<NS, NS + NU + V::SH, V::MM>::type;
 
 // Launches cem_rollout_kernel<V, NS, NU, byout, ...> on `stream` over rp.E * ceil(rp.P / SX_TILE) workgroups with `lds`
 // bytes of dynamic LDS (plan_stream's; with V::MM plan_stream_multi's, and rp.status holds a word per problem).  `sat` is read with V::SAT
-// only and `cons` with V::CONS only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
+// only, `cons` with V::CONS only and `gains` with V::KF only (NULL otherwise).  SX_ERR_UNSUPPORTED for a grid past INT_MAX.
 template <class V, int NS, int NU>
 int launch_stream(const StreamGpArg<V, NS, NU>& gp, const ReachConst<NS, NU>& rc, const CostConst<SX_MAX_M, NS, NU>& cc,
                   const RolloutPtrs& rp, const SatConst<NS>* sat, bool byout, size_t lds, hipStream_t stream,
-                  const ConConst<NS>* cons = nullptr);
+                  const ConConst<NS>* cons = nullptr, const GainConst* gains = nullptr);
 
 }  // namespace sx

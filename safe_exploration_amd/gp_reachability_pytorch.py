@@ -164,6 +164,82 @@ def onestep_reachability(p_center: Tensor, ssm: CemSSM, k_ff: Tensor, l_mu: Tens
     return p1, q1, sigma
 
 
+def fused_gains_form(ssm, n: int) -> int:
+    """The form of the one launch `multistep_reachability` makes over `ssm` and n steps (sx_cem_rollout_gains_form), or
+    -1: a model whose kernel_family is not 'rbf' or whose training set has no streaming form goes step by step."""
+    if getattr(ssm, 'kernel_family', None) != 'rbf':
+        return -1
+    return int(_lib.lib().sx_cem_rollout_gains_form(ctypes.byref(ssm.device_model), n))
+
+
+def multistep_reachability(p_0: Tensor, ssm: CemSSM, k_fb: Tensor, k_ff: Tensor, l_mu: Tensor, l_sigma: Tensor,
+                           q_0: Optional[Tensor] = None, c_safety: float = 1., verbose: int = 1, a: Tensor = None,
+                           b: Tensor = None, k_fb_init: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Ellipsoidal over-approximation of the reachable sets after n actions under u_t = k_fb_{t-1} (x - p_t) + k_ff_t: the
+    reference's gp_reachability.multistep_reachability (name and argument order, :168-221), batched over R rollouts.
+
+    p_0 [R x n_s], k_fb [R x (n-1) x n_u x n_s], k_ff [R x n x n_u], l_mu / l_sigma [n_s], a / b the linear prior.
+    Returns (p_new [R x n_s], q_new [R x n_s x n_s], p_all [R x n x n_s], q_all [R x n x n_s x n_s]).  The reference's own
+    shapes -- p_0 [n_s x 1], k_fb [(n-1) x n_u x n_s], k_ff [n x n_u] -- are accepted too and answered in its shapes
+    (p_new [n_s x 1], q_new [n_s x n_s], p_all [n x n_s], q_all [n x n_s x n_s]).
+    All R rollouts are ONE sx_cem_rollout_gains launch; where `fused_gains_form` has none, every
+    rollout and step is one `onestep_reachability` with that step's gain.  The first step starts from the point p_0: an
+    initial ellipsoid (q_0 / k_fb_init) is not built.
+    """
+    if q_0 is not None or k_fb_init is not None:
+        raise NotImplementedError('multistep_reachability starts from a point: an initial ellipsoid (q_0 / k_fb_init) is '
+                                  'not built')
+    n_s, n_u = ssm.num_states, ssm.num_actions
+    single = k_ff.dim() == 2
+    if single:
+        n = k_ff.shape[0]
+        assert_shape(p_0, (n_s, 1))
+        assert_shape(k_fb, (n - 1, n_u, n_s))
+        assert_shape(k_ff, (n, n_u))
+        p_0, k_fb, k_ff = p_0.reshape(1, n_s), k_fb[None], k_ff[None]
+    r, n = k_ff.shape[0], k_ff.shape[1]
+    assert_shape(p_0, (r, n_s))
+    assert_shape(k_fb, (r, n - 1, n_u, n_s))
+    assert_shape(k_ff, (r, n, n_u))
+    assert_shape(l_mu, (n_s,))
+    assert_shape(l_sigma, (n_s,))
+    assert_shape(a, (n_s, n_s), ignore_if_none=True)
+    assert_shape(b, (n_s, n_u), ignore_if_none=True)
+    if n < 1:
+        raise ValueError('multistep_reachability needs at least one step')
+    _lib.require_gpu(p_0, 'p_0')
+    dev = p_0.device
+    p_0 = p_0.detach().to(torch.float64)
+    k_fb = k_fb.detach().to(dev, torch.float64).contiguous()
+    k_ff = k_ff.detach().to(dev, torch.float64)
+
+    if fused_gains_form(ssm, n) >= 0:
+        from .cem_mpc import cem_rollout_gains   # (cem_mpc imports this module)
+        # nothing but the ellipsoids is asked of the launch: one polytope row that nothing crosses, no action box
+        env = make_env(n_s, n_u, a=_host(a), b=_host(b) if a is not None else None, l_mu=_host(l_mu),
+                       l_sigma=_host(l_sigma), beta=c_safety, h_mat=np.zeros((1, n_s)), h_vec=np.ones(1),
+                       u_min=np.full(n_u, -np.inf), u_max=np.full(n_u, np.inf))
+        rows = torch.cat((p_0, k_ff.reshape(r, n * n_u)), dim=1).reshape(1, r, n_s + n * n_u).contiguous()
+        out = cem_rollout_gains(ssm, env, n, rows=rows, gains=k_fb.reshape(1, r, n - 1, n_u, n_s), want_traj=True)
+        raise_for_status(int(out['status'].item()), 'multistep_reachability',
+                         dump=lambda: save_failure_state(ssm, p_0, k_ff[:, 0]))
+        traj = out['traj'][0]
+        p_all = traj[..., :n_s].contiguous()
+        q_all = traj[..., n_s:].reshape(r, n, n_s, n_s).contiguous()
+    else:
+        p_all = torch.empty((r, n, n_s), dtype=torch.float64, device=dev)
+        q_all = torch.empty((r, n, n_s, n_s), dtype=torch.float64, device=dev)
+        for i in range(r):
+            p, q = p_0[i:i + 1], None
+            for t in range(n):
+                p, q, _ = onestep_reachability(p, ssm, k_ff[i:i + 1, t], l_mu, l_sigma, q, None if t == 0 else k_fb[i, t - 1],
+                                               c_safety, verbose, a, b)
+                p_all[i, t], q_all[i, t] = p[0], q[0]
+    if single:
+        return p_all[0, -1].reshape(n_s, 1), q_all[0, -1], p_all[0], q_all[0]
+    return p_all[:, -1], q_all[:, -1], p_all, q_all
+
+
 def lin_ellipsoid_safety_distance(p_center: Tensor, q_shape: Tensor, h_mat: Tensor, h_vec: Tensor,
                                   c_safety: float = 1.0) -> Tensor:
     """d [N x m] = h_mat p + c_safety sqrt(diag(h_mat Q h_mat^T)) - h_vec; d < 0 everywhere <=> certified inside."""
