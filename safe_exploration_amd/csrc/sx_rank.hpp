@@ -21,7 +21,8 @@ namespace sx {
 //      histograms in three rotating buffers (no clearing barrier), the bin scan done redundantly by every wave (no
 //      broadcast barrier), early exit as soon as the bin holding the k-th key is wholly selected;
 //   4. ballot compaction in index order (ties broken by the lower index) from one table of per-(slot, wave) counts
-//      that every wave scans itself; the best survivor goes to slot 0, the others keep their index order;
+//      that every wave scans itself; the best survivor goes to slot 0, the others keep their index order (whether their
+//      key is below the k-th or ties with it);
 //   5. refit: mean / unbiased std over the elites, rows spread over the whole workgroup, values kept in registers
 //      between the two passes.
 // ---------------------------------------------------------------------------------------------------------------
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(kRankThreads) void cem_rank_kernel(RankArgs ra) {
             }
             acc += cnt;
             cur = walk_min[it];
-            if (cur == ~0ull) break;  // no further value (cannot happen while acc < k <= P, kept for safety)
+            if (cur == ~0ull) break;  // no further value but NaN (every NaN has this key): the passes below find the k-th key
         }
     }
 #ifdef SX_STAMPS
@@ -350,8 +351,8 @@ __global__ __launch_bounds__(kRankThreads) void cem_rank_kernel(RankArgs ra) {
 #endif
     // ---- compaction ----
     // Candidates whose masked key is below the prefix are selected; of those equal to it, the first `need` in index
-    // order (all of them after an early exit).
-    const int n_less_total = k - need;
+    // order (all of them after an early exit).  A selected candidate's slot is the number of selected candidates in front
+    // of it by index -- those below the prefix plus at most `need` of the ties -- so the elites come out in index order.
     unsigned long long my_bl[SLOTS], my_bt[SLOTS];
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
@@ -388,17 +389,17 @@ __global__ __launch_bounds__(kRankThreads) void cem_rank_kernel(RankArgs ra) {
             if (j < sub) off += __builtin_amdgcn_readlane(cell[j], src);
         return off;
     };
-    // where the best candidate would land: it goes to slot 0 instead, those in front of it move up by one
+    // where the best candidate would land: it goes to slot 0 instead, those in front of it move up by one.  (Where it
+    // matches the prefix it is one of the first `need` ties: the first of them, or, after an early exit -- the ties then
+    // differ in their lower bits and it need not be the first -- one of all of them.)
     int best_slot;
     {
-        const bool best_less = ((bh & mh) < ph) || ((bh & mh) == ph && (bl & ml) < pl);
         const int bs = best_idx / kRankThreads, bt = best_idx % kRankThreads;
         const int entry = bs * kRankWaves + (bt >> 6);
         const unsigned long long before = (1ull << (bt & 63)) - 1ull;
-        if (best_less)
-            best_slot = table_offset(tl, ex_l, entry) + __popcll(ball_less[entry] & before);
-        else  // it matches the prefix (after an early exit the ties differ in their lower bits: it need not be the first)
-            best_slot = n_less_total + table_offset(tt, ex_t, entry) + __popcll(ball_tie[entry] & before);
+        const int less_before = table_offset(tl, ex_l, entry) + __popcll(ball_less[entry] & before);
+        const int tie_before = table_offset(tt, ex_t, entry) + __popcll(ball_tie[entry] & before);
+        best_slot = less_before + (tie_before < need ? tie_before : need);
     }
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
@@ -413,12 +414,13 @@ __global__ __launch_bounds__(kRankThreads) void cem_rank_kernel(RankArgs ra) {
         // in a neighbour's slot, leaving a stale index behind (tests/golden/rank_case_r02.npz).
         const int off_less = table_offset(tl, ex_l, entry);
         const int off_tie = table_offset(tt, ex_t, entry);
+        const int lb = off_less + __popcll(my_bl[s] & below);   // candidates below the prefix in front of this one
+        const int r = off_tie + __popcll(my_bt[s] & below);      // ties in front of it
         int slot = -1;
         if ((my_bl[s] >> lane) & 1ull) {
-            slot = off_less + __popcll(my_bl[s] & below);
+            slot = lb + (r < need ? r : need);
         } else if ((my_bt[s] >> lane) & 1ull) {
-            const int r = off_tie + __popcll(my_bt[s] & below);
-            if (r < need) slot = n_less_total + r;
+            if (r < need) slot = lb + r;
         }
         if (slot >= 0) sel_idx[slot == best_slot ? 0 : (slot < best_slot ? slot + 1 : slot)] = i;
     }

@@ -229,11 +229,7 @@ def test_rank_by_counting_edge_shapes(E, P, k, L):
     for e in range(E):
         idx = ocem.rank(con[e], obj[e], k)
         got = out['elite_idx'][e].cpu().numpy()
-        if np.isnan(con[e]).any() and k == P:
-            # (the oracle ties a NaN constraint cost with +inf; the kernels rank NaN behind everything: same set)
-            np.testing.assert_array_equal(np.sort(got), np.sort(idx))
-        else:
-            np.testing.assert_array_equal(got, idx)                     # rank order, ties by index
+        np.testing.assert_array_equal(got, idx)                         # rank order, ties by index, NaN behind +inf
         rows = out['elite_rows'][e].cpu().numpy()
         np.testing.assert_array_equal(rows[:, 0], con[e][got])
         np.testing.assert_array_equal(rows[:, 1], obj[e][got])
@@ -268,13 +264,17 @@ def test_rank_order_of_signed_zeros_infinities_and_nans(P):
 
 
 def test_rank_fuzz_small():
-    """A short run of tools/rank_fuzz.py (random shapes, ties, NaNs, infinities, strided candidate rows; both kernels)."""
+    """A short run of tools/rank_fuzz.py (random shapes, ties, NaNs, infinities, strided candidate rows, the four output
+    modes), which must take each of the four kernels at least 5 times (seed 5 does: 36 / 24 / 13 / 7 of 80 cases)."""
+    import re
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'rank_fuzz.py'), '80', '5'], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    took = re.search(r'80 cases \(count (\d+), select4 (\d+), select8 (\d+), select16 (\d+)\), 0 mismatches', r.stdout)
+    assert took and all(int(n) >= 5 for n in took.groups()), r.stdout[-500:]
 
 
 @pytest.mark.parametrize('E,P,H,k', [(1, 100, 7, 13), (3, 64, 15, 64), (1, 40, 5, 1), (2, 33, 12, 700)])
@@ -339,7 +339,10 @@ def test_gp_predict_far_from_the_data_and_nan_queries():
 def test_rank_regression_case_round2(golden_dir):
     """A ranking that round 1's kernel got wrong (found at BASELINE config 3: 8192 candidates, 12 distinct constraint
     costs, k = 819): one tied elite landed in a neighbour's slot and a stale index stayed behind -- a v_readlane from an
-    inactive lane.  The saved costs must select exactly the oracle's set, every time."""
+    inactive lane.  The saved costs must select exactly the oracle's set, every time.  One problem with rows is ranked by
+    the counting kernel since that arrived, so this now exercises cem_rank_count_kernel on the fixture; the kernel that had
+    the bug, cem_rank_kernel<8>, runs it in
+    tests/test_gpu_rank_kernels.py::test_regression_fixture_on_the_kernel_it_was_written_for."""
     from safe_exploration_amd.cem_mpc import cem_rank_refit
     g = np.load(os.path.join(golden_dir, 'rank_case_r02.npz'))
     con, obj, k = g['con'], g['obj'], int(g['k'])
