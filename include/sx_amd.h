@@ -254,6 +254,38 @@ int sx_gp_append(const sx_gp_model* model, int n_old, const double* y_train, con
                  const double* logdet_old, double* linv, double* alpha, double* logdet, int32_t* status,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Lockstep appends: k rows appended to each of E fitted exact GPs in one launch sequence ----
+ * Every problem e has its own fitted rows (its own N_e) and hyper-parameters; all share (n_s, n_u) and k.  Problem e's linv,
+ * alpha and logdet are those of sx_gp_append for model e alone, BIT FOR BIT: they are independent of which other problems
+ * share the call and of their order.  The per-problem constants and buffers live in a table of SX_GP_APPEND_ENTRY_BYTES
+ * per problem, which sx_gp_append_table writes to HOST memory: the caller copies it to the device (from pinned memory that
+ * needs no wait) and passes the device copy to sx_gp_append_multi, which reads it and copies nothing from the host.
+ *
+ * Bytes of the table for E problems (E * SX_GP_APPEND_ENTRY_BYTES); < 0 for E <= 0. */
+#define SX_GP_APPEND_ENTRY_BYTES 408
+int64_t sx_gp_append_table_bytes(int E);
+/* Lays the E models (host array, each set as for sx_gp_append: n_train = N_e + k, x_train dev [(N_e + k) x D] with the fitted
+ * rows first) out in `table` (HOST memory, sx_gp_append_table_bytes() bytes) with problem e's device buffers (host arrays of
+ * E device pointers, each as the argument of that name of sx_gp_append): y_train[e], linv_old[e], alpha_old[e],
+ * logdet_old[e], linv[e], alpha[e], logdet[e]; workspace[e] dev, workspace_bytes[e] >=
+ * sx_gp_append_workspace_bytes(n_s, N_e + k, k) (the E workspaces may be cut from one allocation); and the shared status
+ * dev int32 [E], one word per problem, or-ed into: SX_STATUS_NOT_PD in word e says that problem e's outputs are
+ * unspecified and nothing about the others'.  No device access.
+ * SX_ERR_ARG for a null pointer (an element of the pointer arrays included), E <= 0, k outside 1 .. 64, models of different
+ * (n_s, n_u), a shape sx_gp_fit refuses, N_e < 1 or a workspace that is too small; SX_ERR_UNSUPPORTED for N_e + k > 4096 or
+ * E * n_s > 65535 (a grid's y-extent). */
+int sx_gp_append_table(const sx_gp_model* models, int E, int k, const double* const* y_train, const double* const* linv_old,
+                       const double* const* alpha_old, const double* const* logdet_old, double* const* linv,
+                       double* const* alpha, double* const* logdet, int32_t* status, void* const* workspace,
+                       const int64_t* workspace_bytes, void* table);
+/* sx_gp_append for the E problems of `table` (dev, the device copy of sx_gp_append_table's output for the same `models` and
+ * k): six launches on `stream` for all of them, each sized by the largest N_e; a workgroup beyond its own problem's extent
+ * returns at once, and every sum keeps the order that its problem's N_e and k give it.  Nothing is waited for.  The checks
+ * of sx_gp_append_table that concern `models`, E and k (before any device access).
+ * Replaces: the refits of the n_scenarios GpCemSSM models between two solves of the exploration loop
+ * (exploration_runner.py), one new row per scenario. */
+int sx_gp_append_multi(const sx_gp_model* models, int E, int k, const void* table, void* stream);
+
 /* ---- E exact GPs' fit and MLL gradient in one launch sequence (batched hyper-parameter training) ----
  * Every problem e has its own training set (its own N <= 4096) and hyper-parameters; all share (n_s, n_u).  Problem e's
  * linv, alpha, logdet, mll and gradient are bit-identical to what sx_gp_fit / sx_gp_mll_grad give for that model alone.

@@ -16,6 +16,12 @@
 //   append_wbot_kernel    -W_s (B^T W) for one 64-column block of W per workgroup; its share of t = W_bot y'
 //   append_copy_alpha_kernel   the old rows into the new stride, alpha'
 // Every sum has a fixed order that depends on N and k only.  The bandwidth of the path is reading W twice.
+//
+// sx_gp_append_multi: the same six launches for E problems that share (n_s, D, k) and differ in N (MM = true).  The kernels
+// then take the device table of the problems' AppendEntry, the grid's output index is e n_s + d and the x-extent of a launch is
+// the largest problem's; a workgroup beyond its own problem's extent returns at once, and every loop over blocks, parts or
+// the copy grid runs over the extents kept in the problem's entry, never the launch's: problem e's sums have the order, and
+// its outputs the bits, of its own sx_gp_append.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,6 +60,37 @@ struct AppendArgs {
     int n, k, D, n_s, nblk, nparts;
 };
 
+// One problem of sx_gp_append_multi: an entry of the device table sx_gp_append_table lays out -- the problem's AppendArgs
+// (status: its own word) and the x-extent of its own append_copy_alpha_kernel launch.
+struct AppendEntry : AppendArgs {
+    int copy_grid;
+    int pad_;
+};
+static_assert(sizeof(AppendEntry) == SX_GP_APPEND_ENTRY_BYTES, "include/sx_amd.h: SX_GP_APPEND_ENTRY_BYTES");
+
+// The argument of the append kernels, after FitArg (sx_fit.hpp): the AppendArgs itself (one model, the grid's output index
+// is the output d), or with MM = true the device table of E problems' AppendEntry, of which the workgroup binds the entry
+// of its problem: the grid's output index is then e n_s + d.  The pointer is restrict-qualified and never written and the
+// index is uniform, so the entry is read through the constant address space (scalar loads, and the device pointers it holds
+// are taken to be global, as those of a kernel argument are).
+// (entry() and output() answer by value, so that the plain mode's statements keep their form and its ISA.)
+template <bool MM>
+struct AppendArg {
+    using type = AppendArgs;
+    __device__ static const AppendArgs& entry(const type& a, int) { return a; }
+    __device__ static int output(const type&, int idx) { return idx; }
+};
+template <>
+struct AppendArg<true> {
+    using type = const AppendEntry* __restrict__;
+    using ConstE = __attribute__((address_space(4))) const AppendEntry;
+    __device__ static int problem(type table, int idx) { return idx / ((const ConstE*)table)[0].n_s; }
+    __device__ static const AppendEntry& entry(type table, int idx) {
+        return *(const AppendEntry*)((const ConstE*)table + problem(table, idx));
+    }
+    __device__ static int output(type table, int idx) { return idx - problem(table, idx) * ((const ConstE*)table)[0].n_s; }
+};
+
 __host__ __device__ inline int append_blocks(int n) { return (n + kAT - 1) / kAT; }
 __host__ __device__ inline int append_parts(int n) { return (append_blocks(n) + kAppendPartBlocks - 1) / kAppendPartBlocks; }
 // doubles of the workspace for n fitted rows and n_s outputs
@@ -61,6 +98,8 @@ inline int64_t append_workspace_doubles(int n_s, int n) {
     return (int64_t)n_s * (2 * (int64_t)n * kAT + 2 * kAT * kAT + (int64_t)append_parts(n) * kAT * kAT
                            + (int64_t)(append_blocks(n) + 1) * kAT);
 }
+// the x-extent of append_copy_alpha_kernel for n fitted rows
+inline int append_copy_grid(int n) { return (n + 7) / 8 < 512 ? (n + 7) / 8 : 512; }
 
 // rows r0 .. r0 + 63, columns c0 .. c0 + 63 of the row-major M (leading dimension ld, `rows` x `cols`) -> LDS [64][kATLd];
 // zero outside the matrix (all 16 loads of a thread are issued before the first store)
@@ -108,8 +147,11 @@ __device__ __forceinline__ void append_for_each(const v4d (&acc)[4], F&& f) {
 }
 
 // K_c [N x 64] (columns >= k zero) and K_cc [64 x 64] (rows and columns < k; the rest is never read): an element per thread
-__global__ __launch_bounds__(kAThreads) void append_kc_kernel(AppendArgs a) {
-    const int d = blockIdx.y, n = a.n, k = a.k;
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_kc_kernel(typename AppendArg<MM>::type arg) {
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.y);
+    const int d = AppendArg<MM>::output(arg, blockIdx.y), n = a.n, k = a.k;
+    // (the bound is the problem's own: beyond it the thread returns, whatever the launch's extent)
     const int64_t idx = (int64_t)blockIdx.x * kAThreads + threadIdx.x;
     if (idx >= (int64_t)(n + k) * kAT) return;
     const int i = (int)(idx >> 6), j = (int)(idx & 63);
@@ -154,10 +196,15 @@ __device__ __forceinline__ void append_two_sum(double p, double& s, double& c) {
 // in use (4 columns each, rounded up to a power of two: cgp) and, where those are fewer than 16, the depth: thread tx works
 // on column group tx % cgp and on every (16 / cgp)-th element of a dot product, and the slices are added at the end, in
 // slice order and with the same care.  The split depends on k only.  N^2 k / 2 terms of ~10 operations: far below the fit.
-__global__ __launch_bounds__(kAThreads) void append_b_kernel(AppendArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_b_kernel(typename AppendArg<MM>::type arg) {
     __shared__ double As[kAT * kATLd];
     __shared__ double Bs[kAT * kATLd];
-    const int bi = blockIdx.x, d = blockIdx.y, n = a.n, k = a.k;
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.y);
+    const int bi = blockIdx.x, d = AppendArg<MM>::output(arg, blockIdx.y), n = a.n, k = a.k;
+    if constexpr (MM) {
+        if (bi >= a.nblk) return;   // beyond this problem's row blocks (uniform; before any barrier)
+    }
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     int cgp = 1;
     while (4 * cgp < k) cgp <<= 1;
@@ -217,9 +264,14 @@ __global__ __launch_bounds__(kAThreads) void append_b_kernel(AppendArgs a) {
 }
 
 // part blockIdx.x of B^T B: the row blocks kAppendPartBlocks p .. of B, in order
-__global__ __launch_bounds__(kAThreads) void append_btb_kernel(AppendArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_btb_kernel(typename AppendArg<MM>::type arg) {
     __shared__ double As[kAT * kATLd];
-    const int p = blockIdx.x, d = blockIdx.y, n = a.n;
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.y);
+    const int d = AppendArg<MM>::output(arg, blockIdx.y), p = blockIdx.x, n = a.n;
+    if constexpr (MM) {
+        if (p >= a.nparts) return;   // beyond this problem's parts (uniform; before any barrier)
+    }
     const int ct = (a.k + 15) >> 4, wave = threadIdx.x >> 6;
     const double* B = a.b + (size_t)d * n * kAT;
     v4d acc[4] = {};
@@ -237,10 +289,12 @@ __global__ __launch_bounds__(kAThreads) void append_btb_kernel(AppendArgs a) {
 // One workgroup per output: S, its Cholesky factor and the factor's inverse -- the work fit_potrf_diag_kernel does for a
 // diagonal block (sx_fit_blocked.hpp), on the leading k x k part of a block padded with the identity: the padding is its
 // own factor and inverse, so the k pivots and the k rows of the substitution are all the work there is
-__global__ __launch_bounds__(kAThreads) void append_schur_kernel(AppendArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_schur_kernel(typename AppendArg<MM>::type arg) {
     __shared__ double L[kAT * kATLd];
     __shared__ double Wd[kAT * kATLd];
-    const int d = blockIdx.x, tid = threadIdx.x, n = a.n, k = a.k, n2 = a.n + a.k;
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.x);
+    const int d = AppendArg<MM>::output(arg, blockIdx.x), tid = threadIdx.x, n = a.n, k = a.k, n2 = a.n + a.k;
     const double* kcc = a.kcc + (size_t)d * kAT * kAT;
     const double* btb = a.btb + (size_t)d * a.nparts * kAT * kAT;
     for (int idx = tid; idx < kAT * kAT; idx += kAThreads) {
@@ -310,10 +364,15 @@ __global__ __launch_bounds__(kAThreads) void append_schur_kernel(AppendArgs a) {
 }
 
 // columns 64 blockIdx.x .. of the new rows: -W_s (B^T W), the sum over the row blocks of W at and below the diagonal
-__global__ __launch_bounds__(kAThreads) void append_wbot_kernel(AppendArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_wbot_kernel(typename AppendArg<MM>::type arg) {
     __shared__ double As[kAT * kATLd];
     __shared__ double Bs[kAT * kATLd];
-    const int cj = blockIdx.x, d = blockIdx.y, n = a.n, k = a.k, n2 = a.n + a.k;
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.y);
+    const int d = AppendArg<MM>::output(arg, blockIdx.y), cj = blockIdx.x, n = a.n, k = a.k, n2 = a.n + a.k;
+    if constexpr (MM) {
+        if (cj >= a.nblk) return;   // beyond this problem's column blocks (uniform; before any barrier)
+    }
     const int rt = (k + 15) >> 4, wave = threadIdx.x >> 6, tid = threadIdx.x;
     const double* W = a.w_old + (size_t)d * n * n;
     const double* B = a.b + (size_t)d * n * kAT;
@@ -349,9 +408,21 @@ __global__ __launch_bounds__(kAThreads) void append_wbot_kernel(AppendArgs a) {
 
 // The old rows of W into the new stride (k zeros appended; nothing above the diagonal is read), and
 // alpha' = [alpha; 0] + W_bot^T t with t the sum of its parts in block order.  Rows and columns are dealt out over the grid.
-__global__ __launch_bounds__(kAThreads) void append_copy_alpha_kernel(AppendArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kAThreads) void append_copy_alpha_kernel(typename AppendArg<MM>::type arg) {
     __shared__ double t[kAT];
-    const int d = blockIdx.y, tid = threadIdx.x, n = a.n, k = a.k, n2 = a.n + a.k;
+    const auto& a = AppendArg<MM>::entry(arg, blockIdx.y);
+    const int d = AppendArg<MM>::output(arg, blockIdx.y), tid = threadIdx.x, n = a.n, k = a.k, n2 = a.n + a.k;
+    // the grid the rows and columns are dealt out over: this problem's own
+    const auto grid = [&]() -> unsigned {
+        if constexpr (MM)
+            return a.copy_grid;
+        else
+            return gridDim.x;
+    };
+    if constexpr (MM) {
+        if (blockIdx.x >= grid()) return;   // (uniform; before the barrier)
+    }
     const double* W = a.w_old + (size_t)d * n * n;
     double* W2 = a.w_new + (size_t)d * n2 * n2;
     if (tid < kAT) {
@@ -359,11 +430,11 @@ __global__ __launch_bounds__(kAThreads) void append_copy_alpha_kernel(AppendArgs
         for (int p = 0; p <= a.nblk; ++p) s += a.tpart[((size_t)d * (a.nblk + 1) + p) * kAT + tid];
         t[tid] = s;
     }
-    for (int i = blockIdx.x; i < n; i += gridDim.x)
+    for (int i = blockIdx.x; i < n; i += grid())
         for (int c = tid; c < n2; c += kAThreads) W2[(size_t)i * n2 + c] = (c <= i) ? W[(size_t)i * n + c] : 0.0;
     __syncthreads();
     // (append_schur_kernel wrote the new rows' own block whole, zeros above its diagonal included)
-    for (int c = blockIdx.x * kAThreads + tid; c < n2; c += gridDim.x * kAThreads) {
+    for (int c = blockIdx.x * kAThreads + tid; c < n2; c += grid() * kAThreads) {
         double s = (c < n) ? a.alpha_old[(size_t)d * n + c] : 0.0;
         for (int r = (c < n) ? 0 : c - n; r < k; ++r) s += W2[(size_t)(n + r) * n2 + c] * t[r];
         a.alpha[(size_t)d * n2 + c] = s;

@@ -40,6 +40,7 @@ class GpCemSSM(CemSSM):
     _subset_idx: Optional[Tensor] = None
     _incremental = False                   # conf.cem_gp_incremental (set by __init__; the weight-space subclass has none)
     _append_ok = False
+    _lockstep = False                      # conf.cem_gp_incremental_lockstep (set by __init__; the weight-space subclass has none)
 
     def __new__(cls, conf=None, *args, **kwargs):
         # one class name for every kernel, as in the reference (gp_ssm_cem.py:45-57): the 'linear' and 'nn' kernels are
@@ -80,6 +81,13 @@ class GpCemSSM(CemSSM):
         self._max_chain: Optional[int] = None if chain is None else int(chain)
         if self._max_chain is not None and self._max_chain < 0:
             raise ValueError(f'cem_gp_incremental_max_chain={chain}: a row count, or None')
+        # conf.cem_gp_incremental_lockstep: update_models_multi appends to the models that have it, qualify and share the
+        # number of new rows in ONE sx_gp_append_multi call (`_append_lockstep`); off: model by model
+        self._lockstep = bool(getattr(conf, 'cem_gp_incremental_lockstep', False))
+        if self._lockstep and not self._incremental:
+            raise ValueError('cem_gp_incremental_lockstep needs cem_gp_incremental: there is nothing to append in lockstep '
+                             'where every update is a full fit')
+        self._lockstep_bufs: Optional['_LockstepBuffers'] = None   # of the groups this model leads
         self._append_ok = False      # may the next update append to the installed fit?  (False after anything but a plain update)
         self._appended = 0           # rows appended since the last full fit
         self._fit_state = None       # the installed fit: (y, logdet on the device, the raw hyper-parameters and the floor)
@@ -185,10 +193,9 @@ class GpCemSSM(CemSSM):
                                  _lib.ptr(logdet), _lib.ptr(status), _lib.stream_ptr(dev)), 'sx_gp_fit')
         return m, linv, alpha, logdet, status
 
-    def _appends_next(self, new_x: Tensor, new_y: Tensor):
-        """Would update_model(new_x, new_y) append to the installed fit?  None, or the merged training set (train_x,
-        train_y) that update_model would store: the decision is made once here (the comparison of the fitted rows is a
-        device round trip) and `_update_appending` acts on it."""
+    def _append_merged(self, new_x: Tensor, new_y: Tensor):
+        """The merged training set (train_x, train_y) update_model(new_x, new_y) would store, where the shapes and devices
+        alone allow an append; else None."""
         if not (self._incremental and self._append_ok and self._x_train is not None and self._y_train is not None
                 and new_x.dim() == 2 and new_y.dim() == 2 and new_x.size(0) == new_y.size(0)
                 and new_x.shape[1:] == self._x_train.shape[1:] and new_y.shape[1:] == self._y_train.shape[1:]
@@ -196,7 +203,16 @@ class GpCemSSM(CemSSM):
             return None
         if not 1 <= new_x.size(0) <= MAX_APPEND_ROWS:
             return None
-        train_x, train_y = torch.cat((self._x_train, new_x), dim=0), torch.cat((self._y_train, new_y), dim=0)
+        return torch.cat((self._x_train, new_x), dim=0), torch.cat((self._y_train, new_y), dim=0)
+
+    def _appends_next(self, new_x: Tensor, new_y: Tensor):
+        """Would update_model(new_x, new_y) append to the installed fit?  None, or the merged training set (train_x,
+        train_y) that update_model would store: the decision is made once here (the comparison of the fitted rows is a
+        device round trip) and `_update_appending` acts on it."""
+        merged = self._append_merged(new_x, new_y)
+        if merged is None:
+            return None
+        train_x, train_y = merged
         if self._append_rows(train_x.detach().contiguous(), train_y.detach().contiguous()) == 0:
             return None
         return train_x, train_y
@@ -251,9 +267,9 @@ class GpCemSSM(CemSSM):
     def _hyper_state(self):
         return (self._raw_lengthscale, self._raw_outputscale, self._raw_noise, self._noise_floor)
 
-    def _append_rows(self, x: Tensor, y: Tensor) -> int:
-        """k, the rows by which (x, y) (device, contiguous) extend the installed fit where the update may append them
-        (conf.cem_gp_incremental); 0: a full fit."""
+    def _append_rows_host(self, x: Tensor) -> int:
+        """`_append_rows` but for the comparison of the fitted rows: every check that the host decides without reading
+        from the device."""
         if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
                 and self._fit_state is not None and self._subset_idx is None):
             return 0
@@ -266,8 +282,18 @@ class GpCemSSM(CemSSM):
         if x.device != fit_x.device or self._fit_ws[1].size(1) != n:
             return 0
         now = self._hyper_state()
-        if now[3] != hyper[3] or not all(torch.equal(a, b) for a, b in zip(now[:3], hyper[:3])):
+        # (host tensors, compared on the host)
+        if now[3] != hyper[3] or not all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(now[:3], hyper[:3])):
             return 0
+        return k
+
+    def _append_rows(self, x: Tensor, y: Tensor) -> int:
+        """k, the rows by which (x, y) (device, contiguous) extend the installed fit where the update may append them
+        (conf.cem_gp_incremental); 0: a full fit."""
+        k = self._append_rows_host(x)
+        if k == 0:
+            return 0
+        fit_x, fit_y, n = self._buffers[0], self._fit_state[0], x.size(0) - k
         # the fitted rows themselves, compared where they live
         if not (torch.equal(x[:n], fit_x) and torch.equal(y[:n], fit_y)):
             return 0
@@ -622,8 +648,131 @@ class _MultiFit:
                                    f'hyper-parameters')
 
 
+class _LockstepBuffers:
+    """What a lockstep append keeps between calls, with the model that leads the group: the one workspace allocation the
+    problems' workspaces are cut from, and the problem table in pinned host memory and on the device.  Each grows on
+    demand.  (A call ends in a host read of its results, so the previous call's copy of the table has completed.)"""
+
+    def __init__(self):
+        self.ws: Optional[Tensor] = None
+        self.host_table: Optional[Tensor] = None
+        self.table: Optional[Tensor] = None
+
+    def workspace(self, nbytes: int, dev) -> Tensor:
+        if self.ws is None or self.ws.numel() * 8 < nbytes or self.ws.device != dev:
+            # (a quarter more than asked for: the training sets grow by a few rows from call to call)
+            self.ws = torch.empty((nbytes + nbytes // 4 + 7) // 8, dtype=torch.float64, device=dev)
+        return self.ws
+
+    def tables(self, nbytes: int, dev) -> Tuple[Tensor, Tensor]:
+        if self.table is None or self.table.numel() < nbytes or self.table.device != dev:
+            self.host_table = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            self.table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self.host_table[:nbytes], self.table[:nbytes]
+
+
+def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k: int) -> None:
+    """`_update_appending` of E >= 2 models that append k rows each, with ONE sx_gp_append_table + sx_gp_append_multi (six
+    launches for all of them) and one host read of the E status words and E x n_s log-determinants; then, per model, the
+    pack and install of `GpCemSSM._append`.  Model e's state afterwards equals, bit for bit, what its own update_model
+    leaves.  A model whose Schur complement is not positive definite is fitted in full, alone, after the others have been
+    installed (and raises there as it always did)."""
+    lib = _lib.lib()
+    E, lead = len(ssms), ssms[0]
+    n_s = lead.num_states
+    data = []
+    for m, (train_x, train_y) in zip(ssms, merged):
+        _lib.require_gpu(train_x, 'train_x')
+        _lib.require_gpu(train_y, 'train_y')
+        data.append((train_x.detach().contiguous(), train_y.detach().contiguous()))
+    dev = data[0][0].device
+    models = (_lib.SxGpModel * E)(*[m._fit_struct(x) for m, (x, _) in zip(ssms, data)])
+    sizes = [int(lib.sx_gp_append_workspace_bytes(n_s, x.size(0), k)) for x, _ in data]
+    if min(sizes) < 0:
+        raise _lib.SxError('sx_gp_append_workspace_bytes: bad argument')
+    if lead._lockstep_bufs is None:
+        lead._lockstep_bufs = _LockstepBuffers()
+    bufs = lead._lockstep_bufs
+    ws = bufs.workspace(sum(sizes), dev)
+    ws_ptrs, at = [], ws.data_ptr()
+    for nbytes in sizes:            # (each a multiple of 8 bytes)
+        ws_ptrs.append(at)
+        at += nbytes
+    linv = [torch.empty((n_s, x.size(0), x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
+    alpha = [torch.empty((n_s, x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
+    logdet = torch.empty((E, n_s), dtype=torch.float64, device=dev)
+    status = torch.zeros(E, dtype=torch.int32, device=dev)
+    host_table, table = bufs.tables(int(lib.sx_gp_append_table_bytes(E)), dev)
+    arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
+    _lib.check(lib.sx_gp_append_table(models, E, k, arr([y for _, y in data]), arr([m._fit_ws[1] for m in ssms]),
+                                      arr([m._alpha for m in ssms]), arr([m._fit_state[1] for m in ssms]), arr(linv),
+                                      arr(alpha), arr(list(logdet)), _lib.ptr(status), (ctypes.c_void_p * E)(*ws_ptrs),
+                                      (ctypes.c_int64 * E)(*sizes), ctypes.c_void_p(host_table.data_ptr())),
+               'sx_gp_append_table')
+    table.copy_(host_table, non_blocking=True)
+    _lib.check(lib.sx_gp_append_multi(models, E, k, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_append_multi')
+    host = torch.cat((status.double(), logdet.reshape(-1))).cpu()      # the call's one read of its results
+    logdets = host[E:].reshape(E, n_s)
+    bad = [bool(int(host[e]) & _lib.SX_STATUS_NOT_PD) for e in range(E)]
+    for e, m in enumerate(ssms):
+        m._x_train, m._y_train = merged[e]
+        if bad[e]:
+            continue    # (its outputs are unspecified and nothing is packed from them)
+        x, y = data[e]
+        model = _lib.SxGpModel.from_buffer_copy(models[e])
+        packed = m._pack(model, linv[e], alpha[e])
+        m._fit_ws = (linv[e].new_empty((n_s, 0, 0)), linv[e])
+        m._install(x, model, packed, alpha[e], logdets[e].clone(), y=y, logdet_dev=logdet[e])
+        m._appended += k
+    for e, m in enumerate(ssms):
+        if bad[e]:
+            m._update_model(*merged[e], may_append=False)
+
+
+def _append_lockstep(ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor]) -> None:
+    """The plain update of models of which some have conf.cem_gp_incremental_lockstep.  The models that have it are decided
+    together: the host checks per model, then the device comparisons of all their fitted rows in one tensor and one read.
+    Those that qualify form groups by the number of new rows (and the device); a group of two or more appends in one call
+    (`_append_group`), a group of one and the qualifying models without the setting append alone, and the models that do not
+    qualify are fitted together first, as update_models_multi fits them."""
+    decided: List[Optional[Tuple[Tensor, Tensor]]] = [None] * len(ssms)
+    cands, flags = [], []
+    for i, (m, new_x, new_y) in enumerate(zip(ssms, xs, ys)):
+        if not m._lockstep:
+            decided[i] = m._appends_next(new_x, new_y)
+            continue
+        merged = m._append_merged(new_x, new_y)
+        if merged is None:
+            continue
+        x, y = merged[0].detach().contiguous(), merged[1].detach().contiguous()
+        k = m._append_rows_host(x)
+        if k == 0:
+            continue
+        n = x.size(0) - k
+        cands.append((i, k, merged))
+        flags.append((x[:n] == m._buffers[0]).all() & (y[:n] == m._fit_state[0]).all())
+    groups: Dict[Tuple[int, Any], List[int]] = {}
+    if cands:
+        same = torch.stack(flags).cpu()                                # the decision's one read
+        for (i, k, merged), ok in zip(cands, same):
+            if bool(ok):
+                decided[i] = merged
+                groups.setdefault((k, merged[0].device), []).append(i)
+    rest = [i for i, a in enumerate(decided) if a is None]
+    if rest:
+        update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest], _decided=True)
+    grouped = set()
+    for (k, _), members in groups.items():
+        if len(members) >= 2:
+            _append_group([ssms[i] for i in members], [decided[i] for i in members], k)
+            grouped.update(members)
+    for i, a in enumerate(decided):
+        if a is not None and i not in grouped:
+            ssms[i]._update_appending(*a)
+
+
 def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequence[Tensor], opt_hyp=False,
-                        replace_old=False) -> None:
+                        replace_old=False, *, _decided=False) -> None:
     """``m.update_model(x, y, opt_hyp, replace_old)`` for every (m, x, y) at once: the reference's n_scenarios models, each
     retrained on its own data after every episode (episode_runner.py:55,123).
 
@@ -636,7 +785,12 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
     e, and then no model's data, hyper-parameters or predictions have changed.  (Each model's fit workspace serves the
     batch from the start, so after such a call its cached W = L^-1 is marked stale, and its next
     predict_variance_jacobian factorises once more -- as after a failed single-model update.)  Any other list of models (other families,
-    JunkDimensionsSSM, differing shapes or iteration counts) is updated one model at a time."""
+    JunkDimensionsSSM, differing shapes or iteration counts) is updated one model at a time.
+
+    conf.cem_gp_incremental: the models whose plain update appends to their fit do so one by one (sx_gp_append), or, with
+    conf.cem_gp_incremental_lockstep, those that add the same number of rows in one sx_gp_append_multi call
+    (`_append_lockstep`); either way each ends in the state its own update_model leaves, bit for bit.
+    (_decided: the caller has found that none of these models appends.)"""
     ssms, xs, ys = list(ssms), list(xs), list(ys)
     if not len(ssms) == len(xs) == len(ys):
         raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
@@ -648,7 +802,10 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
         return
     # conf.cem_gp_incremental: the models whose update appends to their fit (sx_gp_append) do so one by one, after the
     # others have been fitted together as below
-    if not opt_hyp and not replace_old and any(m._incremental for m in ssms):
+    if not _decided and not opt_hyp and not replace_old and any(m._incremental for m in ssms):
+        if any(m._lockstep for m in ssms):
+            _append_lockstep(ssms, xs, ys)
+            return
         appends = [m._appends_next(x, y) for m, x, y in zip(ssms, xs, ys)]
         if any(a is not None for a in appends):
             rest = [i for i, a in enumerate(appends) if a is None]
