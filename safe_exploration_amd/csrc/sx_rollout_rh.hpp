@@ -55,7 +55,10 @@
 #define SX_RH_WFIRST 0     // 1: request the resident W before anything else (the first version; A/B switch)
 #endif
 #ifndef SX_RH_SHARES
-#define SX_RH_SHARES 4, 4, 4, 1, 4, 4, 4   // Kstar phase: relative shares of waves 1 .. 7 (25 pairs of 8 rows at N = 200; wave 4 also runs finish_costs)
+// Kstar phase: relative shares of waves 1 .. 7 (wave 4 also runs finish_costs).  25 pairs of 8 rows at N = 200: 3 | 4 | 4 | 2 | 4 | 4 | 4
+// trips -- SIMD 1 runs seven trips, SIMDs 2 and 3 eight, and wave 4's second trip still ends before theirs (3.85k against 4.03k
+// cycles; at one share -- 4 | 4 | 4 | 1 | 4 | 4 | 4 trips -- a step took 17.55k cycles, now 17.37k: profiles/kstar_lds_stamps_rh.txt)
+#define SX_RH_SHARES 4, 4, 4, 2, 4, 4, 4
 #endif
 
 namespace sx {

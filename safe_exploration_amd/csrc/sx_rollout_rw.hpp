@@ -235,9 +235,15 @@ __device__ __forceinline__ void rw_mfma_phase(const GpConst<NS, D>& gc, GpTileLd
 constexpr double kExpScale2 = 2048.0 / 0.693147180559945309417232;   // 2048 / ln 2 = 8 kExpScale
 constexpr double kExpUnit2 = 0.693147180559945309417232 / 2048.0;
 
+// Row image: what one lane reads in one trip -- its rows 8 q + kk and 8 q + kk + 4 -- is CONTIGUOUS and 16-byte aligned
+// (2 (D + NS) doubles: always a multiple of 16 bytes, so the image is a permutation of the rows, no padding), read with
+// ds_read_b128: 4 LDS-array cycles per 16 bytes and lane instead of the 8 of ds_read2_b64 (at n_s = 2, n_u = 1: 20 instead
+// of 40 per trip).  The 16 lanes of a row group read one address (a broadcast); the four groups' 80-byte pieces share no bank.
+__host__ __device__ constexpr int rw_row_slot(int k) { return (k & ~7) + ((k & 3) << 1) + ((k >> 2) & 1); }
+
 template <int NS, int D>
 struct RwKstarLds {
-    double* rows;   // [n_pad][D + NS]: centred training inputs x' and c_kd (rows >= N: zeros)
+    double* rows;   // [n_pad][D + NS] in rw_row_slot order: centred training inputs x' and c_kd (rows >= N: zeros)
     double* tab;    // [2048] 2^(j/2048), then one NaN (the "table" of a NaN query point), one pad
     double* xbar;   // [D] the centre (+ pad to an even count)
     static __host__ __device__ size_t doubles(int n_pad) { return (size_t)n_pad * (D + NS) + (n_pad & 1) + kExpTab2 + 2 + ((D + 1) & ~1); }
@@ -271,10 +277,11 @@ __device__ __forceinline__ void rw_kstar_setup(const GpConst<NS, D>& gc, const R
 #pragma unroll
             for (int d = 0; d < NS; ++d) cc[d] = fma(gc.k_nh_ils2[d * D + j], xr[j] * xr[j], cc[d]);
         }
+        double* const row = kl.rows + rw_row_slot(k) * (D + NS);
 #pragma unroll
-        for (int j = 0; j < D; ++j) kl.rows[k * (D + NS) + j] = xr[j];
+        for (int j = 0; j < D; ++j) row[j] = xr[j];
 #pragma unroll
-        for (int d = 0; d < NS; ++d) kl.rows[k * (D + NS) + D + d] = cc[d];
+        for (int d = 0; d < NS; ++d) row[D + d] = cc[d];
     }
     for (int i = tid; i < kExpTab2; i += blockDim.x) kl.tab[i] = kExp2Tab2048[i];
     if (tid < 2) kl.tab[kExpTab2 + tid] = __builtin_nan("");
@@ -317,30 +324,33 @@ __device__ __forceinline__ void rw_kstar_phase(const GpConst<NS, D>& gc, const R
     const lds_f64* etab = (const lds_f64*)kl.tab + (znan ? kExpTab2 : 0);
     const int emask = znan ? 0 : kExpTab2 - 1;
     const int k0 = 8 * q_begin + (lane >> 4);
-    const lds_f64* x = (const lds_f64*)kl.rows + k0 * RS;
+    // this lane's piece of the row image (rw_row_slot): RS 16-byte words per trip, 4 RS further on per pair
+    typedef const __attribute__((address_space(3))) v2d lds_v2d;
+    lds_v2d* x = (lds_v2d*)kl.rows + (4 * q_begin + (lane >> 4)) * RS;
     lds_f64* f = (lds_f64*)kfrag + kfrag_index(NS, c, k0, 0);
 
     struct Set {
         double t[M], p[M];   // table entry (in flight after A1); r after A1, the polynomial after A2
         int mi[M];
     };
-    auto load_x = [&](double (&xx)[2 * RS]) {
+    // the two rows of a trip: double h * RS + j of the piece is coordinate j (j >= D: constant j - D) of row k0 + 4 h
+    auto load_x = [&](v2d (&xx)[RS]) {
         asm volatile("" : "+v"(x));
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < RS; ++j) xx[h * RS + j] = x[h * 4 * RS + j];
-        x += 8 * RS;
+        for (int i = 0; i < RS; ++i) xx[i] = x[i];
+        x += 4 * RS;
     };
-    auto stage_a1 = [&](const double (&xx)[2 * RS], Set& s) {
+    // A1, the arithmetic: exponents (the rows are dead behind them), table index, r
+    auto stage_a1 = [&](const v2d (&xx)[RS], Set& s) {
+        auto xd = [&](int i) { return xx[i >> 1][i & 1]; };
         double yc[M], m[M];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int d = 0; d < NS; ++d) {
-                double a = xx[h * RS + D + d] + zz[d];
+                double a = xd(h * RS + D + d) + zz[d];
 #pragma unroll
-                for (int j = 0; j < D; ++j) a = fma(g[d][j], xx[h * RS + j], a);
+                for (int j = 0; j < D; ++j) a = fma(g[d][j], xd(h * RS + j), a);
                 yc[h * NS + d] = a;
             }
 #pragma unroll
@@ -350,13 +360,16 @@ __device__ __forceinline__ void rw_kstar_phase(const GpConst<NS, D>& gc, const R
 #pragma unroll
         for (int i = 0; i < M; ++i) asm("v_cvt_i32_f64 %0, %1" : "=v"(s.mi[i]) : "v"(m[i]));
 #pragma unroll
-        for (int i = 0; i < M; ++i) s.t[i] = etab[s.mi[i] & emask];
-#pragma unroll
 #if SX_RW_POLYFOLD
         for (int i = 0; i < M; ++i) s.p[i] = yc[i] - m[i];   // w = r / u, exact
 #else
         for (int i = 0; i < M; ++i) s.p[i] = (yc[i] - m[i]) * kExpUnit2;   // r (the difference is exact)
 #endif
+    };
+    // A1, the gathers, issued as one group
+    auto stage_a1t = [&](Set& s) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) s.t[i] = etab[s.mi[i] & emask];
     };
     auto stage_a2 = [&](Set& s) {
         double r[M];
@@ -388,17 +401,27 @@ __device__ __forceinline__ void rw_kstar_phase(const GpConst<NS, D>& gc, const R
         }
         f += NS * 128;
     };
-    double xr[2 * RS];
+    // The LDS returns a wave's operations in order, so a wait for one of them waits for everything requested before it.
+    // A trip therefore requests in the order [rows of the next trip][the previous set's fragments][this set's gathers]:
+    // the rows are requested once this trip's arithmetic has consumed the old ones and are awaited at the head of the next
+    // trip with the stores and gathers behind them still in flight (lgkmcnt(6) at n_s = 2; lgkmcnt(4) on the trip the loop is
+    // entered at, where the compiler merges in the prologue's state, which has no stores); the gathers -- conflicted, the
+    // slow ones -- are awaited a whole trip later by stage B, with the next rows behind them.  No full drain in the loop.
+    // (Gathers ahead of the stores keep the old set's table entries live across them: one spilled dword at <2, 1, 13>.)
+    v2d xr[RS];
     Set s0, s1;
     load_x(xr);           // trip 0
     stage_a1(xr, s0);
     load_x(xr);           // trip 1
+    stage_a1t(s0);
     stage_a2(s0);
     auto body = [&](const Set& sold, Set& snew) {
         stage_a1(xr, snew);
         SX_PIN();
         load_x(xr);
+        SX_PIN();
         stage_b(sold);
+        stage_a1t(snew);
         SX_PIN();
         stage_a2(snew);
         SX_PIN();
