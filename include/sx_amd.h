@@ -254,6 +254,29 @@ int sx_gp_append(const sx_gp_model* model, int n_old, const double* y_train, con
                  const double* logdet_old, double* linv, double* alpha, double* logdet, int32_t* status,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The k <= 64 oldest rows removed from a fitted exact GP without refactorising the kept ones ----
+ * linv_old dev [n_s x N x N] as sx_gp_fit (or sx_gp_append, or this entry) wrote it for N = n_old rows; the first k rows are
+ * dropped and m = N - k are kept; y_train dev [m x n_s], the KEPT rows' targets.  No hyper-parameters and no training
+ * inputs are needed.  Per output, with W = linv_old partitioned after the first k rows and columns, W = [ W11 0 ; W21 W22 ]:
+ *     K22 = L22 L22^T + L21 L21^T (a rank-k update, positive sign),  L11 = W11^-1,  V = L22^-1 L21 = -W21 L11 [m x k],
+ *     W' = chol(I + V V^T)^-1 W22,  alpha' = W'^T (W' y),  logdet' = -sum log diag W',
+ * chol(I + V V^T)^-1 applied as k rank-1 stages in one pass over the rows, to every column of W22 independently.
+ * linv dev [n_s x m x m], alpha dev [n_s x m] and logdet dev [n_s] get exactly the layout sx_gp_fit leaves for m rows (zeros
+ * above the diagonal included), so sx_gp_pack, sx_gp_mll_grad, sx_gp_predict_var_jac, sx_gp_append and a further sx_gp_drop
+ * take them unchanged.  The old and the new buffers must be DISTINCT (the row stride changes); the inputs are not written.
+ * status dev int32, or-ed into: SX_STATUS_NOT_PD where a diagonal element of W11 or of W' is not > 0, an element of W11 or
+ * a stage's t + u^2 is not finite, or a NaN appears; the outputs are then unspecified.  workspace dev,
+ * sx_gp_drop_workspace_bytes(n_s, n_old, k) bytes.  Seven launches on `stream`, O(N^2 k) work, every sum in an order that
+ * depends on N and k only, no atomics on doubles; nothing is waited for.
+ * SX_ERR_ARG (before any device access) for a null pointer, n_s outside 1 .. SX_MAX_NS, k outside 1 .. 64, n_old - k < 1 or
+ * a workspace that is too small; SX_ERR_UNSUPPORTED for n_old > 4096.
+ * Replaces: the refit of a GpCemSSM that keeps its most recent rows (conf.cem_gp_window), together with sx_gp_append.
+ *
+ * Bytes of the workspace; < 0 for n_s outside 1 .. SX_MAX_NS, k outside 1 .. 64, n_old - k < 1 or n_old > 4096. */
+int64_t sx_gp_drop_workspace_bytes(int n_s, int n_old, int k);
+int sx_gp_drop(int n_s, int n_old, int k, const double* y_train, const double* linv_old, double* linv, double* alpha,
+               double* logdet, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Lockstep appends: k rows appended to each of E fitted exact GPs in one launch sequence ----
  * Every problem e has its own fitted rows (its own N_e) and hyper-parameters; all share (n_s, n_u) and k.  Problem e's linv,
  * alpha and logdet are those of sx_gp_append for model e alone, BIT FOR BIT: they are independent of which other problems

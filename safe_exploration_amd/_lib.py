@@ -83,6 +83,8 @@ SIGNATURES = {
     'sx_gp_mll_grad': (c_int, [POINTER(SxGpModel)] + [c_void_p] * 8),
     'sx_gp_append_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
     'sx_gp_append': (c_int, [POINTER(SxGpModel), c_int] + [c_void_p] * 9 + [c_int64, c_void_p]),
+    'sx_gp_drop_workspace_bytes': (c_int64, [c_int, c_int, c_int]),
+    'sx_gp_drop': (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p]),
     'sx_gp_append_table_bytes': (c_int64, [c_int]),
     'sx_gp_append_table': (c_int, [POINTER(SxGpModel), c_int, c_int] + [POINTER(c_void_p)] * 7
                            + [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_void_p]),

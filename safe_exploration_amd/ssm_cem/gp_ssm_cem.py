@@ -32,6 +32,14 @@ MAX_TRAINING_POINTS = 4096
 MAX_POOL_POINTS = 65536
 # csrc/sx_gp_append.hpp kAppendMaxK: the rows one sx_gp_append call adds (conf.cem_gp_incremental)
 MAX_APPEND_ROWS = 64
+# csrc/sx_gp_drop.hpp kDropMaxK: the rows one sx_gp_drop call removes (conf.cem_gp_window)
+MAX_DROP_ROWS = 64
+# the rows a windowed model drops in one slide: the largest measured overflow at which drop + append beats the full fit of the
+# window at every window size measured (200, 590, 2000).  Beyond it the update fits in full.
+MAX_SLIDE_ROWS = 16
+# conf.cem_gp_window_max_chain's default: the rows a windowed model appends and slides between two full fits.  The longest
+# chain measured on the device, at which W and alpha still stay within the fit's own error allowance
+WINDOW_MAX_CHAIN = 128
 
 
 class GpCemSSM(CemSSM):
@@ -41,6 +49,7 @@ class GpCemSSM(CemSSM):
     _incremental = False                   # conf.cem_gp_incremental (set by __init__; the weight-space subclass has none)
     _append_ok = False
     _lockstep = False                      # conf.cem_gp_incremental_lockstep (set by __init__; the weight-space subclass has none)
+    _window: Optional[int] = None          # conf.cem_gp_window (set by __init__; the weight-space subclass has none)
 
     def __new__(cls, conf=None, *args, **kwargs):
         # one class name for every kernel, as in the reference (gp_ssm_cem.py:45-57): the 'linear' and 'nn' kernels are
@@ -87,6 +96,26 @@ class GpCemSSM(CemSSM):
         if self._lockstep and not self._incremental:
             raise ValueError('cem_gp_incremental_lockstep needs cem_gp_incremental: there is nothing to append in lockstep '
                              'where every update is a full fit')
+        # conf.cem_gp_window = m: the model keeps the most recent m rows.  Every update trims the stored data to them, and a
+        # plain update that overflows the window by r rows slides it: sx_gp_drop of the r oldest rows, then sx_gp_append of the
+        # new ones, O(N^2 (r + k)), instead of the full fit of the last m rows.  conf.cem_gp_window_max_chain: at most that many
+        # rows are appended or slid between two full fits of a windowed model (None: no limit).
+        window = getattr(conf, 'cem_gp_window', None)
+        self._window: Optional[int] = None if window is None else int(window)
+        if self._window is not None:
+            if not 1 <= self._window <= MAX_TRAINING_POINTS:
+                raise ValueError(f'cem_gp_window={window}: the window holds 1 .. {MAX_TRAINING_POINTS} rows')
+            if not self._incremental:
+                raise ValueError('cem_gp_window needs cem_gp_incremental: without it every update is a full fit, and there '
+                                 'is nothing to slide')
+            if self._subset_size is not None:
+                raise ValueError('cem_gp_window excludes cem_gp_subset_size: the fitted rows are either the most recent or '
+                                 'the max-variance subset')
+        wchain = getattr(conf, 'cem_gp_window_max_chain', WINDOW_MAX_CHAIN)
+        self._window_max_chain: Optional[int] = None if wchain is None else int(wchain)
+        if self._window_max_chain is not None and self._window_max_chain < 0:
+            raise ValueError(f'cem_gp_window_max_chain={wchain}: a row count, or None')
+        self._drop_ws: Optional[Tensor] = None
         self._lockstep_bufs: Optional['_LockstepBuffers'] = None   # of the groups this model leads
         self._append_ok = False      # may the next update append to the installed fit?  (False after anything but a plain update)
         self._appended = 0           # rows appended since the last full fit
@@ -277,15 +306,25 @@ class GpCemSSM(CemSSM):
         n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
         if not 1 <= k <= MAX_APPEND_ROWS or n + k > MAX_TRAINING_POINTS or self._selects(n + k):
             return 0
-        if self._max_chain is not None and self._appended + k > self._max_chain:
+        if not self._chain_allows(k):
             return 0
         if x.device != fit_x.device or self._fit_ws[1].size(1) != n:
             return 0
-        now = self._hyper_state()
-        # (host tensors, compared on the host)
-        if now[3] != hyper[3] or not all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(now[:3], hyper[:3])):
+        if not self._hyper_unchanged():
             return 0
         return k
+
+    def _chain_allows(self, k: int) -> bool:
+        """May k more rows be appended (or slid) before the next full fit?"""
+        if self._max_chain is not None and self._appended + k > self._max_chain:
+            return False
+        return not (self._window is not None and self._window_max_chain is not None
+                    and self._appended + k > self._window_max_chain)
+
+    def _hyper_unchanged(self) -> bool:
+        """Are the hyper-parameters those of the installed fit?  (host tensors, compared on the host)"""
+        now, hyper = self._hyper_state(), self._fit_state[2]
+        return now[3] == hyper[3] and all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(now[:3], hyper[:3]))
 
     def _append_rows(self, x: Tensor, y: Tensor) -> int:
         """k, the rows by which (x, y) (device, contiguous) extend the installed fit where the update may append them
@@ -299,13 +338,36 @@ class GpCemSSM(CemSSM):
             return 0
         return k
 
-    def _append(self, x: Tensor, y: Tensor, k: int) -> bool:
+    def _drop(self, y_kept: Tensor, r: int):
+        """sx_gp_drop of the r oldest rows of the installed fit; y_kept: the kept rows' targets (device, contiguous).  Returns
+        (linv, alpha, logdet, status) of the kept rows in fresh buffers, the status word not yet read."""
+        lib = _lib.lib()
+        dev = y_kept.device
+        n_s, n = self.num_states, self._fit_ws[1].size(1)
+        m = n - r
+        nbytes = int(lib.sx_gp_drop_workspace_bytes(n_s, n, r))
+        if nbytes < 0:
+            raise _lib.SxError('sx_gp_drop_workspace_bytes: bad argument')
+        if self._drop_ws is None or self._drop_ws.numel() * 8 < nbytes or self._drop_ws.device != dev:
+            self._drop_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        linv = torch.empty((n_s, m, m), dtype=torch.float64, device=dev)
+        alpha = torch.empty((n_s, m), dtype=torch.float64, device=dev)
+        logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.sx_gp_drop(n_s, n, r, _lib.ptr(y_kept), _lib.ptr(self._fit_ws[1]), _lib.ptr(linv), _lib.ptr(alpha),
+                                  _lib.ptr(logdet), _lib.ptr(status), _lib.ptr(self._drop_ws), nbytes, _lib.stream_ptr(dev)),
+                   'sx_gp_drop')
+        return linv, alpha, logdet, status
+
+    def _append(self, x: Tensor, y: Tensor, k: int, start=None) -> bool:
         """sx_gp_append of the last k rows of (x, y) to the installed fit, into fresh buffers that become the fit workspace,
-        then the usual pack and install.  False (and nothing changed) where S is not positive definite."""
+        then the usual pack and install.  False (and nothing changed) where S is not positive definite.  start: `_drop`'s
+        answer for the first rows of (x, y), to append to in place of the installed fit (a slide); its status word is shared,
+        so that one read decides for both calls."""
         lib = _lib.lib()
         dev = x.device
         n_s, n2 = self.num_states, x.size(0)
-        _, logdet_old, _ = self._fit_state
+        linv_old, alpha_old, logdet_old = start[:3] if start is not None else (self._fit_ws[1], self._alpha, self._fit_state[1])
         m = self._fit_struct(x)
         nbytes = int(lib.sx_gp_append_workspace_bytes(n_s, n2, k))
         if nbytes < 0:
@@ -315,8 +377,8 @@ class GpCemSSM(CemSSM):
         linv = torch.empty((n_s, n2, n2), dtype=torch.float64, device=dev)
         alpha = torch.empty((n_s, n2), dtype=torch.float64, device=dev)
         logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.sx_gp_append(ctypes.byref(m), n2 - k, _lib.ptr(y), _lib.ptr(self._fit_ws[1]), _lib.ptr(self._alpha),
+        status = start[3] if start is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.sx_gp_append(ctypes.byref(m), n2 - k, _lib.ptr(y), _lib.ptr(linv_old), _lib.ptr(alpha_old),
                                     _lib.ptr(logdet_old), _lib.ptr(linv), _lib.ptr(alpha), _lib.ptr(logdet),
                                     _lib.ptr(status), _lib.ptr(self._append_ws), nbytes, _lib.stream_ptr(dev)), 'sx_gp_append')
         # (the status first: where S is not positive definite the outputs are unspecified and nothing is packed from them)
@@ -329,7 +391,53 @@ class GpCemSSM(CemSSM):
         self._appended += k
         return True
 
+    def _slide_rows(self, x: Tensor, y: Tensor) -> Tuple[int, int]:
+        """(r, k) where the update to (x, y) (device, contiguous, longer than the window) may slide the installed fit: its r
+        oldest rows dropped and the last k rows of (x, y) appended; (0, 0): a full fit of the last m rows.  `_append_rows`'
+        conditions, with the row comparison made against the tail of the fitted rows (the dropped ones no longer matter)."""
+        if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
+                and self._fit_state is not None and self._subset_idx is None):
+            return 0, 0
+        fit_x, fit_y = self._buffers[0], self._fit_state[0]
+        n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
+        r = n + k - self._window
+        if not (1 <= k <= MAX_APPEND_ROWS and 1 <= r <= min(MAX_SLIDE_ROWS, MAX_DROP_ROWS) and r < n):
+            return 0, 0
+        if not self._chain_allows(k):
+            return 0, 0
+        if x.device != fit_x.device or self._fit_ws[1].size(1) != n or not self._hyper_unchanged():
+            return 0, 0
+        # the kept fitted rows themselves, compared where they live
+        if not (torch.equal(x[r:n], fit_x[r:]) and torch.equal(y[r:n], fit_y[r:])):
+            return 0, 0
+        return r, k
+
+    def _slide(self, x: Tensor, y: Tensor, r: int, k: int) -> bool:
+        """The window moved by sx_gp_drop of the r oldest fitted rows and sx_gp_append of the last k rows of (x, y), then the
+        usual pack and install on the rows x[r:].  False (and nothing changed) where either call answers SX_STATUS_NOT_PD."""
+        x_new, y_new = x[r:].contiguous(), y[r:].contiguous()
+        n = self._buffers[0].size(0)
+        start = self._drop(y_new[:n - r].contiguous(), r)
+        return self._append(x_new, y_new, k, start=start)
+
+    def _update_window(self, x_train: Tensor, y_train: Tensor, may_append: bool) -> None:
+        """conf.cem_gp_window: the update to more rows than the window holds.  The stored data are trimmed to the last m rows;
+        the model slides where it may and is fitted on exactly those rows where it may not."""
+        _lib.require_gpu(x_train, 'train_x')
+        _lib.require_gpu(y_train, 'train_y')
+        m = self._window
+        self._x_train, self._y_train = x_train[-m:], y_train[-m:]
+        if may_append:
+            x, y = x_train.detach().contiguous(), y_train.detach().contiguous()
+            r, k = self._slide_rows(x, y)
+            if r and self._slide(x, y, r, k):
+                return
+        self._update_model(self._x_train, self._y_train, may_append=False)
+
     def _update_model(self, x_train: Tensor, y_train: Tensor, may_append: bool = True) -> None:
+        if self._window is not None and x_train.size(0) > self._window:
+            self._update_window(x_train, y_train, may_append)
+            return
         self._check_pool_size(x_train.size(0))
         _lib.require_gpu(x_train, 'train_x')
         _lib.require_gpu(y_train, 'train_y')
@@ -420,6 +528,9 @@ class GpCemSSM(CemSSM):
         softplus chain rule stay on the host."""
         if self._training_iterations <= 0:
             return
+        if self._window is not None:
+            # (the caller's merged data; the update before this call has trimmed the stored rows to the same window)
+            x_train, y_train = x_train[-self._window:], y_train[-self._window:]
         pool_x, pool_y = x_train, y_train
         if self._subset_idx is not None:
             # a bounded model trains on the subset its last fit selected; the closing _update_model selects once more,
@@ -790,11 +901,22 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
     conf.cem_gp_incremental: the models whose plain update appends to their fit do so one by one (sx_gp_append), or, with
     conf.cem_gp_incremental_lockstep, those that add the same number of rows in one sx_gp_append_multi call
     (`_append_lockstep`); either way each ends in the state its own update_model leaves, bit for bit.
+    conf.cem_gp_window: a windowed model is handed to its own update_model (there is no lockstep drop).
     (_decided: the caller has found that none of these models appends.)"""
     ssms, xs, ys = list(ssms), list(xs), list(ys)
     if not len(ssms) == len(xs) == len(ys):
         raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
     if not ssms:
+        return
+    # conf.cem_gp_window: a windowed model trims its data and slides by itself; the others go on together
+    windowed = [i for i, m in enumerate(ssms) if getattr(m, '_window', None) is not None]
+    if windowed:
+        rest = [i for i in range(len(ssms)) if i not in windowed]
+        if rest:
+            update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest], opt_hyp, replace_old,
+                                _decided=_decided)
+        for i in windowed:
+            ssms[i].update_model(xs[i], ys[i], opt_hyp, replace_old)
         return
     if not _multi_fit_applies(ssms, xs):
         for m, x, y in zip(ssms, xs, ys):
