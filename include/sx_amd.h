@@ -309,6 +309,36 @@ int sx_gp_append_table(const sx_gp_model* models, int E, int k, const double* co
  * (exploration_runner.py), one new row per scenario. */
 int sx_gp_append_multi(const sx_gp_model* models, int E, int k, const void* table, void* stream);
 
+/* ---- Lockstep drops: the k oldest rows removed from each of E fitted exact GPs in one launch sequence ----
+ * Every problem e has its own fitted rows (its own N_e = n_old[e]); all share n_s and k.  Problem e's linv, alpha and logdet
+ * are those of sx_gp_drop for model e alone, BIT FOR BIT: they are independent of which other problems share the call and
+ * of their order.  The per-problem buffers live in a table of SX_GP_DROP_ENTRY_BYTES per problem, which sx_gp_drop_table
+ * writes to HOST memory: the caller copies it to the device (from pinned memory that needs no wait) and passes the device
+ * copy to sx_gp_drop_multi, which reads it and copies nothing from the host.
+ *
+ * Bytes of the table for E problems (E * SX_GP_DROP_ENTRY_BYTES); < 0 for E <= 0. */
+#define SX_GP_DROP_ENTRY_BYTES 104
+int64_t sx_gp_drop_table_bytes(int E);
+/* Lays the E problems out in `table` (HOST memory, sx_gp_drop_table_bytes() bytes): n_old host [E], the fitted rows N_e, and
+ * problem e's device buffers (host arrays of E device pointers, each as the argument of that name of sx_gp_drop):
+ * y_train[e] (the m_e = N_e - k KEPT rows' targets), linv_old[e], linv[e], alpha[e], logdet[e]; workspace[e] dev,
+ * workspace_bytes[e] >= sx_gp_drop_workspace_bytes(n_s, N_e, k) (the E workspaces may be cut from one allocation); and the
+ * shared status dev int32 [E], one word per problem, or-ed into: SX_STATUS_NOT_PD in word e says that problem e's outputs are
+ * unspecified and nothing about the others'.  No device access.
+ * SX_ERR_ARG for a null pointer (an element of the pointer arrays included), E <= 0, n_s outside 1 .. SX_MAX_NS, k outside
+ * 1 .. 64, N_e - k < 1 or a workspace that is too small; SX_ERR_UNSUPPORTED for N_e > 4096 or E * n_s > 65535 (a grid's
+ * y-extent). */
+int sx_gp_drop_table(int n_s, int E, int k, const int* n_old, const double* const* y_train, const double* const* linv_old,
+                     double* const* linv, double* const* alpha, double* const* logdet, int32_t* status,
+                     void* const* workspace, const int64_t* workspace_bytes, void* table);
+/* sx_gp_drop for the E problems of `table` (dev, the device copy of sx_gp_drop_table's output for the same n_s, k and n_old):
+ * seven launches on `stream` for all of them, each sized by the largest m_e; a workgroup beyond its own problem's extent
+ * returns before it touches memory, and every sum keeps the order that its problem's N_e and k give it.  Nothing is waited
+ * for.  The checks of sx_gp_drop_table that concern n_s, E, k and n_old (before any device access).
+ * Replaces: the model-by-model slides of the n_scenarios windowed GpCemSSM models between two solves of the exploration
+ * loop (conf.cem_gp_window with conf.cem_gp_incremental_lockstep), together with sx_gp_append_multi. */
+int sx_gp_drop_multi(int n_s, int E, int k, const int* n_old, const void* table, void* stream);
+
 /* ---- E exact GPs' fit and MLL gradient in one launch sequence (batched hyper-parameter training) ----
  * Every problem e has its own training set (its own N <= 4096) and hyper-parameters; all share (n_s, n_u).  Problem e's
  * linv, alpha, logdet, mll and gradient are bit-identical to what sx_gp_fit / sx_gp_mll_grad give for that model alone.

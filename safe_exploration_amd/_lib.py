@@ -14,6 +14,7 @@ SX_SAT_MAX_DIM = SX_MAX_NS + 1
 SX_TILE = 16
 SX_GP_FIT_ENTRY_BYTES = 360
 SX_GP_APPEND_ENTRY_BYTES = 408
+SX_GP_DROP_ENTRY_BYTES = 104
 SX_FEAT_MAX_WIDTH = 32
 SX_FEAT_MAX_LAYERS = 3
 SX_MLP_MAX_HIDDEN = 4
@@ -89,6 +90,10 @@ SIGNATURES = {
     'sx_gp_append_table': (c_int, [POINTER(SxGpModel), c_int, c_int] + [POINTER(c_void_p)] * 7
                            + [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_void_p]),
     'sx_gp_append_multi': (c_int, [POINTER(SxGpModel), c_int, c_int, c_void_p, c_void_p]),
+    'sx_gp_drop_table_bytes': (c_int64, [c_int]),
+    'sx_gp_drop_table': (c_int, [c_int, c_int, c_int, POINTER(c_int)] + [POINTER(c_void_p)] * 5
+                         + [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_void_p]),
+    'sx_gp_drop_multi': (c_int, [c_int, c_int, c_int, POINTER(c_int), c_void_p, c_void_p]),
     'sx_gp_fit_table_bytes': (c_int64, [c_int]),
     'sx_gp_fit_table': (c_int, [POINTER(SxGpModel), c_int] + [POINTER(c_void_p)] * 5 + [c_void_p] * 4),
     'sx_gp_fit_multi': (c_int, [POINTER(SxGpModel), c_int, c_void_p, c_void_p]),

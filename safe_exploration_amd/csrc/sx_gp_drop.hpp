@@ -27,6 +27,17 @@
 // a zero column of V, so u = 0, dinv = 1, coef = 0 and the stage changes nothing, bit for bit; their loops over the stages
 // are straight-line code with static register indices.
 // Every sum has a fixed order that depends on N and k only; no atomics on doubles; nothing waits across workgroups.
+//
+// sx_gp_drop_multi: the same seven launches for E problems that share (n_s, k), hence KB, and differ in N (MM = true).  The
+// kernels then take the device table of the problems' DropEntry and the grid's output index is e n_s + d: x for
+// drop_l11_kernel, drop_table_kernel and drop_logdet_kernel, y for the other four, whose x-extent is the largest problem's.
+// A workgroup beyond its own problem's extent (64-row blocks for drop_v_kernel, drop_main_kernel and drop_alpha_kernel,
+// 4-row blocks for drop_t_kernel) returns before it touches that problem's memory or reaches a barrier; the test is uniform
+// per workgroup.  The contract: no kernel reads gridDim and every loop bound comes from the problem's own n, k, m, so the
+// workgroups of problem e that run are exactly those of its single call, with the same block indices and the same
+// statements: linv, alpha and logdet of problem e are sx_gp_drop's for that model alone, bit for bit, whatever else shares the
+// call and in whatever order.  The status word is the problem's own: one problem that is not positive definite leaves the
+// others valid.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +78,40 @@ struct DropArgs {
     int n, k, m, n_s;
 };
 
+// One problem of sx_gp_drop_multi: an entry of the device table sx_gp_drop_table lays out -- the problem's DropArgs (status:
+// its own word) and the x-extents of its own launches.
+struct DropEntry : DropArgs {
+    int blocks;              // 64-row blocks of the kept rows: drop_v_kernel, drop_main_kernel, drop_alpha_kernel
+    int blocks4;             // 4-row blocks: drop_t_kernel
+};
+static_assert(sizeof(DropEntry) == SX_GP_DROP_ENTRY_BYTES, "include/sx_amd.h: SX_GP_DROP_ENTRY_BYTES");
+
+// The argument of the drop kernels, after AppendArg (sx_gp_append.hpp): the DropArgs itself (one model, the grid's output
+// index is the output d), or with MM = true the device table of E problems' DropEntry, of which the workgroup binds the
+// entry of its problem: the grid's output index is then e n_s + d.  The pointer is restrict-qualified and never written and
+// the index is uniform, so the entry is read through the constant address space (scalar loads, and the device pointers it
+// holds are taken to be global, as those of a kernel argument are).
+// (entry() and output() answer by value, so that the plain mode's statements keep their form and its ISA.)
+template <bool MM>
+struct DropArg {
+    using type = DropArgs;
+    __device__ static const DropArgs& entry(const type& a, int) { return a; }
+    __device__ static int output(const type&, int idx) { return idx; }
+};
+template <>
+struct DropArg<true> {
+    using type = const DropEntry* __restrict__;
+    using ConstE = __attribute__((address_space(4))) const DropEntry;
+    __device__ static int problem(type table, int idx) { return idx / ((const ConstE*)table)[0].n_s; }
+    __device__ static const DropEntry& entry(type table, int idx) {
+        return *(const DropEntry*)((const ConstE*)table + problem(table, idx));
+    }
+    __device__ static int output(type table, int idx) { return idx - problem(table, idx) * ((const ConstE*)table)[0].n_s; }
+};
+
+__host__ __device__ inline int drop_blocks(int m) { return (m + kDT - 1) / kDT; }
+__host__ __device__ inline int drop_blocks4(int m) { return (m + kDThreads / 64 - 1) / (kDThreads / 64); }
+
 // doubles of the workspace for n_s outputs, m kept rows and k dropped ones
 inline int64_t drop_workspace_doubles(int n_s, int m, int k) {
     return (int64_t)n_s * ((int64_t)kDT * kDT + (int64_t)m * kDT + (int64_t)m * drop_stages(k) * 3 + m);
@@ -74,9 +119,11 @@ inline int64_t drop_workspace_doubles(int n_s, int m, int k) {
 
 // One workgroup per output.  W11 into LDS (padded with the identity), checked; L11 = W11^-1 by forward substitution, thread c
 // solves column c and keeps it in registers (static indices, fully unrolled; the rows >= k are the identity's)
-__global__ __launch_bounds__(kDThreads) void drop_l11_kernel(DropArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kDThreads) void drop_l11_kernel(typename DropArg<MM>::type arg) {
     __shared__ double Ws[kDT * kDTLd];
-    const int d = blockIdx.x, tid = threadIdx.x, n = a.n, k = a.k;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.x);
+    const int d = DropArg<MM>::output(arg, blockIdx.x), tid = threadIdx.x, n = a.n, k = a.k;
     const double* W = a.w_old + (size_t)d * n * n;
     bool bad = false;
     for (int idx = tid; idx < kDT * kDT; idx += kDThreads) {
@@ -110,10 +157,15 @@ __global__ __launch_bounds__(kDThreads) void drop_l11_kernel(DropArgs a) {
 
 // V = -W21 L11 for the kept rows 64 blockIdx.x ..: V[i][s] = -sum over q = s .. k - 1 (in that order) of W21[i][q] L11[q][s];
 // the columns s >= k are zero
-__global__ __launch_bounds__(kDThreads) void drop_v_kernel(DropArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kDThreads) void drop_v_kernel(typename DropArg<MM>::type arg) {
     __shared__ double As[kDT * kDTLd];
     __shared__ double Ls[kDT * kDTLd];
-    const int d = blockIdx.y, tid = threadIdx.x, n = a.n, k = a.k, m = a.m, i0 = blockIdx.x * kDT;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.y);
+    const int d = DropArg<MM>::output(arg, blockIdx.y), tid = threadIdx.x, n = a.n, k = a.k, m = a.m, i0 = blockIdx.x * kDT;
+    if constexpr (MM) {
+        if ((int)blockIdx.x >= a.blocks) return;   // beyond this problem's row blocks (uniform; before any barrier)
+    }
     const double* W = a.w_old + (size_t)d * n * n;
     const double* l11 = a.l11 + (size_t)d * kDT * kDT;
     for (int idx = tid; idx < kDT * kDT; idx += kDThreads) {
@@ -138,11 +190,12 @@ __global__ __launch_bounds__(kDThreads) void drop_v_kernel(DropArgs a) {
 // in its registers, from values nobody reads again: the loop over q is straight-line code without a lane mask.)  The rows
 // of V are fetched a chunk at a time, one chunk ahead in registers and one more in the ring; a row lives in the ring from at
 // most 2 kDropChunk - 1 ticks before its stage 0 to its last stage: kDropRing slots.
-template <int KB>
-__global__ __launch_bounds__(kDT) void drop_table_kernel(DropArgs a) {
+template <int KB, bool MM = false>
+__global__ __launch_bounds__(kDT) void drop_table_kernel(typename DropArg<MM>::type arg) {
     static_assert(KB <= kDT && kDropRing >= kDT + 2 * kDropChunk, "a row's slot is reused while a stage still needs it");
     __shared__ double R[kDropRing * kDTLd];
-    const int d = blockIdx.x, lane = threadIdx.x, m = a.m;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.x);
+    const int d = DropArg<MM>::output(arg, blockIdx.x), lane = threadIdx.x, m = a.m;
     const double* V = a.v + (size_t)d * m * kDT;
     double* tab = a.tab + (size_t)d * m * KB * 3;
     double sv[KB];
@@ -199,13 +252,18 @@ __global__ __launch_bounds__(kDT) void drop_table_kernel(DropArgs a) {
 // for every lane.  The rows above the block are written as zeros.  The scalars of drop_rows_ahead(KB) rows at a time go through
 // LDS, where every lane reads the same word; they are fetched into registers a group ahead, beside the group's rows of W22,
 // so that no load waits behind the stores of the rows in work.  (The rows past m of the last group meet zeros for scalars.)
-template <int KB>
-__global__ __launch_bounds__(kDT) void drop_main_kernel(DropArgs a) {
+template <int KB, bool MM = false>
+__global__ __launch_bounds__(kDT) void drop_main_kernel(typename DropArg<MM>::type arg) {
     constexpr int kDropRowsAhead = drop_rows_ahead(KB);
     constexpr int kGroup = kDropRowsAhead * KB * 3;      // scalars of a group of rows
     constexpr int kPer = (kGroup + kDT - 1) / kDT;       // ... per lane
     __shared__ double T[kPer * kDT];
-    const int d = blockIdx.y, lane = threadIdx.x, n = a.n, k = a.k, m = a.m, c0 = blockIdx.x * kDT, c = c0 + lane;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.y);
+    const int d = DropArg<MM>::output(arg, blockIdx.y), lane = threadIdx.x, n = a.n, k = a.k, m = a.m, c0 = blockIdx.x * kDT,
+              c = c0 + lane;
+    if constexpr (MM) {
+        if ((int)blockIdx.x >= a.blocks) return;   // beyond this problem's column blocks (uniform)
+    }
     const double* W = a.w_old + (size_t)d * n * n + (size_t)k * n + k;   // W22, leading dimension n
     const double* tab = a.tab + (size_t)d * m * KB * 3;
     double* W2 = a.w_new + (size_t)d * m * m;
@@ -267,8 +325,14 @@ __device__ __forceinline__ double drop_wave_sum(double v) {
 }
 
 // t = W' y2: wave w of workgroup b has row i = 4 b + w; lane l adds the columns l, l + 64, .. <= i in order
-__global__ __launch_bounds__(kDThreads) void drop_t_kernel(DropArgs a) {
-    const int d = blockIdx.y, lane = threadIdx.x & 63, m = a.m, i = blockIdx.x * (kDThreads / 64) + (threadIdx.x >> 6);
+template <bool MM = false>
+__global__ __launch_bounds__(kDThreads) void drop_t_kernel(typename DropArg<MM>::type arg) {
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.y);
+    const int d = DropArg<MM>::output(arg, blockIdx.y), lane = threadIdx.x & 63, m = a.m,
+              i = blockIdx.x * (kDThreads / 64) + (threadIdx.x >> 6);
+    if constexpr (MM) {
+        if ((int)blockIdx.x >= a.blocks4) return;   // beyond this problem's rows (uniform per workgroup)
+    }
     if (i >= m) return;   // (uniform per wave; no barrier below)
     const double* row = a.w_new + (size_t)d * m * m + (size_t)i * m;
     double s = 0.0;
@@ -282,9 +346,15 @@ __global__ __launch_bounds__(kDThreads) void drop_t_kernel(DropArgs a) {
 
 // alpha' = W'^T t for the columns 64 blockIdx.x ..: lane l of wave w adds the rows i >= c with i mod 4 = w in order, and the
 // four classes are added in class order
-__global__ __launch_bounds__(kDThreads) void drop_alpha_kernel(DropArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kDThreads) void drop_alpha_kernel(typename DropArg<MM>::type arg) {
     __shared__ double part[kDropAlphaWaves][kDT];
-    const int d = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = a.m, c0 = blockIdx.x * kDT, c = c0 + lane;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.y);
+    const int d = DropArg<MM>::output(arg, blockIdx.y), lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = a.m,
+              c0 = blockIdx.x * kDT, c = c0 + lane;
+    if constexpr (MM) {
+        if ((int)blockIdx.x >= a.blocks) return;   // beyond this problem's column blocks (uniform; before the barrier)
+    }
     const double* W2 = a.w_new + (size_t)d * m * m;
     const double* t = a.t + (size_t)d * m;
     double s = 0.0;
@@ -305,9 +375,11 @@ __global__ __launch_bounds__(kDThreads) void drop_alpha_kernel(DropArgs a) {
 }
 
 // logdet' = -sum log diag W': thread t adds the rows t, t + 256, .. in order, then the threads' sums in a fixed tree
-__global__ __launch_bounds__(kDThreads) void drop_logdet_kernel(DropArgs a) {
+template <bool MM = false>
+__global__ __launch_bounds__(kDThreads) void drop_logdet_kernel(typename DropArg<MM>::type arg) {
     __shared__ double part[kDThreads];
-    const int d = blockIdx.x, tid = threadIdx.x, m = a.m;
+    const auto& a = DropArg<MM>::entry(arg, blockIdx.x);
+    const int d = DropArg<MM>::output(arg, blockIdx.x), tid = threadIdx.x, m = a.m;
     const double* W2 = a.w_new + (size_t)d * m * m;
     double s = 0.0;
     bool bad = false;

@@ -91,7 +91,9 @@ class GpCemSSM(CemSSM):
         if self._max_chain is not None and self._max_chain < 0:
             raise ValueError(f'cem_gp_incremental_max_chain={chain}: a row count, or None')
         # conf.cem_gp_incremental_lockstep: update_models_multi appends to the models that have it, qualify and share the
-        # number of new rows in ONE sx_gp_append_multi call (`_append_lockstep`); off: model by model
+        # number of new rows in ONE sx_gp_append_multi call (`_append_lockstep`); off: model by model.  With conf.cem_gp_window
+        # the models that overflow their windows by the same number of rows slide in ONE sx_gp_drop_multi and ONE
+        # sx_gp_append_multi call (`_slide_group`)
         self._lockstep = bool(getattr(conf, 'cem_gp_incremental_lockstep', False))
         if self._lockstep and not self._incremental:
             raise ValueError('cem_gp_incremental_lockstep needs cem_gp_incremental: there is nothing to append in lockstep '
@@ -391,14 +393,13 @@ class GpCemSSM(CemSSM):
         self._appended += k
         return True
 
-    def _slide_rows(self, x: Tensor, y: Tensor) -> Tuple[int, int]:
-        """(r, k) where the update to (x, y) (device, contiguous, longer than the window) may slide the installed fit: its r
-        oldest rows dropped and the last k rows of (x, y) appended; (0, 0): a full fit of the last m rows.  `_append_rows`'
-        conditions, with the row comparison made against the tail of the fitted rows (the dropped ones no longer matter)."""
+    def _slide_rows_host(self, x: Tensor) -> Tuple[int, int]:
+        """`_slide_rows` but for the comparison of the kept fitted rows: every check that the host decides without reading
+        from the device."""
         if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
                 and self._fit_state is not None and self._subset_idx is None):
             return 0, 0
-        fit_x, fit_y = self._buffers[0], self._fit_state[0]
+        fit_x = self._buffers[0]
         n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
         r = n + k - self._window
         if not (1 <= k <= MAX_APPEND_ROWS and 1 <= r <= min(MAX_SLIDE_ROWS, MAX_DROP_ROWS) and r < n):
@@ -407,6 +408,16 @@ class GpCemSSM(CemSSM):
             return 0, 0
         if x.device != fit_x.device or self._fit_ws[1].size(1) != n or not self._hyper_unchanged():
             return 0, 0
+        return r, k
+
+    def _slide_rows(self, x: Tensor, y: Tensor) -> Tuple[int, int]:
+        """(r, k) where the update to (x, y) (device, contiguous, longer than the window) may slide the installed fit: its r
+        oldest rows dropped and the last k rows of (x, y) appended; (0, 0): a full fit of the last m rows.  `_append_rows`'
+        conditions, with the row comparison made against the tail of the fitted rows (the dropped ones no longer matter)."""
+        r, k = self._slide_rows_host(x)
+        if r == 0:
+            return 0, 0
+        fit_x, fit_y, n = self._buffers[0], self._fit_state[0], x.size(0) - k
         # the kept fitted rows themselves, compared where they live
         if not (torch.equal(x[r:n], fit_x[r:]) and torch.equal(y[r:n], fit_y[r:])):
             return 0, 0
@@ -420,16 +431,17 @@ class GpCemSSM(CemSSM):
         start = self._drop(y_new[:n - r].contiguous(), r)
         return self._append(x_new, y_new, k, start=start)
 
-    def _update_window(self, x_train: Tensor, y_train: Tensor, may_append: bool) -> None:
+    def _update_window(self, x_train: Tensor, y_train: Tensor, may_append: bool, slide: Optional[Tuple[int, int]] = None) -> None:
         """conf.cem_gp_window: the update to more rows than the window holds.  The stored data are trimmed to the last m rows;
-        the model slides where it may and is fitted on exactly those rows where it may not."""
+        the model slides where it may and is fitted on exactly those rows where it may not.  slide: `_slide_rows`' answer
+        (r, k) where the caller has it already (`_append_lockstep`), so that it is not asked for again."""
         _lib.require_gpu(x_train, 'train_x')
         _lib.require_gpu(y_train, 'train_y')
         m = self._window
         self._x_train, self._y_train = x_train[-m:], y_train[-m:]
         if may_append:
             x, y = x_train.detach().contiguous(), y_train.detach().contiguous()
-            r, k = self._slide_rows(x, y)
+            r, k = slide if slide is not None else self._slide_rows(x, y)
             if r and self._slide(x, y, r, k):
                 return
         self._update_model(self._x_train, self._y_train, may_append=False)
@@ -768,6 +780,15 @@ class _LockstepBuffers:
         self.ws: Optional[Tensor] = None
         self.host_table: Optional[Tensor] = None
         self.table: Optional[Tensor] = None
+        self._drop: Optional['_LockstepBuffers'] = None
+
+    @property
+    def drop(self) -> '_LockstepBuffers':
+        """The same three for the lockstep drop of a slide (`_slide_group`): its table is still being copied when the append's
+        is written, so the two calls do not share one."""
+        if self._drop is None:
+            self._drop = _LockstepBuffers()
+        return self._drop
 
     def workspace(self, nbytes: int, dev) -> Tensor:
         if self.ws is None or self.ws.numel() * 8 < nbytes or self.ws.device != dev:
@@ -782,20 +803,37 @@ class _LockstepBuffers:
         return self.host_table[:nbytes], self.table[:nbytes]
 
 
-def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k: int) -> None:
+def _cut(ws: Tensor, sizes: List[int]) -> List[int]:
+    """the problems' workspaces (device addresses) cut from one allocation; each size is a multiple of 8 bytes"""
+    ptrs, at = [], ws.data_ptr()
+    for nbytes in sizes:
+        ptrs.append(at)
+        at += nbytes
+    return ptrs
+
+
+def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k: int, data=None, start=None,
+                  status: Optional[Tensor] = None) -> None:
     """`_update_appending` of E >= 2 models that append k rows each, with ONE sx_gp_append_table + sx_gp_append_multi (six
     launches for all of them) and one host read of the E status words and E x n_s log-determinants; then, per model, the
     pack and install of `GpCemSSM._append`.  Model e's state afterwards equals, bit for bit, what its own update_model
     leaves.  A model whose Schur complement is not positive definite is fitted in full, alone, after the others have been
-    installed (and raises there as it always did)."""
+    installed (and raises there as it always did).
+    merged[e]: the training set model e stores.  data[e]: the rows (x, y) (device, contiguous) whose last k are appended and
+    which the model is then fitted on; merged[e] by default.  start[e]: (linv, alpha, logdet) of data[e]'s first rows, to
+    append to in place of the installed fit, and `status` [E] the words of the call that made them, which this call shares
+    (`_slide_group`), as `GpCemSSM._append(..., start=)` does for one model."""
     lib = _lib.lib()
     E, lead = len(ssms), ssms[0]
     n_s = lead.num_states
-    data = []
-    for m, (train_x, train_y) in zip(ssms, merged):
-        _lib.require_gpu(train_x, 'train_x')
-        _lib.require_gpu(train_y, 'train_y')
-        data.append((train_x.detach().contiguous(), train_y.detach().contiguous()))
+    if data is None:
+        data = []
+        for m, (train_x, train_y) in zip(ssms, merged):
+            _lib.require_gpu(train_x, 'train_x')
+            _lib.require_gpu(train_y, 'train_y')
+            data.append((train_x.detach().contiguous(), train_y.detach().contiguous()))
+    if start is None:
+        start = [(m._fit_ws[1], m._alpha, m._fit_state[1]) for m in ssms]
     dev = data[0][0].device
     models = (_lib.SxGpModel * E)(*[m._fit_struct(x) for m, (x, _) in zip(ssms, data)])
     sizes = [int(lib.sx_gp_append_workspace_bytes(n_s, x.size(0), k)) for x, _ in data]
@@ -804,19 +842,16 @@ def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k
     if lead._lockstep_bufs is None:
         lead._lockstep_bufs = _LockstepBuffers()
     bufs = lead._lockstep_bufs
-    ws = bufs.workspace(sum(sizes), dev)
-    ws_ptrs, at = [], ws.data_ptr()
-    for nbytes in sizes:            # (each a multiple of 8 bytes)
-        ws_ptrs.append(at)
-        at += nbytes
+    ws_ptrs = _cut(bufs.workspace(sum(sizes), dev), sizes)
     linv = [torch.empty((n_s, x.size(0), x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
     alpha = [torch.empty((n_s, x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
     logdet = torch.empty((E, n_s), dtype=torch.float64, device=dev)
-    status = torch.zeros(E, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.zeros(E, dtype=torch.int32, device=dev)
     host_table, table = bufs.tables(int(lib.sx_gp_append_table_bytes(E)), dev)
     arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
-    _lib.check(lib.sx_gp_append_table(models, E, k, arr([y for _, y in data]), arr([m._fit_ws[1] for m in ssms]),
-                                      arr([m._alpha for m in ssms]), arr([m._fit_state[1] for m in ssms]), arr(linv),
+    _lib.check(lib.sx_gp_append_table(models, E, k, arr([y for _, y in data]), arr([st[0] for st in start]),
+                                      arr([st[1] for st in start]), arr([st[2] for st in start]), arr(linv),
                                       arr(alpha), arr(list(logdet)), _lib.ptr(status), (ctypes.c_void_p * E)(*ws_ptrs),
                                       (ctypes.c_int64 * E)(*sizes), ctypes.c_void_p(host_table.data_ptr())),
                'sx_gp_append_table')
@@ -840,12 +875,66 @@ def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k
             m._update_model(*merged[e], may_append=False)
 
 
+def _slide_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], r: int, k: int) -> None:
+    """`GpCemSSM._update_window` of E >= 2 windowed models that each drop their r oldest fitted rows and append k: ONE
+    sx_gp_drop_table + sx_gp_drop_multi (seven launches for all of them) into fresh per-model buffers, then `_append_group`
+    onto those outputs -- ONE sx_gp_append_table + sx_gp_append_multi, sharing the E status words, so that its one host
+    read decides for both calls, as the single-model slide shares its word.  The stored data are trimmed to the last m
+    rows; per model the pack and install of `GpCemSSM._slide` on the rows x[r:].  Model e's state afterwards equals, bit for
+    bit, what its own update_model leaves.  A model that either call finds not positive definite gets the full fit of its
+    last m rows, alone, after the others have been installed; nothing is packed from its outputs.
+    merged[e]: the untrimmed training set (stored rows, then the new ones)."""
+    lib = _lib.lib()
+    E, lead = len(ssms), ssms[0]
+    n_s = lead.num_states
+    stored, data, kept_y = [], [], []
+    for m, (train_x, train_y) in zip(ssms, merged):
+        _lib.require_gpu(train_x, 'train_x')
+        _lib.require_gpu(train_y, 'train_y')
+        stored.append((train_x[-m._window:], train_y[-m._window:]))
+        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
+        x_new, y_new = x[r:].contiguous(), y[r:].contiguous()
+        data.append((x_new, y_new))
+        kept_y.append(y_new[:m._buffers[0].size(0) - r].contiguous())
+    dev = data[0][0].device
+    n_old = [m._fit_ws[1].size(1) for m in ssms]
+    sizes = [int(lib.sx_gp_drop_workspace_bytes(n_s, n, r)) for n in n_old]
+    if min(sizes) < 0:
+        raise _lib.SxError('sx_gp_drop_workspace_bytes: bad argument')
+    if lead._lockstep_bufs is None:
+        lead._lockstep_bufs = _LockstepBuffers()
+    bufs = lead._lockstep_bufs.drop
+    ws_ptrs = _cut(bufs.workspace(sum(sizes), dev), sizes)
+    linv = [torch.empty((n_s, n - r, n - r), dtype=torch.float64, device=dev) for n in n_old]
+    alpha = [torch.empty((n_s, n - r), dtype=torch.float64, device=dev) for n in n_old]
+    logdet = torch.empty((E, n_s), dtype=torch.float64, device=dev)
+    status = torch.zeros(E, dtype=torch.int32, device=dev)
+    host_table, table = bufs.tables(int(lib.sx_gp_drop_table_bytes(E)), dev)
+    arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
+    n_arr = (ctypes.c_int * E)(*n_old)
+    _lib.check(lib.sx_gp_drop_table(n_s, E, r, n_arr, arr(kept_y), arr([m._fit_ws[1] for m in ssms]), arr(linv), arr(alpha),
+                                    arr(list(logdet)), _lib.ptr(status), (ctypes.c_void_p * E)(*ws_ptrs),
+                                    (ctypes.c_int64 * E)(*sizes), ctypes.c_void_p(host_table.data_ptr())),
+               'sx_gp_drop_table')
+    table.copy_(host_table, non_blocking=True)
+    _lib.check(lib.sx_gp_drop_multi(n_s, E, r, n_arr, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_drop_multi')
+    # (the status words are not read here: where the drop is not positive definite the append runs on unspecified inputs,
+    # writes only its own outputs, and the shared word says so to the one read)
+    _append_group(ssms, stored, k, data=data, start=[(linv[e], alpha[e], logdet[e]) for e in range(E)], status=status)
+
+
 def _append_lockstep(ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor]) -> None:
     """The plain update of models of which some have conf.cem_gp_incremental_lockstep.  The models that have it are decided
     together: the host checks per model, then the device comparisons of all their fitted rows in one tensor and one read.
-    Those that qualify form groups by the number of new rows (and the device); a group of two or more appends in one call
-    (`_append_group`), a group of one and the qualifying models without the setting append alone, and the models that do not
-    qualify are fitted together first, as update_models_multi fits them."""
+    Those that qualify for an append form groups by the number of new rows (and the device); a group of two or more appends
+    in one call (`_append_group`), a group of one and the qualifying models without the setting append alone, and the models
+    that do not qualify are fitted together first, as update_models_multi fits them.
+    conf.cem_gp_window: a model with the setting whose update stays within its window is an append candidate like any other;
+    one whose update overflows it by r rows is a slide candidate, its comparison (the kept fitted rows) a flag of the same
+    tensor.  The sliding models form groups by (r, k, device): two or more slide in one call each of sx_gp_drop_multi and
+    sx_gp_append_multi (`_slide_group`), one slides alone (`GpCemSSM._slide`), and one that may not slide is fitted on its last
+    m rows with the rest.  (The windowed models WITHOUT the setting never get here: update_models_multi hands them to their
+    own update_model.)"""
     decided: List[Optional[Tuple[Tensor, Tensor]]] = [None] * len(ssms)
     cands, flags = [], []
     for i, (m, new_x, new_y) in enumerate(zip(ssms, xs, ys)):
@@ -856,29 +945,48 @@ def _append_lockstep(ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor])
         if merged is None:
             continue
         x, y = merged[0].detach().contiguous(), merged[1].detach().contiguous()
+        if m._window is not None and x.size(0) > m._window:
+            r, k = m._slide_rows_host(x)
+            if r == 0:
+                continue
+            n = x.size(0) - k
+            cands.append((i, (r, k), merged))
+            flags.append((x[r:n] == m._buffers[0][r:]).all() & (y[r:n] == m._fit_state[0][r:]).all())
+            continue
         k = m._append_rows_host(x)
         if k == 0:
             continue
         n = x.size(0) - k
-        cands.append((i, k, merged))
+        cands.append((i, (0, k), merged))
         flags.append((x[:n] == m._buffers[0]).all() & (y[:n] == m._fit_state[0]).all())
-    groups: Dict[Tuple[int, Any], List[int]] = {}
+    groups: Dict[Tuple[int, int, Any], List[int]] = {}
     if cands:
         same = torch.stack(flags).cpu()                                # the decision's one read
-        for (i, k, merged), ok in zip(cands, same):
+        for (i, (r, k), merged), ok in zip(cands, same):
             if bool(ok):
                 decided[i] = merged
-                groups.setdefault((k, merged[0].device), []).append(i)
+                groups.setdefault((r, k, merged[0].device), []).append(i)
     rest = [i for i, a in enumerate(decided) if a is None]
     if rest:
         update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest], _decided=True)
     grouped = set()
-    for (k, _), members in groups.items():
+    slides = {}
+    for (r, k, _), members in groups.items():
+        if r:
+            slides.update({i: (r, k) for i in members})
         if len(members) >= 2:
-            _append_group([ssms[i] for i in members], [decided[i] for i in members], k)
+            picked = [ssms[i] for i in members], [decided[i] for i in members]
+            if r:
+                _slide_group(*picked, r, k)
+            else:
+                _append_group(*picked, k)
             grouped.update(members)
     for i, a in enumerate(decided):
-        if a is not None and i not in grouped:
+        if a is None or i in grouped:
+            continue
+        if i in slides:
+            ssms[i]._update_window(*a, may_append=True, slide=slides[i])
+        else:
             ssms[i]._update_appending(*a)
 
 
@@ -901,15 +1009,24 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
     conf.cem_gp_incremental: the models whose plain update appends to their fit do so one by one (sx_gp_append), or, with
     conf.cem_gp_incremental_lockstep, those that add the same number of rows in one sx_gp_append_multi call
     (`_append_lockstep`); either way each ends in the state its own update_model leaves, bit for bit.
-    conf.cem_gp_window: a windowed model is handed to its own update_model (there is no lockstep drop).
-    (_decided: the caller has found that none of these models appends.)"""
+    conf.cem_gp_window: a windowed model is handed to its own update_model -- unless it has conf.cem_gp_incremental_lockstep
+    and the update is a plain one (no opt_hyp, no replace_old).  Then it takes part in the lockstep update: below its window
+    it appends with the others, and the windowed models that overflow their windows by the same r rows with the same k new
+    ones slide together, ONE sx_gp_drop_multi and ONE sx_gp_append_multi for all of them and two host reads whatever their
+    number (`_slide_group`); one that may not slide is fitted on its last m rows with the models that are fitted.  Every
+    model's stored data are trimmed to its window, and every model ends in the state its own update_model leaves, bit for
+    bit.
+    (_decided: the caller has found that none of these models appends or slides.)"""
     ssms, xs, ys = list(ssms), list(xs), list(ys)
     if not len(ssms) == len(xs) == len(ys):
         raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
     if not ssms:
         return
-    # conf.cem_gp_window: a windowed model trims its data and slides by itself; the others go on together
-    windowed = [i for i, m in enumerate(ssms) if getattr(m, '_window', None) is not None]
+    # conf.cem_gp_window: a windowed model trims its data and slides by itself; the others go on together -- with them the
+    # windowed models that have conf.cem_gp_incremental_lockstep, where the update is a plain one
+    plain = not opt_hyp and not replace_old
+    windowed = [i for i, m in enumerate(ssms)
+                if getattr(m, '_window', None) is not None and not (plain and getattr(m, '_lockstep', False))]
     if windowed:
         rest = [i for i in range(len(ssms)) if i not in windowed]
         if rest:
@@ -945,6 +1062,8 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
         assert_shape(y, (n, m.num_states))
         if not replace_old and m._x_train is not None and m._y_train is not None:
             x, y = torch.cat((m._x_train, x), dim=0), torch.cat((m._y_train, y), dim=0)
+        if m._window is not None:
+            x, y = x[-m._window:], y[-m._window:]     # (a windowed lockstep model that neither appends nor slides)
         m._check_pool_size(x.size(0))
         _lib.require_gpu(x, 'train_x')
         _lib.require_gpu(y, 'train_y')

@@ -1,0 +1,284 @@
+"""GPU: the lockstep drop -- sx_gp_drop_table / sx_gp_drop_multi, the k oldest rows removed from each of E fitted exact GPs in
+one launch sequence -- through the C ABI and through update_models_multi with conf.cem_gp_window and
+conf.cem_gp_incremental_lockstep.
+
+The contract is bit-equality: problem e's linv, alpha and logdet are those of sx_gp_drop for model e alone.  So every case
+here is compared with `torch.equal` against the single entry, which tests/test_gpu_gp_drop.py checks against the long-double
+factorisation; one call is checked against that truth directly, in the unit and at the allowance of that file.  The cases
+mix sizes inside one call, so that the early exits and the per-problem extents are exercised: m = 1, 16 and 65 (below one
+prefetch chunk of the table kernel, exactly one, and across a 64-block), m = 191 (past the 96-row ring), every compiled
+stage count in use (KB = 1, 2, 16, 64), and m = 2 beside m = 309, where most workgroups of the small problem return at
+once.  The problems are those of tests/warm_path_reference.py; the single-model results are computed once per problem and
+shared.  Every output buffer and every workspace ends in a canary."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import drop_reference as D
+import test_gpu_gp_append as SA
+import test_gpu_gp_append_multi as AM
+import test_gpu_gp_drop as SD
+import test_gpu_warm_path as WP
+import warm_path_reference as R
+from safe_exploration_amd import _lib
+
+pytestmark = pytest.mark.gpu
+DEV = WP.DEV
+QUANTITIES = SA.QUANTITIES
+CASES = (((2, 17, 66), 1), ((65, 97, 193), 2), ((40, 130, 161), 16), ((66, 130, 346), 37), ((65, 161), 64), ((130,), 37))  # (N_e; k)
+SHAPES = ((1, 1), (2, 1), (4, 2))
+WIDE = ((1, 5),)
+RATIOS = (1e-2, 1e-6)
+GRID = [(ns, k, sh) for ns, k in CASES for sh in SHAPES] + [(ns, k, sh) for ns, k in (CASES[0], CASES[3]) for sh in WIDE]
+NOT_PD = _lib.SX_STATUS_NOT_PD
+
+_singles = {}
+
+
+def single(shape, n, k, ratio, rows=None):
+    """(p, fit of p's first n rows, the kept rows' targets on the device, sx_gp_drop of the first k rows): computed once per
+    problem, never modified.  rows: the rows of p (n by default; a slide's problem has the new rows behind)."""
+    key = (shape, n, k, ratio, rows)
+    if key not in _singles:
+        p = R.problem(*shape, rows if rows is not None else n, ratio)
+        old = SA.fit_head(p, n)
+        y = WP._dev(p.Y[k:n])
+        b = SD.run_drop(p.n_s, old['linv'].t, y, k)
+        assert int(b['status'].t.item()) == 0
+        _singles[key] = (p, old, y, b)
+    return _singles[key]
+
+
+def run_drop_multi(items, k, status=None):
+    """sx_gp_drop_table + sx_gp_drop_multi of `items` = [(linv_old device [n_s x N x N], y_kept device [m x n_s])].  Returns
+    (per-problem canaried buffers, the status Buf [E])."""
+    lib = _lib.lib()
+    E, n_s = len(items), items[0][0].size(0)
+    n_old = [linv.size(1) for linv, _ in items]
+    sizes = [int(lib.sx_gp_drop_workspace_bytes(n_s, n, k)) for n in n_old]
+    assert min(sizes) > 0 and all(s % 8 == 0 for s in sizes)
+    bufs = [dict(linv=WP.Buf(n_s, n - k, n - k), alpha=WP.Buf(n_s, n - k), logdet=WP.Buf(n_s), ws=WP.Buf(s // 8))
+            for n, s in zip(n_old, sizes)]
+    status = status if status is not None else WP.Buf(E, dtype=torch.int32)
+    arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
+    n_arr = (ctypes.c_int * E)(*n_old)
+    host = ctypes.create_string_buffer(int(lib.sx_gp_drop_table_bytes(E)))
+    _lib.check(lib.sx_gp_drop_table(n_s, E, k, n_arr, arr([y for _, y in items]), arr([linv for linv, _ in items]),
+                                    arr([b['linv'].t for b in bufs]), arr([b['alpha'].t for b in bufs]),
+                                    arr([b['logdet'].t for b in bufs]), _lib.ptr(status.t), arr([b['ws'].t for b in bufs]),
+                                    (ctypes.c_int64 * E)(*sizes), host), 'sx_gp_drop_table')
+    table = torch.tensor(np.frombuffer(host.raw, dtype=np.uint8), device=DEV)
+    _lib.check(lib.sx_gp_drop_multi(n_s, E, k, n_arr, _lib.ptr(table), _lib.stream_ptr(torch.device(DEV))), 'sx_gp_drop_multi')
+    torch.cuda.synchronize()
+    return bufs, status
+
+
+def _intact(bufs, status, where):
+    assert status.intact(), f'{where}: the canary after `status` was overwritten'
+    for e, b in enumerate(bufs):
+        for key, buf in b.items():
+            assert buf.intact(), f'{where}: the canary after `{key}` of problem {e} was overwritten'
+
+
+def _same_bits(b, want, where):
+    for q in QUANTITIES:
+        assert torch.equal(b[q].t, want[q].t), f'{where}: `{q}` differs from the single call\'s'
+
+
+def _items(alone):
+    return [(old['linv'].t, y) for _, old, y, _ in alone]
+
+
+# ---- a. every problem of a call is its single call, bit for bit ----------------------------------------------------------------
+
+@pytest.mark.parametrize('ratio', RATIOS)
+@pytest.mark.parametrize('ns,k,shape', GRID, ids=lambda v: str(v).replace(' ', ''))
+def test_every_problem_is_its_single_call(ns, k, shape, ratio):
+    alone = [single(shape, n, k, ratio) for n in ns]
+    before = [{q: old[q].t.clone() for q in QUANTITIES} for _, old, _, _ in alone]
+    bufs, status = run_drop_multi(_items(alone), k)
+    where = f'{shape} N={ns}-{k} ratio={ratio:g}'
+    _intact(bufs, status, where)
+    assert status.t.tolist() == [0] * len(ns), where
+    for e, (b, (p, old, y, want)) in enumerate(zip(bufs, alone)):
+        _same_bits(b, want, f'{where} problem {e}')
+        assert int(torch.count_nonzero(torch.triu(b['linv'].t, 1))) == 0, f'{where} problem {e}: linv is not lower triangular'
+        # the inputs are untouched
+        assert all(old[q].intact() and torch.equal(old[q].t, before[e][q]) for q in QUANTITIES), (where, e)
+        assert torch.equal(y, WP._dev(p.Y[k:ns[e]])), (where, e)
+
+
+def test_repeated_permuted_and_partial_calls_give_the_same_bits():
+    ns, k, shape = (66, 130, 346), 37, (2, 1)
+    alone = [single(shape, n, k, 1e-2) for n in ns]
+    items = _items(alone)
+    first, s1 = run_drop_multi(items, k)
+    again, s2 = run_drop_multi(items, k)
+    assert s1.t.tolist() == s2.t.tolist() == [0] * 3
+    for b, c in zip(first, again):
+        _same_bits(c, b, 'the same call again')
+    for perm in ((2, 1, 0), (1, 2, 0)):
+        got, s = run_drop_multi([items[i] for i in perm], k)
+        _intact(got, s, f'order {perm}')
+        assert s.t.tolist() == [0] * 3
+        for slot, i in enumerate(perm):
+            _same_bits(got[slot], first[i], f'order {perm} problem {i}')
+    # ... and a problem is independent of which others share the call
+    got, s = run_drop_multi([items[2], items[0]], k)
+    _same_bits(got[0], first[2], 'a pair')
+    _same_bits(got[1], first[0], 'a pair')
+
+
+# ---- b. against the long-double factorisation, at the single entry's allowance ----------------------------------------------------
+
+def test_one_call_against_the_long_double_factorisation():
+    """(2,1), N = 66 and 130, k = 37, noise / outputscale = 1e-6: error / max(LAPACK's error, 8 eps) <= 32 on linv, alpha and
+    logdet against the long-double factorisation of the kept rows, the unit and the allowance of
+    test_gpu_gp_drop.test_drop_products (WP.forward prints each figure before it asserts)"""
+    ns, k, shape, ratio = (66, 130), 37, (2, 1), 1e-6
+    alone = [single(shape, n, k, ratio) for n in ns]
+    bufs, status = run_drop_multi(_items(alone), k)
+    assert status.t.tolist() == [0, 0]
+    for b, (p, _, _, _) in zip(bufs, alone):
+        kept, case = D.tail(p, k), SD._case(p, k)
+        SA._healthy({q: b[q] for q in QUANTITIES}, case)
+        WP.forward('sx_gp_drop_multi', case, kept, QUANTITIES, {q: b[q].np() for q in QUANTITIES})
+
+
+# ---- c. not positive definite: the problem's own word, and nothing else -----------------------------------------------------------
+
+def test_nan_in_w11_keeps_to_its_own_problem():
+    """N = 65, 70 and 130, k = 5: a NaN in W11 of the middle problem"""
+    k = 5
+    healthy = [single((2, 1), n, k, 1e-2) for n in (65, 130)]
+    p, old, y, _ = single((2, 1), 70, k, 1e-2)
+    spoiled = old['linv'].t.clone()
+    spoiled[1, 3, 1] = float('nan')
+    items = [_items(healthy)[0], (spoiled, y), _items(healthy)[1]]
+    bufs, status = run_drop_multi(items, k)
+    _intact(bufs, status, 'NaN in W11')
+    assert status.t.tolist() == [0, NOT_PD, 0]
+    _same_bits(bufs[0], healthy[0][3], 'before the bad problem')
+    _same_bits(bufs[2], healthy[1][3], 'after the bad problem')
+    # the next call is unaffected
+    good, s = run_drop_multi([items[0], items[2]], k)
+    assert s.t.tolist() == [0, 0]
+    _same_bits(good[0], healthy[0][3], 'the next call')
+    _same_bits(good[1], healthy[1][3], 'the next call')
+    # the words are or-ed into: a set bit stays, in its own word
+    kept, s = run_drop_multi([items[2], items[0], items[0]], k, status=status)
+    assert s.t.tolist() == [0, NOT_PD, 0]
+    _same_bits(kept[1], healthy[0][3], 'beside a word that was set')
+
+
+# ---- d. the slide: sx_gp_append_multi takes sx_gp_drop_multi's outputs and its status words --------------------------------------
+
+def test_slide_chain_is_the_single_slides_bit_for_bit():
+    """(2,1), N = 97, 130 and 70, r = 3 rows dropped and k = 3 appended: sx_gp_drop_multi then sx_gp_append_multi on its outputs
+    with the status words shared, against sx_gp_drop then sx_gp_append of each model alone"""
+    ns, r, k = (97, 130, 70), 3, 3
+    alone = [single((2, 1), n, r, 1e-2, rows=n + k) for n in ns]
+    wins = [D.window(p, r, n + k) for (p, _, _, _), n in zip(alone, ns)]
+    want = []
+    for (p, old, y, _), win, n in zip(alone, wins, ns):
+        dropped = SD.run_drop(2, old['linv'].t, y, r)
+        b = SA.run_append(win, n - r, SA._old(dropped), status=dropped['status'])
+        assert int(b['status'].t.item()) == 0
+        want.append(b)
+    dropped, status = run_drop_multi(_items(alone), r)
+    bufs, status = AM.run_append_multi([(win, n - r, SA._old(d)) for win, n, d in zip(wins, ns, dropped)], status=status)
+    _intact(dropped, status, 'slide: the drop')
+    _intact(bufs, status, 'slide: the append')
+    assert status.t.tolist() == [0, 0, 0]
+    for e, (b, w) in enumerate(zip(bufs, want)):
+        _same_bits(b, w, f'slide problem {e}')
+
+
+# ---- e. through Python -----------------------------------------------------------------------------------------------------------
+
+class _Conf:
+    device, exact_gp_kernel, exact_gp_training_iterations, cem_gp_incremental = DEV, 'rbf', 0, True
+
+    def __init__(self, window, lockstep):
+        self.cem_gp_window, self.cem_gp_incremental_lockstep = window, lockstep
+
+
+def _gps(probs, windows, first, lockstep):
+    from safe_exploration_amd.ssm_cem.gp_ssm_cem import GpCemSSM
+    out = []
+    for p, w, n in zip(probs, windows, first):
+        ssm = GpCemSSM(_Conf(w, lockstep), p.n_s, p.n_u)
+        ssm.set_hyperparameters(p.ls, p.s, p.noise)
+        ssm.update_model(WP._dev(p.X[:n]), WP._dev(p.Y[:n]))
+        out.append(ssm)
+    return out
+
+
+def test_lockstep_slides_equal_single_slides_bit_for_bit(monkeypatch):
+    """Three (2,1) models with windows 40, 97 and 130 start 2 rows below them and get one row each, twelve times: two lockstep
+    appends, then ten lockstep slides; update_models_multi with the setting on against update_model on twin models"""
+    from safe_exploration_amd.ssm_cem.gp_ssm_cem import update_models_multi
+    windows, steps = (40, 97, 130), 12
+    first = [w - 2 for w in windows]
+    probs = [R.problem(2, 1, n + steps) for n in first]
+    z = WP._dev(R.queries(probs[0], 7, far=False))
+    alone, together = _gps(probs, windows, first, False), _gps(probs, windows, first, True)
+    spy = SA._Spy(_lib.lib())
+    monkeypatch.setattr(_lib, '_lib', spy)
+    for step in range(steps):
+        xs = [WP._dev(p.X[n + step:n + step + 1]) for p, n in zip(probs, first)]
+        ys = [WP._dev(p.Y[n + step:n + step + 1]) for p, n in zip(probs, first)]
+        for m, x, y in zip(alone, xs, ys):
+            m.update_model(x, y)
+        spy.calls.clear()
+        update_models_multi(together, xs, ys)
+        got = tuple(spy.calls[n] for n in ('sx_gp_drop_multi', 'sx_gp_append_multi', 'sx_gp_drop', 'sx_gp_append', 'sx_gp_fit',
+                                           'sx_gp_fit_multi', 'sx_gp_pack'))
+        assert got == ((0, 1, 0, 0, 0, 0, 3) if step < 2 else (1, 1, 0, 0, 0, 0, 3)), step
+        # (the packed buffers are compared on the elements sx_gp_pack writes: AM._pack_writes)
+        for e, (a, b) in enumerate(zip(alone, together)):
+            assert b._appended == step + 1 and b.x_train.size(0) == min(windows[e], first[e] + step + 1)
+            AM._same_state(a, b, z, f'step {step} model {e}')
+
+
+def test_safempc_action_after_lockstep_slides():
+    """two pendulum solvers with full windows of 64 rows, slid twice in lockstep, against twins slid one by one"""
+    from safe_exploration_amd import problems
+    from safe_exploration_amd.safempc_cem import MpcResult
+    from safe_exploration_amd.ssm_cem.gp_ssm_cem import update_models_multi
+
+    class Conf:
+        mpc_time_horizon, cem_num_rollouts, cem_num_elites, cem_num_iterations, cem_init_std = 5, 128, 12, 3, 0.2
+        device, use_state_constraint, use_prior_model = DEV, True, True
+        exact_gp_training_iterations, exact_gp_kernel = 0, 'rbf'
+        plot_cem_optimisation = plot_cem_terminal_states = False
+        cem_gp_incremental, cem_gp_window = True, 64
+
+    class Lockstep(Conf):
+        cem_gp_incremental_lockstep = True
+
+    specs = [problems.pendulum(n_train=64, seed=s) for s in (0, 1)]
+    together = [problems.make_solver(spec, Lockstep())[0] for spec in specs]
+    alone = [problems.make_solver(spec, Conf())[0] for spec in specs]
+    rng = np.random.default_rng(5)
+    for _ in range(2):
+        new = [(WP._dev(rng.uniform(-0.3, 0.3, size=(1, 3))), WP._dev(rng.uniform(-0.05, 0.05, size=(1, 2)))) for _ in specs]
+        for solver, (x, y) in zip(alone, new):
+            solver._ssm.update_model(x, y)
+        update_models_multi([s._ssm for s in together], [x for x, _ in new], [y for _, y in new])
+    for a, b in zip(alone, together):
+        assert a._ssm._appended == b._ssm._appended == 2 and b._ssm.x_train.size(0) == 64
+        assert torch.equal(a._ssm._alpha, b._ssm._alpha) and torch.equal(a._ssm.x_train, b._ssm.x_train)
+    assert together[0]._ssm._lockstep_bufs is not None and together[0]._ssm._lockstep_bufs.drop.ws is not None
+    noise = rng.normal(size=(Conf.cem_num_iterations, Conf.cem_num_rollouts, Conf.mpc_time_horizon, 1))
+    x0 = np.array([0.02, -0.03])
+    actions = []
+    for solver in (together[0], alone[0]):
+        it = iter(noise)
+        solver._solver().sample_noise = lambda episodes=1, it=it: WP._dev(next(it)[None])
+        action, result = solver.get_action(x0)
+        assert result == MpcResult.FOUND_SOLUTION
+        actions.append(action)
+    np.testing.assert_allclose(actions[0], actions[1], rtol=0, atol=1e-9)
