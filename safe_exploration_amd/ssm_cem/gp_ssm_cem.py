@@ -13,7 +13,7 @@ Hyper-parameters follow gpytorch's parameterisation (softplus of a raw parameter
 1e-4 floor).  gpytorch is not available to check these defaults against: "parity unpinned" (DESIGN.md).
 """
 import ctypes
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -40,6 +40,49 @@ MAX_SLIDE_ROWS = 16
 # conf.cem_gp_window_max_chain's default: the rows a windowed model appends and slides between two full fits.  The longest
 # chain measured on the device, at which W and alpha still stay within the fit's own error allowance
 WINDOW_MAX_CHAIN = 128
+
+
+# ---- what the single-model and the lockstep calls share -------------------------------------------------------------------------
+def _workspace_bytes(query, *args) -> int:
+    """`query(*args)`, the size query of a library entry (`lib.sx_..._workspace_bytes`); a negative answer is a bad argument."""
+    nbytes = int(query(*args))
+    if nbytes < 0:
+        raise _lib.SxError(f'{getattr(query, "__name__", "workspace_bytes")}: bad argument')
+    return nbytes
+
+
+def _grown(ws: Optional[Tensor], nbytes: int, dev, slack: int = 0) -> Tensor:
+    """A workspace of at least nbytes on dev: `ws` where it is one already, else a new one with `slack` bytes to spare."""
+    if ws is None or ws.numel() * 8 < nbytes or ws.device != dev:
+        ws = torch.empty((nbytes + slack + 7) // 8, dtype=torch.float64, device=dev)
+    return ws
+
+
+def _ptr_array(ts: Sequence[Tensor]):
+    """the tensors' device addresses as the void* array the table entries take"""
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _outputs(n_s: int, ns: Sequence[int], dev, status: Optional[Tensor] = None):
+    """Fresh output buffers of a factor update of E = len(ns) problems, problem e with ns[e] rows: (linv [E] of [n_s x n x n],
+    alpha [E] of [n_s x n], logdet [E n_s] (problem e's n_s values at e n_s), status [E], zeroed).  status: the words of the
+    call before, which this one shares so that one read decides for both (a slide's drop and append)."""
+    linv = [torch.empty((n_s, n, n), dtype=torch.float64, device=dev) for n in ns]
+    alpha = [torch.empty((n_s, n), dtype=torch.float64, device=dev) for n in ns]
+    logdet = torch.empty(len(ns) * n_s, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(len(ns), dtype=torch.int32, device=dev)
+    return linv, alpha, logdet, status
+
+
+def _adam_grads(raw: Sequence[Tensor], grad: Tensor, n: int) -> None:
+    """Sets the gradients of the loss -sum_d mll_d / n on the raw parameters `raw` = (lengthscale, outputscale, noise) from
+    grad [n_s x (D + 2)] = d mll / d (lengthscale, outputscale, noise): d loss / d raw = -(1/n) d mll / d theta * sigmoid(raw)
+    (theta = softplus(raw) [+ floor])."""
+    d_in = grad.size(1) - 2
+    raw[0].grad = -(grad[:, :d_in] / n) * torch.sigmoid(raw[0].detach())
+    raw[1].grad = -(grad[:, d_in] / n) * torch.sigmoid(raw[1].detach())
+    raw[2].grad = -(grad[:, d_in + 1] / n) * torch.sigmoid(raw[2].detach())
 
 
 class GpCemSSM(CemSSM):
@@ -91,9 +134,9 @@ class GpCemSSM(CemSSM):
         if self._max_chain is not None and self._max_chain < 0:
             raise ValueError(f'cem_gp_incremental_max_chain={chain}: a row count, or None')
         # conf.cem_gp_incremental_lockstep: update_models_multi appends to the models that have it, qualify and share the
-        # number of new rows in ONE sx_gp_append_multi call (`_append_lockstep`); off: model by model.  With conf.cem_gp_window
+        # number of new rows in ONE sx_gp_append_multi call (`_increment_group`); off: model by model.  With conf.cem_gp_window
         # the models that overflow their windows by the same number of rows slide in ONE sx_gp_drop_multi and ONE
-        # sx_gp_append_multi call (`_slide_group`)
+        # sx_gp_append_multi call
         self._lockstep = bool(getattr(conf, 'cem_gp_incremental_lockstep', False))
         if self._lockstep and not self._incremental:
             raise ValueError('cem_gp_incremental_lockstep needs cem_gp_incremental: there is nothing to append in lockstep '
@@ -236,27 +279,6 @@ class GpCemSSM(CemSSM):
             return None
         return torch.cat((self._x_train, new_x), dim=0), torch.cat((self._y_train, new_y), dim=0)
 
-    def _appends_next(self, new_x: Tensor, new_y: Tensor):
-        """Would update_model(new_x, new_y) append to the installed fit?  None, or the merged training set (train_x,
-        train_y) that update_model would store: the decision is made once here (the comparison of the fitted rows is a
-        device round trip) and `_update_appending` acts on it."""
-        merged = self._append_merged(new_x, new_y)
-        if merged is None:
-            return None
-        train_x, train_y = merged
-        if self._append_rows(train_x.detach().contiguous(), train_y.detach().contiguous()) == 0:
-            return None
-        return train_x, train_y
-
-    def _update_appending(self, train_x: Tensor, train_y: Tensor) -> None:
-        """update_model of the new rows behind `_appends_next`'s answer (train_x, train_y), without asking again."""
-        _lib.require_gpu(train_x, 'train_x')
-        _lib.require_gpu(train_y, 'train_y')
-        self._x_train, self._y_train = train_x, train_y
-        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
-        if not self._append(x, y, x.size(0) - self._buffers[0].size(0)):
-            self._update_model(train_x, train_y, may_append=False)
-
     def _selects(self, n: int) -> bool:
         """Is a pool of n points cut down to conf.cem_gp_subset_size before it is fitted?"""
         return self._subset_size is not None and n > self._subset_size
@@ -298,23 +320,33 @@ class GpCemSSM(CemSSM):
     def _hyper_state(self):
         return (self._raw_lengthscale, self._raw_outputscale, self._raw_noise, self._noise_floor)
 
-    def _append_rows_host(self, x: Tensor) -> int:
-        """`_append_rows` but for the comparison of the fitted rows: every check that the host decides without reading
-        from the device."""
+    def _increment_rows_host(self, x: Tensor) -> Tuple[int, int]:
+        """(r, k) where the update to the rows x (device, contiguous) may extend the installed fit by its last k rows after
+        dropping the r oldest fitted ones (conf.cem_gp_incremental; r > 0: a slide of conf.cem_gp_window), as far as the host
+        decides without reading from the device: all but the comparison of the kept fitted rows (`_compared`).  (0, 0): a
+        full fit.
+        One set of checks serves the append and the slide, and answers as the two separate ones would.  The limits on the
+        total (N + k within the fit's size, no subset selected from it) are the append's, asked where r = 0; a windowed model
+        below its window passes them as it always did, and a slide needs neither: a window excludes
+        conf.cem_gp_subset_size and holds at most MAX_TRAINING_POINTS rows, and the slid fit has exactly that many.  The
+        limits on r are the slide's; r > 0 exactly where the rows overflow the window."""
         if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
                 and self._fit_state is not None and self._subset_idx is None):
-            return 0
-        fit_x, (fit_y, _, hyper) = self._buffers[0], self._fit_state
+            return 0, 0
+        fit_x = self._buffers[0]
         n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
-        if not 1 <= k <= MAX_APPEND_ROWS or n + k > MAX_TRAINING_POINTS or self._selects(n + k):
-            return 0
+        r = 0 if self._window is None else max(0, n + k - self._window)
+        if not 1 <= k <= MAX_APPEND_ROWS:
+            return 0, 0
+        if r == 0 and (n + k > MAX_TRAINING_POINTS or self._selects(n + k)):
+            return 0, 0
+        if r > 0 and not (r <= min(MAX_SLIDE_ROWS, MAX_DROP_ROWS) and r < n):
+            return 0, 0
         if not self._chain_allows(k):
-            return 0
-        if x.device != fit_x.device or self._fit_ws[1].size(1) != n:
-            return 0
-        if not self._hyper_unchanged():
-            return 0
-        return k
+            return 0, 0
+        if x.device != fit_x.device or self._fit_ws[1].size(1) != n or not self._hyper_unchanged():
+            return 0, 0
+        return r, k
 
     def _chain_allows(self, k: int) -> bool:
         """May k more rows be appended (or slid) before the next full fit?"""
@@ -328,17 +360,32 @@ class GpCemSSM(CemSSM):
         now, hyper = self._hyper_state(), self._fit_state[2]
         return now[3] == hyper[3] and all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(now[:3], hyper[:3]))
 
-    def _append_rows(self, x: Tensor, y: Tensor) -> int:
-        """k, the rows by which (x, y) (device, contiguous) extend the installed fit where the update may append them
-        (conf.cem_gp_incremental); 0: a full fit."""
-        k = self._append_rows_host(x)
+    def _compared(self, x: Tensor, y: Tensor, r: int, k: int):
+        """The row blocks (new x, fitted x, new y, fitted y) whose pairwise equality makes (x, y) the installed fit less its r
+        oldest rows plus k new ones: the kept fitted rows themselves (the dropped ones no longer matter), compared where
+        they live."""
+        n = x.size(0) - k
+        fit_x, fit_y = self._buffers[0], self._fit_state[0]
+        if r:
+            fit_x, fit_y = fit_x[r:], fit_y[r:]
+        return x[r:n], fit_x, y[r:n], fit_y
+
+    def _increment_rows(self, x: Tensor, y: Tensor) -> Tuple[int, int]:
+        """`_increment_rows_host` and the comparison of the kept fitted rows, which reads from the device: (r, k) where the
+        update to the merged data (x, y) (on the device; any strides) may drop the r oldest fitted rows and append its
+        last k; (0, 0): a full fit."""
+        r, k = self._increment_rows_host(x)
         if k == 0:
-            return 0
-        fit_x, fit_y, n = self._buffers[0], self._fit_state[0], x.size(0) - k
-        # the fitted rows themselves, compared where they live
-        if not (torch.equal(x[:n], fit_x) and torch.equal(y[:n], fit_y)):
-            return 0
-        return k
+            return 0, 0
+        new_x, fit_x, new_y, fit_y = self._compared(x, y, r, k)
+        return (r, k) if torch.equal(new_x, fit_x) and torch.equal(new_y, fit_y) else (0, 0)
+
+    def _append_rows(self, x: Tensor, y: Tensor) -> int:
+        """k, the rows by which (x, y) (device) extend the installed fit where the update may append them
+        (conf.cem_gp_incremental); 0: a full fit.  `_increment_rows` where nothing is dropped, which is all a model without
+        a window can ask for."""
+        r, k = self._increment_rows(x, y)
+        return k if r == 0 else 0
 
     def _drop(self, y_kept: Tensor, r: int):
         """sx_gp_drop of the r oldest rows of the installed fit; y_kept: the kept rows' targets (device, contiguous).  Returns
@@ -346,119 +393,66 @@ class GpCemSSM(CemSSM):
         lib = _lib.lib()
         dev = y_kept.device
         n_s, n = self.num_states, self._fit_ws[1].size(1)
-        m = n - r
-        nbytes = int(lib.sx_gp_drop_workspace_bytes(n_s, n, r))
-        if nbytes < 0:
-            raise _lib.SxError('sx_gp_drop_workspace_bytes: bad argument')
-        if self._drop_ws is None or self._drop_ws.numel() * 8 < nbytes or self._drop_ws.device != dev:
-            self._drop_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        linv = torch.empty((n_s, m, m), dtype=torch.float64, device=dev)
-        alpha = torch.empty((n_s, m), dtype=torch.float64, device=dev)
-        logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = _workspace_bytes(lib.sx_gp_drop_workspace_bytes, n_s, n, r)
+        self._drop_ws = _grown(self._drop_ws, nbytes, dev)
+        (linv,), (alpha,), logdet, status = _outputs(n_s, (n - r,), dev)
         _lib.check(lib.sx_gp_drop(n_s, n, r, _lib.ptr(y_kept), _lib.ptr(self._fit_ws[1]), _lib.ptr(linv), _lib.ptr(alpha),
                                   _lib.ptr(logdet), _lib.ptr(status), _lib.ptr(self._drop_ws), nbytes, _lib.stream_ptr(dev)),
                    'sx_gp_drop')
         return linv, alpha, logdet, status
 
-    def _append(self, x: Tensor, y: Tensor, k: int, start=None) -> bool:
-        """sx_gp_append of the last k rows of (x, y) to the installed fit, into fresh buffers that become the fit workspace,
-        then the usual pack and install.  False (and nothing changed) where S is not positive definite.  start: `_drop`'s
-        answer for the first rows of (x, y), to append to in place of the installed fit (a slide); its status word is shared,
-        so that one read decides for both calls."""
+    def _increment(self, x: Tensor, y: Tensor, r: int, k: int) -> bool:
+        """The increment (r, k) of the installed fit to the rows x[r:] of (x, y) (device, contiguous) through the single-model
+        entries: sx_gp_drop of the r oldest fitted rows (r > 0: a slide), then sx_gp_append of the last k rows onto its
+        outputs (onto the installed fit where r = 0), into fresh buffers that become the fit workspace, and `_commit`.  The
+        two calls share one status word, so that one read decides for both.  False (and nothing changed) where either
+        answers SX_STATUS_NOT_PD."""
         lib = _lib.lib()
         dev = x.device
-        n_s, n2 = self.num_states, x.size(0)
-        linv_old, alpha_old, logdet_old = start[:3] if start is not None else (self._fit_ws[1], self._alpha, self._fit_state[1])
+        n_s = self.num_states
+        linv_old, alpha_old, logdet_old, status = self._fit_ws[1], self._alpha, self._fit_state[1], None
+        if r:
+            x, y = x[r:].contiguous(), y[r:].contiguous()
+            linv_old, alpha_old, logdet_old, status = self._drop(y[:self._buffers[0].size(0) - r].contiguous(), r)
+        n2 = x.size(0)
         m = self._fit_struct(x)
-        nbytes = int(lib.sx_gp_append_workspace_bytes(n_s, n2, k))
-        if nbytes < 0:
-            raise _lib.SxError('sx_gp_append_workspace_bytes: bad argument')
-        if self._append_ws is None or self._append_ws.numel() * 8 < nbytes or self._append_ws.device != dev:
-            self._append_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        linv = torch.empty((n_s, n2, n2), dtype=torch.float64, device=dev)
-        alpha = torch.empty((n_s, n2), dtype=torch.float64, device=dev)
-        logdet = torch.empty((n_s,), dtype=torch.float64, device=dev)
-        status = start[3] if start is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = _workspace_bytes(lib.sx_gp_append_workspace_bytes, n_s, n2, k)
+        self._append_ws = _grown(self._append_ws, nbytes, dev)
+        (linv,), (alpha,), logdet, status = _outputs(n_s, (n2,), dev, status)
         _lib.check(lib.sx_gp_append(ctypes.byref(m), n2 - k, _lib.ptr(y), _lib.ptr(linv_old), _lib.ptr(alpha_old),
                                     _lib.ptr(logdet_old), _lib.ptr(linv), _lib.ptr(alpha), _lib.ptr(logdet),
                                     _lib.ptr(status), _lib.ptr(self._append_ws), nbytes, _lib.stream_ptr(dev)), 'sx_gp_append')
         # (the status first: where S is not positive definite the outputs are unspecified and nothing is packed from them)
         if int(status.item()) & _lib.SX_STATUS_NOT_PD:
             return False
-        packed = self._pack(m, linv, alpha)
-        # (no `work` of this size exists: the next full fit allocates its own)
-        self._fit_ws = (linv.new_empty((n_s, 0, 0)), linv)
-        self._install(x, m, packed, alpha, logdet.cpu(), y=y, logdet_dev=logdet)
-        self._appended += k
+        self._commit(x, y, m, linv, alpha, logdet, k)
         return True
 
-    def _slide_rows_host(self, x: Tensor) -> Tuple[int, int]:
-        """`_slide_rows` but for the comparison of the kept fitted rows: every check that the host decides without reading
-        from the device."""
-        if not (self._incremental and self._append_ok and self._linv_current and self._model is not None
-                and self._fit_state is not None and self._subset_idx is None):
-            return 0, 0
-        fit_x = self._buffers[0]
-        n, k = fit_x.size(0), x.size(0) - fit_x.size(0)
-        r = n + k - self._window
-        if not (1 <= k <= MAX_APPEND_ROWS and 1 <= r <= min(MAX_SLIDE_ROWS, MAX_DROP_ROWS) and r < n):
-            return 0, 0
-        if not self._chain_allows(k):
-            return 0, 0
-        if x.device != fit_x.device or self._fit_ws[1].size(1) != n or not self._hyper_unchanged():
-            return 0, 0
-        return r, k
+    def _commit(self, x: Tensor, y: Tensor, m: _lib.SxGpModel, linv: Tensor, alpha: Tensor, logdet_dev: Tensor, k: int,
+                logdet: Optional[Tensor] = None) -> None:
+        """Makes the increment by k rows (m, linv, alpha, logdet_dev), checked to be positive definite, the model's fit of the
+        rows (x, y): sx_gp_pack, the fresh linv as the fit workspace, `_install`, and k more rows counted since the last full
+        fit.  logdet: the host copy of logdet_dev where the caller has read it already (the lockstep call's one read)."""
+        packed = self._pack(m, linv, alpha)
+        # (no `work` of this size exists: the next full fit allocates its own)
+        self._fit_ws = (linv.new_empty((self.num_states, 0, 0)), linv)
+        self._install(x, m, packed, alpha, logdet_dev.cpu() if logdet is None else logdet, y=y, logdet_dev=logdet_dev)
+        self._appended += k
 
-    def _slide_rows(self, x: Tensor, y: Tensor) -> Tuple[int, int]:
-        """(r, k) where the update to (x, y) (device, contiguous, longer than the window) may slide the installed fit: its r
-        oldest rows dropped and the last k rows of (x, y) appended; (0, 0): a full fit of the last m rows.  `_append_rows`'
-        conditions, with the row comparison made against the tail of the fitted rows (the dropped ones no longer matter)."""
-        r, k = self._slide_rows_host(x)
-        if r == 0:
-            return 0, 0
-        fit_x, fit_y, n = self._buffers[0], self._fit_state[0], x.size(0) - k
-        # the kept fitted rows themselves, compared where they live
-        if not (torch.equal(x[r:n], fit_x[r:]) and torch.equal(y[r:n], fit_y[r:])):
-            return 0, 0
-        return r, k
-
-    def _slide(self, x: Tensor, y: Tensor, r: int, k: int) -> bool:
-        """The window moved by sx_gp_drop of the r oldest fitted rows and sx_gp_append of the last k rows of (x, y), then the
-        usual pack and install on the rows x[r:].  False (and nothing changed) where either call answers SX_STATUS_NOT_PD."""
-        x_new, y_new = x[r:].contiguous(), y[r:].contiguous()
-        n = self._buffers[0].size(0)
-        start = self._drop(y_new[:n - r].contiguous(), r)
-        return self._append(x_new, y_new, k, start=start)
-
-    def _update_window(self, x_train: Tensor, y_train: Tensor, may_append: bool, slide: Optional[Tuple[int, int]] = None) -> None:
-        """conf.cem_gp_window: the update to more rows than the window holds.  The stored data are trimmed to the last m rows;
-        the model slides where it may and is fitted on exactly those rows where it may not.  slide: `_slide_rows`' answer
-        (r, k) where the caller has it already (`_append_lockstep`), so that it is not asked for again."""
-        _lib.require_gpu(x_train, 'train_x')
-        _lib.require_gpu(y_train, 'train_y')
-        m = self._window
-        self._x_train, self._y_train = x_train[-m:], y_train[-m:]
-        if may_append:
-            x, y = x_train.detach().contiguous(), y_train.detach().contiguous()
-            r, k = slide if slide is not None else self._slide_rows(x, y)
-            if r and self._slide(x, y, r, k):
-                return
-        self._update_model(self._x_train, self._y_train, may_append=False)
-
-    def _update_model(self, x_train: Tensor, y_train: Tensor, may_append: bool = True) -> None:
-        if self._window is not None and x_train.size(0) > self._window:
-            self._update_window(x_train, y_train, may_append)
+    def _apply(self, train_x: Tensor, train_y: Tensor, r: int = 0, k: int = 0) -> None:
+        """The update to the merged data (train_x, train_y) whose verdict is (r, k), `_increment_rows`' or the lockstep
+        decision's: the stored data are trimmed to the window's last m rows (conf.cem_gp_window), the increment is applied,
+        and where there is none (k = 0), or it answers SX_STATUS_NOT_PD, the model is fitted in full on exactly the stored
+        rows.  The caller has checked the data (`_check_data`)."""
+        trims = self._window is not None and train_x.size(0) > self._window
+        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
+        if trims:
+            train_x, train_y = train_x[-self._window:], train_y[-self._window:]
+        self._x_train, self._y_train = train_x, train_y
+        if k and self._increment(x, y, r, k):
             return
-        self._check_pool_size(x_train.size(0))
-        _lib.require_gpu(x_train, 'train_x')
-        _lib.require_gpu(y_train, 'train_y')
-        x = x_train.detach().contiguous()
-        y = y_train.detach().contiguous()
-        if self._incremental and may_append:
-            k = self._append_rows(x, y)
-            if k and self._append(x, y, k):
-                return
+        if trims:
+            x, y = x[-self._window:], y[-self._window:]
         # conf.cem_gp_subset_size: the max-variance subset of a larger pool (sx_gp_select) is what gets fitted
         x, y = self._subset_of(x, y)
         # factorise on the device (sx_gp_fit), then lay the operands out for the matrix cores (sx_gp_pack)
@@ -468,6 +462,19 @@ class GpCemSSM(CemSSM):
             raise RuntimeError('the kernel matrix K + noise I is not positive definite for the current hyper-parameters')
         self._install(x, m, packed, alpha, logdet.cpu(), y=y, logdet_dev=logdet)
         self._appended = 0
+
+    def _check_data(self, train_x: Tensor, train_y: Tensor) -> None:
+        """Raises where the merged data are more rows than the model holds (a window holds any number: it keeps the last m)
+        or do not live on the GPU as float64."""
+        if self._window is None or train_x.size(0) <= self._window:
+            self._check_pool_size(train_x.size(0))
+        _lib.require_gpu(train_x, 'train_x')
+        _lib.require_gpu(train_y, 'train_y')
+
+    def _update_model(self, x_train: Tensor, y_train: Tensor) -> None:
+        """The warm path of one model: the data checked, one decision (`_increment_rows`), then `_apply`."""
+        self._check_data(x_train, y_train)
+        self._apply(x_train, y_train, *self._increment_rows(x_train, y_train))
 
     def _pack(self, m: _lib.SxGpModel, linv: Tensor, alpha: Tensor) -> Tuple[Tensor, Tensor]:
         """sx_gp_pack of a fitted model into new buffers: (a_pack, stage_tab), which `m` then points at."""
@@ -522,8 +529,7 @@ class GpCemSSM(CemSSM):
         """Scratch for the large-training-set rollout path (grown on demand, reused across calls)."""
         if nbytes <= 0:
             return None
-        if self._workspace is None or self._workspace.numel() * 8 < nbytes:
-            self._workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self._buffers[0].device)
+        self._workspace = _grown(self._workspace, nbytes, self._buffers[0].device)
         return self._workspace
 
     @property
@@ -550,7 +556,6 @@ class GpCemSSM(CemSSM):
             x_train = x_train.detach()[self._subset_idx].contiguous()
             y_train = y_train.detach()[self._subset_idx].contiguous()
         n = x_train.size(0)
-        d_in = self.num_states + self.num_actions
         raw = [self._raw_lengthscale.clone().requires_grad_(True), self._raw_outputscale.clone().requires_grad_(True),
                self._raw_noise.clone().requires_grad_(True)]
         opt = torch.optim.Adam(raw, lr=0.01)
@@ -559,10 +564,7 @@ class GpCemSSM(CemSSM):
             self._raw_lengthscale, self._raw_outputscale, self._raw_noise = (t.detach() for t in raw)
             mll, grad = self.mll_and_grad(x_train, y_train)
             losses.append(float(-(mll / n).sum()))
-            # d loss / d raw = -(1/N) d mll / d theta * sigmoid(raw)   (theta = softplus(raw) [+ floor])
-            raw[0].grad = -(grad[:, :d_in] / n) * torch.sigmoid(raw[0].detach())
-            raw[1].grad = -(grad[:, d_in] / n) * torch.sigmoid(raw[1].detach())
-            raw[2].grad = -(grad[:, d_in + 1] / n) * torch.sigmoid(raw[2].detach())
+            _adam_grads(raw, grad, n)
             opt.step()
         self._raw_lengthscale, self._raw_outputscale, self._raw_noise = (t.detach().clone() for t in raw)
         self._last_training_losses = losses
@@ -691,9 +693,7 @@ def select_subsets_multi(ssms: Sequence['GpCemSSM'], xs: Sequence[Tensor], m: in
             seeds = None
     raws = list(raws) if raws is not None else [None] * E
     models = (_lib.SxGpModel * E)(*[s._fit_struct(x, raw) for s, x, raw in zip(ssms, pools, raws)])
-    nbytes = int(lib.sx_gp_select_workspace_bytes(first.num_states, E, n_max, m))
-    if nbytes < 0:
-        raise _lib.SxError('sx_gp_select_workspace_bytes: bad argument')
+    nbytes = _workspace_bytes(lib.sx_gp_select_workspace_bytes, first.num_states, E, n_max, m)
     workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
     idx = torch.empty((E, m), dtype=torch.int32, device=dev)
     sel_var = torch.empty((E, m), dtype=torch.float64, device=dev)
@@ -751,7 +751,7 @@ class _MultiFit:
         lib = _lib.lib()
         E = self.E
         models = (_lib.SxGpModel * E)(*[m._fit_struct(x, raw) for m, x, raw in zip(self.ssms, self.xs, raws)])
-        arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
+        arr = _ptr_array
         _lib.check(lib.sx_gp_fit_table(models, E, arr(self.ys), arr([w[0] for w in self.ws]), arr([w[1] for w in self.ws]),
                                        arr(self.alpha), arr(list(self.logdet)), _lib.ptr(self.status), _lib.ptr(self.mll),
                                        _lib.ptr(self.grad), ctypes.c_void_p(self.host_table.data_ptr())), 'sx_gp_fit_table')
@@ -772,7 +772,7 @@ class _MultiFit:
 
 
 class _LockstepBuffers:
-    """What a lockstep append keeps between calls, with the model that leads the group: the one workspace allocation the
+    """What a lockstep increment keeps between calls, with the model that leads the group: the one workspace allocation the
     problems' workspaces are cut from, and the problem table in pinned host memory and on the device.  Each grows on
     demand.  (A call ends in a host read of its results, so the previous call's copy of the table has completed.)"""
 
@@ -784,276 +784,148 @@ class _LockstepBuffers:
 
     @property
     def drop(self) -> '_LockstepBuffers':
-        """The same three for the lockstep drop of a slide (`_slide_group`): its table is still being copied when the append's
-        is written, so the two calls do not share one."""
+        """The same three for the lockstep drop of a slide (`_increment_group`): its table is still being copied when the
+        append's is written, so the two calls do not share one."""
         if self._drop is None:
             self._drop = _LockstepBuffers()
         return self._drop
 
-    def workspace(self, nbytes: int, dev) -> Tensor:
-        if self.ws is None or self.ws.numel() * 8 < nbytes or self.ws.device != dev:
-            # (a quarter more than asked for: the training sets grow by a few rows from call to call)
-            self.ws = torch.empty((nbytes + nbytes // 4 + 7) // 8, dtype=torch.float64, device=dev)
-        return self.ws
-
-    def tables(self, nbytes: int, dev) -> Tuple[Tensor, Tensor]:
-        if self.table is None or self.table.numel() < nbytes or self.table.device != dev:
-            self.host_table = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            self.table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self.host_table[:nbytes], self.table[:nbytes]
-
-
-def _cut(ws: Tensor, sizes: List[int]) -> List[int]:
-    """the problems' workspaces (device addresses) cut from one allocation; each size is a multiple of 8 bytes"""
-    ptrs, at = [], ws.data_ptr()
-    for nbytes in sizes:
-        ptrs.append(at)
-        at += nbytes
-    return ptrs
+    def operands(self, sizes: List[int], table_bytes: int, dev):
+        """What one table call over E = len(sizes) problems takes from here: (the problems' workspaces (void* [E]) cut from
+        the one allocation, their sizes (int64 [E], each a multiple of 8 bytes), the host table, the device table)."""
+        # (a quarter more than asked for: the training sets grow by a few rows from call to call)
+        self.ws = _grown(self.ws, sum(sizes), dev, slack=sum(sizes) // 4)
+        ptrs, at = [], self.ws.data_ptr()
+        for nbytes in sizes:
+            ptrs.append(at)
+            at += nbytes
+        if self.table is None or self.table.numel() < table_bytes or self.table.device != dev:
+            self.host_table = torch.empty(table_bytes, dtype=torch.uint8, pin_memory=True)
+            self.table = torch.empty(table_bytes, dtype=torch.uint8, device=dev)
+        E = len(sizes)
+        return ((ctypes.c_void_p * E)(*ptrs), (ctypes.c_int64 * E)(*sizes), self.host_table[:table_bytes],
+                self.table[:table_bytes])
 
 
-def _append_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], k: int, data=None, start=None,
-                  status: Optional[Tensor] = None) -> None:
-    """`_update_appending` of E >= 2 models that append k rows each, with ONE sx_gp_append_table + sx_gp_append_multi (six
-    launches for all of them) and one host read of the E status words and E x n_s log-determinants; then, per model, the
-    pack and install of `GpCemSSM._append`.  Model e's state afterwards equals, bit for bit, what its own update_model
-    leaves.  A model whose Schur complement is not positive definite is fitted in full, alone, after the others have been
-    installed (and raises there as it always did).
-    merged[e]: the training set model e stores.  data[e]: the rows (x, y) (device, contiguous) whose last k are appended and
-    which the model is then fitted on; merged[e] by default.  start[e]: (linv, alpha, logdet) of data[e]'s first rows, to
-    append to in place of the installed fit, and `status` [E] the words of the call that made them, which this call shares
-    (`_slide_group`), as `GpCemSSM._append(..., start=)` does for one model."""
+class _Increment(NamedTuple):
+    """A model's verdict where its plain update extends the installed fit: the r oldest fitted rows dropped (0: an append,
+    > 0: a slide), the last k rows of the merged data (train_x, train_y) appended."""
+    r: int
+    k: int
+    train_x: Tensor
+    train_y: Tensor
+
+
+_ALONE, _FIT = 'alone', 'fit'     # the other two verdicts: the model's own update_model; fitted together with the other `fit` models
+
+
+def _increment_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], r: int, k: int) -> None:
+    """`GpCemSSM._apply` of E >= 2 models with one verdict (r, k), through the table entries.  r > 0: ONE sx_gp_drop_table +
+    sx_gp_drop_multi (seven launches for all of them) of the r oldest fitted rows into fresh per-model buffers.  Then ONE
+    sx_gp_append_table + sx_gp_append_multi (six launches) of the last k rows onto those outputs (onto the installed fits where
+    r = 0), sharing the E status words, and one host read of the words and the E x n_s log-determinants, which decides for
+    both calls as the single-model increment's one word does.  (The words are not read after the drop: where it is not
+    positive definite the append runs on unspecified inputs, writes only its own outputs, and the shared word says so.)
+    Then, per model, `GpCemSSM._commit` on the rows x[r:].  Model e's state afterwards equals, bit for bit, what its own
+    update_model leaves.  A model that either call finds not positive definite is fitted in full on its stored rows, alone,
+    after the others have been installed (and raises there as it always did); nothing is packed from its outputs.
+    merged[e]: the untrimmed training set (stored rows, then the new ones)."""
     lib = _lib.lib()
     E, lead = len(ssms), ssms[0]
     n_s = lead.num_states
-    if data is None:
-        data = []
-        for m, (train_x, train_y) in zip(ssms, merged):
-            _lib.require_gpu(train_x, 'train_x')
-            _lib.require_gpu(train_y, 'train_y')
-            data.append((train_x.detach().contiguous(), train_y.detach().contiguous()))
-    if start is None:
-        start = [(m._fit_ws[1], m._alpha, m._fit_state[1]) for m in ssms]
-    dev = data[0][0].device
-    models = (_lib.SxGpModel * E)(*[m._fit_struct(x) for m, (x, _) in zip(ssms, data)])
-    sizes = [int(lib.sx_gp_append_workspace_bytes(n_s, x.size(0), k)) for x, _ in data]
-    if min(sizes) < 0:
-        raise _lib.SxError('sx_gp_append_workspace_bytes: bad argument')
     if lead._lockstep_bufs is None:
         lead._lockstep_bufs = _LockstepBuffers()
-    bufs = lead._lockstep_bufs
-    ws_ptrs = _cut(bufs.workspace(sum(sizes), dev), sizes)
-    linv = [torch.empty((n_s, x.size(0), x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
-    alpha = [torch.empty((n_s, x.size(0)), dtype=torch.float64, device=dev) for x, _ in data]
-    logdet = torch.empty((E, n_s), dtype=torch.float64, device=dev)
-    if status is None:
-        status = torch.zeros(E, dtype=torch.int32, device=dev)
-    host_table, table = bufs.tables(int(lib.sx_gp_append_table_bytes(E)), dev)
-    arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
-    _lib.check(lib.sx_gp_append_table(models, E, k, arr([y for _, y in data]), arr([st[0] for st in start]),
-                                      arr([st[1] for st in start]), arr([st[2] for st in start]), arr(linv),
-                                      arr(alpha), arr(list(logdet)), _lib.ptr(status), (ctypes.c_void_p * E)(*ws_ptrs),
-                                      (ctypes.c_int64 * E)(*sizes), ctypes.c_void_p(host_table.data_ptr())),
-               'sx_gp_append_table')
+    data = []
+    for m, (train_x, train_y) in zip(ssms, merged):
+        m._check_data(train_x, train_y)
+        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
+        data.append((x[r:].contiguous(), y[r:].contiguous()) if r else (x, y))
+    dev = data[0][0].device
+    start, status = [(m._fit_ws[1], m._alpha, m._fit_state[1]) for m in ssms], None
+    if r:
+        n_old = [m._fit_ws[1].size(1) for m in ssms]
+        kept_y = [y[:n - r].contiguous() for (_, y), n in zip(data, n_old)]
+        sizes = [_workspace_bytes(lib.sx_gp_drop_workspace_bytes, n_s, n, r) for n in n_old]
+        linv, alpha, logdet, status = _outputs(n_s, [n - r for n in n_old], dev)
+        logdet = logdet.view(E, n_s)
+        ws, ws_bytes, host_table, table = lead._lockstep_bufs.drop.operands(sizes, int(lib.sx_gp_drop_table_bytes(E)), dev)
+        n_arr = (ctypes.c_int * E)(*n_old)
+        _lib.check(lib.sx_gp_drop_table(n_s, E, r, n_arr, _ptr_array(kept_y), _ptr_array([st[0] for st in start]),
+                                        _ptr_array(linv), _ptr_array(alpha), _ptr_array(list(logdet)), _lib.ptr(status), ws,
+                                        ws_bytes, ctypes.c_void_p(host_table.data_ptr())), 'sx_gp_drop_table')
+        table.copy_(host_table, non_blocking=True)
+        _lib.check(lib.sx_gp_drop_multi(n_s, E, r, n_arr, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_drop_multi')
+        start = list(zip(linv, alpha, logdet))
+    models = (_lib.SxGpModel * E)(*[m._fit_struct(x) for m, (x, _) in zip(ssms, data)])
+    sizes = [_workspace_bytes(lib.sx_gp_append_workspace_bytes, n_s, x.size(0), k) for x, _ in data]
+    linv, alpha, logdet, status = _outputs(n_s, [x.size(0) for x, _ in data], dev, status)
+    logdet = logdet.view(E, n_s)
+    ws, ws_bytes, host_table, table = lead._lockstep_bufs.operands(sizes, int(lib.sx_gp_append_table_bytes(E)), dev)
+    _lib.check(lib.sx_gp_append_table(models, E, k, _ptr_array([y for _, y in data]), _ptr_array([st[0] for st in start]),
+                                      _ptr_array([st[1] for st in start]), _ptr_array([st[2] for st in start]),
+                                      _ptr_array(linv), _ptr_array(alpha), _ptr_array(list(logdet)), _lib.ptr(status), ws,
+                                      ws_bytes, ctypes.c_void_p(host_table.data_ptr())), 'sx_gp_append_table')
     table.copy_(host_table, non_blocking=True)
     _lib.check(lib.sx_gp_append_multi(models, E, k, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_append_multi')
     host = torch.cat((status.double(), logdet.reshape(-1))).cpu()      # the call's one read of its results
     logdets = host[E:].reshape(E, n_s)
     bad = [bool(int(host[e]) & _lib.SX_STATUS_NOT_PD) for e in range(E)]
-    for e, m in enumerate(ssms):
-        m._x_train, m._y_train = merged[e]
+    for e, (m, (train_x, train_y)) in enumerate(zip(ssms, merged)):
         if bad[e]:
             continue    # (its outputs are unspecified and nothing is packed from them)
-        x, y = data[e]
-        model = _lib.SxGpModel.from_buffer_copy(models[e])
-        packed = m._pack(model, linv[e], alpha[e])
-        m._fit_ws = (linv[e].new_empty((n_s, 0, 0)), linv[e])
-        m._install(x, model, packed, alpha[e], logdets[e].clone(), y=y, logdet_dev=logdet[e])
-        m._appended += k
+        # (r > 0 only where the merged rows overflow the window: the stored data are its last m rows)
+        m._x_train, m._y_train = (train_x[-m._window:], train_y[-m._window:]) if r else (train_x, train_y)
+        m._commit(*data[e], _lib.SxGpModel.from_buffer_copy(models[e]), linv[e], alpha[e], logdet[e], k,
+                  logdet=logdets[e].clone())
     for e, m in enumerate(ssms):
         if bad[e]:
-            m._update_model(*merged[e], may_append=False)
+            m._apply(*merged[e])
 
 
-def _slide_group(ssms: List['GpCemSSM'], merged: List[Tuple[Tensor, Tensor]], r: int, k: int) -> None:
-    """`GpCemSSM._update_window` of E >= 2 windowed models that each drop their r oldest fitted rows and append k: ONE
-    sx_gp_drop_table + sx_gp_drop_multi (seven launches for all of them) into fresh per-model buffers, then `_append_group`
-    onto those outputs -- ONE sx_gp_append_table + sx_gp_append_multi, sharing the E status words, so that its one host
-    read decides for both calls, as the single-model slide shares its word.  The stored data are trimmed to the last m
-    rows; per model the pack and install of `GpCemSSM._slide` on the rows x[r:].  Model e's state afterwards equals, bit for
-    bit, what its own update_model leaves.  A model that either call finds not positive definite gets the full fit of its
-    last m rows, alone, after the others have been installed; nothing is packed from its outputs.
-    merged[e]: the untrimmed training set (stored rows, then the new ones)."""
-    lib = _lib.lib()
-    E, lead = len(ssms), ssms[0]
-    n_s = lead.num_states
-    stored, data, kept_y = [], [], []
-    for m, (train_x, train_y) in zip(ssms, merged):
-        _lib.require_gpu(train_x, 'train_x')
-        _lib.require_gpu(train_y, 'train_y')
-        stored.append((train_x[-m._window:], train_y[-m._window:]))
-        x, y = train_x.detach().contiguous(), train_y.detach().contiguous()
-        x_new, y_new = x[r:].contiguous(), y[r:].contiguous()
-        data.append((x_new, y_new))
-        kept_y.append(y_new[:m._buffers[0].size(0) - r].contiguous())
-    dev = data[0][0].device
-    n_old = [m._fit_ws[1].size(1) for m in ssms]
-    sizes = [int(lib.sx_gp_drop_workspace_bytes(n_s, n, r)) for n in n_old]
-    if min(sizes) < 0:
-        raise _lib.SxError('sx_gp_drop_workspace_bytes: bad argument')
-    if lead._lockstep_bufs is None:
-        lead._lockstep_bufs = _LockstepBuffers()
-    bufs = lead._lockstep_bufs.drop
-    ws_ptrs = _cut(bufs.workspace(sum(sizes), dev), sizes)
-    linv = [torch.empty((n_s, n - r, n - r), dtype=torch.float64, device=dev) for n in n_old]
-    alpha = [torch.empty((n_s, n - r), dtype=torch.float64, device=dev) for n in n_old]
-    logdet = torch.empty((E, n_s), dtype=torch.float64, device=dev)
-    status = torch.zeros(E, dtype=torch.int32, device=dev)
-    host_table, table = bufs.tables(int(lib.sx_gp_drop_table_bytes(E)), dev)
-    arr = lambda ts: (ctypes.c_void_p * E)(*[t.data_ptr() for t in ts])
-    n_arr = (ctypes.c_int * E)(*n_old)
-    _lib.check(lib.sx_gp_drop_table(n_s, E, r, n_arr, arr(kept_y), arr([m._fit_ws[1] for m in ssms]), arr(linv), arr(alpha),
-                                    arr(list(logdet)), _lib.ptr(status), (ctypes.c_void_p * E)(*ws_ptrs),
-                                    (ctypes.c_int64 * E)(*sizes), ctypes.c_void_p(host_table.data_ptr())),
-               'sx_gp_drop_table')
-    table.copy_(host_table, non_blocking=True)
-    _lib.check(lib.sx_gp_drop_multi(n_s, E, r, n_arr, _lib.ptr(table), _lib.stream_ptr(dev)), 'sx_gp_drop_multi')
-    # (the status words are not read here: where the drop is not positive definite the append runs on unspecified inputs,
-    # writes only its own outputs, and the shared word says so to the one read)
-    _append_group(ssms, stored, k, data=data, start=[(linv[e], alpha[e], logdet[e]) for e in range(E)], status=status)
-
-
-def _append_lockstep(ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor]) -> None:
-    """The plain update of models of which some have conf.cem_gp_incremental_lockstep.  The models that have it are decided
-    together: the host checks per model, then the device comparisons of all their fitted rows in one tensor and one read.
-    Those that qualify for an append form groups by the number of new rows (and the device); a group of two or more appends
-    in one call (`_append_group`), a group of one and the qualifying models without the setting append alone, and the models
-    that do not qualify are fitted together first, as update_models_multi fits them.
-    conf.cem_gp_window: a model with the setting whose update stays within its window is an append candidate like any other;
-    one whose update overflows it by r rows is a slide candidate, its comparison (the kept fitted rows) a flag of the same
-    tensor.  The sliding models form groups by (r, k, device): two or more slide in one call each of sx_gp_drop_multi and
-    sx_gp_append_multi (`_slide_group`), one slides alone (`GpCemSSM._slide`), and one that may not slide is fitted on its last
-    m rows with the rest.  (The windowed models WITHOUT the setting never get here: update_models_multi hands them to their
-    own update_model.)"""
-    decided: List[Optional[Tuple[Tensor, Tensor]]] = [None] * len(ssms)
+def _verdicts(ssms: List[CemSSM], xs: List[Tensor], ys: List[Tensor], plain: bool):
+    """The one verdict of every model of an update_models_multi call -- `_ALONE`, `_FIT` or an `_Increment` -- and the
+    models that go alone in the order in which they do.
+    Alone: a windowed model (conf.cem_gp_window) unless it has conf.cem_gp_incremental_lockstep and the update is a `plain`
+    one (no opt_hyp, no replace_old); these go last.  And, once they are taken out, every model of a list that does not train
+    together (`_multi_fit_applies`).  The others are fitted together -- but for those whose plain update extends their
+    installed fit.  A model without conf.cem_gp_incremental_lockstep (it has no window here) decides by itself, reading its
+    row comparison from the device, in index order (`_append_rows`); the models with the setting are decided together: the
+    host checks per model, then the comparisons of all their kept fitted rows as one flag each, stacked and read once."""
+    last = [i for i, m in enumerate(ssms)
+            if getattr(m, '_window', None) is not None and not (plain and getattr(m, '_lockstep', False))]
+    rest = [i for i in range(len(ssms)) if i not in last]
+    if rest and not _multi_fit_applies([ssms[i] for i in rest], [xs[i] for i in rest]):
+        return [_ALONE] * len(ssms), rest + last
+    verdicts: List[Any] = [_ALONE if i in last else _FIT for i in range(len(ssms))]
     cands, flags = [], []
-    for i, (m, new_x, new_y) in enumerate(zip(ssms, xs, ys)):
-        if not m._lockstep:
-            decided[i] = m._appends_next(new_x, new_y)
-            continue
-        merged = m._append_merged(new_x, new_y)
+    for i in rest if plain else ():
+        m = ssms[i]
+        merged = m._append_merged(xs[i], ys[i])
         if merged is None:
             continue
-        x, y = merged[0].detach().contiguous(), merged[1].detach().contiguous()
-        if m._window is not None and x.size(0) > m._window:
-            r, k = m._slide_rows_host(x)
-            if r == 0:
-                continue
-            n = x.size(0) - k
-            cands.append((i, (r, k), merged))
-            flags.append((x[r:n] == m._buffers[0][r:]).all() & (y[r:n] == m._fit_state[0][r:]).all())
+        x, y = merged
+        if not m._lockstep:
+            k = m._append_rows(x, y)
+            if k:
+                verdicts[i] = _Increment(0, k, *merged)
             continue
-        k = m._append_rows_host(x)
-        if k == 0:
-            continue
-        n = x.size(0) - k
-        cands.append((i, (0, k), merged))
-        flags.append((x[:n] == m._buffers[0]).all() & (y[:n] == m._fit_state[0]).all())
-    groups: Dict[Tuple[int, int, Any], List[int]] = {}
+        r, k = m._increment_rows_host(x)
+        if k:
+            cands.append((i, _Increment(r, k, *merged)))
+            new_x, fit_x, new_y, fit_y = m._compared(x, y, r, k)
+            flags.append((new_x == fit_x).all() & (new_y == fit_y).all())
     if cands:
         same = torch.stack(flags).cpu()                                # the decision's one read
-        for (i, (r, k), merged), ok in zip(cands, same):
+        for (i, verdict), ok in zip(cands, same):
             if bool(ok):
-                decided[i] = merged
-                groups.setdefault((r, k, merged[0].device), []).append(i)
-    rest = [i for i, a in enumerate(decided) if a is None]
-    if rest:
-        update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest], _decided=True)
-    grouped = set()
-    slides = {}
-    for (r, k, _), members in groups.items():
-        if r:
-            slides.update({i: (r, k) for i in members})
-        if len(members) >= 2:
-            picked = [ssms[i] for i in members], [decided[i] for i in members]
-            if r:
-                _slide_group(*picked, r, k)
-            else:
-                _append_group(*picked, k)
-            grouped.update(members)
-    for i, a in enumerate(decided):
-        if a is None or i in grouped:
-            continue
-        if i in slides:
-            ssms[i]._update_window(*a, may_append=True, slide=slides[i])
-        else:
-            ssms[i]._update_appending(*a)
+                verdicts[i] = verdict
+    return verdicts, last
 
 
-def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequence[Tensor], opt_hyp=False,
-                        replace_old=False, *, _decided=False) -> None:
-    """``m.update_model(x, y, opt_hyp, replace_old)`` for every (m, x, y) at once: the reference's n_scenarios models, each
-    retrained on its own data after every episode (episode_runner.py:55,123).
-
-    Exact RBF GPs of one (n_s, n_u) and one iteration count train in lockstep: per Adam step ONE sx_gp_fit_multi and ONE
-    sx_gp_mll_grad_multi launch sequence for all of them and one host read, then one batched fit and an sx_gp_pack per
-    model.  Adam is the recipe of GpCemSSM._train_model, one optimizer over every model's raw parameters; its update is
-    elementwise, and each model keeps its own parameter tensors, so each follows the trajectory it would follow alone:
-    the hyper-parameters, loss curves (``_last_training_losses``) and predictions equal those of per-model
-    ``update_model`` bit for bit.  A kernel matrix that is not positive definite in problem e raises RuntimeError naming
-    e, and then no model's data, hyper-parameters or predictions have changed.  (Each model's fit workspace serves the
-    batch from the start, so after such a call its cached W = L^-1 is marked stale, and its next
-    predict_variance_jacobian factorises once more -- as after a failed single-model update.)  Any other list of models (other families,
-    JunkDimensionsSSM, differing shapes or iteration counts) is updated one model at a time.
-
-    conf.cem_gp_incremental: the models whose plain update appends to their fit do so one by one (sx_gp_append), or, with
-    conf.cem_gp_incremental_lockstep, those that add the same number of rows in one sx_gp_append_multi call
-    (`_append_lockstep`); either way each ends in the state its own update_model leaves, bit for bit.
-    conf.cem_gp_window: a windowed model is handed to its own update_model -- unless it has conf.cem_gp_incremental_lockstep
-    and the update is a plain one (no opt_hyp, no replace_old).  Then it takes part in the lockstep update: below its window
-    it appends with the others, and the windowed models that overflow their windows by the same r rows with the same k new
-    ones slide together, ONE sx_gp_drop_multi and ONE sx_gp_append_multi for all of them and two host reads whatever their
-    number (`_slide_group`); one that may not slide is fitted on its last m rows with the models that are fitted.  Every
-    model's stored data are trimmed to its window, and every model ends in the state its own update_model leaves, bit for
-    bit.
-    (_decided: the caller has found that none of these models appends or slides.)"""
-    ssms, xs, ys = list(ssms), list(xs), list(ys)
-    if not len(ssms) == len(xs) == len(ys):
-        raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
-    if not ssms:
-        return
-    # conf.cem_gp_window: a windowed model trims its data and slides by itself; the others go on together -- with them the
-    # windowed models that have conf.cem_gp_incremental_lockstep, where the update is a plain one
-    plain = not opt_hyp and not replace_old
-    windowed = [i for i, m in enumerate(ssms)
-                if getattr(m, '_window', None) is not None and not (plain and getattr(m, '_lockstep', False))]
-    if windowed:
-        rest = [i for i in range(len(ssms)) if i not in windowed]
-        if rest:
-            update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest], opt_hyp, replace_old,
-                                _decided=_decided)
-        for i in windowed:
-            ssms[i].update_model(xs[i], ys[i], opt_hyp, replace_old)
-        return
-    if not _multi_fit_applies(ssms, xs):
-        for m, x, y in zip(ssms, xs, ys):
-            m.update_model(x, y, opt_hyp, replace_old)
-        return
-    # conf.cem_gp_incremental: the models whose update appends to their fit (sx_gp_append) do so one by one, after the
-    # others have been fitted together as below
-    if not _decided and not opt_hyp and not replace_old and any(m._incremental for m in ssms):
-        if any(m._lockstep for m in ssms):
-            _append_lockstep(ssms, xs, ys)
-            return
-        appends = [m._appends_next(x, y) for m, x, y in zip(ssms, xs, ys)]
-        if any(a is not None for a in appends):
-            rest = [i for i, a in enumerate(appends) if a is None]
-            if rest:
-                update_models_multi([ssms[i] for i in rest], [xs[i] for i in rest], [ys[i] for i in rest])
-            for i, a in enumerate(appends):
-                if a is not None:
-                    ssms[i]._update_appending(*a)
-            return
+def _fit_together(ssms: List['GpCemSSM'], xs: List[Tensor], ys: List[Tensor], opt_hyp: bool, replace_old: bool) -> None:
+    """The update of the models whose verdict is `_FIT` (they train together, `_multi_fit_applies`): hyper-parameter
+    training in lockstep where the update asks for it, then one batched fit and a commit per model.  Nothing is committed
+    before the final fit has succeeded everywhere."""
     # the merged training sets, checked before anything changes
     merged = []
     for m, x, y in zip(ssms, xs, ys):
@@ -1103,12 +975,9 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
             grads = host[E * n_s:-E].reshape(E, n_s, d_in + 2)
             for e, (x, p) in enumerate(zip(fit.xs, params)):
                 n = x.size(0)
-                mll, grad = host[e * n_s:(e + 1) * n_s].clone(), grads[e]
+                mll = host[e * n_s:(e + 1) * n_s].clone()
                 losses[e].append(float(-(mll / n).sum()))
-                # d loss / d raw = -(1/N) d mll / d theta * sigmoid(raw), as GpCemSSM._train_model
-                p[0].grad = -(grad[:, :d_in] / n) * torch.sigmoid(p[0].detach())
-                p[1].grad = -(grad[:, d_in] / n) * torch.sigmoid(p[1].detach())
-                p[2].grad = -(grad[:, d_in + 1] / n) * torch.sigmoid(p[2].detach())
+                _adam_grads(p, grads[e], n)
             opt.step()
         raws = [tuple(t.detach().clone() for t in p) for p in params]
         if selecting:
@@ -1133,3 +1002,57 @@ def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequen
         m._appended = 0
         if opt_hyp or m.parametric:
             m._append_ok = False    # as update_model: the update after hyper-parameter training is a full fit
+
+
+def update_models_multi(ssms: Sequence[CemSSM], xs: Sequence[Tensor], ys: Sequence[Tensor], opt_hyp=False,
+                        replace_old=False) -> None:
+    """``m.update_model(x, y, opt_hyp, replace_old)`` for every (m, x, y) at once: the reference's n_scenarios models, each
+    retrained on its own data after every episode (episode_runner.py:55,123).  Every model ends in the state its own
+    update_model leaves, bit for bit: data (trimmed to conf.cem_gp_window), hyper-parameters, loss curves
+    (``_last_training_losses``) and predictions.
+
+    One pass (`_verdicts`) gives every model one of four verdicts, and the work is done in this order:
+
+    * **fit**: exact RBF GPs of one (n_s, n_u) and one iteration count train in lockstep (`_fit_together`), first: per Adam
+      step ONE sx_gp_fit_multi and ONE sx_gp_mll_grad_multi launch sequence for all of them and one host read, then one
+      batched fit and an sx_gp_pack per model.  Adam is the recipe of GpCemSSM._train_model, one optimizer over every
+      model's raw parameters; its update is elementwise, and each model keeps its own parameter tensors, so each follows
+      the trajectory it would follow alone.  A kernel matrix that is not positive definite in problem e (counted among the
+      fitted models) raises RuntimeError naming e, and then none of these models' data, hyper-parameters or predictions
+      have changed.  (Each model's fit workspace serves the batch from the start, so after such a call its cached
+      W = L^-1 is marked stale, and its next predict_variance_jacobian factorises once more -- as after a failed
+      single-model update.)  Where some of them select a max-variance subset (conf.cem_gp_subset_size) and others do not,
+      or not one size, they are updated one model at a time instead.
+    * **append (k)** and **slide (r, k)** (conf.cem_gp_incremental, a plain update -- no opt_hyp, no replace_old -- whose
+      data extend the installed fit by k rows, after dropping its r oldest where it overflows conf.cem_gp_window): the
+      models with conf.cem_gp_incremental_lockstep that share (r, k) and the device form a group, the groups of two or
+      more go next, in the order in which their first members stand in the list, each in ONE sx_gp_append_multi call, after
+      ONE sx_gp_drop_multi call where r > 0 (`_increment_group`); two host reads for all lockstep models whatever their
+      number, one for the decision and one for the results.  Then the remaining ones, alone and in the order of the list
+      (sx_gp_append, after sx_gp_drop where r > 0: `GpCemSSM._apply`).  A model that is not positive definite there is fitted
+      in full, alone, after the others of its group have been installed.
+    * **alone**, last: its own update_model.  A windowed model goes alone unless it has conf.cem_gp_incremental_lockstep
+      and the update is a plain one; so does every model of any other list (other families, JunkDimensionsSSM, differing
+      shapes or iteration counts, data on several devices)."""
+    ssms, xs, ys = list(ssms), list(xs), list(ys)
+    if not len(ssms) == len(xs) == len(ys):
+        raise ValueError(f'{len(ssms)} models, {len(xs)} input sets, {len(ys)} target sets')
+    verdicts, alone = _verdicts(ssms, xs, ys, plain=not opt_hyp and not replace_old)
+    fitted = [i for i, v in enumerate(verdicts) if v is _FIT]
+    if fitted:
+        _fit_together([ssms[i] for i in fitted], [xs[i] for i in fitted], [ys[i] for i in fitted], opt_hyp, replace_old)
+    groups: Dict[Tuple[int, int, Any], List[int]] = {}
+    for i, v in enumerate(verdicts):
+        if isinstance(v, _Increment) and ssms[i]._lockstep:
+            groups.setdefault((v.r, v.k, v.train_x.device), []).append(i)
+    grouped = set()
+    for (r, k, _), members in groups.items():
+        if len(members) >= 2:
+            _increment_group([ssms[i] for i in members], [verdicts[i][2:] for i in members], r, k)
+            grouped.update(members)
+    for i, v in enumerate(verdicts):
+        if isinstance(v, _Increment) and i not in grouped:
+            ssms[i]._check_data(v.train_x, v.train_y)
+            ssms[i]._apply(v.train_x, v.train_y, v.r, v.k)
+    for i in alone:
+        ssms[i].update_model(xs[i], ys[i], opt_hyp, replace_old)

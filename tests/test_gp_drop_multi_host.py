@@ -393,6 +393,37 @@ def test_window_chain_is_respected(fake):
     assert ms.fitted_on_the_last_rows() and [m._appended for m in ms.ssms] == [1, 4, 4]
 
 
+def test_one_call_with_every_kind_of_update(fake):
+    """One update_models_multi call in which every way a model can be updated occurs: two lockstep models that append two rows
+    (one unwindowed, one below its window), two that slide by a row, one that slides by three, a windowed model without the
+    setting, a model without conf.cem_gp_incremental and one whose installed fit may not be appended to.  The two that are
+    fitted go first, together; then the groups in the order their first members stand in the list; then the lone slider;
+    the windowed model without the setting last."""
+    confs = [Conf(None), Conf(25), Conf(40), Conf(30), Conf(35), Conf(28, lockstep=False),
+             Conf(None, lockstep=False, cem_gp_incremental=False), Conf(None)]
+    ms = Models(fake, confs, (22, 25, 30, 30, 35, 28, 20, 21))
+    ms.ssms[7]._append_ok = False
+    ms.update([2, 1, 2, 1, 3, 1, 1, 2])
+    order = [n for n in fake.calls if n in ('sx_gp_fit_multi', 'sx_gp_append_multi', 'sx_gp_drop_multi', 'sx_gp_drop',
+                                            'sx_gp_append')]              # (a Counter keeps its keys in first-call order)
+    assert order == ['sx_gp_fit_multi', 'sx_gp_append_multi', 'sx_gp_drop_multi', 'sx_gp_drop', 'sx_gp_append']
+    assert fake.calls['sx_gp_drop_table'] == 1 and fake.calls['sx_gp_append_table'] == 2 and fake.calls['sx_gp_fit_table'] == 1
+    assert ms.counts() == (1, 2, 2, 2, 0, 1, 8)
+    (a2, k2, n2, _), (d, rd, n_old, words_d), (a, ka, n_train, words_a) = fake.log
+    assert (a2, k2, n2) == ('append', 2, [24, 32])
+    assert (d, rd, n_old) == ('drop', 1, [25, 30]) and (a, ka, n_train) == ('append', 1, [25, 30]) and words_d == words_a
+    assert [m._appended for m in ms.ssms] == [2, 1, 2, 1, 3, 1, 0, 0]
+    assert [m._append_ok for m in ms.ssms] == [True] * 6 + [False, True]
+    assert ms.ssms[0]._lockstep_bufs.ws is not None and ms.ssms[1]._lockstep_bufs.drop.ws is not None
+    assert all(m._lockstep_bufs is None for m in ms.ssms[2:])
+    # (the model without conf.cem_gp_incremental keeps no fitted targets to compare: its rows are checked here, the others' by
+    # `fitted_on_the_last_rows`)
+    plain, (x, y) = ms.ssms.pop(6), ms.all.pop(6)
+    assert torch.equal(plain._buffers[0], x) and torch.equal(plain.x_train, x) and torch.equal(plain.y_train, y)
+    assert plain.device_model.n_train == 21 and plain._fit_state is None and plain._linv_current
+    assert ms.fitted_on_the_last_rows()
+
+
 # ---- host waits ---------------------------------------------------------------------------------------------------------------
 
 def _reads(monkeypatch, fake, E, lockstep):

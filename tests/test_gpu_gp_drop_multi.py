@@ -243,6 +243,68 @@ def test_lockstep_slides_equal_single_slides_bit_for_bit(monkeypatch):
             AM._same_state(a, b, z, f'step {step} model {e}')
 
 
+@pytest.mark.parametrize('k', [1, 3])
+def test_one_call_with_every_kind_of_update_equals_single_updates_bit_for_bit(monkeypatch, k):
+    """One update_models_multi call in which every way a model can be updated occurs, (2,1) models with windows of 64 and 65
+    rows (one on each side of the 64-row block) and unwindowed ones at 40 rows, k new rows each: two that slide together, two
+    that append together (one unwindowed, one below its window), one that slides alone by k + 1 rows, a windowed model
+    without conf.cem_gp_incremental_lockstep, and three that are fitted together: two whose installed fit may not be
+    appended to, one of them windowed, and one without conf.cem_gp_incremental (None in the last column); against
+    update_model on twin models"""
+    from safe_exploration_amd.ssm_cem.gp_ssm_cem import GpCemSSM, update_models_multi
+    # (window, lockstep, fitted rows, new rows, may the installed fit be appended to)
+    spec = [(64, True, 64, k, True), (65, True, 65, k, True), (None, True, 40, k, True), (64, True, 40, k, True),
+            (65, True, 65, k + 1, True), (64, False, 64, k, True), (None, True, 40, k, False), (65, True, 65, k, False),
+            (None, False, 40, k, None)]
+    probs = [R.problem(2, 1, n + new + 8 + e) for e, (_, _, n, new, _) in enumerate(spec)]
+    z = WP._dev(R.queries(probs[0], 7, far=False))
+
+    def gps(lockstep_too):
+        out = []
+        for p, (w, lockstep, n, _, may) in zip(probs, spec):
+            conf = _Conf(w, lockstep and lockstep_too)
+            conf.cem_gp_incremental = may is not None
+            ssm = GpCemSSM(conf, p.n_s, p.n_u)
+            ssm.set_hyperparameters(p.ls, p.s, p.noise)
+            ssm.update_model(WP._dev(p.X[:n]), WP._dev(p.Y[:n]))
+            ssm._append_ok = bool(may)
+            out.append(ssm)
+        return out
+
+    alone, together = gps(False), gps(True)
+    xs = [WP._dev(p.X[n:n + new]) for p, (_, _, n, new, _) in zip(probs, spec)]
+    ys = [WP._dev(p.Y[n:n + new]) for p, (_, _, n, new, _) in zip(probs, spec)]
+    for m, x, y in zip(alone, xs, ys):
+        m.update_model(x, y)
+    spy = SA._Spy(_lib.lib())
+    monkeypatch.setattr(_lib, '_lib', spy)
+    update_models_multi(together, xs, ys)
+    got = tuple(spy.calls[n] for n in ('sx_gp_drop_multi', 'sx_gp_append_multi', 'sx_gp_drop', 'sx_gp_append', 'sx_gp_fit',
+                                       'sx_gp_fit_multi', 'sx_gp_pack'))
+    assert got == (1, 2, 2, 2, 0, 1, 9)
+    assert [m._appended for m in together] == [k, k, k, k, k + 1, k, 0, 0, 0]
+    for e, (a, b) in enumerate(zip(alone, together)):
+        w, _, n, new, may = spec[e]
+        assert b.x_train.size(0) == (n + new if w is None else min(w, n + new))
+        if may is None:
+            # (without conf.cem_gp_incremental a model keeps no fitted targets and no device log-determinant for the helper
+            # to compare: its fields are compared here)
+            where = f'k {k} model {e}'
+            assert a._fit_state is None and b._fit_state is None and not a._append_ok and not b._append_ok, where
+            assert torch.equal(a.x_train, b.x_train) and torch.equal(a.y_train, b.y_train), where
+            assert torch.equal(a._alpha, b._alpha) and torch.equal(a._fit_ws[1], b._fit_ws[1]), where
+            assert a._fit_ws[0].shape == b._fit_ws[0].shape and torch.equal(a._buffers[0], b._buffers[0]), where
+            for u, v, written in zip(a._buffers[1:], b._buffers[1:], AM._pack_writes(a)):
+                assert u.shape == v.shape and torch.equal(AM._bits(u)[written], AM._bits(v)[written]), where
+            assert np.array_equal(a.information_gain(), b.information_gain()), where
+            assert (a._appended, a._linv_current) == (b._appended, b._linv_current) == (0, True), where
+            assert a.device_model.n_train == b.device_model.n_train == n + new
+            for u, v in zip(a.predict_with_jacobians(z[:, :2], z[:, 2:]), b.predict_with_jacobians(z[:, :2], z[:, 2:])):
+                assert torch.equal(u, v), where
+            continue
+        AM._same_state(a, b, z, f'k {k} model {e}')
+
+
 def test_safempc_action_after_lockstep_slides():
     """two pendulum solvers with full windows of 64 rows, slid twice in lockstep, against twins slid one by one"""
     from safe_exploration_amd import problems
