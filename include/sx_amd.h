@@ -525,6 +525,20 @@ int64_t sx_cem_rollout_workspace_bytes(const sx_gp_model* model, int E, int P, i
 #define SX_FORM_BIG 4
 int sx_cem_rollout_form(const sx_gp_model* model, int H);
 
+/* How the three-launch path (SX_FORM_BIG, and sx_gp_predict beyond its single launch) tiles the triangular product of this
+ * model (its n_s and n_pad) over `particles` query points -- E * P of a rollout, P of a prediction -- (no launch, no device
+ * access):
+ *   pt       particle tiles of 16 per workgroup: 8 (128 x 128 tiles) or 4 (128 x 64)
+ *   order    tile order: 16 = paired row tiles, 8 = longest tile first, 1 = XCD-contiguous, 0 = plain (+ the diagnostic bits)
+ *   variant  <fragment pairs per K-chunk><LDS buffers> of the kernel: 13, 12, 22 or 23
+ *   grid     workgroups of the launch
+ * The shape decides, and the process's SX_TRMM_ORDER / SX_TRMM_VARIANT / SX_TRMM_PT as in the launch itself:
+ * the answer is the one the launcher acts on.  It is given for any model, whether or not its training set takes that path
+ * (sx_cem_rollout_form, sx_gp_predict_workspace_bytes say so).  SX_ERR_ARG for null pointers, particles < 0 or a model
+ * without sizes.  Reporting only, as sx_cem_rollout_form.
+ * No counterpart in the reference. */
+int sx_gp_big_tiling(const sx_gp_model* model, int64_t particles, int* pt, int* order, int* variant, int64_t* grid);
+
 /* sx_cem_rollout with a start state per particle (static exploration: the start is a decision variable of the optimiser).
  * The CEM row of a particle is [x0 (n_s) | u_0 .. u_{H-1} (H n_u)], L = n_s + H n_u entries with one Gaussian each:
  *   mean,std dev [E x L]               sampling distribution of the rows (ignored when noise == NULL)

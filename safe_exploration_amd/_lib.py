@@ -214,6 +214,8 @@ SIGNATURES = {
     'sx_profile_disable': (c_int, []),
     'sx_cem_rank_counts': (c_int, [c_int, c_int]),
     'sx_cem_rollout_form': (c_int, [POINTER(SxGpModel), c_int]),
+    'sx_gp_big_tiling': (c_int, [POINTER(SxGpModel), c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                 POINTER(c_int64)]),
     'sx_cem_pack_result': (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'sx_cem_rank_refit': (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64]
                           + [c_void_p] * 7),
@@ -273,6 +275,14 @@ def fill(carray, values) -> None:
     assert len(flat) <= len(carray), (len(flat), len(carray))
     for i, v in enumerate(flat):
         carray[i] = float(v)
+
+
+def big_tiling(model: SxGpModel, particles: int) -> dict:
+    """sx_gp_big_tiling's answer for `model` over `particles` query points: {'pt', 'order', 'variant', 'grid'}."""
+    pt, order, variant, grid = c_int(), c_int(), c_int(), c_int64()
+    check(lib().sx_gp_big_tiling(ctypes.byref(model), particles, ctypes.byref(pt), ctypes.byref(order),
+                                 ctypes.byref(variant), ctypes.byref(grid)), 'sx_gp_big_tiling')
+    return {'pt': pt.value, 'order': order.value, 'variant': variant.value, 'grid': grid.value}
 
 
 def profile_collect() -> dict:

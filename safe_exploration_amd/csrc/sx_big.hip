@@ -1,7 +1,6 @@
 // The large-N path: the kernels of sx_big.hpp and the two predict helpers, launch_predict_big and launch_rollout_big
-// (sx_big_launch.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES.
+// (sx_big_launch.hpp) for every shift-0 shape of SX_ROLLOUT_SHAPES, and sx_gp_big_tiling, which reports the tiling they launch.
 #include <cstdlib>
-#include <vector>
 
 #include "sx_big.hpp"
 #include "sx_big_launch.hpp"
@@ -11,77 +10,46 @@
 
 namespace sx {
 
-// trmm_reduce_kernel variants, selectable for A/B measurements (tools/cfg4_probe.py):
+// trmm_reduce_kernel variants, selectable for A/B measurements (tools/cfg4_probe.py), read once per process:
 //   SX_TRMM_ORDER   = tile order bits: 16 paired tiles (default for small grids), 8 longest-first (default otherwise),
 //                     1 XCD-contiguous with the row tile fastest, 0 plain;
 //                     + 2 / + 4: timing-only diagnostics (every workgroup reads the same Kstar / W tile: no fabric traffic)
 //   SX_TRMM_VARIANT = <pairs per chunk><LDS buffers>: 13 (default), 12, 22, 23
+//   SX_TRMM_PT      = particle tiles per workgroup: 8 | 4 (default: 4 where 8 would leave a compute unit with at most two
+//                     workgroups, see plan_big_tiling in sx_big_launch.hpp)
 // Measured at config 4 (N = 2000, 16 384 particles), per launch: plain order 7.2 ms, XCD-contiguous 4.73 ms, longest-first
 // 3.92 ms -- whatever the variant, and the same with the fabric traffic removed (order + 6): the kernel was never
 // memory-bound, its tiles differ 16-fold in work and the tail of the launch was what it lost.
-static const int g_trmm_order = std::getenv("SX_TRMM_ORDER") ? std::atoi(std::getenv("SX_TRMM_ORDER")) : -1;
-static const int g_trmm_variant = std::getenv("SX_TRMM_VARIANT") ? std::atoi(std::getenv("SX_TRMM_VARIANT")) : 13;
-//   SX_TRMM_PT      = particle tiles per workgroup: 8 | 4 (default: 4 where 8 would leave a compute unit with at most two
-//                     workgroups, see launch_trmm)
-static const int g_trmm_pt = std::getenv("SX_TRMM_PT") ? std::atoi(std::getenv("SX_TRMM_PT")) : 0;
-
-template <int NS, int D, int PPC, int NBUF, int PT>
-static void launch_trmm_v(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, int row_tiles, hipStream_t stream) {
-    constexpr int lds = big_lds_bytes<PPC, NBUF, PT>();
-    (void)allow_lds(trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, lds);
-    const int64_t pgroups = p128 / (PT * 16);
-    const int64_t tiles = pgroups * row_tiles * NS;
-    // Tile order.  A large grid runs longest tile first.  A grid of a few rounds is all quantisation: it runs PAIRED tiles
-    // (row tile rt and row_tiles - 1 - rt in one workgroup: equal work) when that deals the work out more evenly than
-    // longest-first does -- judged by dealing the workgroups round-robin onto the 256 CUs and comparing the fullest CU.
-    // SX_TRMM_ORDER overrides.
-    int order = g_trmm_order;
-    if (order < 0) {
-        order = 8;
-        if (tiles <= 3 * 768 && row_tiles > 1) {
-            const int nrb = gc.n_pad >> 4, groups = (int)pgroups * NS;
-            std::vector<double> work(row_tiles);
-            for (int rt = 0; rt < row_tiles; ++rt) {
-                const int rb0 = rt * kBigRb, rb_end = rb0 + kBigRb < nrb ? rb0 + kBigRb : nrb;
-                double w = 0.0;
-                for (int rb = rb0; rb < rb0 + kBigRb; ++rb) w += 2 * (rb + 1) < 2 * rb_end ? 2 * (rb + 1) : 2 * rb_end;
-                work[rt] = w;
-            }
-            auto fullest = [&](const std::vector<double>& per_wg) {     // per_wg: work of the workgroups in dispatch order
-                double cu[256] = {0.0};
-                for (size_t i = 0; i < per_wg.size(); ++i) cu[i & 255] += per_wg[i];
-                double m = 0.0;
-                for (double v : cu) m = v > m ? v : m;
-                return m;
-            };
-            std::vector<double> plain, paired;
-            for (int rt = row_tiles - 1; rt >= 0; --rt) plain.insert(plain.end(), groups, work[rt]);
-            for (int j = 0; j < (row_tiles + 1) / 2; ++j)
-                paired.insert(paired.end(), groups, work[row_tiles - 1 - j] + (j != row_tiles - 1 - j ? work[j] : 0.0));
-            if (fullest(paired) < fullest(plain)) order = 16;
-        }
-    }
-    const dim3 grid((unsigned)((order & 16) ? pgroups * ((row_tiles + 1) / 2) * NS : tiles));
-    if (kind >= 0)
-        launch(kind, trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, grid, dim3(kBigThreads), lds, stream, gc, ws, p128, row_tiles, order);
-    else
-        hipLaunchKernelGGL((trmm_reduce_kernel<NS, D, PPC, NBUF, PT>), grid, dim3(kBigThreads), lds, stream, gc, ws, p128, row_tiles,
-                           order);
+static const TrmmOverride& trmm_override() {
+    static const TrmmOverride o = [] {
+        const char *order = std::getenv("SX_TRMM_ORDER"), *variant = std::getenv("SX_TRMM_VARIANT"), *pt = std::getenv("SX_TRMM_PT");
+        return TrmmOverride{order ? std::atoi(order) : -1, variant ? std::atoi(variant) : 13, pt ? std::atoi(pt) : 0};
+    }();
+    return o;
 }
 
+template <int NS, int D, int PPC, int NBUF, int PT>
+static void launch_trmm_v(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, const BigTiling& t, hipStream_t stream) {
+    constexpr int lds = big_lds_bytes<PPC, NBUF, PT>();
+    (void)allow_lds(trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, lds);
+    const dim3 grid((unsigned)t.grid);
+    if (kind >= 0)
+        launch(kind, trmm_reduce_kernel<NS, D, PPC, NBUF, PT>, grid, dim3(kBigThreads), lds, stream, gc, ws, p128, t.row_tiles, t.order);
+    else
+        hipLaunchKernelGGL((trmm_reduce_kernel<NS, D, PPC, NBUF, PT>), grid, dim3(kBigThreads), lds, stream, gc, ws, p128, t.row_tiles,
+                           t.order);
+}
+
+// trmm_reduce_kernel in the tiling plan_big_tiling (sx_big_launch.hpp) picks for the shape and the process's SX_TRMM_* settings
 template <int NS, int D>
-static void launch_trmm(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, int row_tiles, hipStream_t stream) {
-    // Small grids take 128 x 64 tiles: with 128 x 128 a grid of up to two workgroups per compute unit (N ~ 1000 .. 1400 at
-    // 4096 particles) leaves each SIMD one or two waves that idle through every barrier and DMA wait; twice the workgroups
-    // at half the size fill those gaps (tools/n_sweep.sh: the step at the path switch).
-    const int64_t wgs8 = (p128 / kBigTile) * row_tiles * NS;
-    const bool half = g_trmm_pt ? g_trmm_pt == 4 : wgs8 <= 2 * 768;
-    if (half) return launch_trmm_v<NS, D, 1, 3, 4>(kind, gc, ws, p128, row_tiles, stream);
-    switch (g_trmm_variant) {
-        case 12: return launch_trmm_v<NS, D, 1, 2, 8>(kind, gc, ws, p128, row_tiles, stream);
-        case 22: return launch_trmm_v<NS, D, 2, 2, 8>(kind, gc, ws, p128, row_tiles, stream);
-        case 23: return launch_trmm_v<NS, D, 2, 3, 8>(kind, gc, ws, p128, row_tiles, stream);
-        default: return launch_trmm_v<NS, D, 1, 3, 8>(kind, gc, ws, p128, row_tiles, stream);
+static void launch_trmm(int kind, const GpConst<NS, D>& gc, const BigWs& ws, int64_t p128, hipStream_t stream) {
+    const BigTiling t = plan_big_tiling(NS, gc.n_pad, p128, trmm_override());
+    if (t.pt == 4) return launch_trmm_v<NS, D, 1, 3, 4>(kind, gc, ws, p128, t, stream);
+    switch (t.variant()) {
+        case 12: return launch_trmm_v<NS, D, 1, 2, 8>(kind, gc, ws, p128, t, stream);
+        case 22: return launch_trmm_v<NS, D, 2, 2, 8>(kind, gc, ws, p128, t, stream);
+        case 23: return launch_trmm_v<NS, D, 2, 3, 8>(kind, gc, ws, p128, t, stream);
+        default: return launch_trmm_v<NS, D, 1, 3, 8>(kind, gc, ws, p128, t, stream);
     }
 }
 
@@ -127,7 +95,7 @@ int launch_predict_big(const sx_gp_model* m, const double* z, int P, double* mea
                        (int64_t)P, p128, ws);
     hipLaunchKernelGGL((kstar_big_kernel<NS, D>), dim3((unsigned)(p128 / 16), (unsigned)((m->n_pad + 255) / 256)), dim3(256),
                        0, stream, gc, ws);
-    launch_trmm<NS, D>(-1, gc, ws, p128, row_tiles, stream);
+    launch_trmm<NS, D>(-1, gc, ws, p128, stream);
     hipLaunchKernelGGL((predict_collect_big_kernel<NS, D>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, stream, gc, ws,
                        (int64_t)P, p128, row_tiles * 2, mean, var, jac);
     return check_launch();
@@ -152,7 +120,7 @@ int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const RolloutPtr
     for (int t = 0; t < rp.H; ++t) {
         launch(SX_PROF_KSTAR_BIG, kstar_big_kernel<NS, D>, dim3((unsigned)(p128 / 16), (unsigned)((m->n_pad + 255) / 256)),
                dim3(256), 0, stream, gc, ws);
-        launch_trmm<NS, D>(SX_PROF_TRMM_BIG, gc, ws, p128, row_tiles, stream);
+        launch_trmm<NS, D>(SX_PROF_TRMM_BIG, gc, ws, p128, stream);
         BigStep bs{rp.actions, rp.traj, rp.sigma, rp.obj_cost, rp.con_cost, rp.status, rp.H, t, row_tiles * 2,
                    (t > 0 || rp.q0 != nullptr) ? 1 : 0};
         launch(SX_PROF_STEP_BIG, step_big_kernel<NS, NU>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, gc, rc, cc,
@@ -170,3 +138,14 @@ int launch_rollout_big(const sx_gp_model* m, const sx_env* env, const RolloutPtr
                                                 int64_t, hipStream_t);
 #define SX_BIG_ONE(NS, NU, SH, unused) SX_SHIFT0_##SH(SX_BIG_INSTANTIATE(NS, NU))
 SX_ROLLOUT_SHAPES(SX_BIG_ONE, 0)
+
+extern "C" int sx_gp_big_tiling(const sx_gp_model* model, int64_t particles, int* pt, int* order, int* variant, int64_t* grid) {
+    if (!model || !pt || !order || !variant || !grid || particles < 0 || model->n_s <= 0 || model->n_pad <= 0) return SX_ERR_ARG;
+    const int64_t p128 = (particles + sx::kBigTile - 1) / sx::kBigTile * sx::kBigTile;
+    const sx::BigTiling t = sx::plan_big_tiling(model->n_s, model->n_pad, p128, sx::trmm_override());
+    *pt = t.pt;
+    *order = t.order;
+    *variant = t.variant();
+    *grid = t.grid;
+    return SX_OK;
+}
